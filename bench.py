@@ -4,7 +4,7 @@
 Workload (BASELINE.json configs[1], SURVEY.md 8d "C2"): Illumina 30x single-tech model
 (moe_attention_config_single_tech_old_equivalent_weight_norm), >= 1 M synthetic candidate sites from the
 seeded generator, seeded synthetic weights.  ``--config {C2,C3,C4,C5,hybrid_full}`` makes any other BASELINE.json
-configuration the timed region (same path, any N); the default (C2) run also reports C3, C4, C5 and hybrid_full in a
+configuration the timed region (same path, any N); a ``--full`` run of C2 also reports C3, C4, C5 and hybrid_full in a
 ``configs`` block: host-to-host rate at ``--sites`` sites per launch over ``--config-launches`` launches, the read convolver's
 roofline fraction from the engine's HIP events, and max |delta| against the oracle's per-site answers on 96 check sites.
 
@@ -15,13 +15,20 @@ one pass of the hot path over one batch of ``--launches-per-step`` x ``--sites``
 (10 x 8 192 = 81 920 by default, scored in launches of ``--sites``; the launches cycle a pinned pool of
 ``--pool`` distinct synthetic batches).  Exactly K steps are timed between barrier + synchronize fences, with
 every result harvested to host memory before the closing fence.  The device-resident rate (inputs already in
-HBM, outputs left there) is reported beside it as ``device_resident``: the pipeline hides the PCIe feed behind
-the kernels, so the two agree within a few percent.
+HBM, outputs left there) is reported beside it as ``device_resident`` by a ``--full`` run: the pipeline hides the PCIe
+feed behind the kernels, so the two agree within a few percent.
+
+A plain run does only what the headline needs: it sets up, warms up, times the K steps and prints the line (``value``,
+``ms_per_step`` = milliseconds of one timed step, the timed region's own roofline figures).  Everything else -- the CPU
+baseline, the oracle's reference answers and parity, the device-resident, two-engine, bf16x3, latency, small-batch and
+worker-pool legs, the ``configs`` block and the strong-scaling region at N > 1 -- runs with ``--full``.
+``--dump-outputs DIR`` writes what the last timed step returned to its caller (logits, posteriors, meta weights) as float32
+``DIR/<name>.npy``; the inputs and weights are seeded, so two builds run with the same arguments can be compared output for output.
 
 ``python bench.py --gpus N`` from a plain shell starts its own N ranks (a CHILD ``python -m torch.distributed.run --nnodes=1
 --nproc-per-node N --master-addr 127.0.0.1``, before this process has touched a GPU; never an exec) and relays rank 0's one JSON line;
-under a launcher (RANK / WORLD_SIZE set: the driver's form) the process is a rank.  The CPU baseline is timed on rank 0 at every N,
-before the rendezvous (the other ranks wait idle in it), so the line carries ``cpu_baseline`` at N > 1 too.
+under a launcher (RANK / WORLD_SIZE set: the driver's form) the process is a rank.  A ``--full`` run times the CPU baseline on
+rank 0 at every N, before the rendezvous (the other ranks wait idle in it), so its line carries ``cpu_baseline`` at N > 1 too.
 
 With N > 1 (one process per GPU under torch.distributed.run) the global step batch is N times as large
 (``--scaling weak``, the default) or the same ``--launches-per-step`` launches cut N ways (``--scaling strong``:
@@ -34,11 +41,11 @@ At N > 1 the line also carries the run's audit trail, collected with one ``all_g
 ``ranks`` (per rank: device index, PCI address, UUID, sites, reads, own seconds, launches, pinned bytes, CPUs, ``own_checksum`` of the
 columns it produced), ``distinct_devices``, ``backend``, ``gather_ms`` (two events around the one gather), ``slowest_rank``,
 ``balance`` = min / max reads per rank, ``gather_verified_ranks`` = the number of ranks whose own checksum equals the checksum of
-what rank 0 received for them (the gather proves itself; the run fails when it is not N); and with ``--scaling both`` (the
-default) ``strong_scaling``: a second timed region of the same K steps over the N = 1 stream cut N ways.
+what rank 0 received for them (the gather proves itself; the run fails when it is not N); and with ``--full`` and ``--scaling both``
+(the default) ``strong_scaling``: a second timed region of the same K steps over the N = 1 stream cut N ways.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2|C3|C4|C5|hybrid_full] [--sites S] [--launches-per-step B]
-                    [--scaling weak|strong|both]
+                    [--scaling weak|strong|both] [--full] [--dump-outputs DIR]
 """
 import argparse
 import json
@@ -389,6 +396,29 @@ def checksum(columns):
             "last": float(flat[-1]) if flat.size else None}
 
 
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(directory, arrays, max_bytes=DUMP_BYTES_MAX):
+    """Write ``arrays`` ({name: array}) as float32 ``directory/<name>.npy``.  Beyond ``max_bytes`` in all, every array keeps the same
+    fraction of its entries along its longest axis, at positions drawn from a fixed seed (the same positions on every run with the
+    same arguments).  -> {name: shape written}."""
+    os.makedirs(directory, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    keep = 1.0 if total <= max_bytes else max_bytes / total
+    written = {}
+    for name, x in sorted(arrays.items()):
+        if keep < 1.0:
+            axis = int(np.argmax(x.shape))
+            n = x.shape[axis]
+            idx = np.sort(np.random.default_rng(12345).choice(n, size=max(1, int(n * keep)), replace=False))
+            x = np.ascontiguousarray(np.take(x, idx, axis=axis))
+        np.save(os.path.join(directory, name + ".npy"), x)
+        written[name] = list(x.shape)
+    return written
+
+
 def to_device(batch, dev):
     """A SiteBatch whose pileups (and reference one-hot) are resident on ``dev``."""
     import torch
@@ -432,18 +462,27 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", choices=sorted(BENCH_CONFIGS), default="C2",
                     help="which BASELINE.json configuration the timed region runs (default C2 = configs[1], the one `metric` is "
-                         "quoted on); the default run also reports C3, C4, C5 and hybrid_full in its `configs` block")
+                         "quoted on); a --full run of C2 also reports C3, C4, C5 and hybrid_full in its `configs` block")
     ap.add_argument("--sites", type=int, default=8192, help="candidate sites per engine launch")
     ap.add_argument("--launches-per-step", type=int, default=10,
                     help="launches of --sites sites that make one step's batch on one GPU (10 x 8192 = 81 920 sites: "
                          "20 steps stream 1.64 M sites in ~3.4 s)")
     ap.add_argument("--pool", type=int, default=3, help="distinct pinned synthetic batches the launches cycle through")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: the CPU baseline, the oracle's reference answers and parity, the "
+                         "device-resident, two-engine, bf16x3, latency, small-batch and worker-pool legs, the `configs` block and, at "
+                         "N > 1, the strong-scaling region (each can be switched off with its --no-* option); without it a run sets "
+                         "up, warms up, times the K steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy (float32: "
+                         "logits [experts, alleles], posteriors [4, pairs], meta [sites, 3] for ensemble models; at N > 1 every rank "
+                         "writes its own share as rank<r>_<name>.npy); at most 64 MB in all, a fixed seeded column sample beyond that")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-budget", type=float, default=12.0, help="seconds of the CPU baseline's per-site leg (its batched leg takes half)")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the device-resident, latency, small-batch, parity and other-configuration legs (headline only)")
-    ap.add_argument("--no-configs", action="store_true", help="skip the `configs` block (the other BASELINE configurations)")
-    ap.add_argument("--no-shared-leg", action="store_true", help="skip the worker-pool leg (`per_site_shared`: a child process tree)")
+                    help="--full: skip the device-resident, latency, small-batch, parity and other-configuration legs")
+    ap.add_argument("--no-configs", action="store_true", help="--full: skip the `configs` block (the other BASELINE configurations)")
+    ap.add_argument("--no-shared-leg", action="store_true", help="--full: skip the worker-pool leg (`per_site_shared`: a child process tree)")
     ap.add_argument("--config-launches", type=int, default=40, help="timed launches of each configuration of the `configs` block")
     ap.add_argument("--fused", choices=["full", "trunk", "none"], default="full",
                     help="read convolver: one fused kernel from the bytes / layer-by-layer stem + fused trunk / "
@@ -451,11 +490,13 @@ def main():
     ap.add_argument("--scaling", choices=["weak", "strong", "both"], default="both",
                     help="N > 1: weak = every GPU gets --launches-per-step launches per step (global batch N times as "
                          "large); strong = the N = 1 stream (--launches-per-step launches per step in total) cut N ways; "
-                         "both (default) = `value` is the weak run and a second timed region of the same K steps reports the "
-                         "strong one as `strong_scaling` (at N = 1 the two coincide and only one region runs)")
+                         "both (default) = `value` is the weak run and, with --full, a second timed region of the same K steps "
+                         "reports the strong one as `strong_scaling` (at N = 1 the two coincide and only one region runs)")
     ap.add_argument("--seed", type=int, default=1)
-    ap.add_argument("--op-times", action="store_true", help="print per-op device times to stderr")
+    ap.add_argument("--op-times", action="store_true", help="--full: print per-op device times to stderr")
     args = ap.parse_args()
+    if args.dump_outputs is not None and args.steps < 1:
+        ap.error("--dump-outputs needs at least one timed step")
     cfg = BENCH_CONFIGS[args.config]
 
     under_launcher = "RANK" in os.environ and "WORLD_SIZE" in os.environ
@@ -471,11 +512,11 @@ def main():
     # GPU already).  At N > 1 the other ranks are blocked in the rendezvous below while it runs (no engine, no feeder threads
     # yet), so it has the host to itself exactly as at N = 1 and is over before any timed region starts.
     profiled = any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ) or "rocprof" in os.environ.get("LD_PRELOAD", "")
-    secondary = world == 1 and not args.no_secondary
+    secondary = args.full and world == 1 and not args.no_secondary
     other_configs = [c for c in SECONDARY_CONFIGS if c != args.config] if (secondary and args.config == "C2" and not args.no_configs) else []
     cpu, answers = None, {}
     if rank == 0 and not profiled:
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             try:
                 cpu = cpu_baseline(args.seed, budget_s=args.cpu_budget, config=args.config)
                 if world > 1:
@@ -689,6 +730,16 @@ def main():
 
     headline_mode = "strong" if args.scaling == "strong" else "weak"
     run = timed_region(headline_mode, profile=True)
+    if args.dump_outputs is not None:
+        # what the caller of the timed path received in the last timed step: this rank's launches in submission order
+        last = sorted((item for item in run["results"] if item[0][0] == args.steps - 1), key=lambda item: item[0][1])
+        outs = {"logits": np.concatenate([lg for _, lg, _, _ in last], axis=1),
+                "posteriors": np.concatenate([po for _, _, _, po in last], axis=1)}
+        if eng.has_meta:
+            outs["meta"] = np.concatenate([m for _, _, m, _ in last], axis=0)
+        prefix = f"rank{rank}_" if world > 1 else ""
+        written = dump_outputs(args.dump_outputs, {prefix + k: v for k, v in outs.items()}, max_bytes=DUMP_BYTES_MAX // world)
+        print(f"bench: last timed step's outputs -> {args.dump_outputs}: {written}", file=sys.stderr)
     dt, value, sizes, pieces, piece_batches = run["dt"], run["value"], run["sizes"], run["pieces"], run["piece_batches"]
     n_launches, sites_total = run["n_launches"], run["sites_total"]
     pinned_bytes = run["report"]["pinned_input_bytes"]
@@ -1043,9 +1094,9 @@ def main():
     gather_verified = verify_gather(run, raw_reports)
     reports = shard.summarize_ranks(raw_reports)
     strong = None
-    if args.scaling == "both":
+    if args.scaling == "both" and (args.full or world == 1):
         if world > 1:
-            # a second timed region of the same K steps: the N = 1 stream cut N ways (total work fixed)
+            # a second timed region of the same K steps (--full runs only): the N = 1 stream cut N ways (total work fixed)
             run2 = timed_region("strong", profile=False)
             drift2, finite2 = check_run(run2)
             drift += drift2
@@ -1064,7 +1115,8 @@ def main():
                       "note": "N = 1: the strong and the weak workload are the same stream; one timed region"}
     cpu_reason = None
     if cpu is None:
-        cpu_reason = ("skipped: --no-cpu-baseline" if args.no_cpu_baseline else
+        cpu_reason = ("skipped: runs with --full" if not args.full else
+                      "skipped: --no-cpu-baseline" if args.no_cpu_baseline else
                       "skipped: running under a profiler whose preloaded library has initialised the GPU (the baseline forks)" if profiled else
                       "not run on this rank")
 

@@ -67,6 +67,32 @@ def test_checksum_is_a_function_of_the_bytes():
     assert json.loads(json.dumps(a)) == a
 
 
+def test_dump_outputs_writes_float32_and_samples_the_same_columns_beyond_its_cap(tmp_path):
+    """--dump-outputs: under the cap every array is written whole as float32; beyond it every array keeps the same fraction of its
+    longest axis, at positions that do not change from run to run, and the files stay within the cap."""
+    import bench
+    rng = np.random.default_rng(1)
+    arrays = {"logits": rng.standard_normal((3, 1000)).astype(np.float32), "meta": rng.random((400, 3)),
+              "posteriors": rng.random((4, 3000)).astype(np.float32)}
+    whole = bench.dump_outputs(str(tmp_path / "whole"), arrays)
+    assert whole == {"logits": [3, 1000], "meta": [400, 3], "posteriors": [4, 3000]}
+    for name, x in arrays.items():
+        got = np.load(tmp_path / "whole" / f"{name}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, x.astype(np.float32))
+    cap = 16 * 1024
+    a = bench.dump_outputs(str(tmp_path / "a"), arrays, max_bytes=cap)
+    b = bench.dump_outputs(str(tmp_path / "b"), arrays, max_bytes=cap)
+    assert a == b and a["logits"][0] == 3 and a["meta"][1] == 3 and a["posteriors"][0] == 4 and a["posteriors"][1] < 3000
+    assert sum(os.path.getsize(tmp_path / "a" / f"{n}.npy") - 128 for n in a) <= cap
+    for name in arrays:
+        x, y = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert np.array_equal(x, y)
+    # the sample is columns of the original, in their original order
+    post = arrays["posteriors"]
+    cols = [int(np.flatnonzero((post == c[:, None]).all(axis=0))[0]) for c in np.load(tmp_path / "a" / "posteriors.npy").T]
+    assert cols == sorted(cols) and len(set(cols)) == len(cols)
+
+
 def test_feature_dicts_are_the_per_site_call_arguments():
     """caller_calling.py:631-649: {allele: (float [R, L, C], float [R', L, C] | None)} in allele order + a [1, L, 5] segment."""
     import bench

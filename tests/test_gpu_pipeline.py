@@ -98,14 +98,15 @@ def test_bench_under_torchrun_is_auditable():
     communicator up, the product's partitioner + pipeline + the one gather on the measured path, ONE JSON line -- which carries the
     run's audit trail: the ranks seen with their device's PCI address / UUID and the identity source, sites, reads, own seconds,
     launches, pinned bytes and CPUs; distinct_devices == 1; the event-timed gather; the strong-scaling entry (--scaling both, the
-    default); the sha256 of the library it loaded.  The same workload run plainly scores the same number of sites."""
+    default); the sha256 of the library it loaded.  The same workload run plainly scores the same number of sites.  Run with --full
+    (its legs switched off) so that the CPU baseline's reason is the switch's."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = _bench_env()
-    common = ["--gpus", "1"] + SMALL + ["--no-cpu-baseline"]
+    common = ["--gpus", "1"] + SMALL + ["--full", "--no-cpu-baseline"]
     plain = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + common, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert plain.returncode == 0, plain.stderr[-2000:]
     under = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
@@ -138,19 +139,53 @@ def test_bench_under_torchrun_is_auditable():
     assert len(prov["lib_sha256"]) == 64 and (b["roofline"]["traffic"] is None) == bool(b["roofline"]["traffic_stale"] in (True, None))
 
 
+def test_plain_bench_times_the_headline_only_and_dumps_its_last_step(tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W` without --full: exactly K timed steps, the headline's fields, none of the
+    --full legs; --dump-outputs DIR holds what the last timed step returned (float32 logits [experts, alleles of one step] and
+    posteriors [4, pairs]), the same bytes on a second run with the same arguments."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    small = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--sites", "512", "--launches-per-step", "2"]
+
+    def run(d):
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + small + ["--dump-outputs", str(d)], cwd=root,
+                             env=_bench_env(), capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = _json_lines(out.stdout)
+        assert len(lines) == 1, out.stdout[-2000:]
+        return json.loads(lines[0])
+    z = run(tmp_path / "a")
+    assert z["metric"] == "candidate sites/sec (whole node)" and z["unit"] == "sites/s" and z["higher_is_better"] is True and z["dtype"] == "f32"
+    assert z["steps"] == 3 and z["value"] > 0 and abs(z["ms_per_step"] - 1e3 * z["config"]["timed_region_s"] / 3) < 1.0
+    assert z["config"]["sites_total"] == 3 * 2 * 512 and z["config"]["repeat_passes_bit_identical"] and z["config"]["outputs_finite"]
+    assert z["cpu_baseline"] is None and "--full" in z["cpu_baseline_reason"]
+    assert all(z[k] is None for k in ("device_resident", "two_engines", "bf16x3", "latency", "parity", "small_batch", "per_site_shared", "configs"))
+    (r,) = z["ranks"]
+    a = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("logits", "posteriors")}
+    assert sorted(os.listdir(tmp_path / "a")) == ["logits.npy", "posteriors.npy"]               # single-expert model: no meta weights
+    assert a["logits"].dtype == np.float32 and a["logits"].shape == (1, r["alleles"] // 3) and np.isfinite(a["logits"]).all()
+    assert a["posteriors"].dtype == np.float32 and a["posteriors"].shape[0] == 4 and np.isfinite(a["posteriors"]).all()
+    run(tmp_path / "b")
+    for n, x in a.items():
+        assert np.array_equal(np.load(tmp_path / "b" / f"{n}.npy"), x), n
+
+
 def test_bench_gpus_2_from_a_plain_shell_starts_its_own_ranks():
     """`python bench.py --gpus 2` typed into a plain shell (no launcher, no RANK in the environment) starts its two
     ranks itself as a child torch.distributed.run, and prints rank 0's ONE JSON line -- here with HELLO_BENCH_BACKEND=gloo so that
     both ranks can share this box's one GPU.  The line carries what the contract asks of every line, at N > 1 too: `roofline` and
     `cpu_baseline` (timed on rank 0 before the rendezvous), plus the audit of both ranks and the strong-scaling second region
-    (exercised here at world 2, with its own repeat / gather checks)."""
+    (exercised here at world 2, with its own repeat / gather checks) -- the last two in a --full run."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(_bench_env(), HELLO_BENCH_BACKEND="gloo")
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--cpu-budget", "2"] + SMALL, cwd=root, env=env,
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--full", "--cpu-budget", "2"] + SMALL, cwd=root, env=env,
                          capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = _json_lines(out.stdout)
@@ -179,14 +214,14 @@ def test_bench_gpus_2_runs_the_hybrid_configurations_through_the_gather(config, 
     one GPU) runs BASELINE.json's hybrid configuration as the timed region -- two read technologies per rank, the one gather -- and the
     gather proves itself: every rank ships the checksum of the columns it produced, rank 0 compares it with the checksum of what it
     received (`gather_verified_ranks` == 2, in the weak and in the strong region).  With hybrid_full the three experts' logits AND the
-    per-site meta weights cross the gather."""
+    per-site meta weights cross the gather.  A --full run, for the strong-scaling region."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(_bench_env(), HELLO_BENCH_BACKEND="gloo")
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--config", config, "--no-cpu-baseline"] + SMALL,
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--config", config, "--full", "--no-cpu-baseline"] + SMALL,
                          cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = _json_lines(out.stdout)
@@ -210,7 +245,7 @@ def test_bench_gpus_2_runs_the_hybrid_configurations_through_the_gather(config, 
 
 
 def test_bench_default_run_reports_every_baseline_configuration():
-    """the default (C2) run carries a `configs` block -- C3, C4, C5 and hybrid_full through the headline's path
+    """the --full (C2) run carries a `configs` block -- C3, C4, C5 and hybrid_full through the headline's path
     (pinned host batch -> HostPipeline -> Engine -> posteriors on the host): rate, the read convolver's roofline fraction from the
     engine's HIP events, and max |delta| against the oracle's per-site answers on the check sites.  Small sizes here; the driver's run
     uses 8 192 sites per launch over 40 launches."""
@@ -220,7 +255,7 @@ def test_bench_default_run_reports_every_baseline_configuration():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--sites", "512", "--launches-per-step", "2",
-                          "--cpu-budget", "1", "--config-launches", "4"], cwd=root, env=_bench_env(), capture_output=True, text=True, timeout=1200)
+                          "--full", "--cpu-budget", "1", "--config-launches", "4"], cwd=root, env=_bench_env(), capture_output=True, text=True, timeout=1200)
     assert out.returncode == 0, out.stderr[-3000:]
     z = json.loads(_json_lines(out.stdout)[-1])
     assert z["config"]["name"] == "C2" and z["parity"]["within_tolerance"] and z["parity"]["sites"] == 96 and z["parity"]["sites_with_identical_call"] == 96

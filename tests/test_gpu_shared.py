@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from hello_amd import loader, netspec as ns, synth, weights
+from tests.util import short_tempdir
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -30,8 +31,15 @@ def _as_arrays(result):
 
 
 @pytest.fixture
-def model_file(tmp_path, monkeypatch):
-    monkeypatch.setenv("HELLO_SHARED_DIR", str(tmp_path / "rendezvous"))
+def rendezvous_dir():
+    """The servers' rendezvous directory (sockets, locks, logs): a path a socket name fits behind (tests/util.short_tempdir)."""
+    with short_tempdir() as d:
+        yield os.path.join(d, "rendezvous")
+
+
+@pytest.fixture
+def model_file(tmp_path, monkeypatch, rendezvous_dir):
+    monkeypatch.setenv("HELLO_SHARED_DIR", rendezvous_dir)
     monkeypatch.setenv("HELLO_SHARED_IDLE_EXIT", "1")         # the box admits few processes on its card: a test's server leaves at once
 
     def make(config, seed=11):

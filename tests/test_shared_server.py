@@ -15,6 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from hello_amd import shared, synth                                  # noqa: E402
+from tests.util import short_tempdir                                  # noqa: E402
 
 INFO1 = dict(window=150, channels0=6, channels1=0, n_experts=1, has_meta=False, uses_ref=False, ensemble=False, arithmetic="fp32")
 INFO3 = dict(window=150, channels0=6, channels1=6, n_experts=3, has_meta=True, uses_ref=True, ensemble=True, arithmetic="fp32")
@@ -67,13 +68,20 @@ def _serve(sock, shm, info, scorers, delay, idle, max_clients, ready):
 
 
 @pytest.fixture
-def server(tmp_path):
+def sock_dir():
+    """A directory for the servers' sockets and slot files whose path a socket name fits behind (tests/util.short_tempdir)."""
+    with short_tempdir() as d:
+        yield d
+
+
+@pytest.fixture
+def server(sock_dir):
     """-> start(info, scorers=2, delay=0, idle=None, max_clients=16) -> (socket path, process); every server is torn down afterwards."""
     ctx = mp.get_context("fork")
     started = []
 
     def start(info, scorers=2, delay=0.0, idle=None, max_clients=16):
-        sock, shm = str(tmp_path / f"s{len(started)}.sock"), str(tmp_path / f"s{len(started)}.slots")
+        sock, shm = os.path.join(sock_dir, f"s{len(started)}.sock"), os.path.join(sock_dir, f"s{len(started)}.slots")
         ready = ctx.Event()
         proc = ctx.Process(target=_serve, args=(sock, shm, info, scorers, delay, idle, max_clients, ready), daemon=True)
         proc.start()
@@ -329,7 +337,7 @@ def test_load_shared_refuses_what_load_refuses_and_never_falls_back_to_the_cpu(t
         loader.load(path, shared=True, start_timeout=240)
 
 
-def test_native_server_is_clean_under_threadsanitizer(tmp_path):
+def test_native_server_is_clean_under_threadsanitizer(tmp_path, sock_dir):
     """The server's source compiled as plain host C++ with tests/abi/site_server_tsan.cpp under -fsanitize=thread: ten client THREADS
     speaking the wire protocol (hanging up and reconnecting in the middle of their runs) against three scorer threads with launch
     grouping on -- every answer is the caller's own, every site is scored exactly once in launches of several sites, and
@@ -343,7 +351,7 @@ def test_native_server_is_clean_under_threadsanitizer(tmp_path):
                             os.path.join(ROOT, "hello_amd", "csrc", "site_server.hip"), os.path.join(ROOT, "tests", "abi", "site_server_tsan.cpp"),
                             "-o", exe], capture_output=True, text=True)
     assert build.returncode == 0, build.stderr[-3000:]
-    run = subprocess.run([exe, str(tmp_path)], capture_output=True, text=True, timeout=600,
+    run = subprocess.run([exe, sock_dir], capture_output=True, text=True, timeout=600,
                          env=dict(os.environ, TSAN_OPTIONS="halt_on_error=0:exitcode=66"))
     assert "ThreadSanitizer" not in run.stderr, run.stderr[-4000:]
     assert run.returncode == 0, (run.returncode, run.stdout, run.stderr[-2000:])

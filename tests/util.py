@@ -1,6 +1,9 @@
 """Shared helpers for the test-suite (fixture loading, state digests)."""
+import contextlib
 import hashlib
 import os
+import shutil
+import tempfile
 
 import numpy as np
 
@@ -19,6 +22,21 @@ def state_digest(state):
         h.update(k.encode())
         h.update(np.ascontiguousarray(state[k]).tobytes())
     return h.hexdigest()[:16]
+
+
+@contextlib.contextmanager
+def short_tempdir(prefix="hello-"):
+    """A fresh directory whose path leaves room for Unix socket names (removed on exit): sun_path holds 107 bytes, which pytest's
+    tmp_path under a deep temporary root overruns.  Under the system's temporary root when that is short, else under /tmp."""
+    for base in (tempfile.gettempdir(), "/tmp"):
+        if len(base) <= 48 and os.path.isdir(base) and os.access(base, os.W_OK):
+            d = tempfile.mkdtemp(prefix=prefix, dir=base)
+            try:
+                yield d
+            finally:
+                shutil.rmtree(d, ignore_errors=True)
+            return
+    raise RuntimeError("no writable temporary directory with a path short enough for a Unix socket")
 
 
 def load_fixture(name):
