@@ -170,6 +170,132 @@ long long rows_of(int domain, int32_t S, int32_t A, int64_t R0, int64_t R1) {
     return -1;
 }
 
+const char* op_name(int kind) {
+    static const char* const names[] = {"?", "conv1d", "maxpool", "segsum", "mix", "head", "concat", "add", "readconv_fused",
+                                        "layernorm", "compressor_fused", "xattn_front"};
+    return kind >= 1 && kind <= HELLO_OP_XATTN_FRONT ? names[kind] : names[0];
+}
+
+// The buffer rules stated next to hello_op in the header: what an op reads and writes lies inside buffers of the right
+// domain and size, float input is float, float4 kernels get whole float4s.  Ids are already known to be in range.
+int validate_op_buffers(const hello_model_desc* d, const hello_op& o, int i) {
+    // domain of a buffer's rows; the uint8 inputs: READS0 / READS1 per read, REF per site
+    auto domain_of = [&](int id) { return id == HELLO_BUF_READS0 ? (int)HELLO_ROWS_READS0 : id == HELLO_BUF_READS1 ? (int)HELLO_ROWS_READS1
+                                          : id == HELLO_BUF_REF ? (int)HELLO_ROWS_SITES : d->buffers[id].domain; };
+    auto is_input = [](int id) { return id >= 0 && id < HELLO_BUF_FIRST_SCRATCH; };
+    auto need = [&](int id, const char* what, long long floats) -> int {
+        if (id == HELLO_BUF_NONE || is_input(id)) return 0;
+        if ((long long)d->buffers[id].floats_per_row < floats)
+            return fail(HELLO_ERR_MODEL, "op %d (%s): buffer %d holds %d floats per row, the op's %s needs %lld", i, op_name(o.kind), id,
+                        d->buffers[id].floats_per_row, what, floats);
+        return 0;
+    };
+    auto reads_in = [&](int id, const char* what, int domain) -> int {
+        if (id == HELLO_BUF_NONE || domain_of(id) == domain) return 0;
+        return fail(HELLO_ERR_MODEL, "op %d (%s): %s buffer %d has rows of domain %d, the op reads domain %d", i, op_name(o.kind), what, id,
+                    domain_of(id), domain);
+    };
+    const long long lin = o.lin, lout = o.lout, cin = o.cin, cout = o.cout;
+    if (o.kind == HELLO_OP_HEAD) {
+        if (o.lin <= 0 || o.cin <= 0 || is_input(o.src0))
+            return fail(HELLO_ERR_MODEL, "op %d (head): a HEAD averages lin > 0 positions of cin > 0 float channels", i);
+        // the outputs it writes: logits [n_experts][A] take one value per allele, meta [S][3] up to three per site
+        const bool meta = o.dst == 3;
+        if (meta ? !(d->has_meta && o.domain == HELLO_ROWS_SITES && o.cout <= 3)
+                 : !(o.dst < d->n_experts && o.domain == HELLO_ROWS_ALLELES && o.cout == 1))
+            return fail(HELLO_ERR_MODEL, "op %d (head): output slot %d is %s", i, o.dst,
+                        meta ? "meta [sites][3]: a SITES-domain head of at most 3 outputs, has_meta set"
+                             : "a logit row [alleles]: an ALLELES-domain head of 1 output, slot < n_experts");
+        if (int rc = reads_in(o.src0, "src0", o.domain)) return rc;
+        return need(o.src0, "input (HEAD: lin * cin)", lin * cin);
+    }
+    // the op's own output domain, and the domain its sources' rows must have
+    int in_domain = o.domain;
+    if (o.kind == HELLO_OP_SEGSUM || o.kind == HELLO_OP_READCONV_FUSED)
+        in_domain = o.seg == HELLO_SEG_READS0_TO_ALLELES ? HELLO_ROWS_READS0 : o.seg == HELLO_SEG_READS1_TO_ALLELES ? HELLO_ROWS_READS1
+                                                                                                            : HELLO_ROWS_ALLELES;
+    if ((o.kind == HELLO_OP_SEGSUM || o.kind == HELLO_OP_READCONV_FUSED || o.kind == HELLO_OP_MIX) &&
+        o.domain != (o.kind == HELLO_OP_SEGSUM && o.seg == HELLO_SEG_ALLELES_TO_SITES ? HELLO_ROWS_SITES : HELLO_ROWS_ALLELES))
+        return fail(HELLO_ERR_MODEL, "op %d (%s): op domain %d is not the domain its segment kind writes", i, op_name(o.kind), o.domain);
+    if (d->buffers[o.dst].domain != o.domain)
+        return fail(HELLO_ERR_MODEL, "op %d (%s): dst buffer %d has rows of domain %d, the op writes domain %d", i, op_name(o.kind), o.dst,
+                    d->buffers[o.dst].domain, o.domain);
+    if (int rc = reads_in(o.src0, "src0", in_domain)) return rc;
+    if (o.kind != HELLO_OP_XATTN_FRONT) {          // the front checks its src1 (sites) and res (an output) itself
+        if (int rc = reads_in(o.src1, "src1", o.kind == HELLO_OP_MIX ? (int)HELLO_ROWS_SITES : in_domain)) return rc;
+        if (int rc = reads_in(o.res, "res", o.domain)) return rc;
+    }
+    if (o.dst == o.src0 || o.dst == o.src1)
+        return fail(HELLO_ERR_MODEL, "op %d (%s): dst buffer %d is also a source (no op runs in place)", i, op_name(o.kind), o.dst);
+    // uint8 inputs: only a CONV1D or the fused read convolver reads them, flagged, with that input's channels and window
+    const bool u8 = (o.flags & HELLO_FLAG_SRC_U8) != 0;
+    const bool u8_reader = o.kind == HELLO_OP_CONV1D || o.kind == HELLO_OP_READCONV_FUSED;
+    if (u8 != is_input(o.src0) || (u8 && !u8_reader) || is_input(o.src1) || is_input(o.res))
+        return fail(HELLO_ERR_MODEL, "op %d (%s): HELLO_FLAG_SRC_U8 must be set exactly when src0 is a uint8 input (src1 / res never are)", i,
+                    op_name(o.kind));
+    if (u8) {
+        const int channels = o.src0 == HELLO_BUF_READS0 ? d->channels0 : o.src0 == HELLO_BUF_READS1 ? d->channels1 : (d->uses_ref ? 5 : 0);
+        if (o.cin != channels || o.lin != d->window)
+            return fail(HELLO_ERR_MODEL, "op %d (%s): a uint8 input holds [window %d][%d channels] (%s), the op reads [%d][%d]", i,
+                        op_name(o.kind), d->window, channels, o.src0 == HELLO_BUF_REF ? "REF needs uses_ref" : "channels0 / channels1", o.lin,
+                        o.cin);
+    }
+    switch (o.kind) {
+        case HELLO_OP_CONV1D:
+            if (o.lin + 2 * o.pad < o.k)
+                return fail(HELLO_ERR_MODEL, "op %d: lout inconsistent (the padded row is shorter than the kernel)", i);
+            if (o.src1 != HELLO_BUF_NONE) {
+                if (int rc = need(o.src0, "first source (lin * seg)", lin * o.seg)) return rc;
+                if (int rc = need(o.src1, "second source (lin * (cin - seg))", lin * (cin - o.seg))) return rc;
+            } else if (int rc = need(o.src0, "input (lin * cin)", lin * cin)) {
+                return rc;
+            }
+            if (int rc = need(o.dst, "output (lout * cout)", lout * cout)) return rc;
+            return need(o.res, "residual (lout * cout)", lout * cout);
+        case HELLO_OP_MAXPOOL:
+            if (o.k < 1 || o.stride < 1 || o.pad < 0 || 2 * o.pad > o.k || o.lin <= 0 || o.lin + 2 * o.pad < o.k ||
+                (o.lin + 2 * o.pad - o.k) / o.stride + 1 != o.lout)
+                return fail(HELLO_ERR_MODEL, "op %d (maxpool): MaxPool geometry needs k >= 1, stride >= 1, 0 <= pad <= k / 2 and "
+                                             "lout = (lin + 2 pad - k) / stride + 1", i);
+            break;
+        case HELLO_OP_SEGSUM: case HELLO_OP_MIX: case HELLO_OP_CONCAT: case HELLO_OP_ADD: case HELLO_OP_LAYERNORM:
+            if (o.lin <= 0 || o.lin != o.lout)
+                return fail(HELLO_ERR_MODEL, "op %d (%s): the op keeps the row length: lin == lout > 0", i, op_name(o.kind));
+            break;
+        default: break;
+    }
+    const bool float4_op = o.kind == HELLO_OP_MAXPOOL || o.kind == HELLO_OP_SEGSUM || o.kind == HELLO_OP_MIX ||
+                           o.kind == HELLO_OP_CONCAT || o.kind == HELLO_OP_ADD;
+    if (float4_op && (o.cin <= 0 || o.cin % 4 || (o.kind == HELLO_OP_CONCAT && (o.c1 <= 0 || o.c1 % 4))))
+        return fail(HELLO_ERR_MODEL, "op %d (%s): channel counts must be positive multiples of 4 (the kernel moves float4)", i,
+                    op_name(o.kind));
+    switch (o.kind) {
+        case HELLO_OP_MAXPOOL:
+            if (int rc = need(o.src0, "input (lin * cin)", lin * cin)) return rc;
+            return need(o.dst, "output (lout * cin)", lout * cin);
+        case HELLO_OP_CONCAT:
+            if (int rc = need(o.src0, "first source (lin * cin)", lin * cin)) return rc;
+            if (int rc = need(o.src1, "second source (lin * c1)", lin * o.c1)) return rc;
+            return need(o.dst, "output (lin * (cin + c1))", lin * (cin + o.c1));
+        case HELLO_OP_SEGSUM: case HELLO_OP_MIX: case HELLO_OP_ADD: case HELLO_OP_LAYERNORM:
+            for (int id : {o.src0, o.src1, o.res, o.dst})
+                if (int rc = need(id, "rows (lin * cin)", lin * cin)) return rc;
+            return 0;
+        case HELLO_OP_READCONV_FUSED:
+            if (!u8)
+                if (int rc = need(o.src0, "input (lin * cin)", lin * cin)) return rc;
+            return need(o.dst, "output (lout * cout)", lout * cout);
+        case HELLO_OP_COMPRESSOR_FUSED:
+            if (int rc = need(o.src0, "input (36 * 64)", 36 * 64)) return rc;
+            return need(o.dst, "output (18 * 128)", 18 * 128);
+        case HELLO_OP_XATTN_FRONT:
+            if (int rc = need(o.src0, "allele rows (18 * 128)", 18 * 128)) return rc;
+            if (int rc = need(o.src1, "site rows (18 * 128)", 18 * 128)) return rc;
+            return need(o.dst, "output (9 * 256)", 9 * 256);
+        default: return 0;
+    }
+}
+
 int validate_model(const hello_model_desc* d) {
     if (!d) return fail(HELLO_ERR_ARG, "model description is NULL");
     if (d->abi_version != HELLO_ABI_VERSION)
@@ -272,6 +398,7 @@ int validate_model(const hello_model_desc* d) {
         }
         if (o.kind == HELLO_OP_READCONV_FUSED && !hello::readconv_supports_extra_blocks(o.k))
             return fail(HELLO_ERR_MODEL, "op %d: the fused read convolver takes 0 or 2 extra blocks (k), got %d", i, o.k);
+        if (int rc = validate_op_buffers(d, o, i)) return rc;
     }
     return 0;
 }

@@ -148,6 +148,24 @@ typedef struct hello_op {
     int64_t w_off;       /* float offset of the packed weights in the weight blob */
     int64_t b_off;       /* float offset of the bias */
 } hello_op;
+/* Buffer rules hello_engine_create checks (HELLO_ERR_MODEL) for every op other than a HEAD, before it looks for a device:
+ *   - domains: dst is a buffer of the op's domain; src0 / src1 / res hold rows of the domains the op reads -- its own domain,
+ *     except SEGSUM and READCONV_FUSED, whose src0 is READS0 / READS1 / ALLELES according to `seg` (their domain: ALLELES, or
+ *     SITES for a SEGSUM over HELLO_SEG_ALLELES_TO_SITES), and MIX (domain ALLELES), whose src1 is SITES; the uint8 inputs
+ *     READS0 / READS1 / REF have rows of READS0 / READS1 / SITES;
+ *   - sizes: every buffer's floats_per_row covers what the op reads or writes per row: lout*cout (CONV1D dst and res),
+ *     lin*cin (CONV1D src0; MAXPOOL src0; SEGSUM, MIX, ADD, LAYERNORM all buffers), lout*cin (MAXPOOL dst), lin*cin,
+ *     lin*c1 and lin*(cin+c1) (CONCAT src0, src1, dst), lin*seg and lin*(cin-seg) (the two sources of a two-source CONV1D);
+ *   - uint8 inputs: HELLO_FLAG_SRC_U8 is set exactly when src0 is one of the reserved input ids (only CONV1D and
+ *     READCONV_FUSED read them; never as src1 or res), and then cin == that input's channels (channels0, channels1, 5 for
+ *     HELLO_BUF_REF, which needs uses_ref) and lin == window;
+ *   - float4: MAXPOOL, SEGSUM, MIX, CONCAT (cin and c1) and ADD take channel counts that are positive multiples of 4;
+ *   - lengths: SEGSUM, MIX, CONCAT, ADD and LAYERNORM keep the row length, lin == lout > 0; a CONV1D's padded row is at least
+ *     k long (lin + 2 pad >= k);
+ *   - MAXPOOL: k >= 1, stride >= 1, 0 <= pad <= k/2, lout == (lin + 2 pad - k) / stride + 1;
+ *   - no op runs in place: dst differs from src0 and src1.
+ * A HEAD reads src0 (a float buffer of its domain) holding lin*cin floats per row, lin > 0, cin > 0, and writes a logit row
+ * (slot < n_experts: ALLELES domain, cout 1) or meta (slot 3: has_meta, SITES domain, cout <= 3). */
 
 typedef struct hello_buffer {        /* scratch buffer i (i >= HELLO_BUF_FIRST_SCRATCH) */
     int32_t domain;                  /* hello_domain: rows scale with the batch */
