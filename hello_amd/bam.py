@@ -1,0 +1,147 @@
+"""ctypes binding of the BAM reader in libhello_mi355x.so (include/hello_mi355x.h: ``hello_bam_*``).
+
+It stands in for the ``pysam.AlignmentFile.fetch`` the reference's read containers run per chunk
+(python/PileupContainerLite.py:526-570).  It needs no engine, no model and no GPU.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+from dataclasses import dataclass
+from typing import List, Optional, Tuple
+
+import numpy as np
+
+from .engine import load_library
+
+_ARRAYS = (  # (field, hello_bam_* selector, dtype)
+    ("bases", 0, np.uint8), ("quals", 1, np.uint8), ("read_offsets", 2, np.int64), ("cigars", 3, np.uint32),
+    ("cigar_offsets", 4, np.int64), ("ref_starts", 5, np.int64), ("ref_ends", 6, np.int64), ("mapq", 7, np.uint8),
+    ("flags", 8, np.uint16), ("name_hash", 9, np.uint64), ("strand", 10, np.uint8),
+)
+
+_bound = None
+
+
+def _lib():
+    global _bound
+    if _bound is None:
+        lib = load_library()
+        vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
+        lib.hello_bam_open.argtypes = [C.c_char_p, i32, C.POINTER(vp)]
+        lib.hello_bam_n_references.argtypes = [vp]
+        lib.hello_bam_reference.argtypes = [vp, i32, C.POINTER(C.c_char_p), C.POINTER(i64)]
+        lib.hello_bam_fetch.argtypes = [vp, C.c_char_p, i64, i64, i32, C.POINTER(vp)]
+        lib.hello_bam_reads_info.argtypes = [vp, C.POINTER(i64), C.POINTER(i32), C.POINTER(i64)]
+        lib.hello_bam_reads_array.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(i64)]
+        lib.hello_bam_reads_free.argtypes = [vp]
+        lib.hello_bam_reads_free.restype = None
+        lib.hello_bam_close.argtypes = [vp]
+        lib.hello_bam_close.restype = None
+        _bound = lib
+    return _bound
+
+
+def _check(rc: int) -> None:
+    if rc != 0:
+        raise RuntimeError(_lib().hello_last_error().decode(errors="replace"))
+
+
+@dataclass
+class Reads:
+    """One region's records in file order, as flat arrays (the layout ``hello_engine_featurize`` takes)."""
+    bases: np.ndarray          # uint8 ASCII, all reads concatenated
+    quals: np.ndarray          # uint8
+    read_offsets: np.ndarray   # int64 [R + 1]
+    cigars: np.ndarray         # uint32, BAM packing len << 4 | op
+    cigar_offsets: np.ndarray  # int64 [R + 1]
+    ref_starts: np.ndarray     # int64
+    ref_ends: np.ndarray       # int64 (bam_endpos)
+    mapq: np.ndarray           # uint8
+    flags: np.ndarray          # uint16
+    name_hash: np.ndarray      # uint64, FNV-1a of the read name
+    strand: np.ndarray         # uint8, 1 = reverse
+    used_index: bool = False
+    n_blocks: int = 0
+
+    @property
+    def n_reads(self) -> int:
+        return int(self.ref_starts.shape[0])
+
+    def read(self, i: int) -> Tuple[str, List[Tuple[int, int]], np.ndarray]:
+        """(bases, [(op, length)], qualities) of read i."""
+        a, b = int(self.read_offsets[i]), int(self.read_offsets[i + 1])
+        cig = self.cigars[self.cigar_offsets[i]:self.cigar_offsets[i + 1]]
+        return self.bases[a:b].tobytes().decode(), [(int(c) & 15, int(c) >> 4) for c in cig], self.quals[a:b]
+
+    @staticmethod
+    def concat(parts: List["Reads"]) -> Tuple["Reads", np.ndarray]:
+        """All parts' reads one after the other, and the part (source) of every read."""
+        def offsets(name):
+            out, base = [np.zeros(1, np.int64)], 0
+            for p in parts:
+                o = getattr(p, name)
+                out.append(o[1:] + base)
+                base += int(o[-1])
+            return np.concatenate(out)
+        cat = {f: np.concatenate([getattr(p, f) for p in parts]) for f, _, _ in _ARRAYS if not f.endswith("offsets")}
+        cat["read_offsets"], cat["cigar_offsets"] = offsets("read_offsets"), offsets("cigar_offsets")
+        source = np.concatenate([np.full(p.n_reads, i, np.uint8) for i, p in enumerate(parts)])
+        return Reads(**cat), source
+
+
+class BamFile:
+    """An open BAM: ``references`` from its header, ``fetch(chromosome, start, stop)`` -> ``Reads``.  Not thread-safe."""
+
+    def __init__(self, path: str, threads: int = 16):
+        self.path = path
+        self._lib = _lib()
+        h = C.c_void_p()
+        _check(self._lib.hello_bam_open(os.fsencode(path), int(threads), C.byref(h)))
+        self._h = h
+        self.references: List[Tuple[str, int]] = []
+        for i in range(self._lib.hello_bam_n_references(h)):
+            name, length = C.c_char_p(), C.c_int64()
+            _check(self._lib.hello_bam_reference(h, i, C.byref(name), C.byref(length)))
+            self.references.append((name.value.decode(), int(length.value)))
+
+    def fetch(self, chromosome: str, start: int = 0, stop: Optional[int] = None, use_index: Optional[bool] = None) -> Reads:
+        """Records overlapping [start, stop).  use_index: None = the .bai when there is one, True = require it, False = scan."""
+        if stop is None:
+            stop = dict(self.references).get(chromosome, 0)
+        r = C.c_void_p()
+        _check(self._lib.hello_bam_fetch(self._h, chromosome.encode(), int(start), int(stop),
+                                         -1 if use_index is None else int(bool(use_index)), C.byref(r)))
+        try:
+            n, used, blocks = C.c_int64(), C.c_int32(), C.c_int64()
+            _check(self._lib.hello_bam_reads_info(r, C.byref(n), C.byref(used), C.byref(blocks)))
+            out = {}
+            for field, which, dtype in _ARRAYS:
+                ptr, count = C.c_void_p(), C.c_int64()
+                _check(self._lib.hello_bam_reads_array(r, which, C.byref(ptr), C.byref(count)))
+                k = int(count.value)
+                if k == 0:
+                    out[field] = np.zeros(0, dtype)
+                else:
+                    buf = (C.c_char * (k * np.dtype(dtype).itemsize)).from_address(ptr.value)
+                    out[field] = np.frombuffer(buf, dtype=dtype).copy()
+            return Reads(**out, used_index=bool(used.value), n_blocks=int(blocks.value))
+        finally:
+            self._lib.hello_bam_reads_free(r)
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            self._lib.hello_bam_close(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -247,6 +247,66 @@ int hello_engine_featurize(hello_engine* engine,
                            int64_t n_reads, int32_t n_sites, int32_t feature_length, int32_t channels,
                            uint8_t* out, int32_t flags, void* hip_stream);
 
+/* ---- BAM input and candidate positions (host BAM reader + one GPU kernel; no engine, no model) ------------------------
+ * Additions within ABI version 2.
+ *
+ * hello_bam_*: stands in for pysam.AlignmentFile.fetch as the reference's read containers use it
+ * (python/PileupContainerLite.py:526-570).  BGZF is inflated with zlib on at most 16 host threads.  hello_bam_fetch decodes
+ * every record of `chromosome` overlapping [start, stop) (pos < stop and end > start, end = bam_endpos) in file order into
+ * flat arrays in the layout hello_engine_featurize takes: ASCII bases and base qualities with read offsets [R+1], CIGARs in
+ * BAM packing with CIGAR offsets [R+1], ref_start / ref_end (int64), mapq (uint8), flag (uint16), a 64-bit FNV-1a hash of
+ * the read name (uint64) and the strand (uint8, 1 = reverse).  use_index: 1 = the `.bai` next to the file (x.bam.bai or
+ * x.bai) must be used, 0 = scan the whole file, -1 = the index when there is one.  A CIGAR of more than 65 535 operations is
+ * read from the record's CG:B,I tag (SAM specification 4.2.2).  CRAM input and records without stored
+ * base qualities are refused (HELLO_ERR_ARG).  A hello_bam is used from one thread at a time. */
+typedef struct hello_bam hello_bam;
+typedef struct hello_bam_reads hello_bam_reads;
+enum {
+    HELLO_BAM_BASES = 0, HELLO_BAM_QUALS = 1, HELLO_BAM_READ_OFFSETS = 2, HELLO_BAM_CIGARS = 3, HELLO_BAM_CIGAR_OFFSETS = 4,
+    HELLO_BAM_REF_STARTS = 5, HELLO_BAM_REF_ENDS = 6, HELLO_BAM_MAPQ = 7, HELLO_BAM_FLAGS = 8, HELLO_BAM_NAME_HASH = 9,
+    HELLO_BAM_STRAND = 10
+};
+int hello_bam_open(const char* path, int32_t n_threads, hello_bam** out);
+int hello_bam_n_references(const hello_bam* bam);
+int hello_bam_reference(const hello_bam* bam, int32_t i, const char** name, int64_t* length);
+int hello_bam_fetch(hello_bam* bam, const char* chromosome, int64_t start, int64_t stop, int32_t use_index,
+                    hello_bam_reads** out);
+int hello_bam_reads_info(const hello_bam_reads* reads, int64_t* n_reads, int32_t* used_index, int64_t* n_blocks);
+/* a pointer into `reads` (valid until hello_bam_reads_free) and its element count */
+int hello_bam_reads_array(const hello_bam_reads* reads, int32_t which, const void** data, int64_t* count);
+void hello_bam_reads_free(hello_bam_reads* reads);
+void hello_bam_close(hello_bam* bam);
+
+/* Stands in for: python/HotspotDetectorDVFiltered.py (doOneChunk / hotspotGenerator*, :31-165) over the C++ allele counter it
+ * drives (c++/src/AlleleSearcherLiteFiltered.cpp:19-100 partial resolution, :121-317 counting, :550-646 and :834-890 flagging;
+ * python/AlleleSearcherLite.py:112-190 windows).  Every region [region_starts[k], region_stops[k]) is cut into chunks of 400 bp
+ * (10 000 bp with HELLO_HOTSPOTS_PACBIO or HELLO_HOTSPOTS_TWO_BAMS) counted from its start; the result is the sorted union of the
+ * positions every chunk flags, clipped to the chunk -- the positions the reference writes as {'chromosome', 'position'} lines.
+ *   reads: the arrays of hello_bam_fetch, `source` 0 for the first BAM, 1 for the second (two BAMs: Illumina, then PacBio);
+ *          each source coordinate-sorted in file order.  Reads outside usability (unmapped, secondary, supplementary,
+ *          duplicate, improper pair, mapq 0) are filtered here, as are repeated (name hash, strand) pairs within a chunk.
+ *   reference: the chromosome's text (case kept), reference_length bytes.
+ *   options: HELLO_HOTSPOTS_TWO_BAMS (two read sets, whether or not the second has reads in the regions), HELLO_HOTSPOTS_PACBIO
+ *          (one read set of PacBio reads), HELLO_HOTSPOTS_HYBRID (--hybrid_hotspot).
+ * Counting and flagging run in one kernel launch on `device` (hotspots.hip); host memory in and out. */
+#define HELLO_HOTSPOTS_PACBIO 1
+#define HELLO_HOTSPOTS_HYBRID 2
+#define HELLO_HOTSPOTS_TWO_BAMS 4
+#define HELLO_HOTSPOTS_STATS 10
+typedef struct hello_hotspots hello_hotspots;
+int hello_hotspots_find(const uint8_t* bases, const uint8_t* quals, const int64_t* read_offsets,
+                        const uint32_t* cigars, const int64_t* cigar_offsets, const int64_t* ref_starts,
+                        const int64_t* ref_ends, const uint8_t* mapq, const uint16_t* flags, const uint64_t* name_hash,
+                        const uint8_t* source, int64_t n_reads, const uint8_t* reference, int64_t reference_length,
+                        const int64_t* region_starts, const int64_t* region_stops, int32_t n_regions, int32_t options,
+                        int32_t q_threshold, int32_t mapq_threshold, int32_t device, hello_hotspots** out);
+/* the sorted positions (valid until hello_hotspots_free) */
+int hello_hotspots_positions(const hello_hotspots* hotspots, const int64_t** positions, int64_t* n_positions);
+/* stats[HELLO_HOTSPOTS_STATS]: chunks, chunks without reads, chunks out of bounds, chunks at the read cap, reads counted
+ * (summed over chunks), tiles, events, kernel ms (HIP events), plan ms, total ms */
+int hello_hotspots_stats(const hello_hotspots* hotspots, double* stats);
+void hello_hotspots_free(hello_hotspots* hotspots);
+
 /* The engine's own stream (a hipStream_t): what a call with hip_stream == NULL runs on.  It is created
  * non-blocking, so it is NOT ordered with the legacy default stream: a caller whose other work sits on the default
  * stream (handle 0, indistinguishable from NULL here) orders the two with events on this handle -- the Python
