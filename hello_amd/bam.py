@@ -17,7 +17,7 @@ from .engine import load_library
 _ARRAYS = (  # (field, hello_bam_* selector, dtype)
     ("bases", 0, np.uint8), ("quals", 1, np.uint8), ("read_offsets", 2, np.int64), ("cigars", 3, np.uint32),
     ("cigar_offsets", 4, np.int64), ("ref_starts", 5, np.int64), ("ref_ends", 6, np.int64), ("mapq", 7, np.uint8),
-    ("flags", 8, np.uint16), ("name_hash", 9, np.uint64), ("strand", 10, np.uint8),
+    ("flags", 8, np.uint16), ("name_hash", 9, np.uint64), ("strand", 10, np.uint8), ("hp", 11, np.uint8),
 )
 
 _bound = None
@@ -61,6 +61,7 @@ class Reads:
     flags: np.ndarray          # uint16
     name_hash: np.ndarray      # uint64, FNV-1a of the read name
     strand: np.ndarray         # uint8, 1 = reverse
+    hp: np.ndarray             # uint8, the HP integer tag, 0 when absent
     used_index: bool = False
     n_blocks: int = 0
 

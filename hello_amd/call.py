@@ -228,6 +228,9 @@ def parser() -> argparse.ArgumentParser:
     ap.add_argument("--shards", required=False,
                     help="glob (or directory) of pre-extracted candidate-site shards (hello_amd.shards), one per "
                          "reference shard<N>.txt")
+    ap.add_argument("--from_bam", action="store_true", default=False,
+                    help="start from --ibam and --ref: hotspots, sharding and candidate sites run on the GPU (hello_amd.hotspots, "
+                         "hello_amd.candidates) and the shards they write under --workdir are scored; one Illumina BAM only")
     ap.add_argument("--device", type=int, default=0, help="GPU of a single-process run")
     ap.add_argument("--gpus", type=int, default=1,
                     help="processes / GPUs of this node: > 1 re-launches this command under torch.distributed.run "
@@ -291,8 +294,56 @@ def shard_read_totals(paths: Sequence[str], threads: int = 4) -> np.ndarray:
         return np.array(list(pool.map(total, paths)), np.int64)
 
 
+def shards_from_bam(args) -> str:
+    """python/call.py:111-221 up to the per-shard caller, on the GPU: per chromosome hotspots.txt in the reference's
+    ``hotspots_<chrom>_<bam>`` directory, ``shard<N>.txt`` files beside it (shardHotspots) and one ``shard<N>.hshard`` per
+    shard file in ``<workdir>/shards``.  Returns that directory."""
+    from . import candidates as cd, hotspots as hs
+    logger = logging.getLogger("hello_amd.call")
+    if args.pbam or not args.ibam or "," in args.ibam:
+        raise ValueError(cd.REFUSAL)
+    if not args.ref:
+        raise SystemExit("--from_bam needs --ref")
+    chromosomes = args.chromosomes.split(",") if args.chromosomes else None
+    genome = read_fasta(args.ref, chromosomes)
+    out_dir = os.path.join(args.workdir, "shards")
+    os.makedirs(out_dir, exist_ok=True)
+    ns = argparse.Namespace(bam=args.ibam, ref=args.ref, pacbio=False, hybrid_hotspot=False, workdir=args.workdir,
+                            chromosomes=",".join(chromosomes or list(genome)), q_threshold=cd.DEFAULT_Q_THRESHOLD,
+                            mapq_threshold=cd.DEFAULT_MIN_MAPQ, device=args.device)
+    n = 0
+    for hotspot_name in hs.run_workdir(ns):
+        positions = cd.read_positions(hotspot_name)
+        for chrom, pos in positions.items():
+            for part in cd.shard_positions(pos):
+                name = os.path.join(os.path.dirname(hotspot_name), "shard%d.txt" % n)
+                hs.write_positions(name, chrom, part)
+                _, st = cd.run_activity(args.ibam, args.ref, name, os.path.join(out_dir, "shard%d" % n), device=args.device,
+                                        genome=genome)
+                logger.info("%s: %d sites", name, st.get("sites", 0))
+                n += 1
+    if n == 0:
+        raise SystemExit("no hotspot was found: nothing to call")
+    return out_dir
+
+
 def main(args) -> str:
     logger = logging.getLogger("hello_amd.call")
+    if getattr(args, "from_bam", False) and not args.shards:
+        if "RANK" in os.environ and "WORLD_SIZE" in os.environ:
+            raise SystemExit("--from_bam under an external launcher would build the same shards in every rank: start it as a plain "
+                             "command with --gpus N, or build the shards first and pass --shards")
+        if getattr(args, "gpus", 1) > 1:
+            # the ranks must start before this process touches the GPU (_launch_ranks): the BAM stages run in a child of their own
+            import multiprocessing
+            child = multiprocessing.get_context("spawn").Process(target=shards_from_bam, args=(args,))
+            child.start()
+            child.join()
+            if child.exitcode != 0:
+                raise SystemExit(f"the BAM stages of --from_bam failed (exit status {child.exitcode})")
+            args.shards = os.path.join(args.workdir, "shards")
+        else:
+            args.shards = shards_from_bam(args)
     if not args.shards:
         raise SystemExit("--shards is required: BAM / FASTA ingestion, hotspot detection and allele assembly are upstream of "
                          "this engine (SURVEY.md section 2, rows 9-13); extract candidate-site shards with the reference's "

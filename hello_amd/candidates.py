@@ -1,0 +1,257 @@
+"""Candidate sites from hotspot positions on the GPU: the stage between ``hello_amd.hotspots`` and ``hello_amd.call``.
+
+``python -m hello_amd.candidates --bam B --ref F --activity shardN.txt --outputPrefix P`` does what the reference's
+python/caller_calling.py does up to its featurizer (:784-843) for ONE Illumina BAM, and writes ``P.hshard``
+(hello_amd/shards.py) instead of calling a network: the positions of a hotspot / shard file become active regions, their
+strict differing regions (pass 1), clusters of those, the clusters' own strict differing regions (pass 2, the sites), and per
+site the alleles the reads spell there with every allele's supporting reads.  Both passes and the allele stage run in
+``hello_candidates_find`` (hello_amd/csrc/candidates.hip); DESIGN.md "Candidate sites" states the rules.  ``shard_positions``
+is the reference's python/shardHotspots.py.  PacBio reads, two BAMs and ``--hybrid_hotspot`` are refused: they need the
+PacBio reassembly and read clipping.
+"""
+from __future__ import annotations
+
+import argparse
+import ast
+import ctypes as C
+import logging
+import math
+import os
+import sys
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from . import shards
+from .bam import BamFile, Reads
+from .engine import load_library
+
+DEFAULT_Q_THRESHOLD = 10
+DEFAULT_MIN_MAPQ = 10
+MIN_DISTANCE = 30                  # PileupDataTools.py:21
+FLANKING_BASES = 75                # :24
+N_STATS = 20
+STAT_NAMES = ("active_regions", "regions_without_reads", "regions_out_of_bounds", "regions_at_read_cap", "differing_regions_pass1",
+              "clusters", "clusters_without_reads", "clusters_out_of_bounds", "clusters_at_read_cap", "differing_regions_pass2",
+              "sites", "sites_out_of_bounds", "alleles", "reads_gathered", "record_slots", "pass1_kernel_ms", "pass2_kernel_ms",
+              "allele_kernel_ms", "gather_ms", "total_ms")
+_ARRAYS = (  # (name, hello_candidates_array selector, dtype)
+    ("start", 0, np.int64), ("stop", 1, np.int64), ("window_start", 2, np.int64), ("ref_off", 3, np.int64), ("ref", 4, np.uint8),
+    ("alleles_per_site", 5, np.int32), ("allele_text", 6, np.uint8), ("allele_text_off", 7, np.int64),
+    ("reads_per_allele0", 8, np.int32), ("bases0", 9, np.uint8), ("quals0", 10, np.uint8), ("read_off0", 11, np.int64),
+    ("cigars0", 12, np.uint32), ("cigar_off0", 13, np.int64), ("ref_start0", 14, np.int64), ("mapq0", 15, np.uint8),
+    ("orientation0", 16, np.int8), ("hp0", 17, np.uint8), ("read_index", 18, np.int64), ("regions_pass1", 19, np.int64),
+    ("regions_pass2", 20, np.int64),
+)
+REFUSAL = ("candidate sites are built from one Illumina BAM: PacBio reads, two BAMs and --hybrid_hotspot need the PacBio "
+           "reassembly and read clipping, which hello_amd does not have")
+
+_log = logging.getLogger(__name__)
+_bound = None
+
+
+def _lib():
+    global _bound
+    if _bound is None:
+        lib = load_library()
+        vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
+        lib.hello_candidates_find.argtypes = [vp] * 11 + [i64, vp, i64, vp, i64, i32, i32, i32, i32, i32, C.POINTER(vp)]
+        lib.hello_candidates_array.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(i64)]
+        lib.hello_candidates_stats.argtypes = [vp, C.POINTER(C.c_double)]
+        lib.hello_candidates_free.argtypes = [vp]
+        lib.hello_candidates_free.restype = None
+        _bound = lib
+    return _bound
+
+
+def read_positions(path: str) -> Dict[str, List[int]]:
+    """A hotspot / shard file (one ``str({'chromosome': c, 'position': p})`` line per position) -> positions per chromosome, in
+    file order."""
+    out: Dict[str, List[int]] = {}
+    with open(path) as fh:
+        for line in fh:
+            if line.strip():
+                point = ast.literal_eval(line)
+                out.setdefault(str(point['chromosome']), []).append(int(point['position']))
+    return out
+
+
+def shard_positions(positions: Sequence[int], max_shards: int = 500, min_separation: int = 25) -> List[List[int]]:
+    """python/shardHotspots.py: runs of adjacent positions are items; a shard closes once it holds ceil(items / max_shards)
+    items and the next item starts at least ``min_separation`` behind its last position."""
+    items: List[List[int]] = []
+    for p in positions:
+        if items and p - items[-1][-1] == 1:
+            items[-1].append(int(p))
+        else:
+            items.append([int(p)])
+    min_items = math.ceil(len(items) / max_shards)
+    out: List[List[int]] = []
+    cluster: List[List[int]] = []
+    for item in items:
+        if len(cluster) < min_items or item[0] - cluster[-1][-1] < min_separation:
+            cluster.append(item)
+        else:
+            out.append([p for it in cluster for p in it])
+            cluster = [item]
+    if cluster:
+        out.append([p for it in cluster for p in it])
+    return out
+
+
+def find_sites(reads: Reads, reference: str, positions: Sequence[int], chromosome: str = "chr", feature_length: int = 150,
+               q_threshold: int = DEFAULT_Q_THRESHOLD, mapq_threshold: int = DEFAULT_MIN_MAPQ, device: int = 0,
+               options: int = 0) -> Tuple[shards.PackedShard, Dict[str, float], Dict[str, np.ndarray]]:
+    """One call over already decoded reads -> (validated shard, statistics, {read_index, regions_pass1, regions_pass2})."""
+    ref = np.frombuffer(reference.encode("latin-1"), np.uint8)
+    pos = np.ascontiguousarray(positions, dtype=np.int64)
+    lib = _lib()
+    h = C.c_void_p()
+    ptr = lambda a: a.ctypes.data  # noqa: E731
+    r = reads
+    rc = lib.hello_candidates_find(ptr(r.bases), ptr(r.quals), ptr(r.read_offsets), ptr(r.cigars), ptr(r.cigar_offsets),
+                                   ptr(r.ref_starts), ptr(r.ref_ends), ptr(r.mapq), ptr(r.flags), ptr(r.name_hash), ptr(r.hp),
+                                   int(r.n_reads), ptr(ref), int(ref.shape[0]), ptr(pos), int(pos.shape[0]), int(options),
+                                   int(feature_length), int(q_threshold), int(mapq_threshold), int(device), C.byref(h))
+    if rc != 0:
+        message = lib.hello_last_error().decode(errors="replace")
+        raise (ValueError if rc == -1 else RuntimeError)(message)
+    try:
+        got = {}
+        for name, which, dtype in _ARRAYS:
+            p, n = C.c_void_p(), C.c_int64()
+            lib.hello_candidates_array(h, which, C.byref(p), C.byref(n))
+            k = int(n.value)
+            got[name] = np.zeros(0, dtype) if k == 0 else np.frombuffer(
+                (C.c_char * (k * np.dtype(dtype).itemsize)).from_address(p.value), dtype).copy()
+        st = (C.c_double * N_STATS)()
+        lib.hello_candidates_stats(h, st)
+    finally:
+        lib.hello_candidates_free(h)
+    extra = {k: got.pop(k) for k in ("read_index", "regions_pass1", "regions_pass2")}
+    n_sites = got["start"].shape[0]
+    name = np.frombuffer(chromosome.encode("ascii"), np.uint8)
+    got.update(chromosome_text=name if n_sites else np.zeros(0, np.uint8),
+               chromosome_text_off=np.array([0, name.shape[0]] if n_sites else [0], np.int64),
+               chromosome_of_site=np.zeros(n_sites, np.int32), has_second=np.array(0))
+    return shards.PackedShard(got, feature_length), dict(zip(STAT_NAMES, list(st))), extra
+
+
+def find_candidates(bam, fasta: Optional[str], chromosome: str, positions: Sequence[int], q_threshold: int = DEFAULT_Q_THRESHOLD,
+                    mapq_threshold: int = DEFAULT_MIN_MAPQ, device: int = 0, feature_length: int = 150, pacbio: bool = False,
+                    hybrid_hotspot: bool = False, reference: Optional[str] = None,
+                    stats: Optional[dict] = None) -> shards.PackedShard:
+    """The candidate sites of the sorted hotspot ``positions`` of ``chromosome`` as a validated ``PackedShard``: sites, alleles
+    (reference allele first, then ascending byte order) and every allele's supporting reads (file order).  ``bam``: one path
+    (a list of two, ``pacbio`` and ``hybrid_hotspot`` are refused).  ``stats``: filled with the statistics of the call."""
+    paths = [bam] if isinstance(bam, str) else list(bam)
+    if len(paths) != 1 or pacbio or hybrid_hotspot:
+        raise ValueError(REFUSAL)
+    if reference is None:
+        from .hotspots import _read_reference
+        reference = _read_reference(fasta, chromosome)
+    positions = np.asarray(positions, np.int64)
+    if positions.shape[0] == 0:
+        lo = hi = 0
+    else:       # pass 1 fetches [start - 75, stop + 75) around [first - 15, last + 15]
+        lo = max(0, int(positions.min()) - MIN_DISTANCE // 2 - FLANKING_BASES)
+        hi = int(positions.max()) + MIN_DISTANCE // 2 + FLANKING_BASES
+    with BamFile(paths[0]) as b:
+        reads = b.fetch(chromosome, lo, max(hi, lo))
+    shard, st, extra = find_sites(reads, reference, positions, chromosome, feature_length, q_threshold, mapq_threshold, device)
+    if stats is not None:
+        stats.update(st)
+        stats.update(extra)
+    return shard
+
+
+def write_packed(path: str, shard: shards.PackedShard) -> str:
+    """A ``PackedShard`` as a ``.hshard`` file, array for array."""
+    return shards.write_flat(path, {k: np.asarray(v) for k, v in shard.z.items()})
+
+
+def concat_payloads(parts: Sequence[shards.PackedShard]) -> dict:
+    """The arrays of several single-chromosome shards as one shard's arrays (a shard file may span chromosomes)."""
+    def cat(name):
+        return np.concatenate([np.asarray(p.z[name]) for p in parts])
+
+    def offsets(name):
+        out, base = [np.zeros(1, np.int64)], 0
+        for p in parts:
+            o = np.asarray(p.z[name], np.int64)
+            out.append(o[1:] + base)
+            base += int(o[-1])
+        return np.concatenate(out)
+    names = [p.chromosome_names[0] for p in parts if p.n_sites]
+    out = {k: cat(k) for k in ("start", "stop", "window_start", "ref", "alleles_per_site", "allele_text", "reads_per_allele0", "bases0",
+                               "quals0", "cigars0", "ref_start0", "mapq0", "orientation0", "hp0")}
+    for k in ("ref_off", "allele_text_off", "read_off0", "cigar_off0"):
+        out[k] = offsets(k)
+    out["chromosome_text"], out["chromosome_text_off"] = shards.text_table(np.array(names, dtype="U")) if names else (
+        np.zeros(0, np.uint8), np.zeros(1, np.int64))
+    out["chromosome_of_site"] = np.concatenate([np.full(p.n_sites, i, np.int32) for i, p in enumerate(q for q in parts if q.n_sites)]
+                                               + [np.zeros(0, np.int32)])
+    out["has_second"] = np.array(0)
+    return out
+
+
+def parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(description="Candidate sites of a hotspot shard on the GPU (caller_calling.py's flags where they apply)")
+    p.add_argument("--bam", required=True, help="The Illumina BAM file (one file)")
+    p.add_argument("--ref", required=True, help="Reference FASTA")
+    p.add_argument("--activity", required=True, help="Hotspot / shard file: one {'chromosome', 'position'} line per position")
+    p.add_argument("--outputPrefix", required=True, help="The shard is written to <outputPrefix>.hshard")
+    p.add_argument("--featureLength", type=int, default=150, help="Length of the feature window")
+    p.add_argument("--q_threshold", type=int, default=DEFAULT_Q_THRESHOLD, help="Quality score threshold")
+    p.add_argument("--mapq_threshold", type=int, default=DEFAULT_MIN_MAPQ, help="Mapping quality threshold")
+    p.add_argument("--include_hp", action="store_true", default=False, help="Accepted for the reference's command line: the reads' HP tags are always stored; the scoring "
+                        "driver's --include_hp decides whether they are used")
+    p.add_argument("--pacbio", action="store_true", default=False, help="Refused: PacBio reads need reassembly and clipping")
+    p.add_argument("--hybrid_hotspot", action="store_true", default=False, help="Refused: needs two BAMs")
+    p.add_argument("--debug", action="store_true", default=False, help="Display debug messages")
+    p.add_argument("--device", type=int, default=0, help="GPU index")
+    return p
+
+
+def run_activity(bam: str, fasta: str, activity: str, output_prefix: str, feature_length: int = 150,
+                 q_threshold: int = DEFAULT_Q_THRESHOLD, mapq_threshold: int = DEFAULT_MIN_MAPQ, device: int = 0, genome: Optional[Dict[str, str]] = None) -> Tuple[str, Dict[str, float]]:
+    """One activity file -> ``<output_prefix>.hshard`` and the summed statistics."""
+    from .call import read_fasta
+    by_chromosome = read_positions(activity)
+    if genome is None:
+        genome = read_fasta(fasta, list(by_chromosome))
+    parts, total = [], {}
+    for chromosome, positions in by_chromosome.items():
+        if chromosome not in genome:
+            raise ValueError(f"{fasta}: no sequence named {chromosome!r}")
+        st: dict = {}
+        shard = find_candidates(bam, fasta, chromosome, positions, q_threshold, mapq_threshold, device, feature_length,
+                                reference=genome[chromosome], stats=st)
+        for k in STAT_NAMES:
+            total[k] = total.get(k, 0.0) + st[k]
+        parts.append(shard)
+    path = output_prefix + ".hshard"
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    shards.write_flat(path, concat_payloads(parts))
+    return path, total
+
+
+def main(argv=None) -> str:
+    args = parser().parse_args(argv)
+    logging.basicConfig(level=logging.DEBUG if args.debug else logging.INFO, format="%(asctime)-15s %(message)s")
+    if args.pacbio or args.hybrid_hotspot or len(args.bam.split(",")) != 1:
+        raise ValueError(REFUSAL)
+    logging.info("Started script")
+    path, st = run_activity(args.bam, args.ref, args.activity, args.outputPrefix, args.featureLength, args.q_threshold,
+                            args.mapq_threshold, args.device)
+    logging.info("%d active regions -> %d sites, %d alleles, %d reads in %s", st.get("active_regions", 0), st.get("sites", 0),
+                 st.get("alleles", 0), st.get("reads_gathered", 0), path)
+    for key in ("regions_at_read_cap", "clusters_at_read_cap"):
+        if st.get(key):
+            logging.warning("%d %s: their first reads in file order were kept", st[key], key.replace("_", " "))
+    logging.info("Completed running the script")
+    return path
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])

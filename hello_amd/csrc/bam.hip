@@ -38,7 +38,7 @@ struct hello_bam_reads {
     std::vector<uint8_t> bases, quals;
     std::vector<int64_t> read_off{0}, cigar_off{0}, ref_start, ref_end;
     std::vector<uint32_t> cigars;
-    std::vector<uint8_t> mapq, strand;
+    std::vector<uint8_t> mapq, strand, hp;
     std::vector<uint16_t> flag;
     std::vector<uint64_t> name_hash;
     int32_t used_index = 0;
@@ -281,6 +281,52 @@ const uint8_t* find_cg_tag(const uint8_t* aux, const uint8_t* end, uint32_t* cou
     return nullptr;
 }
 
+// The HP tag (haplotype of a phased read) as an integer of any BAM integer type; 0 when the record has none, when its value does
+// not fit a byte, or when the auxiliary fields cannot be walked (they are nobody else's concern: no error).
+uint8_t find_hp_tag(const uint8_t* aux, const uint8_t* end) {
+    auto scalar = [](uint8_t t) -> int {
+        switch (t) {
+            case 'A': case 'c': case 'C': return 1;
+            case 's': case 'S': return 2;
+            case 'i': case 'I': case 'f': return 4;
+            default: return 0;
+        }
+    };
+    while (end - aux >= 3) {
+        const uint8_t t0 = aux[0], t1 = aux[1], type = aux[2];
+        aux += 3;
+        if (type == 'Z' || type == 'H') {
+            const uint8_t* z = (const uint8_t*)memchr(aux, 0, (size_t)(end - aux));
+            if (!z) return 0;
+            aux = z + 1;
+        } else if (type == 'B') {
+            if (end - aux < 5) return 0;
+            const int w = scalar(aux[0]);
+            const uint32_t n = rd32(aux + 1);
+            if (!w || (uint64_t)n * w > (uint64_t)(end - aux - 5)) return 0;
+            aux += 5 + (size_t)n * w;
+        } else {
+            const int w = scalar(type);
+            if (!w || end - aux < w) return 0;
+            if (t0 == 'H' && t1 == 'P') {
+                int64_t v;
+                switch (type) {
+                    case 'c': v = (int8_t)aux[0]; break;
+                    case 'C': v = aux[0]; break;
+                    case 's': v = (int16_t)rd16(aux); break;
+                    case 'S': v = rd16(aux); break;
+                    case 'i': v = (int32_t)rd32(aux); break;
+                    case 'I': v = rd32(aux); break;
+                    default: return 0;
+                }
+                return (v >= 0 && v <= 255) ? (uint8_t)v : 0;
+            }
+            aux += w;
+        }
+    }
+    return 0;
+}
+
 // append one record (the bytes after its block_size field) to the flat arrays
 void decode(hello_bam_reads* r, const uint8_t* b, int32_t block_size, const std::string& path) {
     const int32_t pos = (int32_t)rd32(b + 4);
@@ -323,6 +369,7 @@ void decode(hello_bam_reads* r, const uint8_t* b, int32_t block_size, const std:
     r->flag.push_back((uint16_t)flag);
     r->strand.push_back((flag & 16) ? 1 : 0);
     r->name_hash.push_back(fnv1a(name, l_name > 0 ? (size_t)l_name - 1 : 0));
+    r->hp.push_back(find_hp_tag(b + need, b + block_size));
 }
 
 }  // namespace
@@ -463,6 +510,7 @@ int hello_bam_reads_array(const hello_bam_reads* r, int32_t which, const void** 
         case HELLO_BAM_FLAGS: *data = r->flag.data(); *count = (int64_t)r->flag.size(); break;
         case HELLO_BAM_NAME_HASH: *data = r->name_hash.data(); *count = (int64_t)r->name_hash.size(); break;
         case HELLO_BAM_STRAND: *data = r->strand.data(); *count = (int64_t)r->strand.size(); break;
+        case HELLO_BAM_HP: *data = r->hp.data(); *count = (int64_t)r->hp.size(); break;
         default: return set_last_error(HELLO_ERR_ARG, "no read array %d", which);
     }
     return HELLO_OK;

@@ -1,0 +1,783 @@
+// Candidate sites from hotspot positions (include/hello_mi355x.h: hello_candidates_find): the stage between the hotspot detector
+// and the scoring engine, for one Illumina BAM.
+//
+// Reference semantics: python/PileupDataTools.py:207-244 (positions -> active regions), :129-158 (the read cap), :302-384 (pass 1:
+// one strict searcher per active region), python/trainDataTools.py:477-514 (clusterLocations), :1039-1103 (pass 2: one strict
+// searcher per cluster, its own differing regions are the sites), :557-640 and :880-977 (alleles of a site, unsupported and long
+// ones dropped), c++/src/Read.cpp:4-172 (a read's allele in a region), c++/src/AlleleSearcherLiteFiltered.cpp:495-547 (strict
+// runs), :648-666,740-831 (supports and partials).  DESIGN.md "Candidate sites" restates the rules and the defined orders.
+//
+// Host: the plan of both passes (read lists with the filters, de-duplication and cap of the hotspot stage, window bounds, tiles
+// and exact event capacities over [start - 102, stop]), the clustering between the passes, exact record slots (reads x the
+// regions they overlap) and the gather of every allele's reads into the flat arrays of a shard.  Device: the differing-position
+// kernel of differing.h for both passes (flags kept on [start - 1, stop] so that the strict rule can be applied), then one
+// workgroup per pass-2 cluster for the alleles: a wave per read, a lane per region the read overlaps, one CIGAR walk each ->
+// (status, read substring, min_q, hash); the workgroup groups the Success records of a region by string (hash, then bytes),
+// resolves the reads' partials against the distinct strings and writes, per region, the alleles in the defined order (reference
+// allele, then ascending bytes) with their supporting reads in file order.  Everything is integer and ordered by index, so two
+// runs give the same bytes.  Records live in global memory (a cluster's few kilobytes stay in L2); nothing is truncated.
+#include <algorithm>
+#include <chrono>
+#include <memory>
+#include <thread>
+#include <unordered_set>
+#include <vector>
+
+#include <hip/hip_runtime.h>
+
+#include "../../include/hello_mi355x.h"
+#include "differing.h"
+
+namespace hello {
+int set_last_error(int code, const char* fmt, ...);      // engine.hip
+int exception_status(const char* where) noexcept;         // engine.hip
+}  // namespace hello
+
+struct hello_candidates {
+    std::vector<int64_t> start, stop, window_start, ref_off{0}, allele_text_off{0}, read_off{0}, cigar_off{0}, ref_start, read_index;
+    std::vector<int64_t> regions1, regions2;         // (start, stop) pairs: the differing regions of pass 1 and of pass 2
+    std::vector<uint8_t> ref, allele_text, bases, quals, mapq, hp;
+    std::vector<int32_t> alleles_per_site, reads_per_allele;
+    std::vector<uint32_t> cigars;
+    std::vector<int8_t> orientation;
+    double stats[HELLO_CANDIDATES_STATS] = {0};
+};
+
+namespace hello {
+namespace {
+
+constexpr int kSuccess = 0, kLeftPartial = 1, kRightPartial = 2, kFailed = 3;     // AlignedBaseStatus (Read.h)
+constexpr int kMaxAlleleLength = 80;                                              // trainDataTools.createTensors
+constexpr int kReach = 102;      // an indel of at most 100 bases planted at p flags up to p + 101: tiles start this far left
+
+struct AlleleArgs {
+    const uint8_t* bases;
+    const uint8_t* quals;
+    const int64_t* read_off;
+    const uint32_t* cigars;
+    const int64_t* cigar_off;
+    const int64_t* ref_start;
+    const uint8_t* mapq;
+    const int64_t* last_pos;          // per read: last M/D position, -1 without one
+    const uint8_t* pflags;            // per read: 1 partial_start, 2 partial_stop (Read.cpp:42-49)
+    const int64_t* cl_read_off;       // [clusters + 1] into cl_reads
+    const int64_t* cl_reads;          // read of every cluster read x
+    const int64_t* cl_reg_off;        // [clusters + 1] regions g of a cluster
+    const int64_t* reg_start;
+    const int64_t* reg_stop;
+    const int64_t* rd_rec_off;        // [cluster reads + 1] first record slot of cluster read x; its slots are consecutive regions
+    const int64_t* slot_g;            // region of slot s
+    const int64_t* slot_x;            // cluster read of slot s
+    const int64_t* reg_list_off;      // [regions + 1] into reg_list: the slots of a region, ascending cluster read
+    const int64_t* reg_list;
+    const uint8_t* ref;               // the chromosome
+    int64_t ref_len;
+    // records
+    int32_t* status;
+    int32_t* q0;                      // allele = bases[read_off[r] + q0, + len)
+    int32_t* len;
+    int32_t* minq;
+    uint64_t* hash;
+    int32_t* pass;                    // Success with mapq and min_q at their thresholds
+    int64_t* first;                   // passing records: the first slot of the region with the same string; else -1
+    int64_t* target;                  // the read's chosen partial: the one matching distinct string's slot; else -1
+    // output, per region at reg_list_off[g]
+    int32_t* n_alleles;               // [regions]
+    int64_t* al_rep;                  // slot holding the allele's string
+    int32_t* al_count;                // supporting reads
+    int64_t* sup;                     // supporting reads (input read index), allele after allele
+    int q_threshold, mapq_threshold;
+};
+
+__device__ void walk_read(const AlleleArgs& a, int64_t r, int64_t s, int64_t e, int64_t slot) {
+    // Read::get_aligned_bases(s, e) (Read.cpp:79-137) over the map of Read::_get_read_mapping (:4-77), without building the map
+    const int64_t rs = a.ref_start[r], last = a.last_pos[r];
+    int status = kFailed, len = 0, minq = 10000;
+    int64_t q0 = -1, q1 = -1;
+    uint64_t h = 1469598103934665603ull;
+    if (last >= 0 && s <= last && rs < e) {                                       // :88
+        bool has_s = false, has_sm1 = false, has_em1 = false, has_e = false, emp_s = false, emp_em1 = false, del = false;
+        auto mark = [&](int64_t p0, int64_t p1, bool empty) {                     // positions [p0, p1) hold an entry
+            if (p0 <= s && s < p1) { has_s = true; emp_s = empty; }
+            if (p0 <= s - 1 && s - 1 < p1) has_sm1 = true;
+            if (p0 <= e - 1 && e - 1 < p1) { has_em1 = true; emp_em1 = empty; }
+            if (p0 <= e && e < p1) has_e = true;
+        };
+        auto take = [&](int64_t b0, int64_t b1) { if (q0 < 0) q0 = b0; q1 = b1; };
+        const int64_t c0 = a.cigar_off[r], n_ops = a.cigar_off[r + 1] - c0;
+        int64_t rf = rs, rd = 0;
+        for (int64_t ci = 0; ci < n_ops && rf <= e + 1; ++ci) {                   // an entry at e needs rf - 1 <= e
+            const unsigned c = a.cigars[c0 + ci];
+            const int op = c & 15u;
+            const int64_t n = c >> 4;
+            if (op == 0 || op == 7 || op == 8) {
+                mark(rf, rf + n, false);
+                const int64_t lo = rf > s ? rf : s, hi = rf + n < e ? rf + n : e;
+                if (lo < hi) take(rd + lo - rf, rd + hi - rf);
+                rf += n; rd += n;
+            } else if (op == 2) {
+                mark(rf, rf + n, true);
+                if ((rf > s ? rf : s) < (rf + n < e ? rf + n : e)) del = true;
+                rf += n;
+            } else if (op == 3) {
+                rf += n;
+            } else if (op == 1) {                                                 // joins (or creates) the entry at rf - 1
+                mark(rf - 1, rf, false);
+                if (s <= rf - 1 && rf - 1 < e) take(rd, rd + n);
+                rd += n;
+            } else if (op == 4) {
+                rd += n;
+            }
+        }
+        const int pf = a.pflags[r];
+        if (!has_s) status = kLeftPartial;                                        // :94-104
+        else if (!has_sm1) status = (pf & 1) ? kLeftPartial : kSuccess;
+        else if (!has_em1) status = kRightPartial;
+        else if (!has_e) status = (pf & 2) ? kRightPartial : kSuccess;
+        else status = kSuccess;
+        if ((has_s && emp_s) || (has_em1 && emp_em1)) status = kFailed;          // :107-117
+        if (q0 < 0) q0 = q1 = 0;
+        len = (int)(q1 - q0);
+        const int64_t off = a.read_off[r] + q0;
+        int m = del ? 60 : 10000;
+        for (int i = 0; i < len; ++i) {
+            const int q = a.quals[off + i];
+            m = q < m ? q : m;
+            h = (h ^ a.bases[off + i]) * 1099511628211ull;
+        }
+        minq = m;
+    }
+    a.status[slot] = status;
+    a.q0[slot] = (int32_t)(q0 < 0 ? 0 : q0);
+    a.len[slot] = len;
+    a.minq[slot] = minq;
+    a.hash[slot] = h;
+    a.pass[slot] = (status == kSuccess && a.mapq[r] >= a.mapq_threshold && minq >= a.q_threshold) ? 1 : 0;   // :766
+    a.first[slot] = -1;
+    a.target[slot] = -1;
+}
+
+__global__ __launch_bounds__(256) void allele_kernel(AlleleArgs a) {
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int64_t c = blockIdx.x;
+    const int64_t x0 = a.cl_read_off[c], x1 = a.cl_read_off[c + 1];
+    const int64_t g0 = a.cl_reg_off[c], g1 = a.cl_reg_off[c + 1];
+    const int64_t s0 = a.rd_rec_off[x0], s1 = a.rd_rec_off[x1];
+    auto text = [&](int64_t slot) { return a.bases + a.read_off[a.cl_reads[a.slot_x[slot]]] + a.q0[slot]; };
+
+    // ---- records: Read::extract_alleles (Read.cpp:139-172), a wave per read, a lane per region the read overlaps
+    for (int64_t x = x0 + wave; x < x1; x += 4) {
+        const int64_t r = a.cl_reads[x];
+        for (int64_t slot = a.rd_rec_off[x] + lane; slot < a.rd_rec_off[x + 1]; slot += 64) {
+            const int64_t g = a.slot_g[slot];
+            walk_read(a, r, a.reg_start[g], a.reg_stop[g], slot);
+        }
+    }
+    __syncthreads();
+
+    // ---- the distinct supported strings of every region (AlleleSearcherLiteFiltered.cpp:764-775): hash, then bytes
+    for (int64_t slot = s0 + tid; slot < s1; slot += 256) {
+        if (!a.pass[slot]) continue;
+        const int64_t g = a.slot_g[slot];
+        const int n = a.len[slot];
+        const uint64_t h = a.hash[slot];
+        const uint8_t* mine = text(slot);
+        int64_t found = slot;
+        for (int64_t i = a.reg_list_off[g]; i < a.reg_list_off[g + 1]; ++i) {
+            const int64_t o = a.reg_list[i];
+            if (o >= slot) break;
+            if (!a.pass[o] || a.hash[o] != h || a.len[o] != n) continue;
+            const uint8_t* other = text(o);
+            bool eq = true;
+            for (int k = 0; k < n && eq; ++k) eq = other[k] == mine[k];
+            if (eq) { found = o; break; }
+        }
+        a.first[slot] = found;
+    }
+    __syncthreads();
+
+    // ---- partials (:812-831): a read's last left partial, else its last right partial, against the distinct strings of its region
+    for (int64_t x = x0 + tid; x < x1; x += 256) {
+        int64_t chosen = -1;
+        for (int64_t slot = a.rd_rec_off[x + 1] - 1; slot >= a.rd_rec_off[x]; --slot)
+            if (a.status[slot] == kLeftPartial) { chosen = slot; break; }
+        if (chosen < 0)
+            for (int64_t slot = a.rd_rec_off[x + 1] - 1; slot >= a.rd_rec_off[x]; --slot)
+                if (a.status[slot] == kRightPartial) { chosen = slot; break; }
+        if (chosen < 0) continue;
+        const bool left = a.status[chosen] == kLeftPartial;
+        const int64_t g = a.slot_g[chosen];
+        const int n = a.len[chosen];
+        const uint8_t* mine = text(chosen);
+        int matches = 0;
+        int64_t hit = -1;
+        for (int64_t i = a.reg_list_off[g]; i < a.reg_list_off[g + 1] && matches < 2; ++i) {
+            const int64_t o = a.reg_list[i];
+            if (a.first[o] != o || a.len[o] < n) continue;
+            const uint8_t* other = text(o) + (left ? a.len[o] - n : 0);
+            bool eq = true;
+            for (int k = 0; k < n && eq; ++k) eq = other[k] == mine[k];
+            if (eq) { ++matches; hit = o; }
+        }
+        if (matches == 1) a.target[chosen] = hit;
+    }
+    __syncthreads();
+
+    // ---- per region: the reference allele if supported, then the supported strings without N in ascending byte order, none
+    // longer than kMaxAlleleLength; every allele's reads in ascending index (trainDataTools.py:612-635,924-946)
+    for (int64_t g = g0 + tid; g < g1; g += 256) {
+        const int64_t l0 = a.reg_list_off[g], l1 = a.reg_list_off[g + 1];
+        const int64_t s = a.reg_start[g], e = a.reg_stop[g];
+        int n_out = 0;
+        int64_t n_sup = 0;
+        auto emit = [&](int64_t rep) {
+            int count = 0;
+            for (int64_t i = l0; i < l1; ++i) {
+                const int64_t o = a.reg_list[i];
+                if ((a.pass[o] && a.first[o] == rep) || a.target[o] == rep) {
+                    a.sup[l0 + n_sup++] = a.cl_reads[a.slot_x[o]];
+                    ++count;
+                }
+            }
+            a.al_rep[l0 + n_out] = rep;
+            a.al_count[l0 + n_out] = count;
+            ++n_out;
+        };
+        auto is_ref = [&](int64_t o) {
+            if (a.len[o] != e - s || e > a.ref_len) return false;
+            const uint8_t* t = text(o);
+            for (int64_t k = 0; k < e - s; ++k)
+                if (t[k] != a.ref[s + k]) return false;
+            return true;
+        };
+        auto less = [&](int64_t x, int64_t y) {                      // bytes of x < bytes of y
+            const uint8_t* tx = text(x);
+            const uint8_t* ty = text(y);
+            const int nx = a.len[x], ny = a.len[y], n = nx < ny ? nx : ny;
+            for (int k = 0; k < n; ++k)
+                if (tx[k] != ty[k]) return tx[k] < ty[k];
+            return nx < ny;
+        };
+        int64_t ref_rep = -1;
+        for (int64_t i = l0; i < l1 && ref_rep < 0; ++i) {
+            const int64_t o = a.reg_list[i];
+            if (a.first[o] == o && is_ref(o)) ref_rep = o;
+        }
+        if (ref_rep >= 0 && e - s <= kMaxAlleleLength) emit(ref_rep);
+        int64_t prev = -1;
+        for (;;) {                                                    // the smallest string above the previous one
+            int64_t best = -1;
+            for (int64_t i = l0; i < l1; ++i) {
+                const int64_t o = a.reg_list[i];
+                if (a.first[o] != o || o == ref_rep || a.len[o] > kMaxAlleleLength) continue;
+                if (prev >= 0 && !less(prev, o)) continue;
+                if (best >= 0 && !less(o, best)) continue;
+                bool has_n = false;
+                const uint8_t* t = text(o);
+                for (int k = 0; k < a.len[o] && !has_n; ++k) has_n = t[k] == 'N';
+                if (!has_n) best = o;
+            }
+            if (best < 0) break;
+            emit(best);
+            prev = best;
+        }
+        a.n_alleles[g] = n_out;
+    }
+}
+
+struct KernelTimer {               // HIP events around a launch on the default stream; destroyed on every path
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    KernelTimer() = default;
+    void start() {
+        HS_HIP(hipEventCreate(&e0));
+        HS_HIP(hipEventCreate(&e1));
+        HS_HIP(hipEventRecord(e0, 0));
+    }
+    float stop() {
+        float ms = 0.0f;
+        HS_HIP(hipEventRecord(e1, 0));
+        HS_HIP(hipEventSynchronize(e1));
+        HS_HIP(hipEventElapsedTime(&ms, e0, e1));
+        return ms;
+    }
+    ~KernelTimer() {
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    }
+    KernelTimer(const KernelTimer&) = delete;
+    KernelTimer& operator=(const KernelTimer&) = delete;
+};
+
+struct ReadsIn {
+    const uint8_t* bases; const uint8_t* quals; const int64_t* read_off; const uint32_t* cigars; const int64_t* cigar_off;
+    const int64_t* ref_start; const int64_t* ref_end; const uint8_t* mapq; const uint16_t* flags; const uint64_t* name_hash;
+    int64_t n;
+};
+
+struct Job {                       // one searcher: an active region (pass 1) or a cluster (pass 2)
+    int64_t start, stop;           // the searcher's region
+    int64_t fetch_lo, fetch_hi;    // the reads fetched for it
+    std::vector<int64_t> reads;    // kept reads, file order
+    std::vector<std::pair<int64_t, int64_t>> regions;   // strict differing regions
+    bool run = false;
+};
+
+struct JobStats { int64_t empty = 0, bounds = 0, capped = 0, counted = 0, tiles = 0, events = 0; float ms = 0; };
+
+// The reads, window and differing regions of every job (AlleleSearcherLite.__init__ + determineDifferingRegions(strict = True)).
+void differing_regions(std::vector<Job>& jobs, const ReadsIn& in, int64_t max_span, const std::vector<int64_t>& plant_off,
+                       const std::vector<int64_t>& plant, int64_t reference_length, int mapq_threshold, HotspotArgs a, JobStats& st) {
+    std::vector<int64_t> flo, fhi, bit_base, creads_off{0}, creads, tile_lo, tile_ev_off{0};
+    std::vector<int32_t> tile_chunk, chunk_job;
+    std::unordered_set<std::pair<uint64_t, int>, PairHash> seen;
+    int64_t bits = 0;
+    for (size_t j = 0; j < jobs.size(); ++j) {
+        Job& job = jobs[j];
+        const int64_t span = job.fetch_hi - job.fetch_lo;
+        const double cap = span > 30 ? 1000.0 / 30.0 * (double)span : 1000.0;      // PileupDataTools.py:139-146
+        bool capped = false;
+        seen.clear();
+        const int64_t* begin = in.ref_start;
+        const int64_t* it = std::lower_bound(begin, begin + in.n, job.fetch_lo - max_span);
+        for (int64_t r = it - begin; r < in.n && in.ref_start[r] < job.fetch_hi; ++r) {
+            if (in.ref_end[r] <= job.fetch_lo || !usable(in.flags[r], in.mapq[r])) continue;
+            if (!seen.insert({in.name_hash[r], (in.flags[r] & 16) ? 1 : 0}).second) continue;
+            if (!((double)job.reads.size() < cap)) { capped = true; continue; }
+            job.reads.push_back(r);
+        }
+        if (job.reads.empty()) { ++st.empty; continue; }
+        int64_t ws = job.start, we = INT64_MIN;                                      // AlleleSearcherLite.py:135-151
+        for (int64_t r : job.reads) { ws = std::min(ws, in.ref_start[r]); we = std::max(we, in.ref_end[r]); }
+        ws -= 10;
+        if (ws < 0 || we > reference_length) { ++st.bounds; job.reads.clear(); continue; }
+        st.capped += capped;                                                         // counted for searchers that run
+        job.run = true;
+        const int32_t chunk = (int32_t)flo.size();
+        chunk_job.push_back((int32_t)j);
+        flo.push_back(job.start - 1);                                                // the strict rule looks at start - 1 and at stop
+        fhi.push_back(job.stop + 1);
+        bit_base.push_back(bits);
+        bits += job.stop - job.start + 2;
+        int64_t lo0 = INT64_MAX, hi0 = INT64_MIN;
+        const size_t first = creads.size();
+        for (int64_t r : job.reads)
+            if (in.mapq[r] >= mapq_threshold) {
+                creads.push_back(r);
+                lo0 = std::min(lo0, in.ref_start[r] - 1);
+                hi0 = std::max(hi0, in.ref_end[r]);
+            }
+        creads_off.push_back((int64_t)creads.size());
+        lo0 = std::max(lo0, job.start - kReach);
+        hi0 = std::min(hi0, job.stop + 1);
+        if (creads.size() == first || lo0 >= hi0) continue;
+        const int64_t nt = (hi0 - lo0 + kTile - 1) / kTile;
+        std::vector<int64_t> capacity(nt, 0);
+        for (size_t k = first; k < creads.size(); ++k) {
+            const int64_t r = creads[k];
+            for (int64_t i = plant_off[r]; i < plant_off[r + 1]; ++i)
+                if (plant[i] >= lo0 && plant[i] < lo0 + nt * kTile) ++capacity[(plant[i] - lo0) / kTile];
+        }
+        for (int64_t t = 0; t < nt; ++t) {
+            tile_chunk.push_back(chunk);
+            tile_lo.push_back(lo0 + t * kTile);
+            tile_ev_off.push_back(tile_ev_off.back() + capacity[t]);
+        }
+    }
+    st.counted = (int64_t)creads.size();
+    st.tiles = (int64_t)tile_lo.size();
+    st.events = tile_ev_off.back();
+    if (tile_lo.empty()) return;
+    DevMem m;
+    a.chunk_reads = m.put(creads.data(), creads.size());
+    a.chunk_reads_off = m.put(creads_off.data(), creads_off.size());
+    a.flag_lo = m.put(flo.data(), flo.size());
+    a.flag_hi = m.put(fhi.data(), fhi.size());
+    a.bit_base = m.put(bit_base.data(), bit_base.size());
+    a.tile_chunk = m.put(tile_chunk.data(), tile_chunk.size());
+    a.tile_lo = m.put(tile_lo.data(), tile_lo.size());
+    a.tile_ev_off = m.put(tile_ev_off.data(), tile_ev_off.size());
+    a.events = m.zeros<HsEvent>((size_t)tile_ev_off.back());
+    const int64_t words = (bits + 31) / 32;
+    a.bitmap = m.zeros<unsigned>((size_t)words);
+    {
+        KernelTimer timer;
+        timer.start();
+        hipLaunchKernelGGL(hotspot_kernel, dim3((unsigned)tile_lo.size()), dim3(256), 0, 0, a);
+        HS_HIP(hipGetLastError());
+        st.ms = timer.stop();
+    }
+    std::vector<unsigned> bitsv((size_t)words);
+    HS_HIP(hipMemcpy(bitsv.data(), a.bitmap, bitsv.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
+    auto bit = [&](int64_t i) { return (bitsv[i >> 5] >> (i & 31)) & 1u; };
+    for (size_t c = 0; c < chunk_job.size(); ++c) {            // cluster_differing_regions_helper + pushRegions(strict) (:495-547)
+        Job& job = jobs[chunk_job[c]];
+        const int64_t n = job.stop - job.start + 2;
+        for (int64_t i = 0; i < n;) {
+            if (!bit(bit_base[c] + i)) { ++i; continue; }
+            int64_t k = i;
+            while (k + 1 < n && bit(bit_base[c] + k + 1)) ++k;
+            const int64_t first = job.start - 1 + i, last = job.start - 1 + k;
+            if (!(first < job.start || last + 1 > job.stop)) job.regions.push_back({first, last + 1});
+            i = k + 1;
+        }
+    }
+}
+
+}  // namespace
+}  // namespace hello
+
+extern "C" {
+
+int hello_candidates_find(const uint8_t* bases, const uint8_t* quals, const int64_t* read_offsets, const uint32_t* cigars,
+                          const int64_t* cigar_offsets, const int64_t* ref_starts, const int64_t* ref_ends, const uint8_t* mapq,
+                          const uint16_t* flags, const uint64_t* name_hash, const uint8_t* hp, int64_t n_reads,
+                          const uint8_t* reference, int64_t reference_length, const int64_t* positions, int64_t n_positions,
+                          int32_t options, int32_t feature_length, int32_t q_threshold, int32_t mapq_threshold, int32_t device,
+                          hello_candidates** out) try {
+    using namespace hello;
+    using clock = std::chrono::steady_clock;
+    const auto t0 = clock::now();
+    if (!out || !read_offsets || !cigar_offsets || (n_reads > 0 && (!bases || !quals || !cigars || !ref_starts || !ref_ends ||
+        !mapq || !flags || !name_hash || !hp)) || !reference || (n_positions > 0 && !positions))
+        return set_last_error(HELLO_ERR_ARG, "NULL pointer");
+    *out = nullptr;
+    if (n_reads < 0 || n_positions < 0 || reference_length < 0 || feature_length <= 0)
+        return set_last_error(HELLO_ERR_ARG, "negative count");
+    if (options & (HELLO_HOTSPOTS_PACBIO | HELLO_HOTSPOTS_TWO_BAMS | HELLO_HOTSPOTS_HYBRID))
+        return set_last_error(HELLO_ERR_ARG, "candidate sites are built from one Illumina BAM: PacBio reads, two BAMs and hybrid "
+                                             "hotspots need the PacBio reassembly and read clipping, which this library does not have");
+    if (options) return set_last_error(HELLO_ERR_ARG, "options %d", options);
+    for (int64_t i = 1; i < n_positions; ++i)
+        if (positions[i] < positions[i - 1]) return set_last_error(HELLO_ERR_ARG, "position %lld: positions are not sorted", (long long)i);
+
+    // ---- validation of every usable read (the kernels read within its bases), its planting positions, and what
+    // Read::_get_read_mapping knows about it as a whole: last_position, partial_start, partial_stop
+    int64_t max_span = 0;
+    std::vector<int64_t> plant_off(n_reads + 1, 0), plant, last_pos(n_reads, -1);
+    std::vector<uint8_t> pflags(n_reads, 0);
+    for (int64_t r = 0; r < n_reads; ++r) {
+        plant_off[r + 1] = plant_off[r];
+        if (r > 0 && ref_starts[r] < ref_starts[r - 1])
+            return set_last_error(HELLO_ERR_ARG, "read %lld: reads are not coordinate-sorted (the BAM must be)", (long long)r);
+        if (read_offsets[r + 1] < read_offsets[r] || cigar_offsets[r + 1] < cigar_offsets[r])
+            return set_last_error(HELLO_ERR_SHAPE, "read %lld: offsets decrease", (long long)r);
+        if (!usable(flags[r], mapq[r])) continue;
+        int64_t qlen = 0, rlen = 0;
+        const int64_t c0 = cigar_offsets[r], c1 = cigar_offsets[r + 1];
+        bool prev = false, aligned = false;
+        for (int64_t c = c0; c < c1; ++c) {
+            const int op = cigars[c] & 15;
+            const int64_t len = cigars[c] >> 4;
+            if (op > 8) return set_last_error(HELLO_ERR_ARG, "read %lld: CIGAR operation %d", (long long)r, op);
+            if (len == 0) return set_last_error(HELLO_ERR_ARG, "read %lld: zero-length CIGAR operation", (long long)r);
+            if (op == 1 || op == 2) plant.push_back(ref_starts[r] + rlen - 1);
+            if (op == 0 || op == 1 || op == 4 || op == 7 || op == 8) qlen += len;
+            if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) rlen += len;
+            if (op == 0 || op == 2 || op == 7 || op == 8) { last_pos[r] = ref_starts[r] + rlen - 1; prev = true; aligned = true; }
+            else if (op == 3) prev = false;
+            else if (op == 1) {
+                if (!prev) pflags[r] |= 1;
+                else if (c == c1 - 1) pflags[r] |= 2;
+                prev = true;
+                aligned = true;
+            } else if (op == 4 && aligned) {                       // a clip inside the alignment would split a region's read bytes
+                for (int64_t k = c + 1; k < c1; ++k)
+                    if ((cigars[k] & 15) != 4 && (cigars[k] & 15) != 5)
+                        return set_last_error(HELLO_ERR_ARG, "read %lld: a soft clip between aligned operations", (long long)r);
+            }
+        }
+        plant_off[r + 1] = (int64_t)plant.size();
+        if (qlen != read_offsets[r + 1] - read_offsets[r])
+            return set_last_error(HELLO_ERR_SHAPE, "read %lld: CIGAR query length %lld, %lld bases", (long long)r, (long long)qlen,
+                                  (long long)(read_offsets[r + 1] - read_offsets[r]));
+        if (ref_starts[r] < 0 || ref_ends[r] != ref_starts[r] + std::max<int64_t>(rlen, 1))
+            return set_last_error(HELLO_ERR_SHAPE, "read %lld: ref_end does not match its CIGAR", (long long)r);
+        for (int64_t i = read_offsets[r]; i < read_offsets[r + 1]; ++i)
+            if (!strchr("=ACMGRSVTWYHKDBN", bases[i]) || !bases[i])
+                return set_last_error(HELLO_ERR_ARG, "read %lld: base '%c' is not a BAM base code", (long long)r, bases[i]);
+        max_span = std::max(max_span, ref_ends[r] - ref_starts[r]);
+    }
+    const ReadsIn in{bases, quals, read_offsets, cigars, cigar_offsets, ref_starts, ref_ends, mapq, flags, name_hash, n_reads};
+
+    // ---- pass 1 plan: hotspotsReader (PileupDataTools.py:207-244) and candidateReader's fetch (:347-352)
+    std::vector<Job> jobs1;
+    for (int64_t i = 0; i < n_positions;) {
+        int64_t k = i;
+        while (k + 1 < n_positions && positions[k + 1] - positions[k] <= 30) ++k;
+        Job j;
+        j.start = positions[i] - 15;
+        j.stop = positions[k] + 15;
+        j.fetch_lo = std::max<int64_t>(0, j.start - 75);
+        j.fetch_hi = j.stop + 75;
+        jobs1.push_back(std::move(j));
+        i = k + 1;
+    }
+    auto res = std::make_unique<hello_candidates>();
+    JobStats st1, st2;
+    float allele_ms = 0.0f;
+    double ms_gather = 0.0;
+    int64_t n_slots = 0, n_clusters = 0, sites_oob = 0;
+    if (n_reads == 0) st1.empty = (int64_t)jobs1.size();
+    if (!jobs1.empty() && n_reads > 0) {
+        int n_dev = 0;
+        if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) return set_last_error(HELLO_ERR_NOGPU, "no GPU visible");
+        if (device < 0 || device >= n_dev) return set_last_error(HELLO_ERR_ARG, "device %d of %d", device, n_dev);
+        hipDeviceProp_t prop;
+        HS_HIP(hipGetDeviceProperties(&prop, device));
+        if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+            return set_last_error(HELLO_ERR_NOGPU, "device %d is %s; this library is built for gfx950 only", device, prop.gcnArchName);
+        HS_HIP(hipSetDevice(device));
+        DevMem m;
+        HotspotArgs a{};
+        const int64_t nb = read_offsets[n_reads], nc = cigar_offsets[n_reads];
+        std::vector<uint8_t> table(n_reads, 0);                      // every read counts in the Illumina table
+        a.bases = m.put(bases, (size_t)nb);
+        a.quals = m.put(quals, (size_t)nb);
+        a.read_off = m.put(read_offsets, (size_t)n_reads + 1);
+        a.cigars = m.put(cigars, (size_t)nc);
+        a.cigar_off = m.put(cigar_offsets, (size_t)n_reads + 1);
+        a.ref_start = m.put(ref_starts, (size_t)n_reads);
+        a.ref_end = m.put(ref_ends, (size_t)n_reads);
+        a.table = m.put(table.data(), table.size());
+        a.ref_lo = 0;
+        a.ref_len = reference_length;
+        a.ref = m.put(reference, (size_t)reference_length);
+        a.q_threshold = q_threshold;
+        a.hybrid = 0;
+
+        differing_regions(jobs1, in, max_span, plant_off, plant, reference_length, mapq_threshold, a, st1);
+        std::vector<std::pair<int64_t, int64_t>> locations;
+        for (const Job& j : jobs1)
+            for (const auto& reg : j.regions) {
+                // strict runs lie inside [first - 15, last + 15] and points of different active regions are > 30 apart: the
+                // reference's merge_overlaps (:377-378) has nothing to merge
+                if (!locations.empty() && reg.first <= locations.back().second) raise(HELLO_ERR_ARG, "internal: differing regions overlap");
+                locations.push_back(reg);
+            }
+        for (const auto& reg : locations) { res->regions1.push_back(reg.first); res->regions1.push_back(reg.second); }
+
+        // ---- pass 2 plan: clusterLocations (trainDataTools.py:477-514, MAX_ITEMS_PER_GROUP = 1024, caller_calling.py:859) and
+        // the searcher of every cluster (:1045-1065)
+        std::vector<Job> jobs2;
+        {
+            std::vector<std::pair<int64_t, int64_t>> cluster;
+            auto close = [&]() {
+                if (cluster.empty()) return;
+                Job j;
+                j.start = cluster.front().first - 15;
+                j.stop = cluster.back().second + 14;
+                j.fetch_lo = j.start;
+                j.fetch_hi = j.stop;
+                jobs2.push_back(std::move(j));
+                cluster.clear();
+            };
+            for (const auto& loc : locations) {
+                if (loc.second - loc.first > kMaxAlleleLength && !cluster.empty()) { close(); continue; }   // the location is dropped
+                if (cluster.empty()) cluster.push_back(loc);
+                else if (loc.first - cluster.back().second < 30 && cluster.size() < 1024) cluster.push_back(loc);
+                else { close(); cluster.push_back(loc); }
+            }
+            close();
+        }
+        n_clusters = (int64_t)jobs2.size();
+        differing_regions(jobs2, in, max_span, plant_off, plant, reference_length, mapq_threshold, a, st2);
+
+        // ---- allele stage plan: record slots = reads x the regions they overlap, counted exactly
+        std::vector<int64_t> cl_read_off{0}, cl_reads, cl_reg_off{0}, reg_start, reg_stop, rd_rec_off{0}, slot_g, slot_x;
+        for (const Job& j : jobs2) {
+            if (j.regions.empty()) continue;
+            const int64_t gbase = (int64_t)reg_start.size();
+            for (const auto& reg : j.regions) {
+                reg_start.push_back(reg.first);
+                reg_stop.push_back(reg.second);
+                res->regions2.push_back(reg.first);
+                res->regions2.push_back(reg.second);
+            }
+            const int64_t ng = (int64_t)j.regions.size();
+            for (int64_t r : j.reads) {
+                const int64_t x = (int64_t)cl_reads.size();
+                cl_reads.push_back(r);
+                if (last_pos[r] >= 0)                                  // Read.cpp:88: start <= last_position && reference_start < stop
+                    for (int64_t g = 0; g < ng; ++g)
+                        if (j.regions[g].first <= last_pos[r] && ref_starts[r] < j.regions[g].second) {
+                            slot_g.push_back(gbase + g);
+                            slot_x.push_back(x);
+                        }
+                rd_rec_off.push_back((int64_t)slot_g.size());
+            }
+            cl_read_off.push_back((int64_t)cl_reads.size());
+            cl_reg_off.push_back((int64_t)reg_start.size());
+        }
+        n_slots = (int64_t)slot_g.size();
+        const int64_t n_reg = (int64_t)reg_start.size(), n_cl = (int64_t)cl_read_off.size() - 1;
+        std::vector<int64_t> reg_list_off(n_reg + 1, 0), reg_list((size_t)n_slots);
+        for (int64_t s = 0; s < n_slots; ++s) ++reg_list_off[slot_g[s] + 1];
+        for (int64_t g = 0; g < n_reg; ++g) reg_list_off[g + 1] += reg_list_off[g];
+        {
+            std::vector<int64_t> fill(reg_list_off.begin(), reg_list_off.end() - 1);
+            for (int64_t s = 0; s < n_slots; ++s) reg_list[fill[slot_g[s]]++] = s;      // ascending slot = ascending read
+        }
+        std::vector<int32_t> n_alleles((size_t)n_reg, 0), al_count((size_t)n_slots), rec_q0((size_t)n_slots), rec_len((size_t)n_slots);
+        std::vector<int64_t> al_rep((size_t)n_slots), sup((size_t)n_slots);
+        if (n_cl > 0 && n_slots > 0) {
+            AlleleArgs b{};
+            b.bases = a.bases; b.quals = a.quals; b.read_off = a.read_off; b.cigars = a.cigars; b.cigar_off = a.cigar_off;
+            b.ref_start = a.ref_start;
+            b.mapq = m.put(mapq, (size_t)n_reads);
+            b.last_pos = m.put(last_pos.data(), last_pos.size());
+            b.pflags = m.put(pflags.data(), pflags.size());
+            b.cl_read_off = m.put(cl_read_off.data(), cl_read_off.size());
+            b.cl_reads = m.put(cl_reads.data(), cl_reads.size());
+            b.cl_reg_off = m.put(cl_reg_off.data(), cl_reg_off.size());
+            b.reg_start = m.put(reg_start.data(), reg_start.size());
+            b.reg_stop = m.put(reg_stop.data(), reg_stop.size());
+            b.rd_rec_off = m.put(rd_rec_off.data(), rd_rec_off.size());
+            b.slot_g = m.put(slot_g.data(), slot_g.size());
+            b.slot_x = m.put(slot_x.data(), slot_x.size());
+            b.reg_list_off = m.put(reg_list_off.data(), reg_list_off.size());
+            b.reg_list = m.put(reg_list.data(), reg_list.size());
+            b.ref = a.ref;
+            b.ref_len = reference_length;
+            b.status = m.zeros<int32_t>((size_t)n_slots);
+            b.q0 = m.zeros<int32_t>((size_t)n_slots);
+            b.len = m.zeros<int32_t>((size_t)n_slots);
+            b.minq = m.zeros<int32_t>((size_t)n_slots);
+            b.hash = m.zeros<uint64_t>((size_t)n_slots);
+            b.pass = m.zeros<int32_t>((size_t)n_slots);
+            b.first = m.zeros<int64_t>((size_t)n_slots);
+            b.target = m.zeros<int64_t>((size_t)n_slots);
+            b.n_alleles = m.zeros<int32_t>((size_t)n_reg);
+            b.al_rep = m.zeros<int64_t>((size_t)n_slots);
+            b.al_count = m.zeros<int32_t>((size_t)n_slots);
+            b.sup = m.zeros<int64_t>((size_t)n_slots);
+            b.q_threshold = q_threshold;
+            b.mapq_threshold = mapq_threshold;
+            {
+                KernelTimer timer;
+                timer.start();
+                hipLaunchKernelGGL(allele_kernel, dim3((unsigned)n_cl), dim3(256), 0, 0, b);
+                HS_HIP(hipGetLastError());
+                allele_ms = timer.stop();
+            }
+            HS_HIP(hipMemcpy(n_alleles.data(), b.n_alleles, n_alleles.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+            HS_HIP(hipMemcpy(al_count.data(), b.al_count, al_count.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+            HS_HIP(hipMemcpy(al_rep.data(), b.al_rep, al_rep.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
+            HS_HIP(hipMemcpy(sup.data(), b.sup, sup.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
+            HS_HIP(hipMemcpy(rec_q0.data(), b.q0, rec_q0.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+            HS_HIP(hipMemcpy(rec_len.data(), b.len, rec_len.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        }
+
+        // ---- sites and the gather of every allele's reads into the arrays of a shard (hello_amd/shards.py)
+        const auto tg = clock::now();
+        hello_candidates& o = *res;
+        for (int64_t g = 0; g < n_reg; ++g) {
+            if (n_alleles[g] == 0) continue;                                             // caller_calling.py:876
+            const int64_t s = reg_start[g], e = reg_stop[g], L = feature_length;
+            const int64_t lo = (s + e) / 2 - L / 2;
+            const int64_t ws = std::min(lo, s - 1), we = std::max(lo + L, e);            // one anchor base left of the site
+            if (ws < 0 || we > reference_length) { ++sites_oob; continue; }
+            o.start.push_back(s);
+            o.stop.push_back(e);
+            o.window_start.push_back(ws);
+            o.ref.insert(o.ref.end(), reference + ws, reference + we);
+            o.ref_off.push_back((int64_t)o.ref.size());
+            o.alleles_per_site.push_back(n_alleles[g]);
+            int64_t at = reg_list_off[g];
+            for (int32_t k = 0; k < n_alleles[g]; ++k) {
+                const int64_t rep = al_rep[reg_list_off[g] + k];
+                const uint8_t* t = bases + read_offsets[cl_reads[slot_x[rep]]] + rec_q0[rep];
+                o.allele_text.insert(o.allele_text.end(), t, t + rec_len[rep]);
+                o.allele_text_off.push_back((int64_t)o.allele_text.size());
+                const int32_t n = al_count[reg_list_off[g] + k];
+                o.reads_per_allele.push_back(n);
+                for (int32_t i = 0; i < n; ++i) {
+                    const int64_t r = sup[at + i];
+                    o.read_index.push_back(r);
+                    o.read_off.push_back(o.read_off.back() + (read_offsets[r + 1] - read_offsets[r]));
+                    o.cigar_off.push_back(o.cigar_off.back() + (cigar_offsets[r + 1] - cigar_offsets[r]));
+                }
+                at += n;
+            }
+        }
+        const int64_t R = (int64_t)o.read_index.size();
+        o.bases.resize((size_t)o.read_off.back());
+        o.quals.resize((size_t)o.read_off.back());
+        o.cigars.resize((size_t)o.cigar_off.back());
+        o.ref_start.resize((size_t)R);
+        o.mapq.resize((size_t)R);
+        o.orientation.resize((size_t)R);
+        o.hp.resize((size_t)R);
+        const int n_threads = (int)std::max<int64_t>(1, std::min<int64_t>({16, (int64_t)std::thread::hardware_concurrency(), R / 4096 + 1}));
+        auto copy = [&](int64_t i0, int64_t i1) {
+            for (int64_t i = i0; i < i1; ++i) {
+                const int64_t r = o.read_index[i];
+                std::copy(bases + read_offsets[r], bases + read_offsets[r + 1], o.bases.begin() + o.read_off[i]);
+                std::copy(quals + read_offsets[r], quals + read_offsets[r + 1], o.quals.begin() + o.read_off[i]);
+                std::copy(cigars + cigar_offsets[r], cigars + cigar_offsets[r + 1], o.cigars.begin() + o.cigar_off[i]);
+                o.ref_start[i] = ref_starts[r];
+                o.mapq[i] = mapq[r];
+                o.orientation[i] = (flags[r] & 16) ? -1 : 1;
+                o.hp[i] = hp[r];
+            }
+        };
+        std::vector<std::thread> pool;
+        for (int t = 1; t < n_threads; ++t) pool.emplace_back(copy, R * t / n_threads, R * (t + 1) / n_threads);
+        copy(0, R / n_threads);
+        for (auto& th : pool) th.join();
+        ms_gather = std::chrono::duration<double, std::milli>(clock::now() - tg).count();
+    }
+    const double ms_total = std::chrono::duration<double, std::milli>(clock::now() - t0).count();
+    const double st[HELLO_CANDIDATES_STATS] = {
+        (double)jobs1.size(), (double)st1.empty, (double)st1.bounds, (double)st1.capped, (double)(res->regions1.size() / 2),
+        (double)n_clusters, (double)st2.empty, (double)st2.bounds, (double)st2.capped, (double)(res->regions2.size() / 2),
+        (double)res->start.size(), (double)sites_oob, (double)res->reads_per_allele.size(), (double)res->read_index.size(),
+        (double)n_slots, (double)st1.ms, (double)st2.ms, (double)allele_ms, ms_gather, ms_total};
+    std::copy(st, st + HELLO_CANDIDATES_STATS, res->stats);
+    *out = res.release();
+    return HELLO_OK;
+} catch (const hello::Fail& f) {
+    return hello::set_last_error(f.code, "%s", f.msg.c_str());
+} catch (...) {
+    return hello::exception_status("hello_candidates_find");
+}
+
+int hello_candidates_array(const hello_candidates* c, int32_t which, const void** data, int64_t* count) {
+    if (!c || !data || !count) return hello::set_last_error(HELLO_ERR_ARG, "NULL pointer");
+#define HELLO_CAND_CASE(id, v) case id: *data = c->v.data(); *count = (int64_t)c->v.size(); break
+    switch (which) {
+        HELLO_CAND_CASE(HELLO_CAND_START, start);
+        HELLO_CAND_CASE(HELLO_CAND_STOP, stop);
+        HELLO_CAND_CASE(HELLO_CAND_WINDOW_START, window_start);
+        HELLO_CAND_CASE(HELLO_CAND_REF_OFF, ref_off);
+        HELLO_CAND_CASE(HELLO_CAND_REF, ref);
+        HELLO_CAND_CASE(HELLO_CAND_ALLELES_PER_SITE, alleles_per_site);
+        HELLO_CAND_CASE(HELLO_CAND_ALLELE_TEXT, allele_text);
+        HELLO_CAND_CASE(HELLO_CAND_ALLELE_TEXT_OFF, allele_text_off);
+        HELLO_CAND_CASE(HELLO_CAND_READS_PER_ALLELE, reads_per_allele);
+        HELLO_CAND_CASE(HELLO_CAND_BASES, bases);
+        HELLO_CAND_CASE(HELLO_CAND_QUALS, quals);
+        HELLO_CAND_CASE(HELLO_CAND_READ_OFF, read_off);
+        HELLO_CAND_CASE(HELLO_CAND_CIGARS, cigars);
+        HELLO_CAND_CASE(HELLO_CAND_CIGAR_OFF, cigar_off);
+        HELLO_CAND_CASE(HELLO_CAND_REF_START, ref_start);
+        HELLO_CAND_CASE(HELLO_CAND_MAPQ, mapq);
+        HELLO_CAND_CASE(HELLO_CAND_ORIENTATION, orientation);
+        HELLO_CAND_CASE(HELLO_CAND_HP, hp);
+        HELLO_CAND_CASE(HELLO_CAND_READ_INDEX, read_index);
+        HELLO_CAND_CASE(HELLO_CAND_REGIONS_PASS1, regions1);
+        HELLO_CAND_CASE(HELLO_CAND_REGIONS_PASS2, regions2);
+        default: return hello::set_last_error(HELLO_ERR_ARG, "no candidate array %d", which);
+    }
+#undef HELLO_CAND_CASE
+    return HELLO_OK;
+}
+
+int hello_candidates_stats(const hello_candidates* c, double* stats) {
+    if (!c || !stats) return hello::set_last_error(HELLO_ERR_ARG, "NULL pointer");
+    std::copy(c->stats, c->stats + HELLO_CANDIDATES_STATS, stats);
+    return HELLO_OK;
+}
+
+void hello_candidates_free(hello_candidates* c) { delete c; }
+
+}  // extern "C"

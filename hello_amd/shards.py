@@ -2,8 +2,9 @@
 it featurises and scores it (reference python/caller_calling.py:795-843: reads sampled from the BAMs, candidate
 alleles and read -> allele support from AlleleSearcherLite, the site's reference window), stored as flat arrays.
 
-BAM / FASTA ingestion, hotspot detection and allele assembly are upstream of the scoring path (SURVEY.md section 2,
-rows 9-13: they need pysam and the C++ searcher) and stay with the reference; a shard file is the hand-over point.
+A shard file is the hand-over point between candidate-site construction and scoring.  For one Illumina BAM
+``hello_amd.candidates`` writes it on the GPU (hotspot positions -> sites, alleles, supporting reads); two BAMs and PacBio
+reads still come from the reference's searcher through ``write_shard``.
 One file per shard (the reference's unit of work, ``shard<N>.txt``, python/call.py:162-221):
 
   site arrays   chromosome names (byte table) + chromosome_of_site, start, stop (allele span, genome coordinates),

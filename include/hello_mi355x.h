@@ -264,7 +264,8 @@ typedef struct hello_bam_reads hello_bam_reads;
 enum {
     HELLO_BAM_BASES = 0, HELLO_BAM_QUALS = 1, HELLO_BAM_READ_OFFSETS = 2, HELLO_BAM_CIGARS = 3, HELLO_BAM_CIGAR_OFFSETS = 4,
     HELLO_BAM_REF_STARTS = 5, HELLO_BAM_REF_ENDS = 6, HELLO_BAM_MAPQ = 7, HELLO_BAM_FLAGS = 8, HELLO_BAM_NAME_HASH = 9,
-    HELLO_BAM_STRAND = 10
+    HELLO_BAM_STRAND = 10,
+    HELLO_BAM_HP = 11          /* uint8: the HP integer tag (types c/C/s/S/i/I), 0 when absent or outside 0..255 */
 };
 int hello_bam_open(const char* path, int32_t n_threads, hello_bam** out);
 int hello_bam_n_references(const hello_bam* bam);
@@ -306,6 +307,56 @@ int hello_hotspots_positions(const hello_hotspots* hotspots, const int64_t** pos
  * (summed over chunks), tiles, events, kernel ms (HIP events), plan ms, total ms */
 int hello_hotspots_stats(const hello_hotspots* hotspots, double* stats);
 void hello_hotspots_free(hello_hotspots* hotspots);
+
+/* Stands in for: python/caller_calling.py main (:795-843) up to the featurizer, for ONE Illumina BAM -- python/PileupDataTools.py
+ * hotspotsReader and candidateReader (:207-244,302-384: pass 1, one strict searcher per active region), python/trainDataTools.py
+ * clusterLocations and data (:477-514,1039-1103: pass 2, one strict searcher per cluster whose own differing regions are the
+ * sites), get_labeled_candidates and createTensors (:557-640,880-977), c++/src/Read.cpp:4-172 (a read's allele in a region) and
+ * c++/src/AlleleSearcherLiteFiltered.cpp:495-547,648-666,740-831 (strict runs, supports, partials).  DESIGN.md "Candidate
+ * sites" restates the rules, the two defined orders (alternative alleles in ascending byte order after the reference allele,
+ * supporting reads in file order) and the deviations (the first reads are kept at the read cap; a cluster whose window leaves
+ * the chromosome is skipped and counted; a site whose feature window leaves the chromosome is dropped and counted).
+ *   reads: the arrays of hello_bam_fetch, coordinate-sorted, holding every read that overlaps [first position - 90, last
+ *          position + 90) (pass 1 fetches 75 bp either side of [first - 15, last + 15]; more reads do no harm); hp = selector
+ *          HELLO_BAM_HP.  positions: the sorted positions of a hotspot / shard file on this chromosome.
+ *   options: 0.  HELLO_HOTSPOTS_PACBIO, HELLO_HOTSPOTS_TWO_BAMS and HELLO_HOTSPOTS_HYBRID are refused (HELLO_ERR_ARG): those paths
+ *          need the PacBio reassembly and read clipping.
+ * Three kernel launches on `device` (candidates.hip: differing regions of pass 1, of pass 2, alleles and supports); the reads of
+ * every allele are gathered on at most 16 host threads.  The result holds the arrays of a shard (hello_amd/shards.py) without
+ * the chromosome table, plus read_index (the input read of every gathered read) and the differing regions of both passes as
+ * (start, stop) pairs. */
+enum {
+    HELLO_CAND_START = 0, HELLO_CAND_STOP = 1, HELLO_CAND_WINDOW_START = 2, HELLO_CAND_REF_OFF = 3,      /* int64 */
+    HELLO_CAND_REF = 4,                                                                                  /* uint8 */
+    HELLO_CAND_ALLELES_PER_SITE = 5,                                                                     /* int32 */
+    HELLO_CAND_ALLELE_TEXT = 6,                                                                          /* uint8 */
+    HELLO_CAND_ALLELE_TEXT_OFF = 7,                                                                      /* int64 */
+    HELLO_CAND_READS_PER_ALLELE = 8,                                                                     /* int32 */
+    HELLO_CAND_BASES = 9, HELLO_CAND_QUALS = 10,                                                         /* uint8 */
+    HELLO_CAND_READ_OFF = 11,                                                                            /* int64 */
+    HELLO_CAND_CIGARS = 12,                                                                              /* uint32 */
+    HELLO_CAND_CIGAR_OFF = 13, HELLO_CAND_REF_START = 14,                                                /* int64 */
+    HELLO_CAND_MAPQ = 15,                                                                                /* uint8 */
+    HELLO_CAND_ORIENTATION = 16,                                                                         /* int8 */
+    HELLO_CAND_HP = 17,                                                                                  /* uint8 */
+    HELLO_CAND_READ_INDEX = 18, HELLO_CAND_REGIONS_PASS1 = 19, HELLO_CAND_REGIONS_PASS2 = 20             /* int64 */
+};
+#define HELLO_CANDIDATES_STATS 20
+typedef struct hello_candidates hello_candidates;
+int hello_candidates_find(const uint8_t* bases, const uint8_t* quals, const int64_t* read_offsets,
+                          const uint32_t* cigars, const int64_t* cigar_offsets, const int64_t* ref_starts,
+                          const int64_t* ref_ends, const uint8_t* mapq, const uint16_t* flags, const uint64_t* name_hash,
+                          const uint8_t* hp, int64_t n_reads, const uint8_t* reference, int64_t reference_length,
+                          const int64_t* positions, int64_t n_positions, int32_t options, int32_t feature_length,
+                          int32_t q_threshold, int32_t mapq_threshold, int32_t device, hello_candidates** out);
+/* a pointer into `candidates` (valid until hello_candidates_free) and its element count */
+int hello_candidates_array(const hello_candidates* candidates, int32_t which, const void** data, int64_t* count);
+/* stats[HELLO_CANDIDATES_STATS]: active regions, without reads, out of bounds, at the read cap, differing regions of pass 1;
+ * clusters, without reads, out of bounds, at the read cap, differing regions of pass 2; sites, sites whose feature window leaves
+ * the chromosome, alleles, reads gathered, record slots; ms of the pass-1 kernel, the pass-2 kernel, the allele kernel (HIP
+ * events), the host gather, the whole call */
+int hello_candidates_stats(const hello_candidates* candidates, double* stats);
+void hello_candidates_free(hello_candidates* candidates);
 
 /* The engine's own stream (a hipStream_t): what a call with hip_stream == NULL runs on.  It is created
  * non-blocking, so it is NOT ordered with the legacy default stream: a caller whose other work sits on the default
