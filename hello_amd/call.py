@@ -229,8 +229,9 @@ def parser() -> argparse.ArgumentParser:
                     help="glob (or directory) of pre-extracted candidate-site shards (hello_amd.shards), one per "
                          "reference shard<N>.txt")
     ap.add_argument("--from_bam", action="store_true", default=False,
-                    help="start from --ibam and --ref: hotspots, sharding and candidate sites run on the GPU (hello_amd.hotspots, "
-                         "hello_amd.candidates) and the shards they write under --workdir are scored; one Illumina BAM only")
+                    help="start from --ibam (or --pbam) and --ref: hotspots, sharding and candidate sites run on the GPU "
+                         "(hello_amd.hotspots, hello_amd.candidates / hello_amd.pacbio) and the shards they write under --workdir are "
+                         "scored; one Illumina BAM or one PacBio BAM")
     ap.add_argument("--device", type=int, default=0, help="GPU of a single-process run")
     ap.add_argument("--gpus", type=int, default=1,
                     help="processes / GPUs of this node: > 1 re-launches this command under torch.distributed.run "
@@ -294,21 +295,32 @@ def shard_read_totals(paths: Sequence[str], threads: int = 4) -> np.ndarray:
         return np.array(list(pool.map(total, paths)), np.int64)
 
 
+def from_bam_route(ibam: Optional[str], pbam: Optional[str]):
+    """python/call.py:90-109 for --from_bam: one Illumina BAM, or one PacBio BAM (``pacbio = pbam and not ibam``).  -> (the BAM,
+    pacbio, the function that builds a chromosome's candidate sites).  Both BAMs and comma lists are refused."""
+    from . import candidates as cd
+    if (ibam and pbam) or not (ibam or pbam) or "," in (ibam or pbam):
+        raise ValueError(cd.REFUSAL)
+    if pbam:
+        from .pacbio import find_pacbio_candidates
+        return pbam, True, find_pacbio_candidates
+    return ibam, False, cd.find_candidates
+
+
 def shards_from_bam(args) -> str:
     """python/call.py:111-221 up to the per-shard caller, on the GPU: per chromosome hotspots.txt in the reference's
     ``hotspots_<chrom>_<bam>`` directory, ``shard<N>.txt`` files beside it (shardHotspots) and one ``shard<N>.hshard`` per
     shard file in ``<workdir>/shards``.  Returns that directory."""
     from . import candidates as cd, hotspots as hs
     logger = logging.getLogger("hello_amd.call")
-    if args.pbam or not args.ibam or "," in args.ibam:
-        raise ValueError(cd.REFUSAL)
+    bam, pacbio, find = from_bam_route(args.ibam, args.pbam)
     if not args.ref:
         raise SystemExit("--from_bam needs --ref")
     chromosomes = args.chromosomes.split(",") if args.chromosomes else None
     genome = read_fasta(args.ref, chromosomes)
     out_dir = os.path.join(args.workdir, "shards")
     os.makedirs(out_dir, exist_ok=True)
-    ns = argparse.Namespace(bam=args.ibam, ref=args.ref, pacbio=False, hybrid_hotspot=False, workdir=args.workdir,
+    ns = argparse.Namespace(bam=bam, ref=args.ref, pacbio=pacbio, hybrid_hotspot=False, workdir=args.workdir,
                             chromosomes=",".join(chromosomes or list(genome)), q_threshold=cd.DEFAULT_Q_THRESHOLD,
                             mapq_threshold=cd.DEFAULT_MIN_MAPQ, device=args.device)
     n = 0
@@ -318,8 +330,8 @@ def shards_from_bam(args) -> str:
             for part in cd.shard_positions(pos):
                 name = os.path.join(os.path.dirname(hotspot_name), "shard%d.txt" % n)
                 hs.write_positions(name, chrom, part)
-                _, st = cd.run_activity(args.ibam, args.ref, name, os.path.join(out_dir, "shard%d" % n), device=args.device,
-                                        genome=genome)
+                _, st = cd.run_activity(bam, args.ref, name, os.path.join(out_dir, "shard%d" % n), device=args.device,
+                                        genome=genome, find=find)
                 logger.info("%s: %d sites", name, st.get("sites", 0))
                 n += 1
     if n == 0:

@@ -6,8 +6,9 @@ python/caller_calling.py does up to its featurizer (:784-843) for ONE Illumina B
 strict differing regions (pass 1), clusters of those, the clusters' own strict differing regions (pass 2, the sites), and per
 site the alleles the reads spell there with every allele's supporting reads.  Both passes and the allele stage run in
 ``hello_candidates_find`` (hello_amd/csrc/candidates.hip); DESIGN.md "Candidate sites" states the rules.  ``shard_positions``
-is the reference's python/shardHotspots.py.  PacBio reads, two BAMs and ``--hybrid_hotspot`` are refused: they need the
-PacBio reassembly and read clipping.
+is the reference's python/shardHotspots.py.  Two BAMs and ``--hybrid_hotspot`` are refused: they need the two-BAM reassembly.
+One PacBio BAM has its own entry points in ``hello_amd.pacbio``; ``pacbio=True`` / ``--pacbio`` here are refused with a pointer
+to them.
 """
 from __future__ import annotations
 
@@ -30,11 +31,11 @@ DEFAULT_Q_THRESHOLD = 10
 DEFAULT_MIN_MAPQ = 10
 MIN_DISTANCE = 30                  # PileupDataTools.py:21
 FLANKING_BASES = 75                # :24
-N_STATS = 20
+N_STATS = 22
 STAT_NAMES = ("active_regions", "regions_without_reads", "regions_out_of_bounds", "regions_at_read_cap", "differing_regions_pass1",
               "clusters", "clusters_without_reads", "clusters_out_of_bounds", "clusters_at_read_cap", "differing_regions_pass2",
               "sites", "sites_out_of_bounds", "alleles", "reads_gathered", "record_slots", "pass1_kernel_ms", "pass2_kernel_ms",
-              "allele_kernel_ms", "gather_ms", "total_ms")
+              "allele_kernel_ms", "gather_ms", "total_ms", "clip_kernel_ms", "reads_clipped")
 _ARRAYS = (  # (name, hello_candidates_array selector, dtype)
     ("start", 0, np.int64), ("stop", 1, np.int64), ("window_start", 2, np.int64), ("ref_off", 3, np.int64), ("ref", 4, np.uint8),
     ("alleles_per_site", 5, np.int32), ("allele_text", 6, np.uint8), ("allele_text_off", 7, np.int64),
@@ -43,8 +44,8 @@ _ARRAYS = (  # (name, hello_candidates_array selector, dtype)
     ("orientation0", 16, np.int8), ("hp0", 17, np.uint8), ("read_index", 18, np.int64), ("regions_pass1", 19, np.int64),
     ("regions_pass2", 20, np.int64),
 )
-REFUSAL = ("candidate sites are built from one Illumina BAM: PacBio reads, two BAMs and --hybrid_hotspot need the PacBio "
-           "reassembly and read clipping, which hello_amd does not have")
+REFUSAL = ("candidate sites are built from one Illumina BAM: two BAMs and --hybrid_hotspot need the two-BAM reassembly, which "
+           "hello_amd does not have; one PacBio BAM goes through hello_amd.pacbio (python -m hello_amd.pacbio)")
 
 _log = logging.getLogger(__name__)
 _bound = None
@@ -206,7 +207,7 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--mapq_threshold", type=int, default=DEFAULT_MIN_MAPQ, help="Mapping quality threshold")
     p.add_argument("--include_hp", action="store_true", default=False, help="Accepted for the reference's command line: the reads' HP tags are always stored; the scoring "
                         "driver's --include_hp decides whether they are used")
-    p.add_argument("--pacbio", action="store_true", default=False, help="Refused: PacBio reads need reassembly and clipping")
+    p.add_argument("--pacbio", action="store_true", default=False, help="Refused: use python -m hello_amd.pacbio for one PacBio BAM")
     p.add_argument("--hybrid_hotspot", action="store_true", default=False, help="Refused: needs two BAMs")
     p.add_argument("--debug", action="store_true", default=False, help="Display debug messages")
     p.add_argument("--device", type=int, default=0, help="GPU index")
@@ -214,8 +215,11 @@ def parser() -> argparse.ArgumentParser:
 
 
 def run_activity(bam: str, fasta: str, activity: str, output_prefix: str, feature_length: int = 150,
-                 q_threshold: int = DEFAULT_Q_THRESHOLD, mapq_threshold: int = DEFAULT_MIN_MAPQ, device: int = 0, genome: Optional[Dict[str, str]] = None) -> Tuple[str, Dict[str, float]]:
-    """One activity file -> ``<output_prefix>.hshard`` and the summed statistics."""
+                 q_threshold: int = DEFAULT_Q_THRESHOLD, mapq_threshold: int = DEFAULT_MIN_MAPQ, device: int = 0, genome: Optional[Dict[str, str]] = None,
+                 find=None) -> Tuple[str, Dict[str, float]]:
+    """One activity file -> ``<output_prefix>.hshard`` and the summed statistics.  ``find``: the function with
+    ``find_candidates``' signature that builds one chromosome's shard (default: ``find_candidates``)."""
+    find = find or find_candidates
     from .call import read_fasta
     by_chromosome = read_positions(activity)
     if genome is None:
@@ -225,8 +229,8 @@ def run_activity(bam: str, fasta: str, activity: str, output_prefix: str, featur
         if chromosome not in genome:
             raise ValueError(f"{fasta}: no sequence named {chromosome!r}")
         st: dict = {}
-        shard = find_candidates(bam, fasta, chromosome, positions, q_threshold, mapq_threshold, device, feature_length,
-                                reference=genome[chromosome], stats=st)
+        shard = find(bam, fasta, chromosome, positions, q_threshold, mapq_threshold, device, feature_length,
+                     reference=genome[chromosome], stats=st)
         for k in STAT_NAMES:
             total[k] = total.get(k, 0.0) + st[k]
         parts.append(shard)

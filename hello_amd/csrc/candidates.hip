@@ -1,5 +1,5 @@
 // Candidate sites from hotspot positions (include/hello_mi355x.h: hello_candidates_find): the stage between the hotspot detector
-// and the scoring engine, for one Illumina BAM.
+// and the scoring engine, for one Illumina BAM or one PacBio BAM.
 //
 // Reference semantics: python/PileupDataTools.py:207-244 (positions -> active regions), :129-158 (the read cap), :302-384 (pass 1:
 // one strict searcher per active region), python/trainDataTools.py:477-514 (clusterLocations), :1039-1103 (pass 2: one strict
@@ -16,6 +16,11 @@
 // resolves the reads' partials against the distinct strings and writes, per region, the alleles in the defined order (reference
 // allele, then ascending bytes) with their supporting reads in file order.  Everything is integer and ordered by index, so two
 // runs give the same bytes.  Records live in global memory (a cluster's few kilobytes stay in L2); nothing is truncated.
+//
+// PacBio (HELLO_HOTSPOTS_PACBIO): reads are selected on their original alignment, then every (searcher, kept read) pair is
+// strictly clipped (python/PileupContainerLite.py:255-468,554-573: left at the fetch interval's start, then right at its end,
+// 201 read bases kept outward of either) by clip_plan_kernel / clip_write_kernel into a derived read set per pass, which the
+// kernels above consume unmodified through their read lists; every derived read counts in table 1.
 #include <algorithm>
 #include <chrono>
 #include <memory>
@@ -319,33 +324,381 @@ struct Job {                       // one searcher: an active region (pass 1) or
     int64_t fetch_lo, fetch_hi;    // the reads fetched for it
     std::vector<int64_t> reads;    // kept reads, file order
     std::vector<std::pair<int64_t, int64_t>> regions;   // strict differing regions
-    bool run = false;
+    bool run = false, capped = false;
 };
 
-struct JobStats { int64_t empty = 0, bounds = 0, capped = 0, counted = 0, tiles = 0, events = 0; float ms = 0; };
+struct JobStats { int64_t empty = 0, bounds = 0, capped = 0, counted = 0, tiles = 0, events = 0, clipped = 0; float ms = 0, clip_ms = 0; };
 
-// The reads, window and differing regions of every job (AlleleSearcherLite.__init__ + determineDifferingRegions(strict = True)).
-void differing_regions(std::vector<Job>& jobs, const ReadsIn& in, int64_t max_span, const std::vector<int64_t>& plant_off,
-                       const std::vector<int64_t>& plant, int64_t reference_length, int mapq_threshold, HotspotArgs a, JobStats& st) {
-    std::vector<int64_t> flo, fhi, bit_base, creads_off{0}, creads, tile_lo, tile_ev_off{0};
-    std::vector<int32_t> tile_chunk, chunk_job;
+// The reads every stage after the selection sees: the input reads themselves, or the clipped copies of one pass (PacBio).
+struct ReadSet {
+    const uint8_t* bases = nullptr; const uint8_t* quals = nullptr; const int64_t* read_off = nullptr;
+    const uint32_t* cigars = nullptr; const int64_t* cigar_off = nullptr; const int64_t* ref_start = nullptr;
+    const int64_t* ref_end = nullptr; const uint8_t* mapq = nullptr;
+    const int64_t* origin = nullptr;          // the input read of every read; nullptr: these are the input reads
+    int64_t n = 0;
+    std::vector<int64_t> plant_off, plant, last_pos;    // planting positions of the I/D operations; last M/D position or -1
+    std::vector<uint8_t> pflags;                        // 1 partial_start, 2 partial_stop (Read.cpp:42-49)
+    // on the device
+    const uint8_t* d_bases = nullptr; const uint8_t* d_quals = nullptr; const int64_t* d_read_off = nullptr;
+    const uint32_t* d_cigars = nullptr; const int64_t* d_cigar_off = nullptr; const int64_t* d_ref_start = nullptr;
+    const int64_t* d_ref_end = nullptr; const uint8_t* d_table = nullptr;
+    DevMem mem;
+    // storage of a derived set
+    std::vector<uint8_t> v_bases, v_quals, v_mapq;
+    std::vector<int64_t> v_read_off, v_cigar_off, v_ref_start, v_ref_end, v_origin;
+    std::vector<uint32_t> v_cigars;
+    int64_t input(int64_t r) const { return origin ? origin[r] : r; }
+};
+
+inline bool is_query_op(int op) { return op == 0 || op == 1 || op == 4 || op == 7 || op == 8; }
+inline bool is_ref_op(int op) { return op == 0 || op == 2 || op == 3 || op == 7 || op == 8; }
+
+// Validation of every usable read (the kernels read within its bases), its planting positions, and what Read::_get_read_mapping
+// knows about it as a whole: last_position, partial_start, partial_stop.  `flags` == nullptr: every read is used (a derived
+// set).  `clip_input`: the reads are about to be clipped -- the refusal of a soft clip between aligned operations waits for the
+// clipped CIGARs, and what the clip kernels rely on is checked instead.  -> the longest reference span.
+int64_t describe_reads(ReadSet& s, const uint16_t* flags, bool clip_input) {
+    int64_t max_span = 0;
+    s.plant_off.assign((size_t)s.n + 1, 0);
+    s.plant.clear();
+    s.last_pos.assign((size_t)s.n, -1);
+    s.pflags.assign((size_t)s.n, 0);
+    for (int64_t r = 0; r < s.n; ++r) {
+        s.plant_off[r + 1] = s.plant_off[r];
+        if (flags && r > 0 && s.ref_start[r] < s.ref_start[r - 1])
+            raise(HELLO_ERR_ARG, "read %lld: reads are not coordinate-sorted (the BAM must be)", (long long)r);
+        if (s.read_off[r + 1] < s.read_off[r] || s.cigar_off[r + 1] < s.cigar_off[r])
+            raise(HELLO_ERR_SHAPE, "read %lld: offsets decrease", (long long)r);
+        if (flags && !usable(flags[r], s.mapq[r])) continue;
+        int64_t qlen = 0, rlen = 0;
+        const int64_t c0 = s.cigar_off[r], c1 = s.cigar_off[r + 1];
+        bool prev = false, aligned = false;
+        for (int64_t c = c0; c < c1; ++c) {
+            const int op = s.cigars[c] & 15;
+            const int64_t len = s.cigars[c] >> 4;
+            if (op > 8) raise(HELLO_ERR_ARG, "read %lld: CIGAR operation %d", (long long)r, op);
+            if (len == 0) raise(HELLO_ERR_ARG, "read %lld: zero-length CIGAR operation", (long long)r);
+            if (op == 1 || op == 2) s.plant.push_back(s.ref_start[r] + rlen - 1);
+            if (is_query_op(op)) qlen += len;
+            if (is_ref_op(op)) rlen += len;
+            if (op == 0 || op == 2 || op == 7 || op == 8) { s.last_pos[r] = s.ref_start[r] + rlen - 1; prev = true; aligned = true; }
+            else if (op == 3) prev = false;
+            else if (op == 1) {
+                if (!prev) s.pflags[r] |= 1;
+                else if (c == c1 - 1) s.pflags[r] |= 2;
+                prev = true;
+                aligned = true;
+            } else if (op == 4 && aligned && !clip_input) {        // a clip inside the alignment would split a region's read bytes
+                for (int64_t k = c + 1; k < c1; ++k)
+                    if ((s.cigars[k] & 15) != 4 && (s.cigars[k] & 15) != 5)
+                        raise(HELLO_ERR_ARG, "read %lld: a soft clip between aligned operations", (long long)s.input(r));
+            }
+        }
+        s.plant_off[r + 1] = (int64_t)s.plant.size();
+        if (clip_input && rlen == 0) raise(HELLO_ERR_ARG, "read %lld: no CIGAR operation on the reference", (long long)r);
+        if (qlen != s.read_off[r + 1] - s.read_off[r])
+            raise(HELLO_ERR_SHAPE, "read %lld: CIGAR query length %lld, %lld bases", (long long)r, (long long)qlen,
+                  (long long)(s.read_off[r + 1] - s.read_off[r]));
+        if (s.ref_start[r] < 0 || s.ref_end[r] != s.ref_start[r] + std::max<int64_t>(rlen, 1))
+            raise(HELLO_ERR_SHAPE, "read %lld: ref_end does not match its CIGAR", (long long)r);
+        if (flags)
+            for (int64_t i = s.read_off[r]; i < s.read_off[r + 1]; ++i)
+                if (!strchr("=ACMGRSVTWYHKDBN", s.bases[i]) || !s.bases[i])
+                    raise(HELLO_ERR_ARG, "read %lld: base '%c' is not a BAM base code", (long long)r, s.bases[i]);
+        max_span = std::max(max_span, s.ref_end[r] - s.ref_start[r]);
+    }
+    return max_span;
+}
+
+// ---- strict clipping (python/PileupContainerLite.py: strictClipFn :255-363, strictClipRead :366-468, __get_reads :554-573)
+//
+// A clipped read is a slice [q_lo, q_hi) of the read's bases and the operations [a, b] of its CIGAR with new first and last
+// operations (a new length; an outermost kept I becomes S).  The reference rejoins the halves of a clip with equal centre
+// operations merged: the two halves of the split operation, or, when the clip position is an operation's last base and the next
+// operation is of the same kind (20M 20M), those two -- `fuse_l` / `fuse_r` name the first of such a pair, written as one.
+constexpr int kClipFlank = 200;                                                   // caller_calling.py:795-843 (clipFlank)
+
+struct ClipRec {
+    int64_t a, b;             // first and last kept operation of the read
+    int64_t q_lo, q_hi;       // kept read bases
+    int64_t ref_start, ref_end;
+    int64_t fuse_l, fuse_r;   // operations f and f + 1 are written as one (the left / the right clip's centre); -1: none
+    uint32_t first, last;     // their CIGAR words (equal when a == b)
+    int32_t clipped;          // 1 the left clip applied, 2 the right clip applied
+};
+
+struct ClipArgs {
+    const uint8_t* bases; const uint8_t* quals; const int64_t* read_off; const uint32_t* cigars; const int64_t* cigar_off;
+    const int64_t* ref_start; const int64_t* ref_end;
+    const int64_t* pair_read;         // the input read of every (searcher, kept read) pair
+    const int64_t* pair_lo;           // the searcher's fetch interval: clipped left at lo, then right at hi
+    const int64_t* pair_hi;
+    int64_t n_pairs;
+    int flank;
+    ClipRec* rec;
+    // the second launch
+    const int64_t* out_read_off;      // [pairs + 1], the exclusive scans of the first launch's counts
+    const int64_t* out_cigar_off;
+    uint8_t* out_bases; uint8_t* out_quals; uint32_t* out_cigars;
+};
+
+__device__ __forceinline__ bool dev_query_op(int op) { return op == 0 || op == 1 || op == 4 || op == 7 || op == 8; }
+__device__ __forceinline__ bool dev_ref_op(int op) { return op == 0 || op == 2 || op == 3 || op == 7 || op == 8; }
+
+// First launch, one wave per pair: the lanes stride the CIGAR 64 operations at a time with a wave prefix sum over reference and
+// read consumption until the operations holding both clip positions are known; the walks outward of them (at most flank + 1
+// read bases each) are wave-uniform.
+__global__ __launch_bounds__(256) void clip_plan_kernel(ClipArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int64_t pair = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (pair >= a.n_pairs) return;                                                // wave-uniform
+    const int64_t r = a.pair_read[pair], P = a.pair_lo[pair], P2 = a.pair_hi[pair];
+    const int64_t c0 = a.cigar_off[r], n = a.cigar_off[r + 1] - c0;
+    const int64_t rs = a.ref_start[r], re = a.ref_end[r];
+    const uint32_t* cig = a.cigars + c0;
+    const bool want_l = rs <= P && P < re, want_r = rs <= P2 && P2 < re;         // :386, before either clip: P < P2
+    int64_t il = -1, rc_l = 0, qp_l = 0, ir = -1, rc_r = 0, qp_r = 0;            // the operation holding P / P2, what precedes it
+    int64_t ref_run = rs, q_run = 0;
+    for (int64_t base = 0; base < n && ((want_l && il < 0) || (want_r && ir < 0)); base += 64) {
+        const int64_t idx = base + lane;
+        const uint32_t c = idx < n ? cig[idx] : 0u;
+        const int op = c & 15u;
+        const int64_t len = c >> 4;
+        const int64_t dr = dev_ref_op(op) ? len : 0, dq = dev_query_op(op) ? len : 0;
+        int64_t sr = dr, sq = dq;
+        for (int d = 1; d < 64; d <<= 1) {                                        // inclusive wave scan
+            const int64_t ur = __shfl_up(sr, d), uq = __shfl_up(sq, d);
+            if (lane >= d) { sr += ur; sq += uq; }
+        }
+        const int64_t before = ref_run + sr - dr, after = ref_run + sr, q_before = q_run + sq - dq;
+        if (want_l && il < 0) {
+            const unsigned long long hit = __ballot(idx < n && before <= P && P < after);
+            if (hit) {
+                const int src = __ffsll(hit) - 1;
+                il = base + src; rc_l = __shfl(before, src); qp_l = __shfl(q_before, src);
+            }
+        }
+        if (want_r && ir < 0) {
+            const unsigned long long hit = __ballot(idx < n && before <= P2 && P2 < after);
+            if (hit) {
+                const int src = __ffsll(hit) - 1;
+                ir = base + src; rc_r = __shfl(before, src); qp_r = __shfl(q_before, src);
+            }
+        }
+        ref_run += __shfl(sr, 63);
+        q_run += __shfl(sq, 63);
+    }
+    ClipRec o;
+    o.a = 0; o.b = n - 1; o.q_lo = 0; o.q_hi = a.read_off[r + 1] - a.read_off[r]; o.ref_start = rs; o.ref_end = re;
+    o.first = cig[0]; o.last = cig[n - 1]; o.clipped = 0; o.fuse_l = -1; o.fuse_r = -1;
+    int64_t len_a = o.first >> 4;                                                  // current length of operation a
+    if (il >= 0) {                                                                 // left clip at P (:424-433)
+        const int op_i = cig[il] & 15u;
+        const int64_t len_i = cig[il] >> 4, k = P - rc_l + 1;                      // the left half takes k of operation il (:405)
+        int64_t count = 0, kept_ref = 0, kept_q = 0, keep = 0;
+        for (int64_t idx = il; idx >= 0; --idx) {                                  // strictClipFn, leftwards
+            const int op = cig[idx] & 15u;
+            const int64_t len = idx == il ? k : (int64_t)(cig[idx] >> 4);
+            const int64_t qn = dev_query_op(op) ? len : 0;
+            o.a = idx;
+            if (count <= a.flank && a.flank < count + qn) {                        // :288-301
+                keep = a.flank - count + 1;
+                kept_q += keep;
+                kept_ref += dev_ref_op(op) ? keep : 0;
+                break;
+            }
+            keep = len;
+            kept_q += qn;
+            kept_ref += dev_ref_op(op) ? len : 0;
+            count += qn;
+        }
+        int op_a = cig[o.a] & 15u;
+        if (op_a == 1) op_a = 4;                                                   // a kept leading I becomes S (:315-319)
+        len_a = o.a == il ? keep + (len_i - k) : keep;                             // the halves of operation il are rejoined (:457)
+        o.first = (uint32_t)(len_a << 4) | (uint32_t)op_a;
+        o.ref_start = P + 1 - kept_ref;
+        o.q_lo = qp_l + (dev_query_op(op_i) ? k : 0) - kept_q;
+        o.clipped |= 1;
+        if (o.a == o.b) o.last = o.first;
+        if (k == len_i && il + 1 < n && (int)(cig[il + 1] & 15u) == op_i) o.fuse_l = il;      // equal centre operations (:457)
+    }
+    if (ir >= 0) {                                                                 // right clip at P2 (:434-449), on that result
+        const int op_j = cig[ir] & 15u;
+        const int64_t len_j = cig[ir] >> 4, part = P2 - rc_r + 1, rest = len_j - part;   // operation ir ends where it did
+        int64_t count = 0, kept_ref = 0, kept_q = 0, keep = 0, b = -1;
+        for (int64_t idx = rest > 0 ? ir : ir + 1; idx < n; ++idx) {               // strictClipFn, rightwards
+            const int op = cig[idx] & 15u;
+            const int64_t len = idx == ir ? rest : (int64_t)(cig[idx] >> 4);
+            const int64_t qn = dev_query_op(op) ? len : 0;
+            b = idx;
+            if (count <= a.flank && a.flank < count + qn) {
+                keep = a.flank - count + 1;
+                kept_q += keep;
+                kept_ref += dev_ref_op(op) ? keep : 0;
+                break;
+            }
+            keep = len;
+            kept_q += qn;
+            kept_ref += dev_ref_op(op) ? len : 0;
+            count += qn;
+        }
+        if (b >= 0) {                                                              // an empty right half changes nothing (:434)
+            int op_b = cig[b] & 15u;
+            if (op_b == 1) op_b = 4;                                               // a kept trailing I becomes S (:321-324)
+            const int64_t len_b = b == ir ? (ir == o.a ? len_a : len_j) - rest + keep : keep;
+            o.b = b;
+            o.last = (uint32_t)(len_b << 4) | (uint32_t)op_b;
+            if (o.a == o.b) o.first = o.last;
+            o.ref_end = P2 + 1 + kept_ref;
+            o.q_hi = qp_r + (dev_query_op(op_j) ? part : 0) + kept_q;
+            o.clipped |= 2;
+            if (rest == 0 && (int)(cig[ir + 1] & 15u) == op_j) o.fuse_r = ir;
+        }
+    }
+    if (lane == 0) a.rec[pair] = o;
+}
+
+// Second launch, one wave per pair: the lanes copy the kept operations (first and last replaced) and the kept bases and
+// qualities to the pair's place in the derived set.
+__global__ __launch_bounds__(256) void clip_write_kernel(ClipArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int64_t pair = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (pair >= a.n_pairs) return;
+    const ClipRec o = a.rec[pair];
+    const int64_t r = a.pair_read[pair];
+    const uint32_t* cig = a.cigars + a.cigar_off[r];
+    uint32_t* out = a.out_cigars + a.out_cigar_off[pair];
+    auto word = [&](int64_t x) { return x == o.a ? o.first : (x == o.b ? o.last : cig[x]); };   // operation x as clipped
+    for (int64_t x = o.a + lane; x <= o.b; x += 64) {
+        if ((o.fuse_l >= 0 && x == o.fuse_l + 1) || (o.fuse_r >= 0 && x == o.fuse_r + 1)) continue;     // written with x - 1
+        uint32_t w = word(x);
+        int64_t last = x;                                                          // the run x .. last is one operation
+        if (o.fuse_l >= 0 && last == o.fuse_l) ++last;
+        if (o.fuse_r >= 0 && last == o.fuse_r) ++last;
+        for (int64_t y = x + 1; y <= last; ++y) w += word(y) & ~15u;
+        out[x - o.a - (o.fuse_l >= 0 && x > o.fuse_l ? 1 : 0) - (o.fuse_r >= 0 && x > o.fuse_r ? 1 : 0)] = w;
+    }
+    const int64_t src = a.read_off[r] + o.q_lo, dst = a.out_read_off[pair], n_bases = a.out_read_off[pair + 1] - dst;
+    for (int64_t i = lane; i < n_bases; i += 64) {
+        a.out_bases[dst + i] = a.bases[src + i];
+        a.out_quals[dst + i] = a.quals[src + i];
+    }
+}
+
+// The kept reads of every job (PileupContainerLite.__get_reads :526-570 under the cap of ReadSampler.__call__,
+// PileupDataTools.py:139-146), on the original alignments.
+void select_reads(std::vector<Job>& jobs, const ReadsIn& in, int64_t max_span, bool pacbio, JobStats& st) {
     std::unordered_set<std::pair<uint64_t, int>, PairHash> seen;
-    int64_t bits = 0;
-    for (size_t j = 0; j < jobs.size(); ++j) {
-        Job& job = jobs[j];
+    for (Job& job : jobs) {
         const int64_t span = job.fetch_hi - job.fetch_lo;
-        const double cap = span > 30 ? 1000.0 / 30.0 * (double)span : 1000.0;      // PileupDataTools.py:139-146
-        bool capped = false;
+        const double cap = pacbio ? (span > 100 ? 100.0 / 100.0 * (double)span : 100.0)
+                                  : (span > 30 ? 1000.0 / 30.0 * (double)span : 1000.0);
         seen.clear();
         const int64_t* begin = in.ref_start;
         const int64_t* it = std::lower_bound(begin, begin + in.n, job.fetch_lo - max_span);
         for (int64_t r = it - begin; r < in.n && in.ref_start[r] < job.fetch_hi; ++r) {
             if (in.ref_end[r] <= job.fetch_lo || !usable(in.flags[r], in.mapq[r])) continue;
             if (!seen.insert({in.name_hash[r], (in.flags[r] & 16) ? 1 : 0}).second) continue;
-            if (!((double)job.reads.size() < cap)) { capped = true; continue; }
+            if (!((double)job.reads.size() < cap)) { job.capped = true; continue; }
             job.reads.push_back(r);
         }
-        if (job.reads.empty()) { ++st.empty; continue; }
+        if (job.reads.empty()) ++st.empty;
+    }
+}
+
+// PacBio: the clipped copy of every (job, kept read) pair as the reads of `out`; job.reads become indices into it.
+void clip_reads(std::vector<Job>& jobs, const ReadsIn& in, const ReadSet& input, ReadSet& out, JobStats& st) {
+    std::vector<int64_t> pair_read, pair_lo, pair_hi;
+    for (Job& job : jobs)
+        for (int64_t& r : job.reads) {
+            pair_read.push_back(r);
+            pair_lo.push_back(job.fetch_lo);
+            pair_hi.push_back(job.fetch_hi);
+            r = (int64_t)pair_read.size() - 1;
+        }
+    const int64_t n = (int64_t)pair_read.size();
+    out.n = n;
+    out.v_origin = pair_read;
+    out.v_read_off.assign((size_t)n + 1, 0);
+    out.v_cigar_off.assign((size_t)n + 1, 0);
+    out.v_ref_start.resize((size_t)n);
+    out.v_ref_end.resize((size_t)n);
+    out.v_mapq.resize((size_t)n);
+    if (n > 0) {
+        DevMem m;
+        ClipArgs c{};
+        c.bases = input.d_bases; c.quals = input.d_quals; c.read_off = input.d_read_off; c.cigars = input.d_cigars;
+        c.cigar_off = input.d_cigar_off; c.ref_start = input.d_ref_start; c.ref_end = input.d_ref_end;
+        c.pair_read = m.put(pair_read.data(), pair_read.size());
+        c.pair_lo = m.put(pair_lo.data(), pair_lo.size());
+        c.pair_hi = m.put(pair_hi.data(), pair_hi.size());
+        c.n_pairs = n;
+        c.flank = kClipFlank;
+        c.rec = m.zeros<ClipRec>((size_t)n);
+        const dim3 grid((unsigned)((n + 3) / 4));
+        KernelTimer t1;
+        t1.start();
+        hipLaunchKernelGGL(clip_plan_kernel, grid, dim3(256), 0, 0, c);
+        HS_HIP(hipGetLastError());
+        st.clip_ms = t1.stop();
+        std::vector<ClipRec> rec((size_t)n);
+        HS_HIP(hipMemcpy(rec.data(), c.rec, rec.size() * sizeof(ClipRec), hipMemcpyDeviceToHost));
+        for (int64_t p = 0; p < n; ++p) {                      // the second launch writes within these: checked before it runs
+            const ClipRec& o = rec[p];
+            const int64_t r = pair_read[p], n_ops = in.cigar_off[r + 1] - in.cigar_off[r], n_bases = in.read_off[r + 1] - in.read_off[r];
+            const bool fuse_ok = (o.fuse_l < 0 || (o.fuse_l >= o.a && o.fuse_l < o.b)) && (o.fuse_r < 0 || (o.fuse_r >= o.a && o.fuse_r < o.b)) &&
+                                 (o.fuse_l < 0 || o.fuse_l != o.fuse_r);
+            if (o.a < 0 || o.b < o.a || o.b >= n_ops || o.q_lo < 0 || o.q_hi < o.q_lo || o.q_hi > n_bases || !fuse_ok)
+                raise(HELLO_ERR_ARG, "internal: the clip of read %lld leaves the read", (long long)r);
+            out.v_cigar_off[p + 1] = out.v_cigar_off[p] + (o.b - o.a + 1) - (o.fuse_l >= 0 ? 1 : 0) - (o.fuse_r >= 0 ? 1 : 0);
+            out.v_read_off[p + 1] = out.v_read_off[p] + (o.q_hi - o.q_lo);
+            out.v_ref_start[p] = o.ref_start;
+            out.v_ref_end[p] = o.ref_end;
+            out.v_mapq[p] = in.mapq[r];
+            st.clipped += o.clipped ? 1 : 0;
+        }
+        const size_t nb = (size_t)out.v_read_off[n], nc = (size_t)out.v_cigar_off[n];
+        out.d_read_off = c.out_read_off = out.mem.put(out.v_read_off.data(), out.v_read_off.size());
+        out.d_cigar_off = c.out_cigar_off = out.mem.put(out.v_cigar_off.data(), out.v_cigar_off.size());
+        out.d_bases = c.out_bases = out.mem.zeros<uint8_t>(nb);
+        out.d_quals = c.out_quals = out.mem.zeros<uint8_t>(nb);
+        out.d_cigars = c.out_cigars = out.mem.zeros<uint32_t>(nc);
+        KernelTimer t2;
+        t2.start();
+        hipLaunchKernelGGL(clip_write_kernel, grid, dim3(256), 0, 0, c);
+        HS_HIP(hipGetLastError());
+        st.clip_ms += t2.stop();
+        out.v_bases.resize(nb);
+        out.v_quals.resize(nb);
+        out.v_cigars.resize(nc);
+        if (nb) HS_HIP(hipMemcpy(out.v_bases.data(), c.out_bases, nb, hipMemcpyDeviceToHost));
+        if (nb) HS_HIP(hipMemcpy(out.v_quals.data(), c.out_quals, nb, hipMemcpyDeviceToHost));
+        if (nc) HS_HIP(hipMemcpy(out.v_cigars.data(), c.out_cigars, nc * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        out.d_ref_start = out.mem.put(out.v_ref_start.data(), out.v_ref_start.size());
+        out.d_ref_end = out.mem.put(out.v_ref_end.data(), out.v_ref_end.size());
+        const std::vector<uint8_t> table((size_t)n, 1);             // every read counts in the PacBio table, increment 1
+        out.d_table = out.mem.put(table.data(), table.size());
+    }
+    out.bases = out.v_bases.data(); out.quals = out.v_quals.data(); out.read_off = out.v_read_off.data();
+    out.cigars = out.v_cigars.data(); out.cigar_off = out.v_cigar_off.data(); out.ref_start = out.v_ref_start.data();
+    out.ref_end = out.v_ref_end.data(); out.mapq = out.v_mapq.data(); out.origin = out.v_origin.data();
+    describe_reads(out, nullptr, false);
+}
+
+// The window and differing regions of every job with reads (AlleleSearcherLite.__init__ + determineDifferingRegions(strict = True)).
+void differing_regions(std::vector<Job>& jobs, const ReadSet& in, int64_t reference_length, int mapq_threshold, HotspotArgs a,
+                       JobStats& st) {
+    const std::vector<int64_t>& plant_off = in.plant_off;
+    const std::vector<int64_t>& plant = in.plant;
+    std::vector<int64_t> flo, fhi, bit_base, creads_off{0}, creads, tile_lo, tile_ev_off{0};
+    std::vector<int32_t> tile_chunk, chunk_job;
+    int64_t bits = 0;
+    a.bases = in.d_bases; a.quals = in.d_quals; a.read_off = in.d_read_off; a.cigars = in.d_cigars; a.cigar_off = in.d_cigar_off;
+    a.ref_start = in.d_ref_start; a.ref_end = in.d_ref_end; a.table = in.d_table;
+    for (size_t j = 0; j < jobs.size(); ++j) {
+        Job& job = jobs[j];
+        const bool capped = job.capped;
+        if (job.reads.empty()) continue;
         int64_t ws = job.start, we = INT64_MIN;                                      // AlleleSearcherLite.py:135-151
         for (int64_t r : job.reads) { ws = std::min(ws, in.ref_start[r]); we = std::max(we, in.ref_end[r]); }
         ws -= 10;
@@ -443,60 +796,18 @@ int hello_candidates_find(const uint8_t* bases, const uint8_t* quals, const int6
     *out = nullptr;
     if (n_reads < 0 || n_positions < 0 || reference_length < 0 || feature_length <= 0)
         return set_last_error(HELLO_ERR_ARG, "negative count");
-    if (options & (HELLO_HOTSPOTS_PACBIO | HELLO_HOTSPOTS_TWO_BAMS | HELLO_HOTSPOTS_HYBRID))
+    if (options & (HELLO_HOTSPOTS_TWO_BAMS | HELLO_HOTSPOTS_HYBRID))
         return set_last_error(HELLO_ERR_ARG, "candidate sites are built from one Illumina BAM: PacBio reads, two BAMs and hybrid "
                                              "hotspots need the PacBio reassembly and read clipping, which this library does not have");
-    if (options) return set_last_error(HELLO_ERR_ARG, "options %d", options);
+    if (options & ~HELLO_HOTSPOTS_PACBIO) return set_last_error(HELLO_ERR_ARG, "options %d", options);
+    const bool pacbio = options == HELLO_HOTSPOTS_PACBIO;
     for (int64_t i = 1; i < n_positions; ++i)
         if (positions[i] < positions[i - 1]) return set_last_error(HELLO_ERR_ARG, "position %lld: positions are not sorted", (long long)i);
 
-    // ---- validation of every usable read (the kernels read within its bases), its planting positions, and what
-    // Read::_get_read_mapping knows about it as a whole: last_position, partial_start, partial_stop
-    int64_t max_span = 0;
-    std::vector<int64_t> plant_off(n_reads + 1, 0), plant, last_pos(n_reads, -1);
-    std::vector<uint8_t> pflags(n_reads, 0);
-    for (int64_t r = 0; r < n_reads; ++r) {
-        plant_off[r + 1] = plant_off[r];
-        if (r > 0 && ref_starts[r] < ref_starts[r - 1])
-            return set_last_error(HELLO_ERR_ARG, "read %lld: reads are not coordinate-sorted (the BAM must be)", (long long)r);
-        if (read_offsets[r + 1] < read_offsets[r] || cigar_offsets[r + 1] < cigar_offsets[r])
-            return set_last_error(HELLO_ERR_SHAPE, "read %lld: offsets decrease", (long long)r);
-        if (!usable(flags[r], mapq[r])) continue;
-        int64_t qlen = 0, rlen = 0;
-        const int64_t c0 = cigar_offsets[r], c1 = cigar_offsets[r + 1];
-        bool prev = false, aligned = false;
-        for (int64_t c = c0; c < c1; ++c) {
-            const int op = cigars[c] & 15;
-            const int64_t len = cigars[c] >> 4;
-            if (op > 8) return set_last_error(HELLO_ERR_ARG, "read %lld: CIGAR operation %d", (long long)r, op);
-            if (len == 0) return set_last_error(HELLO_ERR_ARG, "read %lld: zero-length CIGAR operation", (long long)r);
-            if (op == 1 || op == 2) plant.push_back(ref_starts[r] + rlen - 1);
-            if (op == 0 || op == 1 || op == 4 || op == 7 || op == 8) qlen += len;
-            if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) rlen += len;
-            if (op == 0 || op == 2 || op == 7 || op == 8) { last_pos[r] = ref_starts[r] + rlen - 1; prev = true; aligned = true; }
-            else if (op == 3) prev = false;
-            else if (op == 1) {
-                if (!prev) pflags[r] |= 1;
-                else if (c == c1 - 1) pflags[r] |= 2;
-                prev = true;
-                aligned = true;
-            } else if (op == 4 && aligned) {                       // a clip inside the alignment would split a region's read bytes
-                for (int64_t k = c + 1; k < c1; ++k)
-                    if ((cigars[k] & 15) != 4 && (cigars[k] & 15) != 5)
-                        return set_last_error(HELLO_ERR_ARG, "read %lld: a soft clip between aligned operations", (long long)r);
-            }
-        }
-        plant_off[r + 1] = (int64_t)plant.size();
-        if (qlen != read_offsets[r + 1] - read_offsets[r])
-            return set_last_error(HELLO_ERR_SHAPE, "read %lld: CIGAR query length %lld, %lld bases", (long long)r, (long long)qlen,
-                                  (long long)(read_offsets[r + 1] - read_offsets[r]));
-        if (ref_starts[r] < 0 || ref_ends[r] != ref_starts[r] + std::max<int64_t>(rlen, 1))
-            return set_last_error(HELLO_ERR_SHAPE, "read %lld: ref_end does not match its CIGAR", (long long)r);
-        for (int64_t i = read_offsets[r]; i < read_offsets[r + 1]; ++i)
-            if (!strchr("=ACMGRSVTWYHKDBN", bases[i]) || !bases[i])
-                return set_last_error(HELLO_ERR_ARG, "read %lld: base '%c' is not a BAM base code", (long long)r, bases[i]);
-        max_span = std::max(max_span, ref_ends[r] - ref_starts[r]);
-    }
+    ReadSet input;                                     // describe_reads: validation, planting positions, last_position, partials
+    input.bases = bases; input.quals = quals; input.read_off = read_offsets; input.cigars = cigars; input.cigar_off = cigar_offsets;
+    input.ref_start = ref_starts; input.ref_end = ref_ends; input.mapq = mapq; input.n = n_reads;
+    const int64_t max_span = describe_reads(input, flags, pacbio);
     const ReadsIn in{bases, quals, read_offsets, cigars, cigar_offsets, ref_starts, ref_ends, mapq, flags, name_hash, n_reads};
 
     // ---- pass 1 plan: hotspotsReader (PileupDataTools.py:207-244) and candidateReader's fetch (:347-352)
@@ -531,21 +842,24 @@ int hello_candidates_find(const uint8_t* bases, const uint8_t* quals, const int6
         HotspotArgs a{};
         const int64_t nb = read_offsets[n_reads], nc = cigar_offsets[n_reads];
         std::vector<uint8_t> table(n_reads, 0);                      // every read counts in the Illumina table
-        a.bases = m.put(bases, (size_t)nb);
-        a.quals = m.put(quals, (size_t)nb);
-        a.read_off = m.put(read_offsets, (size_t)n_reads + 1);
-        a.cigars = m.put(cigars, (size_t)nc);
-        a.cigar_off = m.put(cigar_offsets, (size_t)n_reads + 1);
-        a.ref_start = m.put(ref_starts, (size_t)n_reads);
-        a.ref_end = m.put(ref_ends, (size_t)n_reads);
-        a.table = m.put(table.data(), table.size());
+        input.d_bases = m.put(bases, (size_t)nb);
+        input.d_quals = m.put(quals, (size_t)nb);
+        input.d_read_off = m.put(read_offsets, (size_t)n_reads + 1);
+        input.d_cigars = m.put(cigars, (size_t)nc);
+        input.d_cigar_off = m.put(cigar_offsets, (size_t)n_reads + 1);
+        input.d_ref_start = m.put(ref_starts, (size_t)n_reads);
+        input.d_ref_end = m.put(ref_ends, (size_t)n_reads);
+        input.d_table = m.put(table.data(), table.size());
+        ReadSet clipped1, clipped2;                                  // PacBio: the clipped reads of pass 1 and of pass 2
         a.ref_lo = 0;
         a.ref_len = reference_length;
         a.ref = m.put(reference, (size_t)reference_length);
         a.q_threshold = q_threshold;
         a.hybrid = 0;
 
-        differing_regions(jobs1, in, max_span, plant_off, plant, reference_length, mapq_threshold, a, st1);
+        select_reads(jobs1, in, max_span, pacbio, st1);
+        if (pacbio) clip_reads(jobs1, in, input, clipped1, st1);
+        differing_regions(jobs1, pacbio ? clipped1 : input, reference_length, mapq_threshold, a, st1);
         std::vector<std::pair<int64_t, int64_t>> locations;
         for (const Job& j : jobs1)
             for (const auto& reg : j.regions) {
@@ -580,7 +894,10 @@ int hello_candidates_find(const uint8_t* bases, const uint8_t* quals, const int6
             close();
         }
         n_clusters = (int64_t)jobs2.size();
-        differing_regions(jobs2, in, max_span, plant_off, plant, reference_length, mapq_threshold, a, st2);
+        select_reads(jobs2, in, max_span, pacbio, st2);                // a fresh fetch from the input reads (trainDataTools.py:1059-1065)
+        if (pacbio) clip_reads(jobs2, in, input, clipped2, st2);
+        const ReadSet& rs2 = pacbio ? clipped2 : input;              // the reads of the clusters, of the alleles and of the shard
+        differing_regions(jobs2, rs2, reference_length, mapq_threshold, a, st2);
 
         // ---- allele stage plan: record slots = reads x the regions they overlap, counted exactly
         std::vector<int64_t> cl_read_off{0}, cl_reads, cl_reg_off{0}, reg_start, reg_stop, rd_rec_off{0}, slot_g, slot_x;
@@ -597,9 +914,9 @@ int hello_candidates_find(const uint8_t* bases, const uint8_t* quals, const int6
             for (int64_t r : j.reads) {
                 const int64_t x = (int64_t)cl_reads.size();
                 cl_reads.push_back(r);
-                if (last_pos[r] >= 0)                                  // Read.cpp:88: start <= last_position && reference_start < stop
+                if (rs2.last_pos[r] >= 0)                              // Read.cpp:88: start <= last_position && reference_start < stop
                     for (int64_t g = 0; g < ng; ++g)
-                        if (j.regions[g].first <= last_pos[r] && ref_starts[r] < j.regions[g].second) {
+                        if (j.regions[g].first <= rs2.last_pos[r] && rs2.ref_start[r] < j.regions[g].second) {
                             slot_g.push_back(gbase + g);
                             slot_x.push_back(x);
                         }
@@ -621,11 +938,11 @@ int hello_candidates_find(const uint8_t* bases, const uint8_t* quals, const int6
         std::vector<int64_t> al_rep((size_t)n_slots), sup((size_t)n_slots);
         if (n_cl > 0 && n_slots > 0) {
             AlleleArgs b{};
-            b.bases = a.bases; b.quals = a.quals; b.read_off = a.read_off; b.cigars = a.cigars; b.cigar_off = a.cigar_off;
-            b.ref_start = a.ref_start;
-            b.mapq = m.put(mapq, (size_t)n_reads);
-            b.last_pos = m.put(last_pos.data(), last_pos.size());
-            b.pflags = m.put(pflags.data(), pflags.size());
+            b.bases = rs2.d_bases; b.quals = rs2.d_quals; b.read_off = rs2.d_read_off; b.cigars = rs2.d_cigars;
+            b.cigar_off = rs2.d_cigar_off; b.ref_start = rs2.d_ref_start;
+            b.mapq = m.put(rs2.mapq, (size_t)rs2.n);
+            b.last_pos = m.put(rs2.last_pos.data(), rs2.last_pos.size());
+            b.pflags = m.put(rs2.pflags.data(), rs2.pflags.size());
             b.cl_read_off = m.put(cl_read_off.data(), cl_read_off.size());
             b.cl_reads = m.put(cl_reads.data(), cl_reads.size());
             b.cl_reg_off = m.put(cl_reg_off.data(), cl_reg_off.size());
@@ -685,7 +1002,7 @@ int hello_candidates_find(const uint8_t* bases, const uint8_t* quals, const int6
             int64_t at = reg_list_off[g];
             for (int32_t k = 0; k < n_alleles[g]; ++k) {
                 const int64_t rep = al_rep[reg_list_off[g] + k];
-                const uint8_t* t = bases + read_offsets[cl_reads[slot_x[rep]]] + rec_q0[rep];
+                const uint8_t* t = rs2.bases + rs2.read_off[cl_reads[slot_x[rep]]] + rec_q0[rep];
                 o.allele_text.insert(o.allele_text.end(), t, t + rec_len[rep]);
                 o.allele_text_off.push_back((int64_t)o.allele_text.size());
                 const int32_t n = al_count[reg_list_off[g] + k];
@@ -693,8 +1010,8 @@ int hello_candidates_find(const uint8_t* bases, const uint8_t* quals, const int6
                 for (int32_t i = 0; i < n; ++i) {
                     const int64_t r = sup[at + i];
                     o.read_index.push_back(r);
-                    o.read_off.push_back(o.read_off.back() + (read_offsets[r + 1] - read_offsets[r]));
-                    o.cigar_off.push_back(o.cigar_off.back() + (cigar_offsets[r + 1] - cigar_offsets[r]));
+                    o.read_off.push_back(o.read_off.back() + (rs2.read_off[r + 1] - rs2.read_off[r]));
+                    o.cigar_off.push_back(o.cigar_off.back() + (rs2.cigar_off[r + 1] - rs2.cigar_off[r]));
                 }
                 at += n;
             }
@@ -711,19 +1028,20 @@ int hello_candidates_find(const uint8_t* bases, const uint8_t* quals, const int6
         auto copy = [&](int64_t i0, int64_t i1) {
             for (int64_t i = i0; i < i1; ++i) {
                 const int64_t r = o.read_index[i];
-                std::copy(bases + read_offsets[r], bases + read_offsets[r + 1], o.bases.begin() + o.read_off[i]);
-                std::copy(quals + read_offsets[r], quals + read_offsets[r + 1], o.quals.begin() + o.read_off[i]);
-                std::copy(cigars + cigar_offsets[r], cigars + cigar_offsets[r + 1], o.cigars.begin() + o.cigar_off[i]);
-                o.ref_start[i] = ref_starts[r];
-                o.mapq[i] = mapq[r];
-                o.orientation[i] = (flags[r] & 16) ? -1 : 1;
-                o.hp[i] = hp[r];
+                std::copy(rs2.bases + rs2.read_off[r], rs2.bases + rs2.read_off[r + 1], o.bases.begin() + o.read_off[i]);
+                std::copy(rs2.quals + rs2.read_off[r], rs2.quals + rs2.read_off[r + 1], o.quals.begin() + o.read_off[i]);
+                std::copy(rs2.cigars + rs2.cigar_off[r], rs2.cigars + rs2.cigar_off[r + 1], o.cigars.begin() + o.cigar_off[i]);
+                o.ref_start[i] = rs2.ref_start[r];
+                o.mapq[i] = rs2.mapq[r];
+                o.orientation[i] = (flags[rs2.input(r)] & 16) ? -1 : 1;
+                o.hp[i] = hp[rs2.input(r)];
             }
         };
         std::vector<std::thread> pool;
         for (int t = 1; t < n_threads; ++t) pool.emplace_back(copy, R * t / n_threads, R * (t + 1) / n_threads);
         copy(0, R / n_threads);
         for (auto& th : pool) th.join();
+        for (int64_t& r : o.read_index) r = rs2.input(r);                      // the input read of a clipped read
         ms_gather = std::chrono::duration<double, std::milli>(clock::now() - tg).count();
     }
     const double ms_total = std::chrono::duration<double, std::milli>(clock::now() - t0).count();
@@ -731,7 +1049,8 @@ int hello_candidates_find(const uint8_t* bases, const uint8_t* quals, const int6
         (double)jobs1.size(), (double)st1.empty, (double)st1.bounds, (double)st1.capped, (double)(res->regions1.size() / 2),
         (double)n_clusters, (double)st2.empty, (double)st2.bounds, (double)st2.capped, (double)(res->regions2.size() / 2),
         (double)res->start.size(), (double)sites_oob, (double)res->reads_per_allele.size(), (double)res->read_index.size(),
-        (double)n_slots, (double)st1.ms, (double)st2.ms, (double)allele_ms, ms_gather, ms_total};
+        (double)n_slots, (double)st1.ms, (double)st2.ms, (double)allele_ms, ms_gather, ms_total,
+        (double)st1.clip_ms + (double)st2.clip_ms, (double)(st1.clipped + st2.clipped)};
     std::copy(st, st + HELLO_CANDIDATES_STATS, res->stats);
     *out = res.release();
     return HELLO_OK;

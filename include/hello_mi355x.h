@@ -308,7 +308,8 @@ int hello_hotspots_positions(const hello_hotspots* hotspots, const int64_t** pos
 int hello_hotspots_stats(const hello_hotspots* hotspots, double* stats);
 void hello_hotspots_free(hello_hotspots* hotspots);
 
-/* Stands in for: python/caller_calling.py main (:795-843) up to the featurizer, for ONE Illumina BAM -- python/PileupDataTools.py
+/* Stands in for: python/caller_calling.py main (:795-843) up to the featurizer, for ONE Illumina BAM or ONE PacBio BAM --
+ * python/PileupDataTools.py
  * hotspotsReader and candidateReader (:207-244,302-384: pass 1, one strict searcher per active region), python/trainDataTools.py
  * clusterLocations and data (:477-514,1039-1103: pass 2, one strict searcher per cluster whose own differing regions are the
  * sites), get_labeled_candidates and createTensors (:557-640,880-977), c++/src/Read.cpp:4-172 (a read's allele in a region) and
@@ -319,12 +320,29 @@ void hello_hotspots_free(hello_hotspots* hotspots);
  *   reads: the arrays of hello_bam_fetch, coordinate-sorted, holding every read that overlaps [first position - 90, last
  *          position + 90) (pass 1 fetches 75 bp either side of [first - 15, last + 15]; more reads do no harm); hp = selector
  *          HELLO_BAM_HP.  positions: the sorted positions of a hotspot / shard file on this chromosome.
- *   options: 0.  HELLO_HOTSPOTS_PACBIO, HELLO_HOTSPOTS_TWO_BAMS and HELLO_HOTSPOTS_HYBRID are refused (HELLO_ERR_ARG): those paths
- *          need the PacBio reassembly and read clipping.
- * Three kernel launches on `device` (candidates.hip: differing regions of pass 1, of pass 2, alleles and supports); the reads of
- * every allele are gathered on at most 16 host threads.  The result holds the arrays of a shard (hello_amd/shards.py) without
- * the chromosome table, plus read_index (the input read of every gathered read) and the differing regions of both passes as
- * (start, stop) pairs. */
+ *   options: 0 (Illumina reads) or HELLO_HOTSPOTS_PACBIO (PacBio reads, below).  HELLO_HOTSPOTS_TWO_BAMS and
+ *          HELLO_HOTSPOTS_HYBRID are refused (HELLO_ERR_ARG): those paths need the two-BAM reassembly.
+ * Three kernel launches on `device` with options == 0 (candidates.hip: differing regions of pass 1, of pass 2, alleles and
+ * supports), seven with HELLO_HOTSPOTS_PACBIO (two clip launches before the differing regions of either pass); the reads of
+ * every allele are gathered on at most 16 host threads.
+ * HELLO_HOTSPOTS_PACBIO (caller_calling.py:795-843 with one PacBio BAM: readRate (100, 100), pacbio = True, clipFlank = 200, no
+ * reassembly): a searcher keeps at most span reads when its fetch interval [lo, hi) is longer than 100 bases (span = hi - lo),
+ * else 100 -- the first in file order, as for Illumina.  Reads are selected on their original alignment; then a copy of every
+ * kept read is strictly clipped (python/PileupContainerLite.py:255-468,554-573), left at lo and then right at hi, the right clip
+ * seeing the left clip's result, and the window tests, counting, alleles, supports and the returned reads (bases, quals, cigars,
+ * ref_start) are those of the clipped copies of pass 2; read_index still names the input read.  A clip at position p happens
+ * only while reference_start <= p < reference_end.  The CIGAR is split inside the operation holding p, whose left half ends at
+ * p.  From the split outwards operations are kept while fewer than 201 read bases (M I S = X) are counted; the operation in
+ * which the count passes 200 is kept up to the 201st base (the left clip counts the base at p, the right clip starts behind
+ * it) and everything beyond is discarded: reference_start grows / reference_end shrinks by the discarded M = X D N lengths, the
+ * bases and qualities lose the discarded M I S = X lengths, hard clips consume nothing.  An outermost kept I becomes S, also
+ * when nothing was discarded, and the two halves are rejoined, equal operations at the centre merged into one (the halves of
+ * the split operation, or 20M 20M when p is the first one's last base).  Every read counts in the PacBio table (increment 1;
+ * an indel needs 2 reads).  A read without an operation on the reference is refused (HELLO_ERR_ARG); the refusal of a soft
+ * clip between aligned operations applies to the clipped CIGARs.  The two clip launches of a pass run one wave per
+ * (searcher, read): the clip's plan, then the clipped operations, bases and qualities.
+ * The result holds the arrays of a shard (hello_amd/shards.py) without the chromosome table, plus read_index (the input read
+ * of every gathered read) and the differing regions of both passes as (start, stop) pairs. */
 enum {
     HELLO_CAND_START = 0, HELLO_CAND_STOP = 1, HELLO_CAND_WINDOW_START = 2, HELLO_CAND_REF_OFF = 3,      /* int64 */
     HELLO_CAND_REF = 4,                                                                                  /* uint8 */
@@ -341,7 +359,7 @@ enum {
     HELLO_CAND_HP = 17,                                                                                  /* uint8 */
     HELLO_CAND_READ_INDEX = 18, HELLO_CAND_REGIONS_PASS1 = 19, HELLO_CAND_REGIONS_PASS2 = 20             /* int64 */
 };
-#define HELLO_CANDIDATES_STATS 20
+#define HELLO_CANDIDATES_STATS 22
 typedef struct hello_candidates hello_candidates;
 int hello_candidates_find(const uint8_t* bases, const uint8_t* quals, const int64_t* read_offsets,
                           const uint32_t* cigars, const int64_t* cigar_offsets, const int64_t* ref_starts,
@@ -354,7 +372,8 @@ int hello_candidates_array(const hello_candidates* candidates, int32_t which, co
 /* stats[HELLO_CANDIDATES_STATS]: active regions, without reads, out of bounds, at the read cap, differing regions of pass 1;
  * clusters, without reads, out of bounds, at the read cap, differing regions of pass 2; sites, sites whose feature window leaves
  * the chromosome, alleles, reads gathered, record slots; ms of the pass-1 kernel, the pass-2 kernel, the allele kernel (HIP
- * events), the host gather, the whole call */
+ * events), the host gather, the whole call; ms of the two clip kernels of both passes, (searcher, read) pairs whose read a clip
+ * applied to (both 0 without HELLO_HOTSPOTS_PACBIO) */
 int hello_candidates_stats(const hello_candidates* candidates, double* stats);
 void hello_candidates_free(hello_candidates* candidates);
 
