@@ -777,7 +777,8 @@ def compile_model(spec: ns.ModelSpec, state, fused: bool = True, winograd: bool 
     the SEGSUM / CONCAT ops (tests compare the two).
     ``lanes``: the program for SMALL launches -- the same ops, but the independent chains of a two-technology / three-expert model
     carry lane numbers (``assign_lanes``) and no two values share a buffer, so that the engine may run the chains concurrently
-    (a launch of a few sites is latency-bound: every chain is a handful of workgroups).  ``n_lanes`` == 1 for single-chain models."""
+    (a launch of a few sites is latency-bound: every chain is a handful of workgroups).  ``n_lanes`` is what ``assign_lanes`` used: 1 where every op continues its producer's
+    lane (single_tech), but a single-chain model whose ops fan out gets lanes too (single_tech_softplus 2, single_tech_layernorm 4)."""
     low = _Lowering(spec, state, fused, winograd, arithmetic)
     n_experts, has_meta = low.lower()
     if arithmetic != "fp32" and not low.used_bf16x3:

@@ -122,7 +122,12 @@ struct hello_engine {
     DevBuf d_logits, d_meta, d_post, d_rcl0, d_rcl1;
     DevBuf d_out_small;        // staged host-output calls too large to be written in place: logits | meta | posteriors in ONE block (one copy back)
     PinnedBuf h_io;            // small host calls: inputs and outputs pass through pinned memory (pageable copies stall)
-    DevBuf d_partial[2];             // fused read convolver partial sums, per read technology (their ops may run on different lanes)
+    // fused read convolver partial sums: scratch its kernels write and readconv_finalize_kernel reads back, outside the program's
+    // buffers -- so the lane analysis cannot order it.  Sequential program (one stream): one block per read technology, shared by that
+    // technology's convolvers (a separate-meta model has two).  Laned program: every fused op its own block, since two convolvers of
+    // one technology sit on different lanes with no event between them.
+    std::vector<DevBuf> d_partial;
+    std::vector<int> partial_of;     // [n_ops]: the block of d_partial op i uses (-1: not a fused read convolver)
     // lanes (programs for small launches: HELLO_FLAG_LANE_*): streams 1.., per-op events where another lane reads the op's output
     int n_lanes = 1;
     std::vector<hipStream_t> lane_streams;      // [n_lanes], entry 0 unused (= the call's stream)
@@ -403,6 +408,52 @@ int validate_model(const hello_model_desc* d) {
     return 0;
 }
 
+// Lanes: which op waits for which, from the buffer ids alone (host work: a malformed laned program is refused before any device is
+// looked up).  A laned program writes every scratch buffer from one op and reads none before its writer.  What an op touches beyond
+// its buffers must be private to the op (hello_engine::d_partial).
+struct LanePlan {
+    int n_lanes = 1;
+    std::vector<std::vector<int>> op_waits;     // [n_ops]: ops on OTHER lanes whose output this op reads
+    std::vector<int> lane_tail;                 // [n_lanes]: the last op of each lane
+    std::vector<char> read_elsewhere;           // [n_ops]: another lane reads this op's output
+};
+
+int lane_of_op(const hello_op& o) { return (o.flags & HELLO_FLAG_LANE_MASK) >> HELLO_FLAG_LANE_SHIFT; }
+
+int analyse_lanes(const hello_model_desc* d, LanePlan& plan) {
+    const int n_ops = d->n_ops;
+    auto lane_of = [&](int i) { return lane_of_op(d->ops[i]); };
+    for (int i = 0; i < n_ops; ++i) plan.n_lanes = lane_of(i) + 1 > plan.n_lanes ? lane_of(i) + 1 : plan.n_lanes;
+    if (plan.n_lanes == 1) return 0;
+    std::vector<int> writer(d->n_buffers, -1);
+    plan.op_waits.assign(n_ops, {});
+    plan.lane_tail.assign(plan.n_lanes, -1);
+    plan.read_elsewhere.assign(n_ops, 0);
+    for (int i = 0; i < n_ops; ++i) {
+        const hello_op& o = d->ops[i];
+        const bool front = o.kind == HELLO_OP_XATTN_FRONT;          // writes dst AND res; every other op reads res
+        const int reads[3] = {o.src0, o.src1, front ? HELLO_BUF_NONE : o.res};
+        for (int b : reads) {
+            if (b < HELLO_BUF_FIRST_SCRATCH) continue;
+            const int w = writer[b];
+            if (w < 0) return fail(HELLO_ERR_MODEL, "laned program: op %d reads buffer %d before any op wrote it", i, b);
+            if (lane_of(w) != lane_of(i)) {
+                plan.op_waits[i].push_back(w);
+                plan.read_elsewhere[w] = 1;
+            }
+        }
+        const int writes[2] = {o.kind == HELLO_OP_HEAD ? HELLO_BUF_NONE : o.dst, front ? o.res : HELLO_BUF_NONE};
+        for (int b : writes) {
+            if (b < HELLO_BUF_FIRST_SCRATCH) continue;
+            if (writer[b] >= 0)
+                return fail(HELLO_ERR_MODEL, "laned program: ops %d and %d both write buffer %d (a program with lanes may not reuse buffers)", writer[b], i, b);
+            writer[b] = i;
+        }
+        plan.lane_tail[lane_of(i)] = i;
+    }
+    return 0;
+}
+
 template <typename T>
 T* carve(char*& cursor, size_t count) {
     T* p = reinterpret_cast<T*>(cursor);
@@ -422,6 +473,8 @@ int hello_engine_create(const hello_model_desc* desc, const void* folded_weights
     if (!out) return fail(HELLO_ERR_ARG, "out is NULL");
     *out = nullptr;
     if (int rc = validate_model(desc)) return rc;
+    LanePlan lanes;
+    if (int rc = analyse_lanes(desc, lanes)) return rc;
     if (!folded_weights || nbytes == 0 || (nbytes % 4)) return fail(HELLO_ERR_ARG, "bad weight blob");
     int n_dev = 0;
     if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0)
@@ -487,43 +540,22 @@ int hello_engine_create(const hello_model_desc* desc, const void* folded_weights
         hello_engine_destroy(e);
         return fail(HELLO_ERR_HIP, "engine setup failed: %s", hipGetErrorString(err));
     }
-    // lanes: which op waits for which, from the buffer ids (a laned program writes every scratch buffer from one op)
+    // fused read convolver partial blocks: per technology on one stream, per op in a laned program (see d_partial)
     const int n_ops = (int)e->ops.size();
-    auto lane_of = [&](int i) { return (e->ops[i].flags & HELLO_FLAG_LANE_MASK) >> HELLO_FLAG_LANE_SHIFT; };
-    for (int i = 0; i < n_ops; ++i) e->n_lanes = lane_of(i) + 1 > e->n_lanes ? lane_of(i) + 1 : e->n_lanes;
+    e->n_lanes = lanes.n_lanes;
+    e->partial_of.assign(n_ops, -1);
+    int n_partial = e->n_lanes > 1 ? 0 : 2;
+    for (int i = 0; i < n_ops; ++i)
+        if (e->ops[i].kind == HELLO_OP_READCONV_FUSED)
+            e->partial_of[i] = e->n_lanes > 1 ? n_partial++ : (e->ops[i].seg == HELLO_SEG_READS1_TO_ALLELES ? 1 : 0);
+    e->d_partial.resize(n_partial);
+    // lanes: streams 1.., an event after every op whose output another lane reads and after a lane's last op
     if (e->n_lanes > 1) {
-        std::vector<int> writer(desc->n_buffers, -1);
-        e->op_waits.assign(n_ops, {});
+        auto lane_of = [&](int i) { return lane_of_op(e->ops[i]); };
+        e->op_waits = std::move(lanes.op_waits);
+        e->lane_tail = std::move(lanes.lane_tail);
+        const std::vector<char>& read_elsewhere = lanes.read_elsewhere;
         e->op_done.assign(n_ops, nullptr);
-        e->lane_tail.assign(e->n_lanes, -1);
-        std::vector<char> read_elsewhere(n_ops, 0);
-        for (int i = 0; i < n_ops; ++i) {
-            const hello_op& o = e->ops[i];
-            const bool front = o.kind == HELLO_OP_XATTN_FRONT;          // writes dst AND res; every other op reads res
-            const int reads[3] = {o.src0, o.src1, front ? HELLO_BUF_NONE : o.res};
-            for (int b : reads) {
-                if (b < HELLO_BUF_FIRST_SCRATCH) continue;
-                const int w = writer[b];
-                if (w < 0) {
-                    hello_engine_destroy(e);
-                    return fail(HELLO_ERR_MODEL, "laned program: op %d reads buffer %d before any op wrote it", i, b);
-                }
-                if (lane_of(w) != lane_of(i)) {
-                    e->op_waits[i].push_back(w);
-                    read_elsewhere[w] = 1;
-                }
-            }
-            const int writes[2] = {o.kind == HELLO_OP_HEAD ? HELLO_BUF_NONE : o.dst, front ? o.res : HELLO_BUF_NONE};
-            for (int b : writes) {
-                if (b < HELLO_BUF_FIRST_SCRATCH) continue;
-                if (writer[b] >= 0) {
-                    hello_engine_destroy(e);
-                    return fail(HELLO_ERR_MODEL, "laned program: ops %d and %d both write buffer %d (a program with lanes may not reuse buffers)", writer[b], i, b);
-                }
-                writer[b] = i;
-            }
-            e->lane_tail[lane_of(i)] = i;
-        }
         e->lane_streams.assign(e->n_lanes, nullptr);
         for (int l = 1; l < e->n_lanes && err == hipSuccess; ++l) err = hipStreamCreateWithFlags(&e->lane_streams[l], hipStreamNonBlocking);
         for (int i = 0; i < n_ops && err == hipSuccess; ++i)
@@ -554,8 +586,7 @@ void hello_engine_destroy(hello_engine* e) {
     e->h_io.release();
     e->d_rcl0.release();
     e->d_rcl1.release();
-    e->d_partial[0].release();
-    e->d_partial[1].release();
+    for (auto& b : e->d_partial) b.release();
     for (hipStream_t st : e->lane_streams)
         if (st) (void)hipStreamDestroy(st);
     for (hipEvent_t ev : e->op_done)
@@ -952,9 +983,9 @@ int hello_engine_forward(hello_engine* e, const uint8_t* reads0, const int32_t* 
         const int64_t Rmax = R0 > R1 ? R0 : R1;
         const size_t slots = (size_t)A + (size_t)((Rmax + G - 1) / G) + 1;
         const size_t frame_ch = (e->wide_trunk[0] || e->wide_trunk[1]) ? 128 : 64;
-        for (const hello_op& o : e->ops)
-            if (o.kind == HELLO_OP_READCONV_FUSED)
-                if (int rc = ensure(e->d_partial[o.seg == HELLO_SEG_READS1_TO_ALLELES ? 1 : 0], slots * hello::readconv_frame_rows(d.window) * frame_ch * sizeof(float))) return rc;
+        for (size_t i = 0; i < e->ops.size(); ++i)
+            if (e->partial_of[i] >= 0)
+                if (int rc = ensure(e->d_partial[e->partial_of[i]], slots * hello::readconv_frame_rows(d.window) * frame_ch * sizeof(float))) return rc;
     }
     // experts without a head (ensemble of two: third expert is all-zero logits, :244) stay zero
     if (d.n_experts == 3) HIP_TRY(hipMemsetAsync(d_logits, 0, logit_bytes, stream));
@@ -1106,7 +1137,7 @@ int hello_engine_forward(hello_engine* e, const uint8_t* reads0, const int32_t* 
                 }
                 if (!ptr(o.src0)) return fail(HELLO_ERR_ARG, "op %d reads an input the caller did not supply", op_index);
                 a.w = e->d_weights + o.w_off;
-                a.partial = (float*)e->d_partial[t1 ? 1 : 0].p;
+                a.partial = (float*)e->d_partial[e->partial_of[op_index]].p;
                 a.allele_of_read = t1 ? e->allele_of_read1 : e->allele_of_read0;
                 a.slot_of_group = t1 ? e->group_slot1 : e->group_slot0;
                 a.n_reads = t1 ? R1 : R0;
@@ -1164,7 +1195,7 @@ int hello_engine_forward(hello_engine* e, const uint8_t* reads0, const int32_t* 
                     if (a.stamps)                             // both launches went out: the layout debug_read_stamps reports is theirs
                         for (int i = 0; i < 5; ++i) e->stamp_layout[i] = stamp_lay[i];
                 }
-                HIP_TRY(hello::launch_readconv_finalize((const float*)e->d_partial[t1 ? 1 : 0].p, t1 ? e->slot_off1 : e->slot_off0,
+                HIP_TRY(hello::launch_readconv_finalize((const float*)e->d_partial[e->partial_of[op_index]].p, t1 ? e->slot_off1 : e->slot_off0,
                                                         (float*)ptr(o.dst), A, o.lout, o.cout, stream));
                 break;
             }

@@ -124,7 +124,12 @@ typedef enum hello_op_kind {
  * compressor + expert per technology, the combined expert, the meta network); a launch of a few sites is latency-bound -- every chain
  * is a handful of workgroups -- so a program for SMALL launches puts the chains on lanes and the engine runs them concurrently,
  * ordering lanes with events wherever an op reads what another lane wrote (derived from the buffer ids).  Such a program must write
- * every scratch buffer from ONE op (no buffer reuse): hello_engine_create refuses it otherwise.  Same kernels, same bits. */
+ * every scratch buffer from ONE op (no buffer reuse) and read none before its writer: hello_engine_create refuses it otherwise
+ * (HELLO_ERR_MODEL, decided on the host before any device is looked up).  The buffer ids are ALL the engine orders lanes by, so
+ * whatever device memory an op touches beyond its hello_op buffers is private to that op in a laned engine: the fused read
+ * convolver's partial sums get one block per READCONV_FUSED op there (two convolvers of one technology -- readConv0 and
+ * readConv0Meta of a separate-meta model -- run on different lanes with no event between them); the sequential program, one
+ * stream, keeps one block per read technology.  Same kernels, same bits. */
 #define HELLO_FLAG_LANE_SHIFT 8
 #define HELLO_FLAG_LANE_MASK  (7 << HELLO_FLAG_LANE_SHIFT)
 #define HELLO_MAX_LANES 8

@@ -170,6 +170,46 @@ def test_issue_programs_are_refused(layered):
         assert msg is not None and "(status -3)" in msg, msg
 
 
+# ---- laned programs: the lane analysis runs on the host, before the device lookup ----------------------------------------------
+@pytest.fixture(scope="module")
+def laned():
+    spec = ns.build("hybrid_no_ensemble")
+    prog = cp.compile_model(spec, weights.synth_state(spec, seed=21), lanes=True)
+    assert prog.n_lanes == 3 and _create(prog) is None
+    return prog
+
+
+def test_refuses_a_laned_program_that_reads_a_buffer_before_its_writer(laned):
+    """A consumer submitted before its producer on another lane: there is no event to wait for yet.  The op the engine names is
+    the one tests/lane_model.py finds unordered with the buffer's writer."""
+    from tests import lane_model as lm
+    from tests.test_lane_model import move_consumer_before_producer
+    edited, consumer, producer, buffer = move_consumer_before_producer(laned)
+    msg = _create(edited)
+    assert msg is not None and "(status -3)" in msg, msg
+    found = re.search(r"laned program: op (\d+) reads buffer (\d+) before any op wrote it", msg)
+    assert found, msg
+    assert lm.conflicts(edited) == [(consumer, producer)]
+    assert int(found.group(1)) == consumer and int(found.group(2)) == buffer == edited.ops[producer].dst
+
+
+def test_refuses_a_laned_program_that_writes_a_buffer_twice(laned):
+    """Technology 1's read convolver (op 1, lane 1) writing into the frames of technology 0's (op 0, lane 0): the two ops the
+    engine names are the pair tests/lane_model.py finds unordered (the frames' reader, op 2, follows op 0 on its lane and would
+    wait for op 1)."""
+    from tests import lane_model as lm
+    assert [laned.ops[i].kind for i in (0, 1)] == [cp.OP_READCONV_FUSED] * 2 and lm.lane_of(laned.ops[0]) != lm.lane_of(laned.ops[1])
+    edited = _edit(laned, 1, dst=laned.ops[0].dst)
+    msg = _create(edited)
+    assert msg is not None and "(status -3)" in msg, msg
+    found = re.search(r"laned program: ops (\d+) and (\d+) both write buffer (\d+) \(a program with lanes may not reuse buffers\)", msg)
+    assert found, msg
+    assert lm.conflicts(edited) == [(int(found.group(1)), int(found.group(2)))] == [(0, 1)] and int(found.group(3)) == laned.ops[0].dst
+    # the sequential program reuses buffers by design: no lanes, no refusal
+    spec = ns.build("hybrid_no_ensemble")
+    assert _create(cp.compile_model(spec, weights.synth_state(spec, seed=21))) is None
+
+
 # ---- the launch mirror and the error bound ------------------------------------------------------------------------------
 def test_case_table_reaches_every_instantiation_on_256_cus():
     reached = op.case_instantiations(256)

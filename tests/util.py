@@ -14,6 +14,22 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 FIXTURES = ["single_tech_batched", "single_tech_bn", "single_tech_hp", "single_tech_deep",
             "hybrid_no_ensemble", "hybrid_full", "hybrid_ensemble2", "hybrid_compressor2", "merged_single", "merged_hybrid", "single_tech_addendum", "hybrid_no_ensemble_addendum", "single_tech_softplus", "hybrid_no_ensemble_wide",
             "merged_hybrid_250", "single_tech_layernorm"]
+SEPARATE_META = "merged_hybrid_sepmeta"          # separate_meta_spec(): not a golden fixture, a model built in the tests
+
+
+def separate_meta_spec():
+    """A full-size hybrid MoEMergedAdvanced with useSeparateMeta (MixtureOfExpertsAdvanced.py:327-331,443-463: readConv0Meta and
+    readConv1Meta are the read convolvers' deep copies; without combiners the meta network sees their per-site sums [64, 36], so
+    an allele compressor goes in front of it): canonical convolvers, so all FOUR lower to the fused op -- two per read
+    technology, which no fixture has (mini_merged_sepmeta's 8-channel convolvers are not fusable)."""
+    table = {"readConv0": (ns.read_convolver, {}), "readConv1": (ns.read_convolver, {}),
+             "readConv0Meta": (ns.read_convolver, {}), "readConv1Meta": (ns.read_convolver, {}),
+             "alleleConv0": (ns.compressor, {}), "alleleConv1": (ns.compressor, {}),
+             "expert0": (ns.graph_convolver, {}), "expert1": (ns.graph_convolver, {}), "expert2": (ns.graph_convolver, {}),
+             "meta": (ns.meta_combiner_deeper, {})}
+    nets = ns._nets("moeMerged", table)
+    nets["meta"] = ns.compressor("moeMerged.meta.pre") + nets["meta"]
+    return ns.ModelSpec(nets, name=SEPARATE_META, prefix="moeMerged", family="merged")
 
 
 def state_digest(state):
