@@ -232,6 +232,10 @@ def parser() -> argparse.ArgumentParser:
                     help="start from --ibam (or --pbam) and --ref: hotspots, sharding and candidate sites run on the GPU "
                          "(hello_amd.hotspots, hello_amd.candidates / hello_amd.pacbio) and the shards they write under --workdir are "
                          "scored; one Illumina BAM or one PacBio BAM")
+    ap.add_argument("--from_bams", action="store_true", default=False,
+                    help="start from --ibam AND --pbam and --ref: hotspots over both BAMs (honouring --hybrid_hotspot), sharding and "
+                         "hybrid candidate sites (--reconcilement_size) run on the GPU (hello_amd.hotspots, hello_amd.hybrid) and the "
+                         "two-technology shards they write under --workdir are scored; --network is a two-technology model")
     ap.add_argument("--device", type=int, default=0, help="GPU of a single-process run")
     ap.add_argument("--gpus", type=int, default=1,
                     help="processes / GPUs of this node: > 1 re-launches this command under torch.distributed.run "
@@ -339,8 +343,61 @@ def shards_from_bam(args) -> str:
     return out_dir
 
 
+def shards_from_bams(args) -> str:
+    """``shards_from_bam`` for the hybrid caller (python/call.py:111-221 with both BAMs): hotspots over the Illumina and the
+    PacBio BAM together in the reference's ``hotspots_<chrom>_<ibam>_<pbam>`` directory, ``shard<N>.txt`` beside them and one
+    two-technology ``shard<N>.hshard`` per shard file in ``<workdir>/shards`` (hello_amd.hybrid).  Returns that directory.
+    ``--hybrid_hotspot``, ``--reconcilement_size``, ``--q_threshold`` and ``--mapq_threshold`` reach both stages, as they reach the
+    reference's (python/call.py passes them on); ``shards_from_bam`` runs its stages at the default thresholds and stays as it is."""
+    from . import candidates as cd, hotspots as hs, hybrid as hy
+    logger = logging.getLogger("hello_amd.call")
+    if not (args.ibam and args.pbam) or "," in args.ibam or "," in args.pbam:
+        raise ValueError("--from_bams needs one --ibam and one --pbam (one BAM: --from_bam)")
+    if not args.ref:
+        raise SystemExit("--from_bams needs --ref")
+    chromosomes = args.chromosomes.split(",") if args.chromosomes else None
+    genome = read_fasta(args.ref, chromosomes)
+    out_dir = os.path.join(args.workdir, "shards")
+    os.makedirs(out_dir, exist_ok=True)
+    bams = [args.ibam, args.pbam]
+    ns = argparse.Namespace(bam=",".join(bams), ref=args.ref, pacbio=False, hybrid_hotspot=args.hybrid_hotspot, workdir=args.workdir,
+                            chromosomes=",".join(chromosomes or list(genome)), q_threshold=args.q_threshold,
+                            mapq_threshold=args.mapq_threshold, device=args.device)
+    n = 0
+    for hotspot_name in hs.run_workdir(ns):
+        for chrom, pos in cd.read_positions(hotspot_name).items():
+            for part in cd.shard_positions(pos):
+                name = os.path.join(os.path.dirname(hotspot_name), "shard%d.txt" % n)
+                hs.write_positions(name, chrom, part)
+                _, st = hy.run_activity(bams, args.ref, name, os.path.join(out_dir, "shard%d" % n), args.hybrid_hotspot,
+                                        args.reconcilement_size, q_threshold=args.q_threshold, mapq_threshold=args.mapq_threshold,
+                                        device=args.device, genome=genome)
+                logger.info("%s: %d sites, %d PacBio reads reassigned", name, st.get("sites", 0), st.get("pacbio_reads_reassigned", 0))
+                n += 1
+    if n == 0:
+        raise SystemExit("no hotspot was found: nothing to call")
+    return out_dir
+
+
 def main(args) -> str:
     logger = logging.getLogger("hello_amd.call")
+    if getattr(args, "from_bams", False) and not args.shards:
+        if getattr(args, "from_bam", False):
+            raise SystemExit("--from_bam (one BAM) and --from_bams (an Illumina and a PacBio BAM) exclude each other")
+        if "RANK" in os.environ and "WORLD_SIZE" in os.environ:
+            raise SystemExit("--from_bams under an external launcher would build the same shards in every rank: start it as a plain "
+                             "command with --gpus N, or build the shards first and pass --shards")
+        if getattr(args, "gpus", 1) > 1:
+            # as --from_bam: the ranks must start before this process touches the GPU, so the BAM stages run in a child of their own
+            import multiprocessing
+            child = multiprocessing.get_context("spawn").Process(target=shards_from_bams, args=(args,))
+            child.start()
+            child.join()
+            if child.exitcode != 0:
+                raise SystemExit(f"the BAM stages of --from_bams failed (exit status {child.exitcode})")
+            args.shards = os.path.join(args.workdir, "shards")
+        else:
+            args.shards = shards_from_bams(args)
     if getattr(args, "from_bam", False) and not args.shards:
         if "RANK" in os.environ and "WORLD_SIZE" in os.environ:
             raise SystemExit("--from_bam under an external launcher would build the same shards in every rank: start it as a plain "

@@ -6,7 +6,8 @@ python/caller_calling.py does up to its featurizer (:784-843) for ONE Illumina B
 strict differing regions (pass 1), clusters of those, the clusters' own strict differing regions (pass 2, the sites), and per
 site the alleles the reads spell there with every allele's supporting reads.  Both passes and the allele stage run in
 ``hello_candidates_find`` (hello_amd/csrc/candidates.hip); DESIGN.md "Candidate sites" states the rules.  ``shard_positions``
-is the reference's python/shardHotspots.py.  Two BAMs and ``--hybrid_hotspot`` are refused: they need the two-BAM reassembly.
+is the reference's python/shardHotspots.py.  Two BAMs and ``--hybrid_hotspot`` are refused here: they go through
+``hello_amd.hybrid`` (``hello_candidates_find_hybrid``).
 One PacBio BAM has its own entry points in ``hello_amd.pacbio``; ``pacbio=True`` / ``--pacbio`` here are refused with a pointer
 to them.
 """

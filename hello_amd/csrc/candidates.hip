@@ -1,5 +1,6 @@
 // Candidate sites from hotspot positions (include/hello_mi355x.h: hello_candidates_find): the stage between the hotspot detector
-// and the scoring engine, for one Illumina BAM or one PacBio BAM.
+// and the scoring engine, for one Illumina BAM or one PacBio BAM, and (hello_candidates_find_hybrid, at the end of this comment)
+// for an Illumina and a PacBio BAM together.
 //
 // Reference semantics: python/PileupDataTools.py:207-244 (positions -> active regions), :129-158 (the read cap), :302-384 (pass 1:
 // one strict searcher per active region), python/trainDataTools.py:477-514 (clusterLocations), :1039-1103 (pass 2: one strict
@@ -21,6 +22,17 @@
 // strictly clipped (python/PileupContainerLite.py:255-468,554-573: left at the fetch interval's start, then right at its end,
 // 201 read bases kept outward of either) by clip_plan_kernel / clip_write_kernel into a derived read set per pass, which the
 // kernels above consume unmodified through their read lists; every derived read counts in table 1.
+//
+// Two BAMs (hello_candidates_find_hybrid; python/AlleleSearcherLite.py:100-206,257-268, c++/src/AlleleSearcherLiteFiltered.cpp:
+// 668-738, c++/src/Read.cpp:174-323): every searcher holds the Illumina reads and the clipped PacBio reads, selected and capped
+// per container; a pass's reads are ONE set, the Illumina input reads followed by that pass's clipped PacBio copies, with a table
+// byte per read, so the differing-position kernel is unchanged.  The allele stage runs as two launches of the same stage function
+// (allele_stages) with the reassembly between them: hybrid_records_kernel (records, distinct strings, the Illumina alleles of
+// every region in byte order), reassemble_kernel (one wave per (cluster, spanning PacBio read): the read's haplotype is matched
+// piecewise against the Illumina alleles, a backward reachability pass and a forward pass that takes the smallest allele by bytes,
+// no product is enumerated), hybrid_alleles_kernel (a reassigned read's records are aliases of Illumina records; grouping,
+// partials, alleles with the PacBio share of every allele's reads).  The coverage gate is an integer reduction per cluster on the
+// host.  allele_kernel is the kWhole instantiation of the same function: the single-BAM launches execute what they did.
 #include <algorithm>
 #include <chrono>
 #include <memory>
@@ -46,6 +58,8 @@ struct hello_candidates {
     std::vector<uint32_t> cigars;
     std::vector<int8_t> orientation;
     double stats[HELLO_CANDIDATES_STATS] = {0};
+    std::unique_ptr<hello_candidates> second;        // two BAMs: the read arrays of technology 1 (hello_candidates_array_tech)
+    double hybrid_stats[HELLO_CANDIDATES_HYBRID_STATS - HELLO_CANDIDATES_STATS] = {0};
 };
 
 namespace hello {
@@ -92,6 +106,13 @@ struct AlleleArgs {
     int32_t* al_count;                // supporting reads
     int64_t* sup;                     // supporting reads (input read index), allele after allele
     int q_threshold, mapq_threshold;
+    // two BAMs (hello_candidates_find_hybrid) only
+    const uint8_t* tech;              // per read: 0 Illumina, 1 PacBio
+    int64_t* alias;                   // records of a reassigned read: the Illumina slot holding its new string; else -1
+    uint8_t* reassigned;              // per cluster read
+    int64_t* site_al;                 // per region at reg_list_off[g]: the slots of the distinct passing Illumina strings
+    int32_t* n_site_al;               //   without N, ascending bytes; their number (> 0: an Illumina site)
+    int32_t* al_count1;               // supporting PacBio reads: the last al_count1 of an allele's al_count
 };
 
 __device__ void walk_read(const AlleleArgs& a, int64_t r, int64_t s, int64_t e, int64_t slot) {
@@ -162,36 +183,62 @@ __device__ void walk_read(const AlleleArgs& a, int64_t r, int64_t s, int64_t e, 
     a.target[slot] = -1;
 }
 
-__global__ __launch_bounds__(256) void allele_kernel(AlleleArgs a) {
+// The stages of a cluster's workgroup.  kWhole: all of them, the single-BAM kernel.  Two BAMs run them as two launches with
+// the reassembly between: kRecords (the records, the distinct strings, and per region the distinct passing Illumina strings in
+// byte order) and kAlleles (the distinct strings again, partials and alleles, a reassigned read's records being its aliases).
+constexpr int kWhole = 0, kRecords = 1, kAlleles = 2;
+
+template <int kMode>
+__device__ __forceinline__ void allele_stages(const AlleleArgs& a) {
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int64_t c = blockIdx.x;
     const int64_t x0 = a.cl_read_off[c], x1 = a.cl_read_off[c + 1];
     const int64_t g0 = a.cl_reg_off[c], g1 = a.cl_reg_off[c + 1];
     const int64_t s0 = a.rd_rec_off[x0], s1 = a.rd_rec_off[x1];
-    auto text = [&](int64_t slot) { return a.bases + a.read_off[a.cl_reads[a.slot_x[slot]]] + a.q0[slot]; };
+    auto own_text = [&](int64_t slot) { return a.bases + a.read_off[a.cl_reads[a.slot_x[slot]]] + a.q0[slot]; };
+    // the record a slot stands for: itself, or (kAlleles) the Illumina record a reassigned read was given there
+    auto src = [&](int64_t slot) -> int64_t {
+        if constexpr (kMode == kAlleles) { if (a.reassigned[a.slot_x[slot]] && a.alias[slot] >= 0) return a.alias[slot]; }
+        return slot;
+    };
+    auto passes = [&](int64_t slot) -> bool {
+        if constexpr (kMode == kAlleles) {
+            const int64_t x = a.slot_x[slot];
+            if (a.reassigned[x])                                     // the new records carry min_q 60 (Read.cpp:280)
+                return a.alias[slot] >= 0 && a.mapq[a.cl_reads[x]] >= a.mapq_threshold && 60 >= a.q_threshold;
+        }
+        return a.pass[slot] != 0;
+    };
+    auto text = [&](int64_t slot) { return own_text(src(slot)); };
+    auto length = [&](int64_t slot) { return a.len[src(slot)]; };
 
     // ---- records: Read::extract_alleles (Read.cpp:139-172), a wave per read, a lane per region the read overlaps
-    for (int64_t x = x0 + wave; x < x1; x += 4) {
-        const int64_t r = a.cl_reads[x];
-        for (int64_t slot = a.rd_rec_off[x] + lane; slot < a.rd_rec_off[x + 1]; slot += 64) {
-            const int64_t g = a.slot_g[slot];
-            walk_read(a, r, a.reg_start[g], a.reg_stop[g], slot);
+    if constexpr (kMode != kAlleles) {
+        for (int64_t x = x0 + wave; x < x1; x += 4) {
+            const int64_t r = a.cl_reads[x];
+            for (int64_t slot = a.rd_rec_off[x] + lane; slot < a.rd_rec_off[x + 1]; slot += 64) {
+                const int64_t g = a.slot_g[slot];
+                walk_read(a, r, a.reg_start[g], a.reg_stop[g], slot);
+            }
         }
+        __syncthreads();
     }
-    __syncthreads();
 
     // ---- the distinct supported strings of every region (AlleleSearcherLiteFiltered.cpp:764-775): hash, then bytes
     for (int64_t slot = s0 + tid; slot < s1; slot += 256) {
-        if (!a.pass[slot]) continue;
+        if (!passes(slot)) {
+            if constexpr (kMode == kAlleles) a.first[slot] = -1;     // the records stage's answer for a read since reassigned
+            continue;
+        }
         const int64_t g = a.slot_g[slot];
-        const int n = a.len[slot];
-        const uint64_t h = a.hash[slot];
+        const int n = length(slot);
+        const uint64_t h = a.hash[src(slot)];
         const uint8_t* mine = text(slot);
         int64_t found = slot;
         for (int64_t i = a.reg_list_off[g]; i < a.reg_list_off[g + 1]; ++i) {
             const int64_t o = a.reg_list[i];
             if (o >= slot) break;
-            if (!a.pass[o] || a.hash[o] != h || a.len[o] != n) continue;
+            if (!passes(o) || a.hash[src(o)] != h || length(o) != n) continue;
             const uint8_t* other = text(o);
             bool eq = true;
             for (int k = 0; k < n && eq; ++k) eq = other[k] == mine[k];
@@ -200,6 +247,44 @@ __global__ __launch_bounds__(256) void allele_kernel(AlleleArgs a) {
         a.first[slot] = found;
     }
     __syncthreads();
+    auto less = [&](int64_t x, int64_t y) {                          // bytes of x < bytes of y
+        const uint8_t* tx = text(x);
+        const uint8_t* ty = text(y);
+        const int nx = length(x), ny = length(y), n = nx < ny ? nx : ny;
+        for (int k = 0; k < n; ++k)
+            if (tx[k] != ty[k]) return tx[k] < ty[k];
+        return nx < ny;
+    };
+    auto has_n = [&](int64_t o) {
+        const uint8_t* t = text(o);
+        for (int k = 0; k < length(o); ++k)
+            if (t[k] == 'N') return true;
+        return false;
+    };
+    if constexpr (kMode == kRecords) {
+        // ---- the Illumina alleles of every region (get_alleles_from_reads over the Illumina reads, :698-708), ascending bytes.
+        // Illumina reads come first in a cluster, so the first holder of a string an Illumina read spells is an Illumina record.
+        for (int64_t g = g0 + tid; g < g1; g += 256) {
+            const int64_t l0 = a.reg_list_off[g], l1 = a.reg_list_off[g + 1];
+            int n_out = 0;
+            int64_t prev = -1;
+            for (;;) {
+                int64_t best = -1;
+                for (int64_t i = l0; i < l1; ++i) {
+                    const int64_t o = a.reg_list[i];
+                    if (a.first[o] != o || a.tech[a.cl_reads[a.slot_x[o]]] != 0) continue;
+                    if (prev >= 0 && !less(prev, o)) continue;
+                    if (best >= 0 && !less(o, best)) continue;
+                    if (!has_n(o)) best = o;
+                }
+                if (best < 0) break;
+                a.site_al[l0 + n_out++] = best;
+                prev = best;
+            }
+            a.n_site_al[g] = n_out;
+        }
+        return;
+    }
 
     // ---- partials (:812-831): a read's last left partial, else its last right partial, against the distinct strings of its region
     for (int64_t x = x0 + tid; x < x1; x += 256) {
@@ -213,13 +298,13 @@ __global__ __launch_bounds__(256) void allele_kernel(AlleleArgs a) {
         const bool left = a.status[chosen] == kLeftPartial;
         const int64_t g = a.slot_g[chosen];
         const int n = a.len[chosen];
-        const uint8_t* mine = text(chosen);
+        const uint8_t* mine = own_text(chosen);                      // a partial stays as extracted
         int matches = 0;
         int64_t hit = -1;
         for (int64_t i = a.reg_list_off[g]; i < a.reg_list_off[g + 1] && matches < 2; ++i) {
             const int64_t o = a.reg_list[i];
-            if (a.first[o] != o || a.len[o] < n) continue;
-            const uint8_t* other = text(o) + (left ? a.len[o] - n : 0);
+            if (a.first[o] != o || length(o) < n) continue;
+            const uint8_t* other = text(o) + (left ? length(o) - n : 0);
             bool eq = true;
             for (int k = 0; k < n && eq; ++k) eq = other[k] == mine[k];
             if (eq) { ++matches; hit = o; }
@@ -236,32 +321,26 @@ __global__ __launch_bounds__(256) void allele_kernel(AlleleArgs a) {
         int n_out = 0;
         int64_t n_sup = 0;
         auto emit = [&](int64_t rep) {
-            int count = 0;
+            int count = 0, count1 = 0;
             for (int64_t i = l0; i < l1; ++i) {
                 const int64_t o = a.reg_list[i];
-                if ((a.pass[o] && a.first[o] == rep) || a.target[o] == rep) {
+                if ((passes(o) && a.first[o] == rep) || a.target[o] == rep) {
                     a.sup[l0 + n_sup++] = a.cl_reads[a.slot_x[o]];
                     ++count;
+                    if constexpr (kMode == kAlleles) count1 += a.tech[a.cl_reads[a.slot_x[o]]];
                 }
             }
             a.al_rep[l0 + n_out] = rep;
             a.al_count[l0 + n_out] = count;
+            if constexpr (kMode == kAlleles) a.al_count1[l0 + n_out] = count1;
             ++n_out;
         };
         auto is_ref = [&](int64_t o) {
-            if (a.len[o] != e - s || e > a.ref_len) return false;
+            if (length(o) != e - s || e > a.ref_len) return false;
             const uint8_t* t = text(o);
             for (int64_t k = 0; k < e - s; ++k)
                 if (t[k] != a.ref[s + k]) return false;
             return true;
-        };
-        auto less = [&](int64_t x, int64_t y) {                      // bytes of x < bytes of y
-            const uint8_t* tx = text(x);
-            const uint8_t* ty = text(y);
-            const int nx = a.len[x], ny = a.len[y], n = nx < ny ? nx : ny;
-            for (int k = 0; k < n; ++k)
-                if (tx[k] != ty[k]) return tx[k] < ty[k];
-            return nx < ny;
         };
         int64_t ref_rep = -1;
         for (int64_t i = l0; i < l1 && ref_rep < 0; ++i) {
@@ -274,19 +353,150 @@ __global__ __launch_bounds__(256) void allele_kernel(AlleleArgs a) {
             int64_t best = -1;
             for (int64_t i = l0; i < l1; ++i) {
                 const int64_t o = a.reg_list[i];
-                if (a.first[o] != o || o == ref_rep || a.len[o] > kMaxAlleleLength) continue;
+                if (a.first[o] != o || o == ref_rep || length(o) > kMaxAlleleLength) continue;
                 if (prev >= 0 && !less(prev, o)) continue;
                 if (best >= 0 && !less(o, best)) continue;
-                bool has_n = false;
-                const uint8_t* t = text(o);
-                for (int k = 0; k < a.len[o] && !has_n; ++k) has_n = t[k] == 'N';
-                if (!has_n) best = o;
+                if (!has_n(o)) best = o;
             }
             if (best < 0) break;
             emit(best);
             prev = best;
         }
         a.n_alleles[g] = n_out;
+    }
+}
+
+__global__ __launch_bounds__(256) void allele_kernel(AlleleArgs a) { allele_stages<kWhole>(a); }
+__global__ __launch_bounds__(256) void hybrid_records_kernel(AlleleArgs a) { allele_stages<kRecords>(a); }
+__global__ __launch_bounds__(256) void hybrid_alleles_kernel(AlleleArgs a) { allele_stages<kAlleles>(a); }
+
+// ---- reassembly (AlleleSearcherLiteFiltered.cpp:695-738, Read.cpp:174-323): a PacBio read that spans [start, stop) = [first
+// region - 6, last region + 6) and whose haplotype there -- the reference with its Success records in place -- is spelled by one
+// Illumina allele per Illumina site takes those alleles as its records.  The reference enumerates the product of the sites'
+// alleles; here one wave per (cluster, eligible read) matches the haplotype piecewise: reference segment, site allele, reference
+// segment ...  A state is (site, offset into the haplotype at which the site's allele begins).  A backward pass over the sites
+// marks the states from which the end can be reached, one bit per offset; a forward pass then takes at every site the
+// smallest allele by bytes that leads to a marked state, which is the choice with the lexicographically smallest index tuple
+// (DESIGN.md "Two BAMs").  The wave owns its haplotype bytes and its bits: every loop is wave-uniform, the lanes compare 64
+// bytes per step, lane 0 writes.  The host counted both scratch areas exactly from the records.
+struct ReassemblyArgs {
+    AlleleArgs a;
+    const int64_t* pair_x;            // the cluster read of every (cluster, eligible PacBio read) pair
+    const int64_t* pair_c;            // its cluster
+    const int64_t* hap_off;           // [pairs + 1] into hap: the haplotype's bytes
+    const int64_t* bit_off;           // [pairs + 1] into bits: (regions + 1) rows of (haplotype length + 1) bits, zeroed
+    uint8_t* hap;
+    unsigned* bits;
+    int32_t* result;                  // per pair: 0 unchanged, 1 reassigned, 2 reassigned and several choices spell it, < 0 internal
+    int64_t n_pairs;
+};
+
+__device__ __forceinline__ bool wave_equal(const uint8_t* x, const uint8_t* y, int64_t n, int lane) {
+    for (int64_t i = 0; i < n; i += 64) {
+        const bool differ = i + lane < n && x[i + lane] != y[i + lane];
+        if (__ballot(differ)) return false;
+    }
+    return true;
+}
+
+__global__ __launch_bounds__(64) void reassemble_kernel(ReassemblyArgs q) {
+    const AlleleArgs& a = q.a;
+    const int lane = threadIdx.x;
+    const int64_t pair = blockIdx.x;
+    if (pair >= q.n_pairs) return;
+    const int64_t x = q.pair_x[pair], c = q.pair_c[pair];
+    const int64_t g0 = a.cl_reg_off[c], g1 = a.cl_reg_off[c + 1], ng = g1 - g0;
+    const int64_t slot0 = a.rd_rec_off[x];                           // an eligible read has a record in every region, in order
+    const int64_t start = a.reg_start[g0] - 6, stop = a.reg_stop[g1 - 1] + 6;
+    uint8_t* hap = q.hap + q.hap_off[pair];
+    const int64_t cap = q.hap_off[pair + 1] - q.hap_off[pair];
+    auto own_text = [&](int64_t slot) { return a.bases + a.read_off[a.cl_reads[a.slot_x[slot]]] + a.q0[slot]; };
+    auto fail = [&](int code) { if (lane == 0) q.result[pair] = code; };
+
+    // ---- Read::get_haplotype_string (Read.cpp:174-203)
+    int64_t H = 0;
+    bool fits = true;
+    auto append = [&](const uint8_t* from, int64_t n) {
+        if (H + n > cap) { fits = false; return; }
+        for (int64_t i = lane; i < n; i += 64) hap[H + i] = from[i];
+        H += n;
+    };
+    int64_t cur = start;
+    for (int64_t g = g0; g < g1 && fits; ++g) {
+        const int64_t slot = slot0 + (g - g0);
+        append(a.ref + cur, a.reg_start[g] - cur);
+        if (a.status[slot] == kSuccess) append(own_text(slot), a.len[slot]);
+        else append(a.ref + a.reg_start[g], a.reg_stop[g] - a.reg_start[g]);
+        cur = a.reg_stop[g];
+    }
+    if (fits) append(a.ref + cur, stop - cur);
+    if (!fits || H != cap) { fail(-1); return; }
+    __syncthreads();
+
+    const int64_t W = (H + 1 + 31) / 32;                               // words of a row
+    unsigned* bits = q.bits + q.bit_off[pair];
+    if ((ng + 1) * W != q.bit_off[pair + 1] - q.bit_off[pair]) { fail(-2); return; }
+    auto row = [&](int64_t k) { return bits + k * W; };
+    auto marked = [&](int64_t k, int64_t o) { return (row(k)[o >> 5] >> (o & 31)) & 1u; };
+
+    // ---- backward: the states that reach the end.  Row g - g0 belongs to the site of region g, row ng to the end (offset H).
+    if (lane == 0) row(ng)[H >> 5] |= 1u << (H & 31);
+    __syncthreads();
+    int64_t next_row = ng, next_start = stop;
+    for (int64_t g = g1 - 1; g >= g0; --g) {
+        const int n_al = a.n_site_al[g];
+        if (n_al == 0) continue;                                     // no Illumina site: reference, part of a segment
+        const int64_t seg_lo = a.reg_stop[g], seg_n = next_start - seg_lo, l0 = a.reg_list_off[g];
+        for (int64_t w = 0; w < W; ++w) {
+            unsigned word = row(next_row)[w];
+            while (word) {
+                const int b = __ffs(word) - 1;
+                word &= word - 1;
+                const int64_t p = w * 32 + b - seg_n;                // where the segment behind the allele begins
+                if (p < 0 || !wave_equal(hap + p, a.ref + seg_lo, seg_n, lane)) continue;
+                for (int i = 0; i < n_al; ++i) {
+                    const int64_t al = a.site_al[l0 + i];
+                    const int64_t n = a.len[al], o = p - n;
+                    if (o < 0 || !wave_equal(hap + o, own_text(al), n, lane)) continue;
+                    if (lane == 0) row(g - g0)[o >> 5] |= 1u << (o & 31);
+                }
+            }
+        }
+        __syncthreads();
+        next_row = g - g0;
+        next_start = a.reg_start[g];
+    }
+    if (next_row == ng) { fail(0); return; }                         // no Illumina site: nothing matches (Read.cpp:248-258)
+
+    // ---- forward: the smallest allele by bytes that leads to a marked state, site after site
+    int64_t o = next_start - start;                                  // the first site's allele begins behind the first segment
+    if (o > H || !wave_equal(hap, a.ref + start, o, lane) || !marked(next_row, o)) { fail(0); return; }
+    bool tie = false;
+    for (int64_t g = g0 + next_row; g < g1; ++g) {
+        const int n_al = a.n_site_al[g];
+        if (n_al == 0) continue;
+        int64_t after_row = ng, after_start = stop;
+        for (int64_t k = g + 1; k < g1; ++k)
+            if (a.n_site_al[k] > 0) { after_row = k - g0; after_start = a.reg_start[k]; break; }
+        const int64_t seg_lo = a.reg_stop[g], seg_n = after_start - seg_lo, l0 = a.reg_list_off[g];
+        int64_t chosen = -1, advance = 0;
+        int viable = 0;
+        for (int i = 0; i < n_al; ++i) {
+            const int64_t al = a.site_al[l0 + i];
+            const int64_t n = a.len[al];
+            if (o + n + seg_n > H) continue;
+            if (!wave_equal(hap + o, own_text(al), n, lane) || !wave_equal(hap + o + n, a.ref + seg_lo, seg_n, lane)) continue;
+            if (!marked(after_row, o + n + seg_n)) continue;
+            if (viable++ == 0) { chosen = al; advance = n + seg_n; }
+        }
+        if (chosen < 0) { fail(-3); return; }                        // cannot happen: (g, o) is marked
+        tie = tie || viable > 1;
+        if (lane == 0) a.alias[slot0 + (g - g0)] = chosen;
+        o += advance;
+    }
+    if (lane == 0) {
+        a.reassigned[x] = 1;
+        q.result[pair] = tie ? 2 : 1;
     }
 }
 
@@ -776,6 +986,350 @@ void differing_regions(std::vector<Job>& jobs, const ReadSet& in, int64_t refere
     }
 }
 
+// hotspotsReader (PileupDataTools.py:207-244) and candidateReader's fetch (:347-352): the searchers of pass 1
+std::vector<Job> active_region_jobs(const int64_t* positions, int64_t n_positions) {
+    std::vector<Job> jobs;
+    for (int64_t i = 0; i < n_positions;) {
+        int64_t k = i;
+        while (k + 1 < n_positions && positions[k + 1] - positions[k] <= 30) ++k;
+        Job j;
+        j.start = positions[i] - 15;
+        j.stop = positions[k] + 15;
+        j.fetch_lo = std::max<int64_t>(0, j.start - 75);
+        j.fetch_hi = j.stop + 75;
+        jobs.push_back(std::move(j));
+        i = k + 1;
+    }
+    return jobs;
+}
+
+// The differing regions of pass 1 in order, also as the result's regions1.
+std::vector<std::pair<int64_t, int64_t>> pass1_locations(const std::vector<Job>& jobs1, hello_candidates& res) {
+    std::vector<std::pair<int64_t, int64_t>> locations;
+    for (const Job& j : jobs1)
+        for (const auto& reg : j.regions) {
+            // strict runs lie inside [first - 15, last + 15] and points of different active regions are > 30 apart: the
+            // reference's merge_overlaps (:377-378) has nothing to merge
+            if (!locations.empty() && reg.first <= locations.back().second) raise(HELLO_ERR_ARG, "internal: differing regions overlap");
+            locations.push_back(reg);
+        }
+    for (const auto& reg : locations) { res.regions1.push_back(reg.first); res.regions1.push_back(reg.second); }
+    return locations;
+}
+
+// clusterLocations (trainDataTools.py:477-514, MAX_ITEMS_PER_GROUP = 1024, caller_calling.py:859) and the searcher of every
+// cluster (:1045-1065): the searchers of pass 2
+std::vector<Job> cluster_jobs(const std::vector<std::pair<int64_t, int64_t>>& locations) {
+    std::vector<Job> jobs2;
+    std::vector<std::pair<int64_t, int64_t>> cluster;
+    auto close = [&]() {
+        if (cluster.empty()) return;
+        Job j;
+        j.start = cluster.front().first - 15;
+        j.stop = cluster.back().second + 14;
+        j.fetch_lo = j.start;
+        j.fetch_hi = j.stop;
+        jobs2.push_back(std::move(j));
+        cluster.clear();
+    };
+    for (const auto& loc : locations) {
+        if (loc.second - loc.first > kMaxAlleleLength && !cluster.empty()) { close(); continue; }   // the location is dropped
+        if (cluster.empty()) cluster.push_back(loc);
+        else if (loc.first - cluster.back().second < 30 && cluster.size() < 1024) cluster.push_back(loc);
+        else { close(); cluster.push_back(loc); }
+    }
+    close();
+    return jobs2;
+}
+
+void use_device(int device) {
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) raise(HELLO_ERR_NOGPU, "no GPU visible");
+    if (device < 0 || device >= n_dev) raise(HELLO_ERR_ARG, "device %d of %d", device, n_dev);
+    hipDeviceProp_t prop;
+    HS_HIP(hipGetDeviceProperties(&prop, device));
+    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+        raise(HELLO_ERR_NOGPU, "device %d is %s; this library is built for gfx950 only", device, prop.gcnArchName);
+    HS_HIP(hipSetDevice(device));
+}
+
+// The allele stage's plan: record slots = reads x the regions they overlap, counted exactly.
+struct AllelePlan {
+    std::vector<int64_t> cl_read_off{0}, cl_reads, cl_reg_off{0}, cl_job, reg_start, reg_stop, rd_rec_off{0}, slot_g, slot_x;
+    std::vector<int64_t> reg_list_off, reg_list;
+    int64_t n_slots = 0, n_reg = 0, n_cl = 0;
+
+    void build(const std::vector<Job>& jobs2, const ReadSet& rs2, hello_candidates& res) {
+        for (size_t ji = 0; ji < jobs2.size(); ++ji) {
+            const Job& j = jobs2[ji];
+            if (j.regions.empty()) continue;
+            const int64_t gbase = (int64_t)reg_start.size();
+            for (const auto& reg : j.regions) {
+                reg_start.push_back(reg.first);
+                reg_stop.push_back(reg.second);
+                res.regions2.push_back(reg.first);
+                res.regions2.push_back(reg.second);
+            }
+            const int64_t ng = (int64_t)j.regions.size();
+            for (int64_t r : j.reads) {
+                const int64_t x = (int64_t)cl_reads.size();
+                cl_reads.push_back(r);
+                if (rs2.last_pos[r] >= 0)                              // Read.cpp:88: start <= last_position && reference_start < stop
+                    for (int64_t g = 0; g < ng; ++g)
+                        if (j.regions[g].first <= rs2.last_pos[r] && rs2.ref_start[r] < j.regions[g].second) {
+                            slot_g.push_back(gbase + g);
+                            slot_x.push_back(x);
+                        }
+                rd_rec_off.push_back((int64_t)slot_g.size());
+            }
+            cl_read_off.push_back((int64_t)cl_reads.size());
+            cl_reg_off.push_back((int64_t)reg_start.size());
+            cl_job.push_back((int64_t)ji);
+        }
+        n_slots = (int64_t)slot_g.size();
+        n_reg = (int64_t)reg_start.size();
+        n_cl = (int64_t)cl_read_off.size() - 1;
+        reg_list_off.assign(n_reg + 1, 0);
+        reg_list.resize((size_t)n_slots);
+        for (int64_t s = 0; s < n_slots; ++s) ++reg_list_off[slot_g[s] + 1];
+        for (int64_t g = 0; g < n_reg; ++g) reg_list_off[g + 1] += reg_list_off[g];
+        std::vector<int64_t> fill(reg_list_off.begin(), reg_list_off.end() - 1);
+        for (int64_t s = 0; s < n_slots; ++s) reg_list[fill[slot_g[s]]++] = s;      // ascending slot = ascending read
+    }
+
+    AlleleArgs upload(DevMem& m, const ReadSet& rs2, const uint8_t* d_ref, int64_t reference_length, int q_threshold,
+                      int mapq_threshold) const {
+        AlleleArgs b{};
+        b.bases = rs2.d_bases; b.quals = rs2.d_quals; b.read_off = rs2.d_read_off; b.cigars = rs2.d_cigars;
+        b.cigar_off = rs2.d_cigar_off; b.ref_start = rs2.d_ref_start;
+        b.mapq = m.put(rs2.mapq, (size_t)rs2.n);
+        b.last_pos = m.put(rs2.last_pos.data(), rs2.last_pos.size());
+        b.pflags = m.put(rs2.pflags.data(), rs2.pflags.size());
+        b.cl_read_off = m.put(cl_read_off.data(), cl_read_off.size());
+        b.cl_reads = m.put(cl_reads.data(), cl_reads.size());
+        b.cl_reg_off = m.put(cl_reg_off.data(), cl_reg_off.size());
+        b.reg_start = m.put(reg_start.data(), reg_start.size());
+        b.reg_stop = m.put(reg_stop.data(), reg_stop.size());
+        b.rd_rec_off = m.put(rd_rec_off.data(), rd_rec_off.size());
+        b.slot_g = m.put(slot_g.data(), slot_g.size());
+        b.slot_x = m.put(slot_x.data(), slot_x.size());
+        b.reg_list_off = m.put(reg_list_off.data(), reg_list_off.size());
+        b.reg_list = m.put(reg_list.data(), reg_list.size());
+        b.ref = d_ref;
+        b.ref_len = reference_length;
+        b.status = m.zeros<int32_t>((size_t)n_slots);
+        b.q0 = m.zeros<int32_t>((size_t)n_slots);
+        b.len = m.zeros<int32_t>((size_t)n_slots);
+        b.minq = m.zeros<int32_t>((size_t)n_slots);
+        b.hash = m.zeros<uint64_t>((size_t)n_slots);
+        b.pass = m.zeros<int32_t>((size_t)n_slots);
+        b.first = m.zeros<int64_t>((size_t)n_slots);
+        b.target = m.zeros<int64_t>((size_t)n_slots);
+        b.n_alleles = m.zeros<int32_t>((size_t)n_reg);
+        b.al_rep = m.zeros<int64_t>((size_t)n_slots);
+        b.al_count = m.zeros<int32_t>((size_t)n_slots);
+        b.sup = m.zeros<int64_t>((size_t)n_slots);
+        b.q_threshold = q_threshold;
+        b.mapq_threshold = mapq_threshold;
+        return b;
+    }
+};
+
+template <class T> void fetch(std::vector<T>& to, const T* from) {
+    if (!to.empty()) HS_HIP(hipMemcpy(to.data(), from, to.size() * sizeof(T), hipMemcpyDeviceToHost));
+}
+
+struct AlleleResult {
+    std::vector<int32_t> n_alleles, al_count, al_count1, rec_q0, rec_len;
+    std::vector<int64_t> al_rep, sup;
+    explicit AlleleResult(const AllelePlan& p)
+        : n_alleles((size_t)p.n_reg, 0), al_count((size_t)p.n_slots), rec_q0((size_t)p.n_slots), rec_len((size_t)p.n_slots),
+          al_rep((size_t)p.n_slots), sup((size_t)p.n_slots) {}
+    void download(const AlleleArgs& b) {
+        fetch(n_alleles, b.n_alleles);
+        fetch(al_count, b.al_count);
+        fetch(al_rep, b.al_rep);
+        fetch(sup, b.sup);
+        fetch(rec_q0, b.q0);
+        fetch(rec_len, b.len);
+        if (b.al_count1) { al_count1.resize(al_count.size()); fetch(al_count1, b.al_count1); }
+    }
+};
+
+// The sites and, per technology, every allele's reads as indices into rs2 (read_index) with their offsets.  With two
+// technologies an allele's PacBio reads are the last al_count1 of its supporting reads.  -> sites dropped at the chromosome's ends
+int64_t emit_sites(hello_candidates& o, hello_candidates* second, const AllelePlan& p, const AlleleResult& got, const ReadSet& rs2,
+                   const uint8_t* reference, int64_t reference_length, int64_t feature_length) {
+    int64_t sites_oob = 0;
+    auto add = [&](hello_candidates& to, int64_t r) {
+        to.read_index.push_back(r);
+        to.read_off.push_back(to.read_off.back() + (rs2.read_off[r + 1] - rs2.read_off[r]));
+        to.cigar_off.push_back(to.cigar_off.back() + (rs2.cigar_off[r + 1] - rs2.cigar_off[r]));
+    };
+    for (int64_t g = 0; g < p.n_reg; ++g) {
+        if (got.n_alleles[g] == 0) continue;                                         // caller_calling.py:876
+        const int64_t s = p.reg_start[g], e = p.reg_stop[g], L = feature_length;
+        const int64_t lo = (s + e) / 2 - L / 2;
+        const int64_t ws = std::min(lo, s - 1), we = std::max(lo + L, e);            // one anchor base left of the site
+        if (ws < 0 || we > reference_length) { ++sites_oob; continue; }
+        o.start.push_back(s);
+        o.stop.push_back(e);
+        o.window_start.push_back(ws);
+        o.ref.insert(o.ref.end(), reference + ws, reference + we);
+        o.ref_off.push_back((int64_t)o.ref.size());
+        o.alleles_per_site.push_back(got.n_alleles[g]);
+        int64_t at = p.reg_list_off[g];
+        for (int32_t k = 0; k < got.n_alleles[g]; ++k) {
+            const int64_t rep = got.al_rep[p.reg_list_off[g] + k];
+            const uint8_t* t = rs2.bases + rs2.read_off[p.cl_reads[p.slot_x[rep]]] + got.rec_q0[rep];
+            o.allele_text.insert(o.allele_text.end(), t, t + got.rec_len[rep]);
+            o.allele_text_off.push_back((int64_t)o.allele_text.size());
+            const int32_t n = got.al_count[p.reg_list_off[g] + k];
+            const int32_t n1 = second ? got.al_count1[p.reg_list_off[g] + k] : 0;
+            o.reads_per_allele.push_back(n - n1);
+            for (int32_t i = 0; i < n - n1; ++i) add(o, got.sup[at + i]);
+            if (second) {
+                second->reads_per_allele.push_back(n1);
+                for (int32_t i = n - n1; i < n; ++i) add(*second, got.sup[at + i]);
+            }
+            at += n;
+        }
+    }
+    return sites_oob;
+}
+
+// The gather of every allele's reads into the arrays of a shard (hello_amd/shards.py): read_index names reads of rs2 on entry
+// and the input reads of `flags` / `hp` on return.
+void gather_reads(hello_candidates& o, const ReadSet& rs2, const uint16_t* flags, const uint8_t* hp) {
+    const int64_t R = (int64_t)o.read_index.size();
+    o.bases.resize((size_t)o.read_off.back());
+    o.quals.resize((size_t)o.read_off.back());
+    o.cigars.resize((size_t)o.cigar_off.back());
+    o.ref_start.resize((size_t)R);
+    o.mapq.resize((size_t)R);
+    o.orientation.resize((size_t)R);
+    o.hp.resize((size_t)R);
+    const int n_threads = (int)std::max<int64_t>(1, std::min<int64_t>({16, (int64_t)std::thread::hardware_concurrency(), R / 4096 + 1}));
+    auto copy = [&](int64_t i0, int64_t i1) {
+        for (int64_t i = i0; i < i1; ++i) {
+            const int64_t r = o.read_index[i];
+            std::copy(rs2.bases + rs2.read_off[r], rs2.bases + rs2.read_off[r + 1], o.bases.begin() + o.read_off[i]);
+            std::copy(rs2.quals + rs2.read_off[r], rs2.quals + rs2.read_off[r + 1], o.quals.begin() + o.read_off[i]);
+            std::copy(rs2.cigars + rs2.cigar_off[r], rs2.cigars + rs2.cigar_off[r + 1], o.cigars.begin() + o.cigar_off[i]);
+            o.ref_start[i] = rs2.ref_start[r];
+            o.mapq[i] = rs2.mapq[r];
+            o.orientation[i] = (flags[rs2.input(r)] & 16) ? -1 : 1;
+            o.hp[i] = hp[rs2.input(r)];
+        }
+    };
+    std::vector<std::thread> pool;
+    for (int t = 1; t < n_threads; ++t) pool.emplace_back(copy, R * t / n_threads, R * (t + 1) / n_threads);
+    copy(0, R / n_threads);
+    for (auto& th : pool) th.join();
+    for (int64_t& r : o.read_index) r = rs2.input(r);                      // the input read of a clipped read
+}
+
+// ---- two BAMs
+
+// One pass's reads of both technologies as one set: the Illumina input reads, then the clipped PacBio copies (table 1).
+void join_sets(const ReadSet& ill, const ReadSet& clipped, ReadSet& out) {
+    const int64_t ni = ill.n, np = clipped.n;
+    auto cat = [](auto& to, const auto* x, int64_t nx, const auto* y, int64_t ny) {
+        to.assign(x, x + nx);
+        to.insert(to.end(), y, y + ny);
+    };
+    auto cat_off = [](std::vector<int64_t>& to, const int64_t* x, int64_t nx, const int64_t* y, int64_t ny) {
+        to.assign(x, x + nx + 1);
+        for (int64_t i = 1; i <= ny; ++i) to.push_back(x[nx] + y[i]);
+    };
+    out.n = ni + np;
+    cat(out.v_bases, ill.bases, ill.read_off[ni], clipped.bases, clipped.read_off[np]);
+    cat(out.v_quals, ill.quals, ill.read_off[ni], clipped.quals, clipped.read_off[np]);
+    cat(out.v_cigars, ill.cigars, ill.cigar_off[ni], clipped.cigars, clipped.cigar_off[np]);
+    cat_off(out.v_read_off, ill.read_off, ni, clipped.read_off, np);
+    cat_off(out.v_cigar_off, ill.cigar_off, ni, clipped.cigar_off, np);
+    cat(out.v_ref_start, ill.ref_start, ni, clipped.ref_start, np);
+    cat(out.v_ref_end, ill.ref_end, ni, clipped.ref_end, np);
+    cat(out.v_mapq, ill.mapq, ni, clipped.mapq, np);
+    out.v_origin.resize((size_t)(ni + np));
+    for (int64_t r = 0; r < ni; ++r) out.v_origin[r] = r;
+    for (int64_t r = 0; r < np; ++r) out.v_origin[ni + r] = clipped.origin[r];
+    cat_off(out.plant_off, ill.plant_off.data(), ni, clipped.plant_off.data(), np);
+    cat(out.plant, ill.plant.data(), (int64_t)ill.plant.size(), clipped.plant.data(), (int64_t)clipped.plant.size());
+    cat(out.last_pos, ill.last_pos.data(), ni, clipped.last_pos.data(), np);
+    cat(out.pflags, ill.pflags.data(), ni, clipped.pflags.data(), np);
+    out.bases = out.v_bases.data(); out.quals = out.v_quals.data(); out.read_off = out.v_read_off.data();
+    out.cigars = out.v_cigars.data(); out.cigar_off = out.v_cigar_off.data(); out.ref_start = out.v_ref_start.data();
+    out.ref_end = out.v_ref_end.data(); out.mapq = out.v_mapq.data(); out.origin = out.v_origin.data();
+    std::vector<uint8_t> table((size_t)(ni + np), 0);
+    std::fill(table.begin() + ni, table.end(), (uint8_t)1);
+    out.d_bases = out.mem.put(out.bases, out.v_bases.size());
+    out.d_quals = out.mem.put(out.quals, out.v_quals.size());
+    out.d_read_off = out.mem.put(out.read_off, out.v_read_off.size());
+    out.d_cigars = out.mem.put(out.cigars, out.v_cigars.size());
+    out.d_cigar_off = out.mem.put(out.cigar_off, out.v_cigar_off.size());
+    out.d_ref_start = out.mem.put(out.ref_start, out.v_ref_start.size());
+    out.d_ref_end = out.mem.put(out.ref_end, out.v_ref_end.size());
+    out.d_table = out.mem.put(table.data(), table.size());
+}
+
+// The coverage gate of a cluster (python/AlleleSearcherLite.py:264-266: container 0's average_coverage > 14; DESIGN.md "Two
+// BAMs" defines the rule): over the Illumina reads that overlap [lo, hi) and are mapped, primary, not QC-fail, not duplicate and
+// a proper pair if paired -- before de-duplication and the cap -- sum of counts > 14 * columns.
+bool coverage_gate(const ReadsIn& in, int64_t max_span, int64_t lo, int64_t hi) {
+    const int64_t* begin = in.ref_start;
+    const int64_t first = std::lower_bound(begin, begin + in.n, lo - max_span) - begin;
+    // first walk: the reads that count, checked once (they include reads the searchers skip and describe_reads did not look
+    // at), and the span of their columns
+    std::vector<int64_t> counted;
+    int64_t c_lo = INT64_MAX, c_hi = INT64_MIN;
+    for (int64_t r = first; r < in.n && in.ref_start[r] < hi; ++r) {
+        const uint16_t f = in.flags[r];
+        if (in.ref_end[r] <= lo || (f & (0x4 | 0x100 | 0x800 | 0x200 | 0x400)) || ((f & 0x1) && !(f & 0x2))) continue;
+        int64_t qlen = 0, rlen = 0;
+        for (int64_t c = in.cigar_off[r]; c < in.cigar_off[r + 1]; ++c) {
+            const int op = in.cigars[c] & 15;
+            if (op > 8) raise(HELLO_ERR_ARG, "read %lld: CIGAR operation %d", (long long)r, op);
+            if (is_query_op(op)) qlen += in.cigars[c] >> 4;
+            if (is_ref_op(op)) rlen += in.cigars[c] >> 4;
+        }
+        if (qlen != in.read_off[r + 1] - in.read_off[r])
+            raise(HELLO_ERR_SHAPE, "read %lld: CIGAR query length %lld, %lld bases", (long long)r, (long long)qlen,
+                  (long long)(in.read_off[r + 1] - in.read_off[r]));
+        counted.push_back(r);
+        c_lo = std::min(c_lo, in.ref_start[r]);
+        c_hi = std::max(c_hi, in.ref_start[r] + rlen);
+    }
+    if (c_lo >= c_hi) return false;                                  // no column: 0 > 0 is false
+    std::vector<uint8_t> column((size_t)(c_hi - c_lo), 0);
+    int64_t total = 0;
+    for (int64_t r : counted) {
+        const bool good = in.mapq[r] >= 10;
+        const uint8_t* quals = in.quals + in.read_off[r];
+        int64_t rf = in.ref_start[r], rd = 0;
+        for (int64_t c = in.cigar_off[r]; c < in.cigar_off[r + 1]; ++c) {
+            const int op = in.cigars[c] & 15;
+            const int64_t n = in.cigars[c] >> 4;
+            if (op == 0 || op == 7 || op == 8) {
+                for (int64_t j = 0; j < n; ++j) {
+                    column[(size_t)(rf + j - c_lo)] = 1;
+                    total += good && quals[rd + j] >= 13;
+                }
+                rf += n; rd += n;
+            } else if (op == 2 || op == 3) {                          // the quality of the last read base before the operation
+                std::fill(column.begin() + (rf - c_lo), column.begin() + (rf + n - c_lo), (uint8_t)1);
+                if (good && rd > 0 && quals[rd - 1] >= 13) total += n;
+                rf += n;
+            } else if (op == 1 || op == 4) {
+                rd += n;
+            }
+        }
+    }
+    int64_t columns = 0;
+    for (uint8_t c : column) columns += c;
+    return total > 14 * columns;
+}
+
 }  // namespace
 }  // namespace hello
 
@@ -810,19 +1364,7 @@ int hello_candidates_find(const uint8_t* bases, const uint8_t* quals, const int6
     const int64_t max_span = describe_reads(input, flags, pacbio);
     const ReadsIn in{bases, quals, read_offsets, cigars, cigar_offsets, ref_starts, ref_ends, mapq, flags, name_hash, n_reads};
 
-    // ---- pass 1 plan: hotspotsReader (PileupDataTools.py:207-244) and candidateReader's fetch (:347-352)
-    std::vector<Job> jobs1;
-    for (int64_t i = 0; i < n_positions;) {
-        int64_t k = i;
-        while (k + 1 < n_positions && positions[k + 1] - positions[k] <= 30) ++k;
-        Job j;
-        j.start = positions[i] - 15;
-        j.stop = positions[k] + 15;
-        j.fetch_lo = std::max<int64_t>(0, j.start - 75);
-        j.fetch_hi = j.stop + 75;
-        jobs1.push_back(std::move(j));
-        i = k + 1;
-    }
+    std::vector<Job> jobs1 = active_region_jobs(positions, n_positions);
     auto res = std::make_unique<hello_candidates>();
     JobStats st1, st2;
     float allele_ms = 0.0f;
@@ -830,14 +1372,7 @@ int hello_candidates_find(const uint8_t* bases, const uint8_t* quals, const int6
     int64_t n_slots = 0, n_clusters = 0, sites_oob = 0;
     if (n_reads == 0) st1.empty = (int64_t)jobs1.size();
     if (!jobs1.empty() && n_reads > 0) {
-        int n_dev = 0;
-        if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) return set_last_error(HELLO_ERR_NOGPU, "no GPU visible");
-        if (device < 0 || device >= n_dev) return set_last_error(HELLO_ERR_ARG, "device %d of %d", device, n_dev);
-        hipDeviceProp_t prop;
-        HS_HIP(hipGetDeviceProperties(&prop, device));
-        if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-            return set_last_error(HELLO_ERR_NOGPU, "device %d is %s; this library is built for gfx950 only", device, prop.gcnArchName);
-        HS_HIP(hipSetDevice(device));
+        use_device(device);
         DevMem m;
         HotspotArgs a{};
         const int64_t nb = read_offsets[n_reads], nc = cigar_offsets[n_reads];
@@ -860,188 +1395,34 @@ int hello_candidates_find(const uint8_t* bases, const uint8_t* quals, const int6
         select_reads(jobs1, in, max_span, pacbio, st1);
         if (pacbio) clip_reads(jobs1, in, input, clipped1, st1);
         differing_regions(jobs1, pacbio ? clipped1 : input, reference_length, mapq_threshold, a, st1);
-        std::vector<std::pair<int64_t, int64_t>> locations;
-        for (const Job& j : jobs1)
-            for (const auto& reg : j.regions) {
-                // strict runs lie inside [first - 15, last + 15] and points of different active regions are > 30 apart: the
-                // reference's merge_overlaps (:377-378) has nothing to merge
-                if (!locations.empty() && reg.first <= locations.back().second) raise(HELLO_ERR_ARG, "internal: differing regions overlap");
-                locations.push_back(reg);
-            }
-        for (const auto& reg : locations) { res->regions1.push_back(reg.first); res->regions1.push_back(reg.second); }
+        const auto locations = pass1_locations(jobs1, *res);
 
-        // ---- pass 2 plan: clusterLocations (trainDataTools.py:477-514, MAX_ITEMS_PER_GROUP = 1024, caller_calling.py:859) and
-        // the searcher of every cluster (:1045-1065)
-        std::vector<Job> jobs2;
-        {
-            std::vector<std::pair<int64_t, int64_t>> cluster;
-            auto close = [&]() {
-                if (cluster.empty()) return;
-                Job j;
-                j.start = cluster.front().first - 15;
-                j.stop = cluster.back().second + 14;
-                j.fetch_lo = j.start;
-                j.fetch_hi = j.stop;
-                jobs2.push_back(std::move(j));
-                cluster.clear();
-            };
-            for (const auto& loc : locations) {
-                if (loc.second - loc.first > kMaxAlleleLength && !cluster.empty()) { close(); continue; }   // the location is dropped
-                if (cluster.empty()) cluster.push_back(loc);
-                else if (loc.first - cluster.back().second < 30 && cluster.size() < 1024) cluster.push_back(loc);
-                else { close(); cluster.push_back(loc); }
-            }
-            close();
-        }
+        std::vector<Job> jobs2 = cluster_jobs(locations);
         n_clusters = (int64_t)jobs2.size();
         select_reads(jobs2, in, max_span, pacbio, st2);                // a fresh fetch from the input reads (trainDataTools.py:1059-1065)
         if (pacbio) clip_reads(jobs2, in, input, clipped2, st2);
         const ReadSet& rs2 = pacbio ? clipped2 : input;              // the reads of the clusters, of the alleles and of the shard
         differing_regions(jobs2, rs2, reference_length, mapq_threshold, a, st2);
 
-        // ---- allele stage plan: record slots = reads x the regions they overlap, counted exactly
-        std::vector<int64_t> cl_read_off{0}, cl_reads, cl_reg_off{0}, reg_start, reg_stop, rd_rec_off{0}, slot_g, slot_x;
-        for (const Job& j : jobs2) {
-            if (j.regions.empty()) continue;
-            const int64_t gbase = (int64_t)reg_start.size();
-            for (const auto& reg : j.regions) {
-                reg_start.push_back(reg.first);
-                reg_stop.push_back(reg.second);
-                res->regions2.push_back(reg.first);
-                res->regions2.push_back(reg.second);
-            }
-            const int64_t ng = (int64_t)j.regions.size();
-            for (int64_t r : j.reads) {
-                const int64_t x = (int64_t)cl_reads.size();
-                cl_reads.push_back(r);
-                if (rs2.last_pos[r] >= 0)                              // Read.cpp:88: start <= last_position && reference_start < stop
-                    for (int64_t g = 0; g < ng; ++g)
-                        if (j.regions[g].first <= rs2.last_pos[r] && rs2.ref_start[r] < j.regions[g].second) {
-                            slot_g.push_back(gbase + g);
-                            slot_x.push_back(x);
-                        }
-                rd_rec_off.push_back((int64_t)slot_g.size());
-            }
-            cl_read_off.push_back((int64_t)cl_reads.size());
-            cl_reg_off.push_back((int64_t)reg_start.size());
-        }
-        n_slots = (int64_t)slot_g.size();
-        const int64_t n_reg = (int64_t)reg_start.size(), n_cl = (int64_t)cl_read_off.size() - 1;
-        std::vector<int64_t> reg_list_off(n_reg + 1, 0), reg_list((size_t)n_slots);
-        for (int64_t s = 0; s < n_slots; ++s) ++reg_list_off[slot_g[s] + 1];
-        for (int64_t g = 0; g < n_reg; ++g) reg_list_off[g + 1] += reg_list_off[g];
-        {
-            std::vector<int64_t> fill(reg_list_off.begin(), reg_list_off.end() - 1);
-            for (int64_t s = 0; s < n_slots; ++s) reg_list[fill[slot_g[s]]++] = s;      // ascending slot = ascending read
-        }
-        std::vector<int32_t> n_alleles((size_t)n_reg, 0), al_count((size_t)n_slots), rec_q0((size_t)n_slots), rec_len((size_t)n_slots);
-        std::vector<int64_t> al_rep((size_t)n_slots), sup((size_t)n_slots);
-        if (n_cl > 0 && n_slots > 0) {
-            AlleleArgs b{};
-            b.bases = rs2.d_bases; b.quals = rs2.d_quals; b.read_off = rs2.d_read_off; b.cigars = rs2.d_cigars;
-            b.cigar_off = rs2.d_cigar_off; b.ref_start = rs2.d_ref_start;
-            b.mapq = m.put(rs2.mapq, (size_t)rs2.n);
-            b.last_pos = m.put(rs2.last_pos.data(), rs2.last_pos.size());
-            b.pflags = m.put(rs2.pflags.data(), rs2.pflags.size());
-            b.cl_read_off = m.put(cl_read_off.data(), cl_read_off.size());
-            b.cl_reads = m.put(cl_reads.data(), cl_reads.size());
-            b.cl_reg_off = m.put(cl_reg_off.data(), cl_reg_off.size());
-            b.reg_start = m.put(reg_start.data(), reg_start.size());
-            b.reg_stop = m.put(reg_stop.data(), reg_stop.size());
-            b.rd_rec_off = m.put(rd_rec_off.data(), rd_rec_off.size());
-            b.slot_g = m.put(slot_g.data(), slot_g.size());
-            b.slot_x = m.put(slot_x.data(), slot_x.size());
-            b.reg_list_off = m.put(reg_list_off.data(), reg_list_off.size());
-            b.reg_list = m.put(reg_list.data(), reg_list.size());
-            b.ref = a.ref;
-            b.ref_len = reference_length;
-            b.status = m.zeros<int32_t>((size_t)n_slots);
-            b.q0 = m.zeros<int32_t>((size_t)n_slots);
-            b.len = m.zeros<int32_t>((size_t)n_slots);
-            b.minq = m.zeros<int32_t>((size_t)n_slots);
-            b.hash = m.zeros<uint64_t>((size_t)n_slots);
-            b.pass = m.zeros<int32_t>((size_t)n_slots);
-            b.first = m.zeros<int64_t>((size_t)n_slots);
-            b.target = m.zeros<int64_t>((size_t)n_slots);
-            b.n_alleles = m.zeros<int32_t>((size_t)n_reg);
-            b.al_rep = m.zeros<int64_t>((size_t)n_slots);
-            b.al_count = m.zeros<int32_t>((size_t)n_slots);
-            b.sup = m.zeros<int64_t>((size_t)n_slots);
-            b.q_threshold = q_threshold;
-            b.mapq_threshold = mapq_threshold;
+        AllelePlan plan;
+        plan.build(jobs2, rs2, *res);
+        n_slots = plan.n_slots;
+        AlleleResult got(plan);
+        if (plan.n_cl > 0 && n_slots > 0) {
+            const AlleleArgs b = plan.upload(m, rs2, a.ref, reference_length, q_threshold, mapq_threshold);
             {
                 KernelTimer timer;
                 timer.start();
-                hipLaunchKernelGGL(allele_kernel, dim3((unsigned)n_cl), dim3(256), 0, 0, b);
+                hipLaunchKernelGGL(allele_kernel, dim3((unsigned)plan.n_cl), dim3(256), 0, 0, b);
                 HS_HIP(hipGetLastError());
                 allele_ms = timer.stop();
             }
-            HS_HIP(hipMemcpy(n_alleles.data(), b.n_alleles, n_alleles.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-            HS_HIP(hipMemcpy(al_count.data(), b.al_count, al_count.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-            HS_HIP(hipMemcpy(al_rep.data(), b.al_rep, al_rep.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
-            HS_HIP(hipMemcpy(sup.data(), b.sup, sup.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
-            HS_HIP(hipMemcpy(rec_q0.data(), b.q0, rec_q0.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-            HS_HIP(hipMemcpy(rec_len.data(), b.len, rec_len.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+            got.download(b);
         }
 
-        // ---- sites and the gather of every allele's reads into the arrays of a shard (hello_amd/shards.py)
         const auto tg = clock::now();
-        hello_candidates& o = *res;
-        for (int64_t g = 0; g < n_reg; ++g) {
-            if (n_alleles[g] == 0) continue;                                             // caller_calling.py:876
-            const int64_t s = reg_start[g], e = reg_stop[g], L = feature_length;
-            const int64_t lo = (s + e) / 2 - L / 2;
-            const int64_t ws = std::min(lo, s - 1), we = std::max(lo + L, e);            // one anchor base left of the site
-            if (ws < 0 || we > reference_length) { ++sites_oob; continue; }
-            o.start.push_back(s);
-            o.stop.push_back(e);
-            o.window_start.push_back(ws);
-            o.ref.insert(o.ref.end(), reference + ws, reference + we);
-            o.ref_off.push_back((int64_t)o.ref.size());
-            o.alleles_per_site.push_back(n_alleles[g]);
-            int64_t at = reg_list_off[g];
-            for (int32_t k = 0; k < n_alleles[g]; ++k) {
-                const int64_t rep = al_rep[reg_list_off[g] + k];
-                const uint8_t* t = rs2.bases + rs2.read_off[cl_reads[slot_x[rep]]] + rec_q0[rep];
-                o.allele_text.insert(o.allele_text.end(), t, t + rec_len[rep]);
-                o.allele_text_off.push_back((int64_t)o.allele_text.size());
-                const int32_t n = al_count[reg_list_off[g] + k];
-                o.reads_per_allele.push_back(n);
-                for (int32_t i = 0; i < n; ++i) {
-                    const int64_t r = sup[at + i];
-                    o.read_index.push_back(r);
-                    o.read_off.push_back(o.read_off.back() + (rs2.read_off[r + 1] - rs2.read_off[r]));
-                    o.cigar_off.push_back(o.cigar_off.back() + (rs2.cigar_off[r + 1] - rs2.cigar_off[r]));
-                }
-                at += n;
-            }
-        }
-        const int64_t R = (int64_t)o.read_index.size();
-        o.bases.resize((size_t)o.read_off.back());
-        o.quals.resize((size_t)o.read_off.back());
-        o.cigars.resize((size_t)o.cigar_off.back());
-        o.ref_start.resize((size_t)R);
-        o.mapq.resize((size_t)R);
-        o.orientation.resize((size_t)R);
-        o.hp.resize((size_t)R);
-        const int n_threads = (int)std::max<int64_t>(1, std::min<int64_t>({16, (int64_t)std::thread::hardware_concurrency(), R / 4096 + 1}));
-        auto copy = [&](int64_t i0, int64_t i1) {
-            for (int64_t i = i0; i < i1; ++i) {
-                const int64_t r = o.read_index[i];
-                std::copy(rs2.bases + rs2.read_off[r], rs2.bases + rs2.read_off[r + 1], o.bases.begin() + o.read_off[i]);
-                std::copy(rs2.quals + rs2.read_off[r], rs2.quals + rs2.read_off[r + 1], o.quals.begin() + o.read_off[i]);
-                std::copy(rs2.cigars + rs2.cigar_off[r], rs2.cigars + rs2.cigar_off[r + 1], o.cigars.begin() + o.cigar_off[i]);
-                o.ref_start[i] = rs2.ref_start[r];
-                o.mapq[i] = rs2.mapq[r];
-                o.orientation[i] = (flags[rs2.input(r)] & 16) ? -1 : 1;
-                o.hp[i] = hp[rs2.input(r)];
-            }
-        };
-        std::vector<std::thread> pool;
-        for (int t = 1; t < n_threads; ++t) pool.emplace_back(copy, R * t / n_threads, R * (t + 1) / n_threads);
-        copy(0, R / n_threads);
-        for (auto& th : pool) th.join();
-        for (int64_t& r : o.read_index) r = rs2.input(r);                      // the input read of a clipped read
+        sites_oob = emit_sites(*res, nullptr, plan, got, rs2, reference, reference_length, feature_length);
+        gather_reads(*res, rs2, flags, hp);
         ms_gather = std::chrono::duration<double, std::milli>(clock::now() - tg).count();
     }
     const double ms_total = std::chrono::duration<double, std::milli>(clock::now() - t0).count();
@@ -1058,6 +1439,211 @@ int hello_candidates_find(const uint8_t* bases, const uint8_t* quals, const int6
     return hello::set_last_error(f.code, "%s", f.msg.c_str());
 } catch (...) {
     return hello::exception_status("hello_candidates_find");
+}
+
+int hello_candidates_find_hybrid(
+    const uint8_t* bases0, const uint8_t* quals0, const int64_t* read_offsets0, const uint32_t* cigars0, const int64_t* cigar_offsets0,
+    const int64_t* ref_starts0, const int64_t* ref_ends0, const uint8_t* mapq0, const uint16_t* flags0, const uint64_t* name_hash0,
+    const uint8_t* hp0, int64_t n_reads0,
+    const uint8_t* bases1, const uint8_t* quals1, const int64_t* read_offsets1, const uint32_t* cigars1, const int64_t* cigar_offsets1,
+    const int64_t* ref_starts1, const int64_t* ref_ends1, const uint8_t* mapq1, const uint16_t* flags1, const uint64_t* name_hash1,
+    const uint8_t* hp1, int64_t n_reads1,
+    const uint8_t* reference, int64_t reference_length, const int64_t* positions, int64_t n_positions, int32_t options,
+    int32_t reassembly_size, int32_t feature_length, int32_t q_threshold, int32_t mapq_threshold, int32_t device,
+    hello_candidates** out) try {
+    using namespace hello;
+    using clock = std::chrono::steady_clock;
+    const auto t0 = clock::now();
+    auto missing = [](int64_t n, const void* a, const void* b, const void* c, const void* d, const void* e, const void* f, const void* g,
+                      const void* h, const void* i) { return n > 0 && (!a || !b || !c || !d || !e || !f || !g || !h || !i); };
+    if (!out || !read_offsets0 || !cigar_offsets0 || !read_offsets1 || !cigar_offsets1 || !reference || (n_positions > 0 && !positions) ||
+        missing(n_reads0, bases0, quals0, cigars0, ref_starts0, ref_ends0, mapq0, flags0, name_hash0, hp0) ||
+        missing(n_reads1, bases1, quals1, cigars1, ref_starts1, ref_ends1, mapq1, flags1, name_hash1, hp1))
+        return set_last_error(HELLO_ERR_ARG, "NULL pointer");
+    *out = nullptr;
+    if (n_reads0 < 0 || n_reads1 < 0 || n_positions < 0 || reference_length < 0 || feature_length <= 0)
+        return set_last_error(HELLO_ERR_ARG, "negative count");
+    if (options & ~HELLO_HOTSPOTS_HYBRID) return set_last_error(HELLO_ERR_ARG, "options %d: 0 or HELLO_HOTSPOTS_HYBRID", options);
+    for (int64_t i = 1; i < n_positions; ++i)
+        if (positions[i] < positions[i - 1]) return set_last_error(HELLO_ERR_ARG, "position %lld: positions are not sorted", (long long)i);
+
+    ReadSet input0, input1;
+    input0.bases = bases0; input0.quals = quals0; input0.read_off = read_offsets0; input0.cigars = cigars0; input0.cigar_off = cigar_offsets0;
+    input0.ref_start = ref_starts0; input0.ref_end = ref_ends0; input0.mapq = mapq0; input0.n = n_reads0;
+    input1.bases = bases1; input1.quals = quals1; input1.read_off = read_offsets1; input1.cigars = cigars1; input1.cigar_off = cigar_offsets1;
+    input1.ref_start = ref_starts1; input1.ref_end = ref_ends1; input1.mapq = mapq1; input1.n = n_reads1;
+    const int64_t max_span0 = describe_reads(input0, flags0, false), max_span1 = describe_reads(input1, flags1, true);
+    int64_t max_span_all0 = 0;                         // the coverage gate looks at reads the searchers do not use
+    for (int64_t r = 0; r < n_reads0; ++r) max_span_all0 = std::max(max_span_all0, ref_ends0[r] - ref_starts0[r]);
+    const ReadsIn in0{bases0, quals0, read_offsets0, cigars0, cigar_offsets0, ref_starts0, ref_ends0, mapq0, flags0, name_hash0, n_reads0};
+    const ReadsIn in1{bases1, quals1, read_offsets1, cigars1, cigar_offsets1, ref_starts1, ref_ends1, mapq1, flags1, name_hash1, n_reads1};
+
+    std::vector<Job> jobs1 = active_region_jobs(positions, n_positions);
+    auto res = std::make_unique<hello_candidates>();
+    res->second = std::make_unique<hello_candidates>();
+    JobStats st1, st2;
+    float allele_ms = 0.0f, reassembly_ms = 0.0f;
+    double ms_gather = 0.0;
+    int64_t n_slots = 0, n_clusters = 0, sites_oob = 0;
+    int64_t gate_passed = 0, reassembled = 0, eligible = 0, reassigned = 0, by_tie = 0, illumina_sites = 0;
+    if (n_reads0 + n_reads1 == 0) st1.empty = (int64_t)jobs1.size();
+    if (!jobs1.empty() && n_reads0 + n_reads1 > 0) {
+        use_device(device);
+        DevMem m;
+        HotspotArgs a{};
+        input1.d_bases = m.put(bases1, (size_t)read_offsets1[n_reads1]);          // what the clip kernels read
+        input1.d_quals = m.put(quals1, (size_t)read_offsets1[n_reads1]);
+        input1.d_read_off = m.put(read_offsets1, (size_t)n_reads1 + 1);
+        input1.d_cigars = m.put(cigars1, (size_t)cigar_offsets1[n_reads1]);
+        input1.d_cigar_off = m.put(cigar_offsets1, (size_t)n_reads1 + 1);
+        input1.d_ref_start = m.put(ref_starts1, (size_t)n_reads1);
+        input1.d_ref_end = m.put(ref_ends1, (size_t)n_reads1);
+        a.ref_lo = 0;
+        a.ref_len = reference_length;
+        a.ref = m.put(reference, (size_t)reference_length);
+        a.q_threshold = q_threshold;
+        a.hybrid = (options & HELLO_HOTSPOTS_HYBRID) ? 1 : 0;
+
+        // A pass: every searcher's two containers (AlleleSearcherLite.py:116-127), selected and capped each on its own; the
+        // PacBio container's reads clipped; both as one read list with a table byte per read for the differing-position kernel.
+        ReadSet clipped1, clipped2, both1, both2;
+        auto pass = [&](std::vector<Job>& jobs, ReadSet& clipped, ReadSet& both, JobStats& st) {
+            std::vector<Job> container1 = jobs;                      // the same searchers' PacBio containers
+            JobStats each;
+            select_reads(jobs, in0, max_span0, false, each);
+            select_reads(container1, in1, max_span1, true, each);
+            clip_reads(container1, in1, input1, clipped, st);
+            join_sets(input0, clipped, both);
+            for (size_t j = 0; j < jobs.size(); ++j) {
+                for (int64_t r : container1[j].reads) jobs[j].reads.push_back(n_reads0 + r);
+                jobs[j].capped = jobs[j].capped || container1[j].capped;
+                if (jobs[j].reads.empty()) ++st.empty;               // all(self.noReads): no regions
+            }
+            differing_regions(jobs, both, reference_length, mapq_threshold, a, st);
+        };
+        pass(jobs1, clipped1, both1, st1);
+        const auto locations = pass1_locations(jobs1, *res);
+        std::vector<Job> jobs2 = cluster_jobs(locations);
+        n_clusters = (int64_t)jobs2.size();
+        pass(jobs2, clipped2, both2, st2);
+        const ReadSet& rs2 = both2;
+
+        std::vector<uint8_t> gate(jobs2.size(), 0);
+        for (size_t j = 0; j < jobs2.size(); ++j)
+            if (jobs2[j].run) {
+                gate[j] = coverage_gate(in0, max_span_all0, jobs2[j].fetch_lo, jobs2[j].fetch_hi) ? 1 : 0;
+                gate_passed += gate[j];
+            }
+
+        AllelePlan plan;
+        plan.build(jobs2, rs2, *res);
+        n_slots = plan.n_slots;
+        AlleleResult got(plan);
+        if (plan.n_cl > 0 && n_slots > 0) {
+            AlleleArgs b = plan.upload(m, rs2, a.ref, reference_length, q_threshold, mapq_threshold);
+            b.tech = rs2.d_table;
+            b.alias = m.zeros<int64_t>((size_t)n_slots);
+            HS_HIP(hipMemset(b.alias, 0xFF, (size_t)n_slots * sizeof(int64_t)));                 // -1
+            b.reassigned = m.zeros<uint8_t>(plan.cl_reads.size());
+            b.site_al = m.zeros<int64_t>((size_t)n_slots);
+            b.n_site_al = m.zeros<int32_t>((size_t)plan.n_reg);
+            b.al_count1 = m.zeros<int32_t>((size_t)n_slots);
+            {
+                KernelTimer timer;
+                timer.start();
+                hipLaunchKernelGGL(hybrid_records_kernel, dim3((unsigned)plan.n_cl), dim3(256), 0, 0, b);
+                HS_HIP(hipGetLastError());
+                allele_ms = timer.stop();
+            }
+
+            // ---- reassembly plan: the (cluster, eligible PacBio read) pairs and their scratch, counted from the records
+            const auto tr = clock::now();
+            std::vector<int32_t> status((size_t)n_slots), len((size_t)n_slots), n_site_al((size_t)plan.n_reg);
+            fetch(status, b.status);
+            fetch(len, b.len);
+            fetch(n_site_al, b.n_site_al);
+            std::vector<int64_t> pair_x, pair_c, hap_off{0}, bit_off{0};
+            for (int64_t c = 0; c < plan.n_cl; ++c) {
+                const int64_t g0 = plan.cl_reg_off[c], g1 = plan.cl_reg_off[c + 1], ng = g1 - g0;
+                if (!gate[plan.cl_job[c]] || ng >= reassembly_size) continue;                    // :695
+                ++reassembled;
+                for (int64_t g = g0; g < g1; ++g) illumina_sites += n_site_al[g] > 0;
+                const int64_t start = plan.reg_start[g0] - 6, stop = plan.reg_stop[g1 - 1] + 6;  // band_margin (:682-683)
+                for (int64_t x = plan.cl_read_off[c]; x < plan.cl_read_off[c + 1]; ++x) {
+                    const int64_t r = plan.cl_reads[x];
+                    if (r < n_reads0 || rs2.ref_start[r] > start || rs2.last_pos[r] < stop) continue;    // spans it (Read.cpp:211-214)
+                    const int64_t s0 = plan.rd_rec_off[x];
+                    if (plan.rd_rec_off[x + 1] - s0 != ng || start < 0 || stop > reference_length)
+                        raise(HELLO_ERR_ARG, "internal: a spanning read without a record in every region");
+                    int64_t H = stop - start;
+                    for (int64_t g = g0; g < g1; ++g)
+                        if (status[s0 + g - g0] == kSuccess) H += len[s0 + g - g0] - (plan.reg_stop[g] - plan.reg_start[g]);
+                    pair_x.push_back(x);
+                    pair_c.push_back(c);
+                    hap_off.push_back(hap_off.back() + H);
+                    bit_off.push_back(bit_off.back() + (ng + 1) * ((H + 1 + 31) / 32));
+                }
+            }
+            eligible = (int64_t)pair_x.size();
+            if (eligible > 0) {
+                ReassemblyArgs q{};
+                q.a = b;
+                q.pair_x = m.put(pair_x.data(), pair_x.size());
+                q.pair_c = m.put(pair_c.data(), pair_c.size());
+                q.hap_off = m.put(hap_off.data(), hap_off.size());
+                q.bit_off = m.put(bit_off.data(), bit_off.size());
+                q.hap = m.zeros<uint8_t>((size_t)hap_off.back());
+                q.bits = m.zeros<unsigned>((size_t)bit_off.back());
+                q.result = m.zeros<int32_t>((size_t)eligible);
+                q.n_pairs = eligible;
+                hipLaunchKernelGGL(reassemble_kernel, dim3((unsigned)eligible), dim3(64), 0, 0, q);
+                HS_HIP(hipGetLastError());
+                std::vector<int32_t> result((size_t)eligible);
+                fetch(result, (const int32_t*)q.result);
+                for (int32_t v : result) {
+                    if (v < 0) raise(HELLO_ERR_ARG, "internal: reassembly scratch (%d)", v);
+                    reassigned += v > 0;
+                    by_tie += v == 2;
+                }
+            }
+            reassembly_ms = (float)std::chrono::duration<double, std::milli>(clock::now() - tr).count();
+            {
+                KernelTimer timer;
+                timer.start();
+                hipLaunchKernelGGL(hybrid_alleles_kernel, dim3((unsigned)plan.n_cl), dim3(256), 0, 0, b);
+                HS_HIP(hipGetLastError());
+                allele_ms += timer.stop();
+            }
+            got.download(b);
+        } else {
+            got.al_count1.resize(got.al_count.size());
+        }
+
+        const auto tg = clock::now();
+        sites_oob = emit_sites(*res, res->second.get(), plan, got, rs2, reference, reference_length, feature_length);
+        gather_reads(*res, rs2, flags0, hp0);
+        gather_reads(*res->second, rs2, flags1, hp1);
+        ms_gather = std::chrono::duration<double, std::milli>(clock::now() - tg).count();
+    }
+    const double ms_total = std::chrono::duration<double, std::milli>(clock::now() - t0).count();
+    const double st[HELLO_CANDIDATES_STATS] = {
+        (double)jobs1.size(), (double)st1.empty, (double)st1.bounds, (double)st1.capped, (double)(res->regions1.size() / 2),
+        (double)n_clusters, (double)st2.empty, (double)st2.bounds, (double)st2.capped, (double)(res->regions2.size() / 2),
+        (double)res->start.size(), (double)sites_oob, (double)res->reads_per_allele.size(),
+        (double)(res->read_index.size() + res->second->read_index.size()),
+        (double)n_slots, (double)st1.ms, (double)st2.ms, (double)allele_ms, ms_gather, ms_total,
+        (double)st1.clip_ms + (double)st2.clip_ms, (double)(st1.clipped + st2.clipped)};
+    std::copy(st, st + HELLO_CANDIDATES_STATS, res->stats);
+    const double hst[HELLO_CANDIDATES_HYBRID_STATS - HELLO_CANDIDATES_STATS] = {
+        (double)gate_passed, (double)reassembled, (double)eligible, (double)reassigned, (double)by_tie, (double)illumina_sites,
+        (double)reassembly_ms};
+    std::copy(hst, hst + (HELLO_CANDIDATES_HYBRID_STATS - HELLO_CANDIDATES_STATS), res->hybrid_stats);
+    *out = res.release();
+    return HELLO_OK;
+} catch (const hello::Fail& f) {
+    return hello::set_last_error(f.code, "%s", f.msg.c_str());
+} catch (...) {
+    return hello::exception_status("hello_candidates_find_hybrid");
 }
 
 int hello_candidates_array(const hello_candidates* c, int32_t which, const void** data, int64_t* count) {
@@ -1094,6 +1680,22 @@ int hello_candidates_array(const hello_candidates* c, int32_t which, const void*
 int hello_candidates_stats(const hello_candidates* c, double* stats) {
     if (!c || !stats) return hello::set_last_error(HELLO_ERR_ARG, "NULL pointer");
     std::copy(c->stats, c->stats + HELLO_CANDIDATES_STATS, stats);
+    return HELLO_OK;
+}
+
+int hello_candidates_array_tech(const hello_candidates* c, int32_t tech, int32_t which, const void** data, int64_t* count) {
+    if (!c || !data || !count) return hello::set_last_error(HELLO_ERR_ARG, "NULL pointer");
+    if (tech == 0) return hello_candidates_array(c, which, data, count);
+    if (tech != 1 || !c->second) return hello::set_last_error(HELLO_ERR_ARG, "no technology %d in these candidates", tech);
+    if (which < HELLO_CAND_READS_PER_ALLELE || which > HELLO_CAND_READ_INDEX)
+        return hello::set_last_error(HELLO_ERR_ARG, "candidate array %d is not a read array of a technology", which);
+    return hello_candidates_array(c->second.get(), which, data, count);
+}
+
+int hello_candidates_hybrid_stats(const hello_candidates* c, double* stats) {
+    if (!c || !stats) return hello::set_last_error(HELLO_ERR_ARG, "NULL pointer");
+    std::copy(c->stats, c->stats + HELLO_CANDIDATES_STATS, stats);
+    std::copy(c->hybrid_stats, c->hybrid_stats + (HELLO_CANDIDATES_HYBRID_STATS - HELLO_CANDIDATES_STATS), stats + HELLO_CANDIDATES_STATS);
     return HELLO_OK;
 }
 

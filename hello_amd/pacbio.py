@@ -6,7 +6,7 @@ python/call.py:90-109): one read sampler with READ_RATE_PACBIO = (100, 100), str
 reassembly.  It writes ``P.hshard`` like ``hello_amd.candidates``.  The stages are those of ``hello_candidates_find`` with
 ``HELLO_HOTSPOTS_PACBIO`` (hello_amd/csrc/candidates.hip; include/hello_mi355x.h and DESIGN.md "Candidate sites" state the cap
 and the clipping rules): the reads of a shard are the clipped copies of pass 2.  Two BAMs, ``--hybrid_hotspot``, ``--clr``
-and ``--noClip`` are not supported.
+and ``--noClip`` are not supported here; an Illumina and a PacBio BAM together go through ``hello_amd.hybrid``.
 """
 from __future__ import annotations
 

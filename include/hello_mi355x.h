@@ -382,6 +382,47 @@ int hello_candidates_array(const hello_candidates* candidates, int32_t which, co
 int hello_candidates_stats(const hello_candidates* candidates, double* stats);
 void hello_candidates_free(hello_candidates* candidates);
 
+/* hello_candidates_find for an Illumina BAM (read set 0) and a PacBio BAM (read set 1) together: caller_calling.py:784-843 with
+ * two read samplers, python/AlleleSearcherLite.py:100-206,257-268 and the reassembly of c++/src/AlleleSearcherLiteFiltered.cpp:
+ * 668-738 / c++/src/Read.cpp:174-323.  DESIGN.md "Two BAMs" states the rules.  Every searcher of both passes holds two
+ * containers: the Illumina reads under the Illumina cap, unclipped, and the PacBio reads under the PacBio cap, every kept one
+ * strictly clipped with flank 200 as under HELLO_HOTSPOTS_PACBIO; filters, the first-of-(name, strand) rule and the cap apply
+ * per container, the window tests to both (a searcher with two empty containers has no regions).  Illumina reads count in
+ * table 0, PacBio reads in table 1; both tables are flagged and unioned, or, with options == HELLO_HOTSPOTS_HYBRID
+ * (--hybrid_hotspot), flagged by the hybrid rule.  In pass 2 a cluster whose Illumina coverage passes the gate (over the reads
+ * of read set 0 that overlap the cluster's fetch interval and are mapped, primary, not QC-fail, not duplicate and a proper pair
+ * if paired, before de-duplication and the cap: a column is every position one of them covers with M = X D N; a read counts at
+ * a column with mapq >= 10 and base quality >= 13 there, on D N that of its last read base before; the gate is sum of counts >
+ * 14 * columns) and that has fewer than `reassembly_size` differing regions (the reference's --reconcilement_size, 10) is
+ * reassembled: with [start, stop) = [first region - 6, last region + 6), a clipped PacBio read with reference_start <= start and
+ * last_position >= stop whose haplotype there (the reference, every region replaced by the read's Success record) equals the
+ * haplotype of one choice of one allele per Illumina site (a region with a passing Illumina record without N) gets exactly
+ * those alleles as its records, min_q 60, and loses its records elsewhere; its partials stay.  When several choices spell the
+ * haplotype, the sites' strings are ordered by bytes and the smallest index tuple is taken (the reference lets hash order
+ * decide).  An allele is kept when its support summed over both technologies is positive; its reads are split by technology.
+ * Every read keeps its own hp (the reference passes on the last container's list only).
+ * The result answers hello_candidates_array for the site arrays and for technology 0; hello_candidates_array_tech(c, 1, ...)
+ * gives technology 1's reads_per_allele, bases ... hp and read_index (HELLO_CAND_READS_PER_ALLELE .. HELLO_CAND_READ_INDEX):
+ * the clipped copies of pass 2, read_index naming the reads of read set 1. */
+#define HELLO_CANDIDATES_HYBRID_STATS 29
+int hello_candidates_find_hybrid(
+    const uint8_t* bases0, const uint8_t* quals0, const int64_t* read_offsets0, const uint32_t* cigars0,
+    const int64_t* cigar_offsets0, const int64_t* ref_starts0, const int64_t* ref_ends0, const uint8_t* mapq0,
+    const uint16_t* flags0, const uint64_t* name_hash0, const uint8_t* hp0, int64_t n_reads0,
+    const uint8_t* bases1, const uint8_t* quals1, const int64_t* read_offsets1, const uint32_t* cigars1,
+    const int64_t* cigar_offsets1, const int64_t* ref_starts1, const int64_t* ref_ends1, const uint8_t* mapq1,
+    const uint16_t* flags1, const uint64_t* name_hash1, const uint8_t* hp1, int64_t n_reads1,
+    const uint8_t* reference, int64_t reference_length, const int64_t* positions, int64_t n_positions, int32_t options,
+    int32_t reassembly_size, int32_t feature_length, int32_t q_threshold, int32_t mapq_threshold, int32_t device,
+    hello_candidates** out);
+int hello_candidates_array_tech(const hello_candidates* candidates, int32_t tech, int32_t which, const void** data, int64_t* count);
+/* stats[HELLO_CANDIDATES_HYBRID_STATS]: the entries of hello_candidates_stats (reads gathered: both technologies; allele kernel
+ * ms: both launches around the reassembly), then clusters whose coverage gate passed, clusters reassembled, PacBio reads
+ * eligible, reassigned, reassigned where several choices spelled the haplotype (the tie rule), Illumina sites of the reassembled
+ * clusters, ms of the reassembly phase (its plan, its kernel and the copy of its results).  The last seven are 0 for the
+ * candidates of hello_candidates_find. */
+int hello_candidates_hybrid_stats(const hello_candidates* candidates, double* stats);
+
 /* The engine's own stream (a hipStream_t): what a call with hip_stream == NULL runs on.  It is created
  * non-blocking, so it is NOT ordered with the legacy default stream: a caller whose other work sits on the default
  * stream (handle 0, indistinguishable from NULL here) orders the two with events on this handle -- the Python

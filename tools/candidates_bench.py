@@ -3,9 +3,14 @@ end to end (BAM decode included) and split into BAM decode, the three kernels (H
 the call (planning, transfers), plus the CPU restatement (tests/candidate_reference.py) on a slice for context.
 
     python tools/candidates_bench.py [--length 5000000] [--coverage 30] [--read-length 150] [--slice 20000] [--repeats 5] [--pacbio]
+    python tools/candidates_bench.py --hybrid [--pacbio-coverage 25] [--pacbio-read-length 3000] [--hybrid_hotspot] ...
 
 --pacbio: the reads are treated as PacBio reads (give a --read-length of several thousand): PacBio hotspots, the read cap of 100
 per 100 bp, strict clipping -- the two clip kernels are timed with the other stages (clip_kernel_ms).
+
+--hybrid: an Illumina BAM (--coverage, --read-length) and a PacBio BAM (--pacbio-coverage, --pacbio-read-length) of the same donor
+through hello_candidates_find_hybrid: the same stage times plus the reassembly phase (reassembly_ms) and its counts, against
+tests/hybrid_reference.py on the slice.
 
 One warm-up run, then --repeats timed runs; prints one JSON line with the minimum, the median and the spread of each time."""
 import argparse
@@ -39,7 +44,13 @@ def main():
     ap.add_argument("--slice", type=int, default=20000)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--pacbio", action="store_true", default=False, help="PacBio reads: read cap, strict clipping, the clip kernels' time")
+    ap.add_argument("--hybrid", action="store_true", default=False, help="an Illumina and a PacBio BAM together: the reassembly phase's time too")
+    ap.add_argument("--pacbio-coverage", type=float, default=25)
+    ap.add_argument("--pacbio-read-length", type=int, default=3000)
+    ap.add_argument("--hybrid_hotspot", action="store_true", default=False)
     args = ap.parse_args()
+    if args.hybrid:
+        return hybrid(args)
     from hello_amd import candidates as cd, hotspots as hs
     from hello_amd.bam import BamFile
 
@@ -82,6 +93,102 @@ def main():
            "sites_per_s_without_bam_decode": round(sites / min(times["call_s"])),
            "slice_bp": args.slice, "slice_sites": len(want), "slice_cpu_restatement_s": round(t_cpu, 3),
            "cpu_restatement_sites_per_s": round(len(want) / max(t_cpu, 1e-9), 1)}
+    out.update({k: spread(v) for k, v in times.items()})
+    print(json.dumps(out))
+
+
+def pacbio_noise(read, rng, rate=0.01):
+    """`read` with PacBio-like errors inside its M operations, as tests/hotspot_synth._pacbio_noise draws them: a base is dropped
+    (a 1-base deletion) with probability `rate`, a random base is inserted before it with the same probability."""
+    seq, qual, cigar, rd = [], [], [], 0
+
+    def push(op, n):
+        if n > 0:
+            if cigar and cigar[-1][0] == op:
+                cigar[-1] = (op, cigar[-1][1] + n)
+            else:
+                cigar.append((op, n))
+    for op, n in read.cigar:
+        if op != 0:
+            if op in (1, 4):
+                seq.append(read.seq[rd:rd + n]); qual.append(read.qual[rd:rd + n]); rd += n
+            push(op, n)
+            continue
+        u = rng.random(n)
+        events = np.nonzero(u < 2 * rate)[0]
+        at = 0
+        for e in events:
+            e = int(e)
+            if e == 0 and not cigar:
+                continue                                       # the read keeps its first aligned base
+            seq.append(read.seq[rd + at:rd + e]); qual.append(read.qual[rd + at:rd + e]); push(0, e - at)
+            if u[e] < rate:
+                push(2, 1)
+                at = e + 1
+            else:
+                seq.append("ACGT"[int(rng.integers(0, 4))]); qual.append(read.qual[rd + e:rd + e + 1]); push(1, 1)
+                at = e
+        seq.append(read.seq[rd + at:rd + n]); qual.append(read.qual[rd + at:rd + n]); push(0, n - at)
+        rd += n
+    if cigar[-1][0] == 2:                                      # no deletion at the read's end
+        cigar.pop()
+    return type(read)("p" + read.name, read.pos, cigar, "".join(seq), b"".join(bytes(q) for q in qual), read.flag, read.mapq)
+
+
+def hybrid(args):
+    from hello_amd import hotspots as hs, hybrid as hb
+    from hello_amd.bam import BamFile
+    from tests import hybrid_reference as hy
+    ref, illumina = synthesize(args.length, args.coverage, args.read_length)
+    ref1, pacbio = synthesize(args.length, args.pacbio_coverage, args.pacbio_read_length)      # the same seed: the same donor
+    assert ref1 == ref
+    noise = np.random.default_rng(7)
+    pacbio = [pacbio_noise(r, noise) for r in pacbio]           # misaligned single-base indels: what the reassembly reconciles
+    names = ("pass1_kernel_ms", "pass2_kernel_ms", "allele_kernel_ms", "clip_kernel_ms", "reassembly_ms", "gather_ms")
+    with tempfile.TemporaryDirectory() as d:
+        paths = [os.path.join(d, "i.bam"), os.path.join(d, "p.bam")]
+        for path, reads in zip(paths, (illumina, pacbio)):
+            write_bam(path, [("chr1", len(ref))], reads, index=True)
+
+        def decode():
+            out = []
+            for path in paths:
+                with BamFile(path) as b:
+                    out.append(b.fetch("chr1", 0, len(ref)))
+            return out
+        positions, _ = hs.find_positions(decode(), ref, [(0, len(ref))], hybrid_hotspot=args.hybrid_hotspot)
+        times = {k: [] for k in ("end_to_end_s", "bam_decode_s", "call_s", "call_rest_ms") + names}
+        st = {}
+        for i in range(args.repeats + 1):
+            t0 = time.perf_counter()
+            r0, r1 = decode()
+            t1 = time.perf_counter()
+            shard, st, _ = hb.find_sites(r0, r1, ref, positions, "chr1", hybrid_hotspot=args.hybrid_hotspot)
+            t2 = time.perf_counter()
+            if i == 0:
+                continue
+            for k, v in (("end_to_end_s", t2 - t0), ("bam_decode_s", t1 - t0), ("call_s", t2 - t1),
+                         ("call_rest_ms", st["total_ms"] - sum(st[k] for k in names))):
+                times[k].append(v)
+            for k in names:
+                times[k].append(st[k])
+        a = len(ref) // 2
+        sl_pos = [int(p) for p in positions if a <= p < a + args.slice]
+        sl0 = [x for x in illumina if x.pos < a + args.slice + 200 and x.ref_end > a - 200]
+        sl1 = [x for x in pacbio if x.pos < a + args.slice + 200 and x.ref_end > a - 200]
+        t = time.perf_counter()
+        want = hy.find_candidates(sl0, sl1, ref, sl_pos, hybrid_hotspot=args.hybrid_hotspot)
+        t_cpu = time.perf_counter() - t
+    sites = int(st["sites"])
+    out = {"hybrid": True, "hybrid_hotspot": bool(args.hybrid_hotspot), "length": args.length, "coverage": args.coverage,
+           "pacbio_coverage": args.pacbio_coverage, "reads": [len(illumina), len(pacbio)], "positions": int(len(positions)), "sites": sites,
+           "repeats": args.repeats, "sites_per_s_end_to_end": round(sites / min(times["end_to_end_s"])),
+           "sites_per_s_without_bam_decode": round(sites / min(times["call_s"])),
+           "slice_bp": args.slice, "slice_sites": len(want), "slice_cpu_restatement_s": round(t_cpu, 3),
+           "cpu_restatement_sites_per_s": round(len(want) / max(t_cpu, 1e-9), 1)}
+    out.update({k: int(st[k]) for k in ("alleles", "reads_gathered", "record_slots", "active_regions", "clusters", "reads_clipped",
+                                        "clusters_gate_passed", "clusters_reassembled", "pacbio_reads_eligible", "pacbio_reads_reassigned",
+                                        "pacbio_reads_reassigned_by_tie", "illumina_sites")})
     out.update({k: spread(v) for k, v in times.items()})
     print(json.dumps(out))
 
