@@ -236,6 +236,9 @@ def parser() -> argparse.ArgumentParser:
                     help="start from --ibam AND --pbam and --ref: hotspots over both BAMs (honouring --hybrid_hotspot), sharding and "
                          "hybrid candidate sites (--reconcilement_size) run on the GPU (hello_amd.hotspots, hello_amd.hybrid) and the "
                          "two-technology shards they write under --workdir are scored; --network is a two-technology model")
+    ap.add_argument("--resident", action="store_true", default=False,
+                    help="with --from_bam / --from_bams: the candidate sites stay on the GPU and are scored in this process as they "
+                         "are built -- no <workdir>/shards, no read written to disk; the VCF is the same (one GPU)")
     ap.add_argument("--device", type=int, default=0, help="GPU of a single-process run")
     ap.add_argument("--gpus", type=int, default=1,
                     help="processes / GPUs of this node: > 1 re-launches this command under torch.distributed.run "
@@ -311,35 +314,65 @@ def from_bam_route(ibam: Optional[str], pbam: Optional[str]):
     return ibam, False, cd.find_candidates
 
 
-def shards_from_bam(args) -> str:
-    """python/call.py:111-221 up to the per-shard caller, on the GPU: per chromosome hotspots.txt in the reference's
-    ``hotspots_<chrom>_<bam>`` directory, ``shard<N>.txt`` files beside it (shardHotspots) and one ``shard<N>.hshard`` per
-    shard file in ``<workdir>/shards``.  Returns that directory."""
+def _shard_files(ns):
+    """The hotspot stage per chromosome (``hotspots.txt`` in the reference's ``hotspots_<chrom>_<bam>`` directory), then
+    ``shard<N>.txt`` beside it (shardHotspots): yields (N, the shard file) as each is written."""
     from . import candidates as cd, hotspots as hs
-    logger = logging.getLogger("hello_amd.call")
+    n = 0
+    for hotspot_name in hs.run_workdir(ns):
+        for chrom, pos in cd.read_positions(hotspot_name).items():
+            for part in cd.shard_positions(pos):
+                name = os.path.join(os.path.dirname(hotspot_name), "shard%d.txt" % n)
+                hs.write_positions(name, chrom, part)
+                yield n, name
+                n += 1
+    if n == 0:
+        raise SystemExit("no hotspot was found: nothing to call")
+
+
+def _from_bam_stages(args):
+    """--from_bam: -> (genome, the hotspot stage's arguments, the BAM, the function that builds a chromosome's candidate sites).
+    Both stages run at the default thresholds."""
+    from . import candidates as cd
     bam, pacbio, find = from_bam_route(args.ibam, args.pbam)
     if not args.ref:
         raise SystemExit("--from_bam needs --ref")
     chromosomes = args.chromosomes.split(",") if args.chromosomes else None
     genome = read_fasta(args.ref, chromosomes)
-    out_dir = os.path.join(args.workdir, "shards")
-    os.makedirs(out_dir, exist_ok=True)
     ns = argparse.Namespace(bam=bam, ref=args.ref, pacbio=pacbio, hybrid_hotspot=False, workdir=args.workdir,
                             chromosomes=",".join(chromosomes or list(genome)), q_threshold=cd.DEFAULT_Q_THRESHOLD,
                             mapq_threshold=cd.DEFAULT_MIN_MAPQ, device=args.device)
-    n = 0
-    for hotspot_name in hs.run_workdir(ns):
-        positions = cd.read_positions(hotspot_name)
-        for chrom, pos in positions.items():
-            for part in cd.shard_positions(pos):
-                name = os.path.join(os.path.dirname(hotspot_name), "shard%d.txt" % n)
-                hs.write_positions(name, chrom, part)
-                _, st = cd.run_activity(bam, args.ref, name, os.path.join(out_dir, "shard%d" % n), device=args.device,
-                                        genome=genome, find=find)
-                logger.info("%s: %d sites", name, st.get("sites", 0))
-                n += 1
-    if n == 0:
-        raise SystemExit("no hotspot was found: nothing to call")
+    return genome, ns, bam, find
+
+
+def _from_bams_stages(args):
+    """--from_bams: -> (genome, the hotspot stage's arguments, [ibam, pbam]).  ``--hybrid_hotspot``, ``--reconcilement_size``,
+    ``--q_threshold`` and ``--mapq_threshold`` reach both stages, as they reach the reference's (python/call.py passes them on)."""
+    if not (args.ibam and args.pbam) or "," in args.ibam or "," in args.pbam:
+        raise ValueError("--from_bams needs one --ibam and one --pbam (one BAM: --from_bam)")
+    if not args.ref:
+        raise SystemExit("--from_bams needs --ref")
+    chromosomes = args.chromosomes.split(",") if args.chromosomes else None
+    genome = read_fasta(args.ref, chromosomes)
+    bams = [args.ibam, args.pbam]
+    ns = argparse.Namespace(bam=",".join(bams), ref=args.ref, pacbio=False, hybrid_hotspot=args.hybrid_hotspot, workdir=args.workdir,
+                            chromosomes=",".join(chromosomes or list(genome)), q_threshold=args.q_threshold,
+                            mapq_threshold=args.mapq_threshold, device=args.device)
+    return genome, ns, bams
+
+
+def shards_from_bam(args) -> str:
+    """python/call.py:111-221 up to the per-shard caller, on the GPU: per chromosome hotspots.txt in the reference's
+    ``hotspots_<chrom>_<bam>`` directory, ``shard<N>.txt`` files beside it (shardHotspots) and one ``shard<N>.hshard`` per
+    shard file in ``<workdir>/shards``.  Returns that directory."""
+    from . import candidates as cd
+    logger = logging.getLogger("hello_amd.call")
+    genome, ns, bam, find = _from_bam_stages(args)
+    out_dir = os.path.join(args.workdir, "shards")
+    os.makedirs(out_dir, exist_ok=True)
+    for n, name in _shard_files(ns):
+        _, st = cd.run_activity(bam, args.ref, name, os.path.join(out_dir, "shard%d" % n), device=args.device, genome=genome, find=find)
+        logger.info("%s: %d sites", name, st.get("sites", 0))
     return out_dir
 
 
@@ -347,40 +380,96 @@ def shards_from_bams(args) -> str:
     """``shards_from_bam`` for the hybrid caller (python/call.py:111-221 with both BAMs): hotspots over the Illumina and the
     PacBio BAM together in the reference's ``hotspots_<chrom>_<ibam>_<pbam>`` directory, ``shard<N>.txt`` beside them and one
     two-technology ``shard<N>.hshard`` per shard file in ``<workdir>/shards`` (hello_amd.hybrid).  Returns that directory.
-    ``--hybrid_hotspot``, ``--reconcilement_size``, ``--q_threshold`` and ``--mapq_threshold`` reach both stages, as they reach the
-    reference's (python/call.py passes them on); ``shards_from_bam`` runs its stages at the default thresholds and stays as it is."""
-    from . import candidates as cd, hotspots as hs, hybrid as hy
+    ``shards_from_bam`` runs its stages at the default thresholds and stays as it is."""
+    from . import hybrid as hy
     logger = logging.getLogger("hello_amd.call")
-    if not (args.ibam and args.pbam) or "," in args.ibam or "," in args.pbam:
-        raise ValueError("--from_bams needs one --ibam and one --pbam (one BAM: --from_bam)")
-    if not args.ref:
-        raise SystemExit("--from_bams needs --ref")
-    chromosomes = args.chromosomes.split(",") if args.chromosomes else None
-    genome = read_fasta(args.ref, chromosomes)
+    genome, ns, bams = _from_bams_stages(args)
     out_dir = os.path.join(args.workdir, "shards")
     os.makedirs(out_dir, exist_ok=True)
-    bams = [args.ibam, args.pbam]
-    ns = argparse.Namespace(bam=",".join(bams), ref=args.ref, pacbio=False, hybrid_hotspot=args.hybrid_hotspot, workdir=args.workdir,
-                            chromosomes=",".join(chromosomes or list(genome)), q_threshold=args.q_threshold,
-                            mapq_threshold=args.mapq_threshold, device=args.device)
-    n = 0
-    for hotspot_name in hs.run_workdir(ns):
-        for chrom, pos in cd.read_positions(hotspot_name).items():
-            for part in cd.shard_positions(pos):
-                name = os.path.join(os.path.dirname(hotspot_name), "shard%d.txt" % n)
-                hs.write_positions(name, chrom, part)
-                _, st = hy.run_activity(bams, args.ref, name, os.path.join(out_dir, "shard%d" % n), args.hybrid_hotspot,
-                                        args.reconcilement_size, q_threshold=args.q_threshold, mapq_threshold=args.mapq_threshold,
-                                        device=args.device, genome=genome)
-                logger.info("%s: %d sites, %d PacBio reads reassigned", name, st.get("sites", 0), st.get("pacbio_reads_reassigned", 0))
-                n += 1
-    if n == 0:
-        raise SystemExit("no hotspot was found: nothing to call")
+    for n, name in _shard_files(ns):
+        _, st = hy.run_activity(bams, args.ref, name, os.path.join(out_dir, "shard%d" % n), args.hybrid_hotspot,
+                                args.reconcilement_size, q_threshold=args.q_threshold, mapq_threshold=args.mapq_threshold,
+                                device=args.device, genome=genome)
+        logger.info("%s: %d sites, %d PacBio reads reassigned", name, st.get("sites", 0), st.get("pacbio_reads_reassigned", 0))
     return out_dir
+
+
+def check_resident(args) -> None:
+    """The refusals of --resident, each naming the fix."""
+    if not getattr(args, "resident", False):
+        return
+    if not (getattr(args, "from_bam", False) or getattr(args, "from_bams", False)):
+        raise SystemExit("--resident keeps the candidate sites of --from_bam / --from_bams on the GPU: add --from_bam (one BAM) or "
+                         "--from_bams (--ibam and --pbam), or drop --resident")
+    if getattr(args, "from_bam", False) and getattr(args, "from_bams", False):
+        raise SystemExit("--from_bam (one BAM) and --from_bams (an Illumina and a PacBio BAM) exclude each other")
+    if args.shards:
+        raise SystemExit("--resident builds its candidate sites itself and reads no shard files: drop --shards, or drop --resident to "
+                         "score the shard files")
+    if getattr(args, "gpus", 1) > 1 or ("RANK" in os.environ and "WORLD_SIZE" in os.environ):
+        raise SystemExit("--resident builds candidate sites on one GPU in one process: run it with --gpus 1 as a plain command, or drop "
+                         "--resident (the shard files of --from_bam / --from_bams can be dealt to several GPUs)")
+
+
+def run_resident(args) -> str:
+    """--from_bam / --from_bams with --resident: hotspots and ``shard<N>.txt`` as ``shards_from_bam(s)`` write them, then ONE loop
+    in this process: shard file -> candidate sites whose reads stay on the GPU (``candidates.resident_activity``) -> ``ShardScorer``
+    (coalesced up to --sites_per_launch) -> record stage.  No read is written to disk and no ``<workdir>/shards`` exists; the
+    candidate stage runs at the thresholds of the route without --resident, so both give the same bytes."""
+    from . import candidates as cd, shard_pipeline as sp
+    logger = logging.getLogger("hello_amd.call")
+    check_resident(args)
+    if args.from_bams:
+        from . import hybrid as hy
+        genome, ns, bam = _from_bams_stages(args)
+        find, kw = hy.find_hybrid_candidates, dict(hybrid_hotspot=args.hybrid_hotspot, reassembly_size=args.reconcilement_size,
+                                                   q_threshold=args.q_threshold, mapq_threshold=args.mapq_threshold)
+    else:
+        genome, ns, bam, find = _from_bam_stages(args)
+        kw = {}
+    files = list(_shard_files(ns))
+    features_dir = os.path.join(args.workdir, features_dir_name(args.ibam, args.pbam))
+    os.makedirs(features_dir, exist_ok=True)
+    wanted = set(args.chromosomes.split(",")) if args.chromosomes else None
+    threads = max(2, min(args.num_threads, len(os.sched_getaffinity(0))))
+
+    from .loader import load
+    network = load(args.network, device=args.device, arithmetic=getattr(args, "arithmetic", "fp32"))
+    network.eval()
+    network.providePredictions = True                  # caller_calling.py:865-868
+    total: dict = {}
+
+    def candidates_of(name):
+        found = list(cd.resident_activity(bam, args.ref, name, genome=genome, find=find, total=total, device=args.device, **kw))
+        if len(found) != 1:                             # _shard_files writes one chromosome per file
+            raise ValueError(f"{name}: positions on {len(found)} chromosomes; a shard file holds one")
+        logger.info("%s: %d sites", name, found[0].n_sites)
+        return found[0]
+    t0 = time.perf_counter()
+    stats = sp.run(network, [name for _, name in files], lambda n: os.path.join(features_dir, "features%d" % n), args.include_hp,
+                   _genome_bytes(genome), wanted, record_threads=max(1, threads - 1),
+                   sites_per_launch=getattr(args, "sites_per_launch", 8192), tags=[n for n, _ in files], loader=candidates_of,
+                   in_thread=True)
+    network.close()
+    logger.info("%d shard files, %d sites, %d reads in %d launches, %.2f s (candidate stage %.2f s of it, %.1f ms in its kernels; "
+                "staging %.2f s, record stage %.2f s on its threads; resident set after the loop %.0f MB)", len(files), stats.sites,
+                stats.reads, stats.launches, stats.seconds, stats.wait_read,
+                sum(total.get(k, 0.0) for k in ("pass1_kernel_ms", "pass2_kernel_ms", "allele_kernel_ms", "clip_kernel_ms")),
+                stats.stage_seconds, stats.record_seconds, _resident_mb())
+    for out in stats.outputs:                           # call.py:225-229
+        if SENTINEL not in open(out.prefix + ".log").read():
+            raise ValueError("Did not run: log file %s doesn't have termination string" % (out.prefix + ".log"))
+    result_path = os.path.join(args.workdir, "results.output.vcf")
+    lengths = {c: len(g) for c, g in genome.items()}
+    n = sp.merge_final_vcf(stats.outputs, lambda names: header(names, lengths), result_path)
+    logger.info("Completed runs in %.2f s. %d records in %s", time.perf_counter() - t0, n, result_path)
+    return result_path
 
 
 def main(args) -> str:
     logger = logging.getLogger("hello_amd.call")
+    if getattr(args, "resident", False):
+        return run_resident(args)
     if getattr(args, "from_bams", False) and not args.shards:
         if getattr(args, "from_bam", False):
             raise SystemExit("--from_bam (one BAM) and --from_bams (an Illumina and a PacBio BAM) exclude each other")

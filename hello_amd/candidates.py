@@ -103,8 +103,11 @@ def shard_positions(positions: Sequence[int], max_shards: int = 500, min_separat
 
 def find_sites(reads: Reads, reference: str, positions: Sequence[int], chromosome: str = "chr", feature_length: int = 150,
                q_threshold: int = DEFAULT_Q_THRESHOLD, mapq_threshold: int = DEFAULT_MIN_MAPQ, device: int = 0,
-               options: int = 0) -> Tuple[shards.PackedShard, Dict[str, float], Dict[str, np.ndarray]]:
-    """One call over already decoded reads -> (validated shard, statistics, {read_index, regions_pass1, regions_pass2})."""
+               options: int = 0, resident: bool = False) -> Tuple[shards.PackedShard, Dict[str, float], Dict[str, np.ndarray]]:
+    """One call over already decoded reads -> (validated shard, statistics, {read_index, regions_pass1, regions_pass2}).
+    ``resident``: the reads stay on the GPU and the shard is a ``resident.ResidentShard`` (close it, or hand it to
+    ``ShardScorer.submit``, which does); the extra arrays then also hold read_off0 and cigar_off0."""
+    from . import resident as rs
     ref = np.frombuffer(reference.encode("latin-1"), np.uint8)
     pos = np.ascontiguousarray(positions, dtype=np.int64)
     lib = _lib()
@@ -113,11 +116,13 @@ def find_sites(reads: Reads, reference: str, positions: Sequence[int], chromosom
     r = reads
     rc = lib.hello_candidates_find(ptr(r.bases), ptr(r.quals), ptr(r.read_offsets), ptr(r.cigars), ptr(r.cigar_offsets),
                                    ptr(r.ref_starts), ptr(r.ref_ends), ptr(r.mapq), ptr(r.flags), ptr(r.name_hash), ptr(r.hp),
-                                   int(r.n_reads), ptr(ref), int(ref.shape[0]), ptr(pos), int(pos.shape[0]), int(options),
+                                   int(r.n_reads), ptr(ref), int(ref.shape[0]), ptr(pos), int(pos.shape[0]),
+                                   int(options) | (rs.HELLO_CANDIDATES_RESIDENT if resident else 0),
                                    int(feature_length), int(q_threshold), int(mapq_threshold), int(device), C.byref(h))
     if rc != 0:
         message = lib.hello_last_error().decode(errors="replace")
         raise (ValueError if rc == -1 else RuntimeError)(message)
+    keep = False
     try:
         got = {}
         for name, which, dtype in _ARRAYS:
@@ -128,24 +133,36 @@ def find_sites(reads: Reads, reference: str, positions: Sequence[int], chromosom
                 (C.c_char * (k * np.dtype(dtype).itemsize)).from_address(p.value), dtype).copy()
         st = (C.c_double * N_STATS)()
         lib.hello_candidates_stats(h, st)
+        extra = {k: got.pop(k) for k in ("read_index", "regions_pass1", "regions_pass2")}
+        got.update(chromosome_table(chromosome, got["start"].shape[0]), has_second=np.array(0))
+        if resident:
+            extra.update(read_off0=got["read_off0"], cigar_off0=got["cigar_off0"])
+            shard = rs.ResidentShard(h.value, got, feature_length)          # owns the handle from here on, also when it raises
+            keep = True
+        else:
+            shard = shards.PackedShard(got, feature_length)
     finally:
-        lib.hello_candidates_free(h)
-    extra = {k: got.pop(k) for k in ("read_index", "regions_pass1", "regions_pass2")}
-    n_sites = got["start"].shape[0]
+        if not keep:
+            lib.hello_candidates_free(h)
+    return shard, dict(zip(STAT_NAMES, list(st))), extra
+
+
+def chromosome_table(chromosome: str, n_sites: int) -> Dict[str, np.ndarray]:
+    """The chromosome arrays of a shard whose ``n_sites`` sites all lie on ``chromosome``."""
     name = np.frombuffer(chromosome.encode("ascii"), np.uint8)
-    got.update(chromosome_text=name if n_sites else np.zeros(0, np.uint8),
-               chromosome_text_off=np.array([0, name.shape[0]] if n_sites else [0], np.int64),
-               chromosome_of_site=np.zeros(n_sites, np.int32), has_second=np.array(0))
-    return shards.PackedShard(got, feature_length), dict(zip(STAT_NAMES, list(st))), extra
+    return dict(chromosome_text=name if n_sites else np.zeros(0, np.uint8),
+                chromosome_text_off=np.array([0, name.shape[0]] if n_sites else [0], np.int64),
+                chromosome_of_site=np.zeros(n_sites, np.int32))
 
 
 def find_candidates(bam, fasta: Optional[str], chromosome: str, positions: Sequence[int], q_threshold: int = DEFAULT_Q_THRESHOLD,
                     mapq_threshold: int = DEFAULT_MIN_MAPQ, device: int = 0, feature_length: int = 150, pacbio: bool = False,
                     hybrid_hotspot: bool = False, reference: Optional[str] = None,
-                    stats: Optional[dict] = None) -> shards.PackedShard:
+                    stats: Optional[dict] = None, resident: bool = False) -> shards.PackedShard:
     """The candidate sites of the sorted hotspot ``positions`` of ``chromosome`` as a validated ``PackedShard``: sites, alleles
     (reference allele first, then ascending byte order) and every allele's supporting reads (file order).  ``bam``: one path
-    (a list of two, ``pacbio`` and ``hybrid_hotspot`` are refused).  ``stats``: filled with the statistics of the call."""
+    (a list of two, ``pacbio`` and ``hybrid_hotspot`` are refused).  ``stats``: filled with the statistics of the call.
+    ``resident``: a ``resident.ResidentShard`` whose reads stay on the GPU."""
     paths = [bam] if isinstance(bam, str) else list(bam)
     if len(paths) != 1 or pacbio or hybrid_hotspot:
         raise ValueError(REFUSAL)
@@ -160,7 +177,8 @@ def find_candidates(bam, fasta: Optional[str], chromosome: str, positions: Seque
         hi = int(positions.max()) + MIN_DISTANCE // 2 + FLANKING_BASES
     with BamFile(paths[0]) as b:
         reads = b.fetch(chromosome, lo, max(hi, lo))
-    shard, st, extra = find_sites(reads, reference, positions, chromosome, feature_length, q_threshold, mapq_threshold, device)
+    shard, st, extra = find_sites(reads, reference, positions, chromosome, feature_length, q_threshold, mapq_threshold, device,
+                                  resident=resident)
     if stats is not None:
         stats.update(st)
         stats.update(extra)
@@ -168,7 +186,7 @@ def find_candidates(bam, fasta: Optional[str], chromosome: str, positions: Seque
 
 
 def write_packed(path: str, shard: shards.PackedShard) -> str:
-    """A ``PackedShard`` as a ``.hshard`` file, array for array."""
+    """A ``PackedShard`` as a ``.hshard`` file, array for array (a resident shard is refused: its reads are on the GPU)."""
     return shards.write_flat(path, {k: np.asarray(v) for k, v in shard.z.items()})
 
 
@@ -239,6 +257,30 @@ def run_activity(bam: str, fasta: str, activity: str, output_prefix: str, featur
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     shards.write_flat(path, concat_payloads(parts))
     return path, total
+
+
+def resident_activity(bam, fasta: str, activity: str, genome: Optional[Dict[str, str]] = None, find=None, total: Optional[dict] = None,
+                      **kw):
+    """``run_activity`` without the file: yields one ``ResidentShard`` per chromosome of the activity file, in file order (the
+    caller closes them or hands them to ``ShardScorer.submit``).  ``find``: ``find_candidates`` (default),
+    ``pacbio.find_pacbio_candidates`` or ``hybrid.find_hybrid_candidates``; ``kw``: its thresholds and options; ``total``: the
+    statistics are summed into it."""
+    find = find or find_candidates
+    from .call import read_fasta
+    by_chromosome = read_positions(activity)
+    if genome is None:
+        genome = read_fasta(fasta, list(by_chromosome))
+    for chromosome, positions in by_chromosome.items():
+        if chromosome not in genome:
+            raise ValueError(f"{fasta}: no sequence named {chromosome!r}")
+        st: dict = {}
+        shard = find(bam, fasta, chromosome, positions, reference=genome[chromosome], stats=st, resident=True, **kw)
+        shard.path = activity
+        if total is not None:
+            for k, v in st.items():
+                if not isinstance(v, np.ndarray):
+                    total[k] = total.get(k, 0.0) + v
+        yield shard
 
 
 def main(argv=None) -> str:

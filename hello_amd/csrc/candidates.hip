@@ -33,6 +33,10 @@
 // no product is enumerated), hybrid_alleles_kernel (a reassigned read's records are aliases of Illumina records; grouping,
 // partials, alleles with the PacBio share of every allele's reads).  The coverage gate is an integer reduction per cluster on the
 // host.  allele_kernel is the kWhole instantiation of the same function: the single-BAM launches execute what they did.
+//
+// Resident (HELLO_CANDIDATES_RESIDENT): the host gather is skipped; the result keeps the pass-2 reads and a gather table per
+// technology on the device (keep_resident), and hello_candidates_gather has gather_reads_kernel write the featurizer's per-read
+// arrays straight into the scoring loop's launch block.
 #include <algorithm>
 #include <chrono>
 #include <memory>
@@ -50,6 +54,23 @@ int set_last_error(int code, const char* fmt, ...);      // engine.hip
 int exception_status(const char* where) noexcept;         // engine.hip
 }  // namespace hello
 
+namespace hello {
+namespace {
+
+// What hello_candidates_gather reads: the reads of pass 2 (rs2), per read the orientation and hp of its input read, and per
+// technology the gather table (GatherTable::upload).  Everything is owned by `mem`.
+struct Resident {
+    DevMem mem;
+    const uint8_t* bases = nullptr; const uint8_t* quals = nullptr; const int64_t* read_off = nullptr;
+    const uint32_t* cigars = nullptr; const int64_t* cigar_off = nullptr; const int64_t* ref_start = nullptr;
+    const uint8_t* mapq = nullptr; const int8_t* orientation = nullptr; const uint8_t* hp = nullptr;
+    struct Table { const int64_t* source = nullptr; const int64_t* base_off = nullptr; const int64_t* cigar_off = nullptr;
+                   const int32_t* site = nullptr; } table[2];
+};
+
+}  // namespace
+}  // namespace hello
+
 struct hello_candidates {
     std::vector<int64_t> start, stop, window_start, ref_off{0}, allele_text_off{0}, read_off{0}, cigar_off{0}, ref_start, read_index;
     std::vector<int64_t> regions1, regions2;         // (start, stop) pairs: the differing regions of pass 1 and of pass 2
@@ -60,6 +81,10 @@ struct hello_candidates {
     double stats[HELLO_CANDIDATES_STATS] = {0};
     std::unique_ptr<hello_candidates> second;        // two BAMs: the read arrays of technology 1 (hello_candidates_array_tech)
     double hybrid_stats[HELLO_CANDIDATES_HYBRID_STATS - HELLO_CANDIDATES_STATS] = {0};
+    // HELLO_CANDIDATES_RESIDENT: the pass-2 reads and the gather tables on the device (hello_candidates_gather); nullptr for a
+    // result without sites, which holds no device memory
+    bool resident = false;
+    std::unique_ptr<hello::Resident> on_device;
 };
 
 namespace hello {
@@ -1229,6 +1254,145 @@ void gather_reads(hello_candidates& o, const ReadSet& rs2, const uint16_t* flags
     for (int64_t& r : o.read_index) r = rs2.input(r);                      // the input read of a clipped read
 }
 
+// ---- resident candidates (HELLO_CANDIDATES_RESIDENT)
+
+// The featurizer's reads of one technology (shards.py: PackedShard.featurizer_core): every allele's supporting reads, an
+// allele without one gets a dummy read.  source: per output read the index of the supporting read among the technology's
+// supporting reads (allele after allele, the numbering of read_off / cigar_off), -1 for a dummy; base_off / cigar_off: the
+// exclusive scans of the output reads' base and CIGAR counts (a dummy has none); site: the site of every output read.
+struct GatherTable {
+    std::vector<int64_t> source, base_off{0}, cigar_off{0};
+    std::vector<int32_t> site;
+
+    void build(const int32_t* reads_per_allele, int64_t n_alleles, const int64_t* read_off, const int64_t* cig_off,
+               const int32_t* alleles_per_site, int64_t n_sites) {
+        int64_t i = 0, al = 0;
+        auto allele = [&](int32_t s) {
+            const int32_t n = reads_per_allele[al++];
+            for (int32_t k = 0; k < std::max(n, 1); ++k) {
+                const bool real = k < n;
+                source.push_back(real ? i : -1);
+                base_off.push_back(base_off.back() + (real ? read_off[i + 1] - read_off[i] : 0));
+                cigar_off.push_back(cigar_off.back() + (real ? cig_off[i + 1] - cig_off[i] : 0));
+                site.push_back(s);
+                i += real;
+            }
+        };
+        if (alleles_per_site)
+            for (int64_t s = 0; s < n_sites; ++s)
+                for (int32_t k = 0; k < alleles_per_site[s]; ++k) allele((int32_t)s);
+        else
+            while (al < n_alleles) allele(0);
+    }
+};
+
+struct GatherArgs {
+    const uint8_t* bases; const uint8_t* quals; const int64_t* read_off; const uint32_t* cigars; const int64_t* cigar_off;
+    const int64_t* ref_start; const uint8_t* mapq; const int8_t* orientation; const uint8_t* hp;        // the reads of pass 2
+    const int64_t* source; const int64_t* t_base_off; const int64_t* t_cigar_off; const int32_t* site;  // the gather table
+    uint8_t* out_bases; uint8_t* out_quals; int64_t* out_read_off; uint32_t* out_cigars; int64_t* out_cigar_off;
+    int64_t* out_ref_start; uint8_t* out_mapq; int8_t* out_orientation; uint8_t* out_hp; int32_t* out_site;
+    int64_t n_reads, read_shift, base_shift, cigar_shift;
+    int32_t site_shift;
+};
+
+// One wave per output read: the lanes copy the read's bases, qualities and CIGAR words to [base_shift + base_off[i], ...) /
+// [cigar_shift + cigar_off[i], ...) byte by byte and word by word (offsets on either side are arbitrary; nothing outside the
+// read's own range is touched); lane 0 writes the per-read entries at read_shift + i and the offsets behind it.  Every output
+// element has one writer.
+__global__ __launch_bounds__(256) void gather_reads_kernel(GatherArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= a.n_reads) return;
+    const int64_t r = a.source[i];
+    const int64_t b0 = a.t_base_off[i], b1 = a.t_base_off[i + 1], c0 = a.t_cigar_off[i], c1 = a.t_cigar_off[i + 1];
+    if (r >= 0) {
+        const int64_t src = a.read_off[r], dst = a.base_shift + b0, n_bases = b1 - b0;
+        for (int64_t k = lane; k < n_bases; k += 64) {
+            a.out_bases[dst + k] = a.bases[src + k];
+            a.out_quals[dst + k] = a.quals[src + k];
+        }
+        const int64_t csrc = a.cigar_off[r], cdst = a.cigar_shift + c0, n_ops = c1 - c0;
+        for (int64_t k = lane; k < n_ops; k += 64) a.out_cigars[cdst + k] = a.cigars[csrc + k];
+    }
+    if (lane == 0) {
+        const int64_t o = a.read_shift + i;
+        if (i == 0) {
+            a.out_read_off[o] = a.base_shift;
+            a.out_cigar_off[o] = a.cigar_shift;
+        }
+        a.out_read_off[o + 1] = a.base_shift + b1;
+        a.out_cigar_off[o + 1] = a.cigar_shift + c1;
+        a.out_ref_start[o] = r >= 0 ? a.ref_start[r] : 0;                    // the dummy read of featurizer_core
+        a.out_mapq[o] = r >= 0 ? a.mapq[r] : (uint8_t)40;
+        a.out_orientation[o] = r >= 0 ? a.orientation[r] : (int8_t)1;
+        a.out_hp[o] = r >= 0 ? a.hp[r] : (uint8_t)0;
+        a.out_site[o] = a.site[i] + a.site_shift;
+    }
+}
+
+template <class T> const T* device_copy(DevMem& m, const T* from, size_t n) {       // device to device
+    void* p = nullptr;
+    HS_HIP(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)));
+    m.ptrs.push_back(p);
+    if (n) HS_HIP(hipMemcpy(p, from, n * sizeof(T), hipMemcpyDeviceToDevice));
+    return (const T*)p;
+}
+
+// HELLO_CANDIDATES_RESIDENT instead of gather_reads: rs2's device arrays are copied on the device into memory the result
+// owns (the call's own allocations -- the chromosome, the kernels' scratch, pass 1 -- are freed when it returns), the gather
+// table of every technology is uploaded, and read_index is turned into input reads as gather_reads does.  Reads below
+// `n_first` of rs2 take orientation and hp from flags0 / hp0, the others from flags1 / hp1.
+void keep_resident(hello_candidates& o, const ReadSet& rs2, int64_t n_first, const uint16_t* flags0, const uint8_t* hp0,
+                   const uint16_t* flags1, const uint8_t* hp1) {
+    o.resident = true;
+    hello_candidates* tech[2] = {&o, o.second.get()};
+    if (!o.start.empty()) {
+        auto res = std::make_unique<Resident>();
+        DevMem& m = res->mem;
+        const size_t n = (size_t)rs2.n;
+        res->bases = device_copy(m, rs2.d_bases, (size_t)rs2.read_off[n]);
+        res->quals = device_copy(m, rs2.d_quals, (size_t)rs2.read_off[n]);
+        res->read_off = device_copy(m, rs2.d_read_off, n + 1);
+        res->cigars = device_copy(m, rs2.d_cigars, (size_t)rs2.cigar_off[n]);
+        res->cigar_off = device_copy(m, rs2.d_cigar_off, n + 1);
+        res->ref_start = device_copy(m, rs2.d_ref_start, n);
+        res->mapq = m.put(rs2.mapq, n);
+        std::vector<int8_t> orientation(n);
+        std::vector<uint8_t> hp(n);
+        for (int64_t r = 0; r < rs2.n; ++r) {
+            const int64_t in = rs2.input(r);
+            orientation[r] = ((r < n_first ? flags0 : flags1)[in] & 16) ? -1 : 1;
+            hp[r] = (r < n_first ? hp0 : hp1)[in];
+        }
+        res->orientation = m.put(orientation.data(), n);
+        res->hp = m.put(hp.data(), n);
+        for (int t = 0; t < 2 && tech[t]; ++t) {
+            GatherTable table;
+            table.build(tech[t]->reads_per_allele.data(), (int64_t)tech[t]->reads_per_allele.size(), tech[t]->read_off.data(),
+                        tech[t]->cigar_off.data(), o.alleles_per_site.data(), (int64_t)o.alleles_per_site.size());
+            for (int64_t& s : table.source)
+                if (s >= 0) s = tech[t]->read_index[s];                     // the read of rs2
+            res->table[t].source = m.put(table.source.data(), table.source.size());
+            res->table[t].base_off = m.put(table.base_off.data(), table.base_off.size());
+            res->table[t].cigar_off = m.put(table.cigar_off.data(), table.cigar_off.size());
+            res->table[t].site = m.put(table.site.data(), table.site.size());
+        }
+        HS_HIP(hipStreamSynchronize(0));       // the copies are complete before a gather on another stream reads them
+        o.on_device = std::move(res);
+    }
+    for (int t = 0; t < 2 && tech[t]; ++t)
+        for (int64_t& r : tech[t]->read_index) r = rs2.input(r);
+}
+
+// The sizes of a technology's featurizer input, dummy reads included.
+void featurizer_counts(const hello_candidates& c, int64_t& n_reads, int64_t& n_bases, int64_t& n_cigars) {
+    n_reads = 0;
+    for (int32_t n : c.reads_per_allele) n_reads += std::max(n, 1);
+    n_bases = c.read_off.back();
+    n_cigars = c.cigar_off.back();
+}
+
 // ---- two BAMs
 
 // One pass's reads of both technologies as one set: the Illumina input reads, then the clipped PacBio copies (table 1).
@@ -1353,8 +1517,8 @@ int hello_candidates_find(const uint8_t* bases, const uint8_t* quals, const int6
     if (options & (HELLO_HOTSPOTS_TWO_BAMS | HELLO_HOTSPOTS_HYBRID))
         return set_last_error(HELLO_ERR_ARG, "candidate sites are built from one Illumina BAM: PacBio reads, two BAMs and hybrid "
                                              "hotspots need the PacBio reassembly and read clipping, which this library does not have");
-    if (options & ~HELLO_HOTSPOTS_PACBIO) return set_last_error(HELLO_ERR_ARG, "options %d", options);
-    const bool pacbio = options == HELLO_HOTSPOTS_PACBIO;
+    if (options & ~(HELLO_HOTSPOTS_PACBIO | HELLO_CANDIDATES_RESIDENT)) return set_last_error(HELLO_ERR_ARG, "options %d", options);
+    const bool pacbio = (options & HELLO_HOTSPOTS_PACBIO) != 0, resident = (options & HELLO_CANDIDATES_RESIDENT) != 0;
     for (int64_t i = 1; i < n_positions; ++i)
         if (positions[i] < positions[i - 1]) return set_last_error(HELLO_ERR_ARG, "position %lld: positions are not sorted", (long long)i);
 
@@ -1366,6 +1530,7 @@ int hello_candidates_find(const uint8_t* bases, const uint8_t* quals, const int6
 
     std::vector<Job> jobs1 = active_region_jobs(positions, n_positions);
     auto res = std::make_unique<hello_candidates>();
+    res->resident = resident;
     JobStats st1, st2;
     float allele_ms = 0.0f;
     double ms_gather = 0.0;
@@ -1422,8 +1587,12 @@ int hello_candidates_find(const uint8_t* bases, const uint8_t* quals, const int6
 
         const auto tg = clock::now();
         sites_oob = emit_sites(*res, nullptr, plan, got, rs2, reference, reference_length, feature_length);
-        gather_reads(*res, rs2, flags, hp);
-        ms_gather = std::chrono::duration<double, std::milli>(clock::now() - tg).count();
+        if (resident) {
+            keep_resident(*res, rs2, rs2.n, flags, hp, flags, hp);
+        } else {
+            gather_reads(*res, rs2, flags, hp);
+            ms_gather = std::chrono::duration<double, std::milli>(clock::now() - tg).count();
+        }
     }
     const double ms_total = std::chrono::duration<double, std::milli>(clock::now() - t0).count();
     const double st[HELLO_CANDIDATES_STATS] = {
@@ -1463,7 +1632,9 @@ int hello_candidates_find_hybrid(
     *out = nullptr;
     if (n_reads0 < 0 || n_reads1 < 0 || n_positions < 0 || reference_length < 0 || feature_length <= 0)
         return set_last_error(HELLO_ERR_ARG, "negative count");
-    if (options & ~HELLO_HOTSPOTS_HYBRID) return set_last_error(HELLO_ERR_ARG, "options %d: 0 or HELLO_HOTSPOTS_HYBRID", options);
+    if (options & ~(HELLO_HOTSPOTS_HYBRID | HELLO_CANDIDATES_RESIDENT))
+        return set_last_error(HELLO_ERR_ARG, "options %d: HELLO_HOTSPOTS_HYBRID and HELLO_CANDIDATES_RESIDENT are understood", options);
+    const bool resident = (options & HELLO_CANDIDATES_RESIDENT) != 0;
     for (int64_t i = 1; i < n_positions; ++i)
         if (positions[i] < positions[i - 1]) return set_last_error(HELLO_ERR_ARG, "position %lld: positions are not sorted", (long long)i);
 
@@ -1481,6 +1652,7 @@ int hello_candidates_find_hybrid(
     std::vector<Job> jobs1 = active_region_jobs(positions, n_positions);
     auto res = std::make_unique<hello_candidates>();
     res->second = std::make_unique<hello_candidates>();
+    res->resident = resident;
     JobStats st1, st2;
     float allele_ms = 0.0f, reassembly_ms = 0.0f;
     double ms_gather = 0.0;
@@ -1621,9 +1793,13 @@ int hello_candidates_find_hybrid(
 
         const auto tg = clock::now();
         sites_oob = emit_sites(*res, res->second.get(), plan, got, rs2, reference, reference_length, feature_length);
-        gather_reads(*res, rs2, flags0, hp0);
-        gather_reads(*res->second, rs2, flags1, hp1);
-        ms_gather = std::chrono::duration<double, std::milli>(clock::now() - tg).count();
+        if (resident) {
+            keep_resident(*res, rs2, n_reads0, flags0, hp0, flags1, hp1);
+        } else {
+            gather_reads(*res, rs2, flags0, hp0);
+            gather_reads(*res->second, rs2, flags1, hp1);
+            ms_gather = std::chrono::duration<double, std::milli>(clock::now() - tg).count();
+        }
     }
     const double ms_total = std::chrono::duration<double, std::milli>(clock::now() - t0).count();
     const double st[HELLO_CANDIDATES_STATS] = {
@@ -1700,5 +1876,73 @@ int hello_candidates_hybrid_stats(const hello_candidates* c, double* stats) {
 }
 
 void hello_candidates_free(hello_candidates* c) { delete c; }
+
+int hello_candidates_featurizer_counts(const hello_candidates* c, int32_t tech, int64_t* n_reads, int64_t* n_bases, int64_t* n_cigars) {
+    if (!c || !n_reads || !n_bases || !n_cigars) return hello::set_last_error(HELLO_ERR_ARG, "NULL pointer");
+    if (tech != 0 && (tech != 1 || !c->second)) return hello::set_last_error(HELLO_ERR_ARG, "no technology %d in these candidates", tech);
+    hello::featurizer_counts(tech ? *c->second : *c, *n_reads, *n_bases, *n_cigars);
+    return HELLO_OK;
+}
+
+int hello_candidates_gather(const hello_candidates* c, int32_t tech, uint8_t* bases, uint8_t* quals, int64_t* read_off, uint32_t* cigars,
+                            int64_t* cigar_off, int64_t* ref_start, uint8_t* mapq, int8_t* orientation, uint8_t* hp,
+                            int32_t* site_of_read, int64_t read_shift, int64_t base_shift, int64_t cigar_shift, int64_t site_shift,
+                            void* hip_stream) try {
+    using namespace hello;
+    if (!c) return set_last_error(HELLO_ERR_ARG, "NULL pointer");
+    if (!c->resident)
+        return set_last_error(HELLO_ERR_ARG, "these candidates were not built with HELLO_CANDIDATES_RESIDENT: their reads are on the "
+                                             "host (hello_candidates_array)");
+    if (tech != 0 && (tech != 1 || !c->second)) return set_last_error(HELLO_ERR_ARG, "no technology %d in these candidates", tech);
+    if (read_shift < 0 || base_shift < 0 || cigar_shift < 0 || site_shift < 0 || site_shift > INT32_MAX)
+        return set_last_error(HELLO_ERR_ARG, "negative shift (read_shift %lld, base_shift %lld, cigar_shift %lld, site_shift %lld)",
+                              (long long)read_shift, (long long)base_shift, (long long)cigar_shift, (long long)site_shift);
+    int64_t n_reads = 0, n_bases = 0, n_cigars = 0;
+    featurizer_counts(tech ? *c->second : *c, n_reads, n_bases, n_cigars);
+    if (n_reads == 0) return HELLO_OK;
+    if (!bases || !quals || !read_off || !cigars || !cigar_off || !ref_start || !mapq || !orientation || !hp || !site_of_read)
+        return set_last_error(HELLO_ERR_ARG, "NULL destination for %lld reads", (long long)n_reads);
+    if (!c->on_device) return set_last_error(HELLO_ERR_ARG, "internal: resident candidates with reads and no device memory");
+    const Resident& d = *c->on_device;
+    GatherArgs a{};
+    a.bases = d.bases; a.quals = d.quals; a.read_off = d.read_off; a.cigars = d.cigars; a.cigar_off = d.cigar_off;
+    a.ref_start = d.ref_start; a.mapq = d.mapq; a.orientation = d.orientation; a.hp = d.hp;
+    a.source = d.table[tech].source; a.t_base_off = d.table[tech].base_off; a.t_cigar_off = d.table[tech].cigar_off;
+    a.site = d.table[tech].site;
+    a.out_bases = bases; a.out_quals = quals; a.out_read_off = read_off; a.out_cigars = cigars; a.out_cigar_off = cigar_off;
+    a.out_ref_start = ref_start; a.out_mapq = mapq; a.out_orientation = orientation; a.out_hp = hp; a.out_site = site_of_read;
+    a.n_reads = n_reads; a.read_shift = read_shift; a.base_shift = base_shift; a.cigar_shift = cigar_shift;
+    a.site_shift = (int32_t)site_shift;
+    hipLaunchKernelGGL(gather_reads_kernel, dim3((unsigned)((n_reads + 3) / 4)), dim3(256), 0, (hipStream_t)hip_stream, a);
+    HS_HIP(hipGetLastError());
+    return HELLO_OK;
+} catch (const hello::Fail& f) {
+    return hello::set_last_error(f.code, "%s", f.msg.c_str());
+} catch (...) {
+    return hello::exception_status("hello_candidates_gather");
+}
+
+int hello_candidates_gather_table(const int32_t* reads_per_allele, int64_t n_alleles, const int64_t* read_off, const int64_t* cigar_off,
+                                  int64_t capacity, int64_t* source, int64_t* out_read_off, int64_t* out_cigar_off, int64_t* n_reads) try {
+    using namespace hello;
+    if (!n_reads || !read_off || !cigar_off || (n_alleles > 0 && !reads_per_allele)) return set_last_error(HELLO_ERR_ARG, "NULL pointer");
+    if (n_alleles < 0 || capacity < 0) return set_last_error(HELLO_ERR_ARG, "negative count");
+    for (int64_t k = 0; k < n_alleles; ++k)
+        if (reads_per_allele[k] < 0) return set_last_error(HELLO_ERR_ARG, "allele %lld: negative reads_per_allele", (long long)k);
+    GatherTable t;
+    t.build(reads_per_allele, n_alleles, read_off, cigar_off, nullptr, 0);
+    *n_reads = (int64_t)t.source.size();
+    if (!source && !out_read_off && !out_cigar_off) return HELLO_OK;                 // the size only
+    if ((!source && *n_reads > 0) || !out_read_off || !out_cigar_off) return set_last_error(HELLO_ERR_ARG, "NULL pointer");
+    if (capacity < *n_reads) return set_last_error(HELLO_ERR_ARG, "capacity %lld for %lld reads", (long long)capacity, (long long)*n_reads);
+    std::copy(t.source.begin(), t.source.end(), source);
+    std::copy(t.base_off.begin(), t.base_off.end(), out_read_off);
+    std::copy(t.cigar_off.begin(), t.cigar_off.end(), out_cigar_off);
+    return HELLO_OK;
+} catch (const hello::Fail& f) {
+    return hello::set_last_error(f.code, "%s", f.msg.c_str());
+} catch (...) {
+    return hello::exception_status("hello_candidates_gather_table");
+}
 
 }  // extern "C"

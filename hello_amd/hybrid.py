@@ -58,9 +58,11 @@ def _lib():
 def find_sites(illumina: Reads, pacbio: Reads, reference: str, positions: Sequence[int], chromosome: str = "chr",
                hybrid_hotspot: bool = False, reassembly_size: int = DEFAULT_REASSEMBLY_SIZE, feature_length: int = 150,
                q_threshold: int = cd.DEFAULT_Q_THRESHOLD, mapq_threshold: int = cd.DEFAULT_MIN_MAPQ,
-               device: int = 0) -> Tuple[shards.PackedShard, Dict[str, float], Dict[str, np.ndarray]]:
+               device: int = 0, resident: bool = False) -> Tuple[shards.PackedShard, Dict[str, float], Dict[str, np.ndarray]]:
     """One call over already decoded reads -> (validated hybrid shard, statistics, {read_index0, read_index1, regions_pass1,
-    regions_pass2})."""
+    regions_pass2}).  ``resident``: the reads of both technologies stay on the GPU and the shard is a
+    ``resident.ResidentShard``; the extra arrays then also hold read_off<t> and cigar_off<t>."""
+    from . import resident as rs
     ref = np.frombuffer(reference.encode("latin-1"), np.uint8)
     pos = np.ascontiguousarray(positions, dtype=np.int64)
     lib = _lib()
@@ -69,7 +71,8 @@ def find_sites(illumina: Reads, pacbio: Reads, reference: str, positions: Sequen
     for r in (illumina, pacbio):
         sets += [getattr(r, f).ctypes.data for f in _READ_SET_FIELDS] + [int(r.n_reads)]
     rc = lib.hello_candidates_find_hybrid(*sets, ref.ctypes.data, int(ref.shape[0]), pos.ctypes.data, int(pos.shape[0]),
-                                          HOTSPOTS_HYBRID if hybrid_hotspot else 0, int(reassembly_size), int(feature_length),
+                                          (HOTSPOTS_HYBRID if hybrid_hotspot else 0) | (rs.HELLO_CANDIDATES_RESIDENT if resident else 0),
+                                          int(reassembly_size), int(feature_length),
                                           int(q_threshold), int(mapq_threshold), int(device), C.byref(h))
     if rc != 0:
         message = lib.hello_last_error().decode(errors="replace")
@@ -81,6 +84,7 @@ def find_sites(illumina: Reads, pacbio: Reads, reference: str, positions: Sequen
             raise RuntimeError(lib.hello_last_error().decode(errors="replace"))
         k = int(n.value)
         return np.zeros(0, dtype) if k == 0 else np.frombuffer((C.c_char * (k * np.dtype(dtype).itemsize)).from_address(p.value), dtype).copy()
+    keep = False
     try:
         got = {name: array(0, which, dtype) for name, which, dtype in _SITE_ARRAYS}
         extra = {name: array(0, which, dtype) for name, which, dtype in _REGION_ARRAYS}
@@ -92,14 +96,17 @@ def find_sites(illumina: Reads, pacbio: Reads, reference: str, positions: Sequen
                     got[name[:-1] + str(tech)] = array(tech, which, dtype)
         st = (C.c_double * N_STATS)()
         lib.hello_candidates_hybrid_stats(h, st)
+        got.update(cd.chromosome_table(chromosome, got["start"].shape[0]), has_second=np.array(1))
+        if resident:
+            extra.update({f"{k}{t}": got[f"{k}{t}"] for k in ("read_off", "cigar_off") for t in (0, 1)})
+            shard = rs.ResidentShard(h.value, got, feature_length, hybrid=True)     # owns the handle from here on
+            keep = True
+        else:
+            shard = shards.PackedShard(got, feature_length)
     finally:
-        lib.hello_candidates_free(h)
-    n_sites = got["start"].shape[0]
-    name = np.frombuffer(chromosome.encode("ascii"), np.uint8)
-    got.update(chromosome_text=name if n_sites else np.zeros(0, np.uint8),
-               chromosome_text_off=np.array([0, name.shape[0]] if n_sites else [0], np.int64),
-               chromosome_of_site=np.zeros(n_sites, np.int32), has_second=np.array(1))
-    return shards.PackedShard(got, feature_length), dict(zip(STAT_NAMES, list(st))), extra
+        if not keep:
+            lib.hello_candidates_free(h)
+    return shard, dict(zip(STAT_NAMES, list(st))), extra
 
 
 def split_bams(bam) -> Tuple[str, str]:
@@ -114,10 +121,12 @@ def split_bams(bam) -> Tuple[str, str]:
 def find_hybrid_candidates(bams, fasta: Optional[str], chromosome: str, positions: Sequence[int], hybrid_hotspot: bool = False,
                            reassembly_size: int = DEFAULT_REASSEMBLY_SIZE, q_threshold: int = cd.DEFAULT_Q_THRESHOLD,
                            mapq_threshold: int = cd.DEFAULT_MIN_MAPQ, device: int = 0, feature_length: int = 150,
-                           reference: Optional[str] = None, stats: Optional[dict] = None) -> shards.PackedShard:
+                           reference: Optional[str] = None, stats: Optional[dict] = None,
+                           resident: bool = False) -> shards.PackedShard:
     """The candidate sites of the sorted hotspot ``positions`` of ``chromosome`` from ``bams`` = [Illumina BAM, PacBio BAM] as a
     validated hybrid ``PackedShard``: alleles in the order of ``candidates.find_candidates``, every allele's supporting reads
-    per technology in file order, the PacBio reads clipped.  ``stats``: filled with the statistics of the call."""
+    per technology in file order, the PacBio reads clipped.  ``stats``: filled with the statistics of the call.  ``resident``: a
+    ``resident.ResidentShard`` whose reads of both technologies stay on the GPU."""
     ibam, pbam = split_bams(bams)
     if reference is None:
         from .hotspots import _read_reference
@@ -133,7 +142,7 @@ def find_hybrid_candidates(bams, fasta: Optional[str], chromosome: str, position
     with BamFile(pbam) as b:
         pacbio = b.fetch(chromosome, lo, max(hi, lo))
     shard, st, extra = find_sites(illumina, pacbio, reference, positions, chromosome, hybrid_hotspot, reassembly_size, feature_length,
-                                  q_threshold, mapq_threshold, device)
+                                  q_threshold, mapq_threshold, device, resident=resident)
     if stats is not None:
         stats.update(st)
         stats.update(extra)

@@ -26,10 +26,11 @@ from .hotspots import HOTSPOTS_PACBIO
 def find_pacbio_candidates(bam, fasta: Optional[str], chromosome: str, positions: Sequence[int],
                            q_threshold: int = cd.DEFAULT_Q_THRESHOLD, mapq_threshold: int = cd.DEFAULT_MIN_MAPQ, device: int = 0,
                            feature_length: int = 150, reference: Optional[str] = None,
-                           stats: Optional[dict] = None) -> shards.PackedShard:
+                           stats: Optional[dict] = None, resident: bool = False) -> shards.PackedShard:
     """The candidate sites of the sorted hotspot ``positions`` of ``chromosome`` from one PacBio BAM as a validated
     ``PackedShard``; alleles and supporting reads in the orders of ``candidates.find_candidates``, the reads clipped.  ``bam``:
-    one path.  ``stats``: filled with the statistics of the call."""
+    one path.  ``stats``: filled with the statistics of the call.  ``resident``: a ``resident.ResidentShard`` whose reads (the
+    clipped copies) stay on the GPU where the clip kernel wrote them."""
     paths = [bam] if isinstance(bam, str) else list(bam)
     if len(paths) != 1 or "," in paths[0]:
         raise ValueError(cd.REFUSAL)
@@ -45,7 +46,7 @@ def find_pacbio_candidates(bam, fasta: Optional[str], chromosome: str, positions
     with BamFile(paths[0]) as b:
         reads = b.fetch(chromosome, lo, max(hi, lo))
     shard, st, extra = cd.find_sites(reads, reference, positions, chromosome, feature_length, q_threshold, mapq_threshold, device,
-                                     options=HOTSPOTS_PACBIO)
+                                     options=HOTSPOTS_PACBIO, resident=resident)
     if stats is not None:
         stats.update(st)
         stats.update(extra)

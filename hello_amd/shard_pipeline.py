@@ -29,6 +29,7 @@ import numpy as np
 from . import records as rec
 from .engine import n_pairs
 from .featurizer import FEATURIZE_ARRAYS, featurize_device
+from .resident import GATHER_ARRAYS, ResidentShard
 from .shards import PackedShard
 
 SENTINEL = "Completed running the script"            # caller_calling.py:902, checked by call.py:225-229
@@ -45,9 +46,10 @@ def prepare(shard: PackedShard, hybrid: bool, uses_ref: bool) -> PackedShard:
         return shard
     if hybrid and not shard.has_reads(1):
         raise ValueError("this model scores two read technologies: every allele of the shard needs both read sets")
-    shard.featurizer_core(0)
-    if hybrid:
-        shard.featurizer_core(1)
+    if not isinstance(shard, ResidentShard):                  # a resident shard's reads are laid out by the gather kernel
+        shard.featurizer_core(0)
+        if hybrid:
+            shard.featurizer_core(1)
     if uses_ref and shard.n_sites:
         shard.onehot = shard.segment_onehot()
     return shard
@@ -117,11 +119,11 @@ class ShardScorer:
             at += (count * np.dtype(dtype).itemsize + 15) & ~15
         reads = {}
         for t in techs:
-            fa = [sh.featurizer_core(t) for sh in shards]
-            reads[t] = sum(int(f["site_of_read"].shape[0]) for f in fa)
-            place(("bases", t), np.uint8, sum(int(f["bases"].shape[0]) for f in fa) + 1)
-            place(("quals", t), np.uint8, sum(int(f["quals"].shape[0]) for f in fa) + 1)
-            place(("cigars", t), np.uint32, sum(int(f["cigars"].shape[0]) for f in fa) + 1)
+            sizes = [_sizes(sh, t) for sh in shards]
+            reads[t] = sum(n for n, _, _ in sizes)
+            place(("bases", t), np.uint8, sum(n for _, n, _ in sizes) + 1)
+            place(("quals", t), np.uint8, sum(n for _, n, _ in sizes) + 1)
+            place(("cigars", t), np.uint32, sum(n for _, _, n in sizes) + 1)
             place(("read_off", t), np.int64, reads[t] + 1)
             place(("cigar_off", t), np.int64, reads[t] + 1)
             for name in PER_READ:
@@ -134,14 +136,16 @@ class ShardScorer:
             place(("onehot", None), np.uint8, S * self.L * 5)
         return parts, at, reads, S
 
-    def _fill(self, shards, parts, block: np.ndarray, techs):
+    def _fill(self, shards, parts, block: np.ndarray, techs, origin: int = 0):
         """One pass over the launch's bytes: every shard's arrays land at their place in the pinned block, offsets and
         site indices shifted to the coalesced numbering.  ONE NumPy call per field and launch (a concatenation straight into
         the pinned view, then one vector add of the per-shard shifts), not one per field and shard: with reference-sized shards
-        (400 sites, ~20 per launch) the per-shard form spent more host time in Python call overhead than in copying."""
+        (400 sites, ~20 per launch) the per-shard form spent more host time in Python call overhead than in copying.
+        ``techs`` empty and ``origin`` = the offset of the site arrays: only those, into a block that starts there (resident
+        shards: the per-read arrays are written on the device)."""
         def view(key):
             at, dtype, count = parts[key]
-            return block[at:at + count * dtype.itemsize].view(dtype)
+            return block[at - origin:at - origin + count * dtype.itemsize].view(dtype)
 
         def cat(key, arrays, tail=None):
             v = view(key)
@@ -187,6 +191,7 @@ class ShardScorer:
         shards, tags, A, S, P, t0 = slot.pending
         slot.pending = None
         slot.done.synchronize()
+        _release(shards)                                          # the gather kernels that read their device memory have run
         e = self.engine
         n_logits, n_meta = e.n_experts * A, (3 * S if e.has_meta else 0)
         host = slot.out_pinned.numpy()
@@ -203,7 +208,13 @@ class ShardScorer:
         self.count += 1
         finished = [self._harvest(slot)] if slot.pending is not None else []
         live = [(sh, tg) for sh, tg in zip(shards, tags) if sh.n_sites]
+        on_device = [isinstance(sh, ResidentShard) for sh, _ in live]
+        if any(on_device) and not all(on_device):
+            raise ValueError("a launch takes file shards (PackedShard) or resident shards (ResidentShard), not both: submit them in "
+                             "separate launches")
+        resident = any(on_device)
         if not live:                                               # nothing to launch: empty shards still get their files
+            _release(shards)
             finished.append(Scored(shards, tags, np.zeros((4, 0), np.float32), None))
             return finished
         t0 = time.perf_counter()
@@ -211,15 +222,17 @@ class ShardScorer:
         techs = (0, 1) if self.hybrid else (0,)
         scored = [sh for sh, _ in live]
         parts, nbytes, reads, S = self._layout(scored)
-        slot.pinned = _grow(slot.pinned, nbytes, dtype=torch.uint8, pin_memory=True)
-        self._fill(scored, parts, slot.pinned.numpy(), techs)
+        # resident shards: only the site arrays (the tail of the layout) go through the pinned block
+        origin = parts[("ref", None)][0] if resident else 0
+        slot.pinned = _grow(slot.pinned, nbytes - origin, dtype=torch.uint8, pin_memory=True)
+        self._fill(scored, parts, slot.pinned.numpy(), () if resident else techs, origin)
         self.stage_seconds += time.perf_counter() - t0
         with torch.cuda.stream(self.copy):
             slot.dev = _grow(slot.dev, nbytes, dtype=torch.uint8, device=self.device)
-            slot.dev[:nbytes].copy_(slot.pinned[:nbytes], non_blocking=True)
+            slot.dev[origin:nbytes].copy_(slot.pinned[:nbytes - origin], non_blocking=True)
             slot.copied.record(self.copy)
 
-        rpa = [np.concatenate([sh.featurizer_core(t)["reads_per_allele"] for sh in scored]) for t in techs]
+        rpa = [np.concatenate([_reads_per_allele(sh, t) for sh in scored]) for t in techs]
         aps = np.concatenate([sh.alleles_per_site for sh in scored]).astype(np.int32)
         A, P = int(rpa[0].shape[0]), n_pairs(aps)
         sizes = [e.n_experts * A, 3 * S if e.has_meta else 0, 4 * P]
@@ -229,6 +242,8 @@ class ShardScorer:
         base = slot.dev.data_ptr()
         with torch.cuda.stream(self.compute):
             self.compute.wait_event(slot.copied)
+            if resident:
+                self._gather(scored, parts, slot.dev, techs)
             pile = []
             for t in techs:
                 n = reads[t] * self.L * self.channels[t]
@@ -250,10 +265,44 @@ class ShardScorer:
         slot.pending = (shards, tags, A, S, P, t0)
         return finished
 
+    def _gather(self, shards: Sequence[ResidentShard], parts, dev, techs):
+        """The per-read arrays of resident shards, written into the launch's device block by one gather launch per shard and
+        technology on the compute stream, with the shifts that give the coalesced numbering ``_fill`` gives file shards."""
+        base = dev.data_ptr()
+        for t in techs:
+            pointers = {name: base + parts[(name, t)][0] for name in GATHER_ARRAYS}
+            read_shift = base_shift = cigar_shift = site_shift = 0
+            for sh in shards:
+                sh.gather(t, pointers, read_shift, base_shift, cigar_shift, site_shift, self.compute.cuda_stream)
+                n_reads, n_bases, n_cigars = sh.featurizer_counts(t)
+                read_shift, base_shift, cigar_shift, site_shift = (read_shift + n_reads, base_shift + n_bases, cigar_shift + n_cigars,
+                                                                   site_shift + sh.n_sites)
+            for name, used in (("bases", base_shift), ("quals", base_shift), ("cigars", cigar_shift)):
+                at, dtype, _ = parts[(name, t)]                  # the padding element behind each large array, as _fill writes it
+                dev[at + used * dtype.itemsize:at + (used + 1) * dtype.itemsize].zero_()
+
     def flush(self) -> List[Scored]:
         n = len(self.slots)
         order = [self.slots[(self.count + k) % n] for k in range(n)]      # oldest first
         return [self._harvest(s) for s in order if s.pending is not None]
+
+
+def _sizes(shard, tech: int):
+    """(reads, bases, CIGAR words) of one shard's featurizer input for technology ``tech``."""
+    if isinstance(shard, ResidentShard):
+        return shard.featurizer_counts(tech)
+    f = shard.featurizer_core(tech)
+    return int(f["site_of_read"].shape[0]), int(f["bases"].shape[0]), int(f["cigars"].shape[0])
+
+
+def _reads_per_allele(shard, tech: int) -> np.ndarray:
+    return shard.reads_per_allele(tech) if isinstance(shard, ResidentShard) else shard.featurizer_core(tech)["reads_per_allele"]
+
+
+def _release(shards) -> None:
+    for sh in shards:
+        if isinstance(sh, ResidentShard):
+            sh.close()
 
 
 def cat_into(v: np.ndarray, arrays):
@@ -359,10 +408,11 @@ class RecordWriter:
 def run(network, shard_paths: Sequence[str], prefix_of, include_hp: bool = False, genomes=None, wanted=None,
         reader_threads: int = 4, record_threads: int = 0, sites_per_launch: int = 8192, reads_per_launch: int = 320_000,
         read_ahead: Optional[int] = None, depth: int = 2, tags: Optional[list] = None, loader=None, scorer=None,
-        writer_threads: int = 2) -> "RunStats":
+        writer_threads: int = 2, in_thread: bool = False) -> "RunStats":
     """Score shard files in order with bounded read-ahead: at most ``read_ahead`` loaded shards wait for the GPU, at most
     ``depth`` launches are in flight and at most two scored launches wait for the record writer, whatever the number of
-    shards -- host memory is flat over a run."""
+    shards -- host memory is flat over a run.  ``in_thread``: ``loader`` runs in the calling thread, one path at a time, when
+    its shard is due (resident shards: the loader uses the GPU and its result is released by the thread that made it)."""
     from concurrent.futures import ThreadPoolExecutor
     scorer = scorer or ShardScorer(network, include_hp, depth=depth)
     writer = RecordWriter(prefix_of, genomes, wanted, record_threads)
@@ -400,6 +450,16 @@ def run(network, shard_paths: Sequence[str], prefix_of, include_hp: bool = False
             futures, nxt = [], 0
             batch, batch_tags, sites, reads = [], [], 0, 0
 
+            def next_shard():
+                nonlocal nxt
+                if in_thread:
+                    nxt += 1
+                    return load(shard_paths[nxt - 1])
+                while nxt < len(shard_paths) and len(futures) < read_ahead:
+                    futures.append(pool.submit(load, shard_paths[nxt]))
+                    nxt += 1
+                return futures.pop(0).result()
+
             def launch():
                 nonlocal batch, batch_tags, sites, reads
                 for done in scorer.submit(batch, batch_tags):
@@ -408,11 +468,8 @@ def run(network, shard_paths: Sequence[str], prefix_of, include_hp: bool = False
                 batch, batch_tags, sites, reads = [], [], 0, 0
 
             for i in range(len(shard_paths)):
-                while nxt < len(shard_paths) and len(futures) < read_ahead:
-                    futures.append(pool.submit(load, shard_paths[nxt]))
-                    nxt += 1
                 t0 = time.perf_counter()
-                shard = futures.pop(0).result()
+                shard = next_shard()
                 stats.wait_read += time.perf_counter() - t0
                 if failure:
                     raise failure[0]

@@ -272,20 +272,12 @@ QUERY_OPS = np.zeros(16, np.int64)
 QUERY_OPS[[0, 1, 4, 7, 8]] = 1                    # BAM operations that consume read bases: M, I, S, =, X
 
 
-class PackedShard:
-    """A shard kept as the flat arrays of its file: what the featurizer launch and the record stage need, without a
-    Python object per read or per site (unpacking a shard into ``AlignedRead`` objects and flattening them again costs
-    ~7 us per read on the host -- two orders of magnitude more than scoring the read on the GPU).
+class SiteShard:
+    """The site-level arrays of a shard: what the record stage and the launch's small staging arrays need (sites, reference
+    windows, allele and chromosome byte tables), with their validation.  ``PackedShard`` adds the reads as host arrays,
+    ``hello_amd.resident.ResidentShard`` keeps them on the GPU."""
 
-    The file is the hand-over format from the upstream stages, so everything the kernels will index with is checked
-    here, vectorised (``validate``): a malformed shard raises ``ValueError`` naming the site or read instead of
-    producing wrong pileups or an out-of-bounds access."""
-
-    def __init__(self, arrays: dict, feature_length: int = 150, validate: bool = True):
-        if "alleles" in arrays:                              # the arrays of an ``.npz`` shard: strings as NumPy unicode
-            arrays = from_npz_arrays(arrays)
-        self.z = arrays
-        self.hybrid = bool(int(np.asarray(arrays["has_second"]).reshape(-1)[0]))
+    def _init_sites(self, arrays: dict, feature_length: int):
         self.alleles_per_site = np.asarray(arrays["alleles_per_site"], np.int32)
         self.n_sites = int(self.alleles_per_site.shape[0])
         self.allele_off = np.concatenate([[0], np.cumsum(self.alleles_per_site, dtype=np.int64)])
@@ -302,27 +294,6 @@ class PackedShard:
         self.ref = np.asarray(arrays["ref"], np.uint8)
         self.feature_length = feature_length
         self._names = self._chromosomes = self._chromosome_names = self._ref_text = None
-        self._fa = {}
-        if validate:
-            self.validate(feature_length)
-
-    @classmethod
-    def from_file(cls, path: str, feature_length: int = 150) -> "PackedShard":
-        if path.endswith(".npz"):
-            with np.load(path, allow_pickle=False) as z:
-                arrays = {k: z[k] for k in z.files}
-        else:
-            arrays = read_flat(path)
-        try:
-            shard = cls(arrays, feature_length)
-        except ValueError as e:
-            raise ValueError(f"{path}: {e}") from None
-        shard.path = path
-        return shard
-
-    @classmethod
-    def from_sites(cls, sites: Sequence[CandidateSite], feature_length: int = 150) -> "PackedShard":
-        return cls(_payload(sites), feature_length)
 
     def __len__(self):
         return self.n_sites
@@ -355,52 +326,22 @@ class PackedShard:
             self._ref_text = self.ref.tobytes().decode("ascii")
         return self._ref_text[int(self.ref_off[s]):int(self.ref_off[s + 1])]
 
-    def has_reads(self, tech: int) -> bool:
-        """Technology ``tech`` is part of this shard: technology 0 always, technology 1 exactly when ``has_second`` says so
-        (``validate`` refuses a file whose arrays disagree with the flag, so what is consumed is what was checked)."""
-        return f"reads_per_allele{tech}" in self.z and (tech == 0 or self.hybrid)
+    def _bad(self, what, index=None, kind="site"):
+        where = ""
+        if index is not None:
+            i = int(index)
+            named = kind == "site" and i < min(self.n_sites, self.start.shape[0], self.chromosome_of_site.shape[0])
+            where = f" ({kind} {i}" + (f", {self.chromosomes[i]}:{int(self.start[i])}" if named else "") + ")"
+        raise ValueError(f"malformed shard: {what}{where}")
 
-    def n_reads(self, tech: int = 0) -> int:
-        """Reads the featurizer will write for technology ``tech`` (dummy reads of unsupported alleles included)."""
-        if not self.has_reads(tech):
-            return 0
-        return int(np.maximum(np.asarray(self.z[f"reads_per_allele{tech}"], np.int64), 1).sum())
-
-    # -- validation --------------------------------------------------------------------------------------------
-    def validate(self, feature_length: int = 150):
-        S, A = self.n_sites, self.n_alleles
-
-        def bad(what, index=None, kind="site"):
-            where = ""
-            if index is not None:
-                i = int(index)
-                named = kind == "site" and i < min(S, self.start.shape[0], self.chromosome_of_site.shape[0])
-                where = f" ({kind} {i}" + (f", {self.chromosomes[i]}:{int(self.start[i])}" if named else "") + ")"
-            raise ValueError(f"malformed shard: {what}{where}")
-
-        # every array the launch's staging block takes (shard_pipeline._fill concatenates them into typed views of one pinned block)
-        # must be an integer array whose values fit the staging type: a float or out-of-range array is refused here, by name,
-        # not by a casting error in the middle of a launch (or silently wrapped)
-        staged = dict(ref=np.uint8, ref_off=np.int64, window_start=np.int64, start=np.int64, stop=np.int64, alleles_per_site=np.int32)
-        for tech in (0, 1):
-            staged.update({f"{k}{tech}": t for k, t in (("reads_per_allele", np.int32), ("bases", np.uint8), ("quals", np.uint8),
-                                                         ("read_off", np.int64), ("cigars", np.uint32), ("cigar_off", np.int64),
-                                                         ("ref_start", np.int64), ("mapq", np.uint8), ("orientation", np.int8), ("hp", np.uint8))})
-        for name, want in staged.items():
-            if name not in self.z:
-                continue
-            arr = np.asarray(self.z[name])
-            if arr.dtype.kind not in "iu":
-                bad(f"array {name} has dtype {arr.dtype} (the launch stages it as {np.dtype(want).name}: integer arrays only)")
-            if arr.size and arr.dtype != np.dtype(want):
-                lim = np.iinfo(want)
-                if int(arr.min()) < lim.min or int(arr.max()) > lim.max:
-                    bad(f"array {name} ({arr.dtype}) holds values outside {np.dtype(want).name}, the type the launch stages it as")
+    def validate_sites(self, feature_length: int = 150):
+        """The site-level checks: tables and offsets are consistent and every reference window covers its feature window."""
+        S, A, bad = self.n_sites, self.n_alleles, self._bad
         if S and int(self.alleles_per_site.min()) < 1:
             bad("a site without alleles", int(np.argmin(self.alleles_per_site)))
         for name in ("chromosome_of_site", "start", "stop", "window_start"):
-            if np.asarray(self.z[name]).shape[0] != S:
-                bad(f"{name} holds {np.asarray(self.z[name]).shape[0]} entries for {S} sites")
+            if getattr(self, name).shape[0] != S:
+                bad(f"{name} holds {getattr(self, name).shape[0]} entries for {S} sites")
         for text, off, n, what in ((self.allele_text, self.allele_text_off, A, "allele strings"),
                                    (self.chromosome_text, self.chromosome_text_off, None, "chromosome names")):
             if off.shape[0] < 1 or off[0] != 0 or np.any(np.diff(off) < 0) or int(off[-1]) != text.shape[0]:
@@ -425,6 +366,97 @@ class PackedShard:
                 s = int(np.argmax(short))
                 bad(f"the reference window [{int(self.window_start[s])}, {int(window_end[s])}) does not cover the feature window "
                     f"[{int(lo[s])}, {int(lo[s]) + feature_length}) and the allele span", s)
+
+    def validate_counts(self, counts, tech: int) -> np.ndarray:
+        """reads_per_allele of technology ``tech``: one non-negative entry per allele.  -> the counts as int64."""
+        counts = np.asarray(counts).astype(np.int64)
+        if counts.shape[0] != self.n_alleles:
+            self._bad(f"reads_per_allele{tech} holds {counts.shape[0]} entries for {self.n_alleles} alleles")
+        if self.n_alleles and int(counts.min()) < 0:
+            self._bad(f"negative reads_per_allele{tech}", np.argmin(counts), "allele")
+        return counts
+
+    # -- record-stage input ------------------------------------------------------------------------------------
+    def segment_onehot(self, genomes=None) -> np.ndarray:
+        """caller_calling.py:53-97 (get_reference_segment + one_hot_encode) for every site: uint8 [S, L, 5], classes
+        A, C, G, T, other -- from the site's reference window (validated to cover the segment)."""
+        L = self.feature_length
+        lo = (self.start + self.stop) // 2 - L // 2
+        index = (self.ref_off[:-1] + (lo - self.window_start))[:, None] + np.arange(L)[None, :]
+        return ONE_HOT[BASE_CLASS[self.ref[index]]]
+
+
+class PackedShard(SiteShard):
+    """A shard kept as the flat arrays of its file: what the featurizer launch and the record stage need, without a
+    Python object per read or per site (unpacking a shard into ``AlignedRead`` objects and flattening them again costs
+    ~7 us per read on the host -- two orders of magnitude more than scoring the read on the GPU).
+
+    The file is the hand-over format from the upstream stages, so everything the kernels will index with is checked
+    here, vectorised (``validate``): a malformed shard raises ``ValueError`` naming the site or read instead of
+    producing wrong pileups or an out-of-bounds access."""
+
+    def __init__(self, arrays: dict, feature_length: int = 150, validate: bool = True):
+        if "alleles" in arrays:                              # the arrays of an ``.npz`` shard: strings as NumPy unicode
+            arrays = from_npz_arrays(arrays)
+        self.z = arrays
+        self.hybrid = bool(int(np.asarray(arrays["has_second"]).reshape(-1)[0]))
+        self._init_sites(arrays, feature_length)
+        self._fa = {}
+        if validate:
+            self.validate(feature_length)
+
+    @classmethod
+    def from_file(cls, path: str, feature_length: int = 150) -> "PackedShard":
+        if path.endswith(".npz"):
+            with np.load(path, allow_pickle=False) as z:
+                arrays = {k: z[k] for k in z.files}
+        else:
+            arrays = read_flat(path)
+        try:
+            shard = cls(arrays, feature_length)
+        except ValueError as e:
+            raise ValueError(f"{path}: {e}") from None
+        shard.path = path
+        return shard
+
+    @classmethod
+    def from_sites(cls, sites: Sequence[CandidateSite], feature_length: int = 150) -> "PackedShard":
+        return cls(_payload(sites), feature_length)
+
+    def has_reads(self, tech: int) -> bool:
+        """Technology ``tech`` is part of this shard: technology 0 always, technology 1 exactly when ``has_second`` says so
+        (``validate`` refuses a file whose arrays disagree with the flag, so what is consumed is what was checked)."""
+        return f"reads_per_allele{tech}" in self.z and (tech == 0 or self.hybrid)
+
+    def n_reads(self, tech: int = 0) -> int:
+        """Reads the featurizer will write for technology ``tech`` (dummy reads of unsupported alleles included)."""
+        if not self.has_reads(tech):
+            return 0
+        return int(np.maximum(np.asarray(self.z[f"reads_per_allele{tech}"], np.int64), 1).sum())
+
+    # -- validation --------------------------------------------------------------------------------------------
+    def validate(self, feature_length: int = 150):
+        A, bad = self.n_alleles, self._bad
+
+        # every array the launch's staging block takes (shard_pipeline._fill concatenates them into typed views of one pinned block)
+        # must be an integer array whose values fit the staging type: a float or out-of-range array is refused here, by name,
+        # not by a casting error in the middle of a launch (or silently wrapped)
+        staged = dict(ref=np.uint8, ref_off=np.int64, window_start=np.int64, start=np.int64, stop=np.int64, alleles_per_site=np.int32)
+        for tech in (0, 1):
+            staged.update({f"{k}{tech}": t for k, t in (("reads_per_allele", np.int32), ("bases", np.uint8), ("quals", np.uint8),
+                                                         ("read_off", np.int64), ("cigars", np.uint32), ("cigar_off", np.int64),
+                                                         ("ref_start", np.int64), ("mapq", np.uint8), ("orientation", np.int8), ("hp", np.uint8))})
+        for name, want in staged.items():
+            if name not in self.z:
+                continue
+            arr = np.asarray(self.z[name])
+            if arr.dtype.kind not in "iu":
+                bad(f"array {name} has dtype {arr.dtype} (the launch stages it as {np.dtype(want).name}: integer arrays only)")
+            if arr.size and arr.dtype != np.dtype(want):
+                lim = np.iinfo(want)
+                if int(arr.min()) < lim.min or int(arr.max()) > lim.max:
+                    bad(f"array {name} ({arr.dtype}) holds values outside {np.dtype(want).name}, the type the launch stages it as")
+        self.validate_sites(feature_length)
         if not self.hybrid:
             stray = sorted(k for k in self.z if k.endswith("1") and k[:-1] in READ_ARRAYS)
             if stray:
@@ -435,10 +467,7 @@ class PackedShard:
                 bad(("has_second is set but " if tech else "") + f"the arrays of technology {tech} are missing ({', '.join(missing)})")
             g = lambda k: np.asarray(self.z[f"{k}{tech}"])                            # noqa: E731
             counts, read_off, cigar_off = g("reads_per_allele").astype(np.int64), g("read_off").astype(np.int64), g("cigar_off").astype(np.int64)
-            if counts.shape[0] != A:
-                bad(f"reads_per_allele{tech} holds {counts.shape[0]} entries for {A} alleles")
-            if A and int(counts.min()) < 0:
-                bad(f"negative reads_per_allele{tech}", np.argmin(counts), "allele")
+            self.validate_counts(counts, tech)
             R = int(counts.sum())
             for name in ("ref_start", "mapq", "orientation", "hp"):
                 if g(name).shape[0] != R:
@@ -512,15 +541,6 @@ class PackedShard:
         for name, dtype in (("bases", np.uint8), ("quals", np.uint8), ("cigars", np.uint32), ("ref", np.uint8)):
             core[name] = np.concatenate([core[name], np.zeros(1, dtype)])
         return core
-
-    # -- record-stage input ------------------------------------------------------------------------------------
-    def segment_onehot(self, genomes=None) -> np.ndarray:
-        """caller_calling.py:53-97 (get_reference_segment + one_hot_encode) for every site: uint8 [S, L, 5], classes
-        A, C, G, T, other -- from the site's reference window (validated to cover the segment)."""
-        L = self.feature_length
-        lo = (self.start + self.stop) // 2 - L // 2
-        index = (self.ref_off[:-1] + (lo - self.window_start))[:, None] + np.arange(L)[None, :]
-        return ONE_HOT[BASE_CLASS[self.ref[index]]]
 
 
 BASE_CLASS = np.full(256, 4, np.uint8)

@@ -325,7 +325,8 @@ void hello_hotspots_free(hello_hotspots* hotspots);
  *   reads: the arrays of hello_bam_fetch, coordinate-sorted, holding every read that overlaps [first position - 90, last
  *          position + 90) (pass 1 fetches 75 bp either side of [first - 15, last + 15]; more reads do no harm); hp = selector
  *          HELLO_BAM_HP.  positions: the sorted positions of a hotspot / shard file on this chromosome.
- *   options: 0 (Illumina reads) or HELLO_HOTSPOTS_PACBIO (PacBio reads, below).  HELLO_HOTSPOTS_TWO_BAMS and
+ *   options: 0 (Illumina reads) or HELLO_HOTSPOTS_PACBIO (PacBio reads, below), either with HELLO_CANDIDATES_RESIDENT (the reads
+ *          stay on the device: "Resident candidates" below).  HELLO_HOTSPOTS_TWO_BAMS and
  *          HELLO_HOTSPOTS_HYBRID are refused (HELLO_ERR_ARG): those paths need the two-BAM reassembly.
  * Three kernel launches on `device` with options == 0 (candidates.hip: differing regions of pass 1, of pass 2, alleles and
  * supports), seven with HELLO_HOTSPOTS_PACBIO (two clip launches before the differing regions of either pass); the reads of
@@ -388,8 +389,8 @@ void hello_candidates_free(hello_candidates* candidates);
  * containers: the Illumina reads under the Illumina cap, unclipped, and the PacBio reads under the PacBio cap, every kept one
  * strictly clipped with flank 200 as under HELLO_HOTSPOTS_PACBIO; filters, the first-of-(name, strand) rule and the cap apply
  * per container, the window tests to both (a searcher with two empty containers has no regions).  Illumina reads count in
- * table 0, PacBio reads in table 1; both tables are flagged and unioned, or, with options == HELLO_HOTSPOTS_HYBRID
- * (--hybrid_hotspot), flagged by the hybrid rule.  In pass 2 a cluster whose Illumina coverage passes the gate (over the reads
+ * table 0, PacBio reads in table 1; both tables are flagged and unioned, or, with HELLO_HOTSPOTS_HYBRID in options
+ * (--hybrid_hotspot), flagged by the hybrid rule (the only other bit understood is HELLO_CANDIDATES_RESIDENT, below).  In pass 2 a cluster whose Illumina coverage passes the gate (over the reads
  * of read set 0 that overlap the cluster's fetch interval and are mapped, primary, not QC-fail, not duplicate and a proper pair
  * if paired, before de-duplication and the cap: a column is every position one of them covers with M = X D N; a read counts at
  * a column with mapq >= 10 and base quality >= 13 there, on D N that of its last read base before; the gate is sum of counts >
@@ -422,6 +423,45 @@ int hello_candidates_array_tech(const hello_candidates* candidates, int32_t tech
  * clusters, ms of the reassembly phase (its plan, its kernel and the copy of its results).  The last seven are 0 for the
  * candidates of hello_candidates_find. */
 int hello_candidates_hybrid_stats(const hello_candidates* candidates, double* stats);
+
+/* Resident candidates: the hand-over to the scoring engine without the host.  HELLO_CANDIDATES_RESIDENT is a bit of `options`
+ * of hello_candidates_find and hello_candidates_find_hybrid beside the HELLO_HOTSPOTS_* values.  With it the call runs as
+ * without it up to the sites: the site arrays, reads_per_allele, read_off, cigar_off, read_index, the regions and the
+ * statistics are on the host and identical; the reads of the alleles are NOT gathered on the host -- HELLO_CAND_BASES, QUALS,
+ * CIGARS, REF_START, MAPQ, ORIENTATION and HP answer with count 0 and the `ms host gather` statistic is 0.  Instead the result
+ * owns, on `device`, the reads of pass 2 (bases, qualities, CIGARs, their offsets, ref_start, mapq; for PacBio the clipped
+ * copies where the clip kernel wrote them), per such read the orientation and hp of its input read, and per technology the
+ * gather table: for every read the featurizer will see its pass-2 read or -1 (the dummy read of an allele without reads of
+ * that technology), the exclusive scans of the output reads' base and CIGAR counts, and the read's site.  The chromosome and
+ * all scratch are freed before the call returns.  A result without sites (no reads, no positions, no site) holds no device
+ * memory and needs no GPU.  hello_candidates_free releases the device memory, from the creating thread, whatever device is
+ * current. */
+#define HELLO_CANDIDATES_RESIDENT 64
+/* The sizes of technology `tech`'s featurizer input (hello_engine_featurize) with the dummy reads: reads = sum of
+ * max(reads_per_allele, 1), bases and CIGAR words of the supporting reads.  Host only; resident and non-resident results. */
+int hello_candidates_featurizer_counts(const hello_candidates* candidates, int32_t tech, int64_t* n_reads, int64_t* n_bases,
+                                       int64_t* n_cigars);
+/* One launch of gather_reads_kernel (candidates.hip, a wave per read) on `hip_stream`, asynchronous: technology `tech`'s
+ * featurizer input into DEVICE arrays of the caller.  With n = n_reads of hello_candidates_featurizer_counts it writes
+ * ref_start, mapq, orientation, hp, site_of_read [read_shift, read_shift + n); bases / quals from byte base_shift, cigars from
+ * word cigar_shift; read_off[read_shift] = base_shift and read_off[read_shift + i + 1] = base_shift + bases of reads 0..i,
+ * likewise cigar_off with cigar_shift; site_of_read = the site within these candidates + site_shift -- so consecutive gathers of
+ * several results into one block give the coalesced arrays of one featurizer launch.  A dummy read has ref_start 0, mapq 40,
+ * orientation 1, hp 0, no bases and no CIGAR.  Nothing outside those ranges is written, every element has one writer, two
+ * runs give the same bytes.  The candidates must outlive the launch (free them after the stream has passed it) and the
+ * stream's device must be current.  HELLO_ERR_ARG, naming it: candidates built without HELLO_CANDIDATES_RESIDENT, a NULL
+ * destination with n > 0, tech 1 on candidates of one technology, a negative shift.  n == 0 launches nothing. */
+int hello_candidates_gather(const hello_candidates* candidates, int32_t tech, uint8_t* bases, uint8_t* quals, int64_t* read_off,
+                            uint32_t* cigars, int64_t* cigar_off, int64_t* ref_start, uint8_t* mapq, int8_t* orientation,
+                            uint8_t* hp, int32_t* site_of_read, int64_t read_shift, int64_t base_shift, int64_t cigar_shift,
+                            int64_t site_shift, void* hip_stream);
+/* The host half of a gather table from one technology's counts: reads_per_allele[n_alleles] and the offsets
+ * read_off / cigar_off [sum reads_per_allele + 1] of its supporting reads -> per featurizer read the supporting read or -1
+ * (source[n]), and the scans out_read_off / out_cigar_off [n + 1]; *n_reads = n.  With all three outputs NULL only n is
+ * returned; otherwise capacity >= n.  Host only. */
+int hello_candidates_gather_table(const int32_t* reads_per_allele, int64_t n_alleles, const int64_t* read_off,
+                                  const int64_t* cigar_off, int64_t capacity, int64_t* source, int64_t* out_read_off,
+                                  int64_t* out_cigar_off, int64_t* n_reads);
 
 /* The engine's own stream (a hipStream_t): what a call with hip_stream == NULL runs on.  It is created
  * non-blocking, so it is NOT ordered with the legacy default stream: a caller whose other work sits on the default

@@ -12,10 +12,18 @@ per 100 bp, strict clipping -- the two clip kernels are timed with the other sta
 through hello_candidates_find_hybrid: the same stage times plus the reassembly phase (reassembly_ms) and its counts, against
 tests/hybrid_reference.py on the slice.
 
+--resident [--profile FILE]: the resident route (HELLO_CANDIDATES_RESIDENT) beside the host route.  For the Illumina, the --pacbio
+and the --hybrid input, each in a child process of its own under `timeout`, stopping at the first that fails: in one process and
+on one input the host gather's ms (the statistic of a non-resident call) beside the gather kernel's ms (HIP events on its stream),
+both calls' total ms, and the ms of uploading the whole chromosome as every call does.  Then the wall time of
+`python -m hello_amd.call --from_bam` with and without --resident on one synthetic chromosome (--call-length), three interleaved
+runs each.  Every JSON line is printed and, with --profile, appended to FILE.
+
 One warm-up run, then --repeats timed runs; prints one JSON line with the minimum, the median and the spread of each time."""
 import argparse
 import json
 import os
+import subprocess
 import sys
 import tempfile
 import time
@@ -48,7 +56,16 @@ def main():
     ap.add_argument("--pacbio-coverage", type=float, default=25)
     ap.add_argument("--pacbio-read-length", type=int, default=3000)
     ap.add_argument("--hybrid_hotspot", action="store_true", default=False)
+    ap.add_argument("--resident", action="store_true", default=False, help="the resident route beside the host route (see above)")
+    ap.add_argument("--resident-step", choices=["illumina", "pacbio", "hybrid", "call"], help="one step of --resident (its child processes)")
+    ap.add_argument("--call-length", type=int, default=200_000, help="--resident: the chromosome of the call --from_bam runs")
+    ap.add_argument("--step-timeout", type=int, default=420, help="--resident: seconds each child process may take")
+    ap.add_argument("--profile", help="--resident: append the JSON lines to this file")
     args = ap.parse_args()
+    if args.resident_step:
+        return resident_step(args)
+    if args.resident:
+        return resident(args)
     if args.hybrid:
         return hybrid(args)
     from hello_amd import candidates as cd, hotspots as hs
@@ -189,6 +206,130 @@ def hybrid(args):
     out.update({k: int(st[k]) for k in ("alleles", "reads_gathered", "record_slots", "active_regions", "clusters", "reads_clipped",
                                         "clusters_gate_passed", "clusters_reassembled", "pacbio_reads_eligible", "pacbio_reads_reassigned",
                                         "pacbio_reads_reassigned_by_tie", "illumina_sites")})
+    out.update({k: spread(v) for k, v in times.items()})
+    print(json.dumps(out))
+
+
+def resident(args):
+    """The steps of --resident, each a child process under its own time limit; the first failure ends the run."""
+    common = ["--length", str(args.length), "--coverage", str(args.coverage), "--read-length", str(args.read_length), "--repeats",
+              str(args.repeats), "--pacbio-coverage", str(args.pacbio_coverage), "--pacbio-read-length", str(args.pacbio_read_length),
+              "--call-length", str(args.call_length)]
+    for step in ("illumina", "pacbio", "hybrid", "call"):
+        done = subprocess.run(["timeout", "-k", "10", str(args.step_timeout), sys.executable, os.path.abspath(__file__), "--resident-step",
+                               step] + common, capture_output=True, text=True)
+        if done.returncode != 0:
+            sys.stderr.write(done.stderr[-3000:])
+            raise SystemExit(f"step {step} ended with status {done.returncode}: nothing further is started")
+        line = done.stdout.strip().splitlines()[-1]
+        print(line, flush=True)
+        if args.profile:
+            with open(args.profile, "a") as fh:
+                fh.write(line + "\n")
+
+
+def resident_step(args):
+    if args.resident_step == "call":
+        return resident_call(args)
+    import torch
+    from hello_amd import candidates as cd, hotspots as hs, hybrid as hb
+    from hello_amd.bam import BamFile
+    from hello_amd.resident import GATHER_ARRAYS
+    kind = args.resident_step
+    ref, reads = synthesize(args.length, args.coverage, args.read_length) if kind != "pacbio" else synthesize(
+        args.length, args.pacbio_coverage, args.pacbio_read_length)
+    sets = [reads]
+    if kind == "hybrid":
+        _, pacbio = synthesize(args.length, args.pacbio_coverage, args.pacbio_read_length)
+        noise = np.random.default_rng(7)
+        sets.append([pacbio_noise(r, noise) for r in pacbio])
+    sizes = dict(bases=1, quals=1, read_off=8, cigars=4, cigar_off=8, ref_start=8, mapq=1, orientation=1, hp=1, site_of_read=4)
+    stream = torch.cuda.Stream()
+    with tempfile.TemporaryDirectory() as d:
+        decoded = []
+        for i, rs in enumerate(sets):
+            path = os.path.join(d, f"{i}.bam")
+            write_bam(path, [("chr1", len(ref))], rs, index=True)
+            with BamFile(path) as b:
+                decoded.append(b.fetch("chr1", 0, len(ref)))
+    positions, _ = hs.find_positions(decoded, ref, [(0, len(ref))], pacbio=kind == "pacbio")
+
+    def find(resident):
+        if kind == "hybrid":
+            return hb.find_sites(decoded[0], decoded[1], ref, positions, "chr1", resident=resident)
+        return cd.find_sites(decoded[0], ref, positions, "chr1", options=hs.HOTSPOTS_PACBIO if kind == "pacbio" else 0, resident=resident)
+    times = {k: [] for k in ("host_gather_ms", "host_route_call_ms", "gather_kernel_ms", "resident_call_ms", "reference_upload_ms")}
+    chromosome = torch.from_numpy(np.frombuffer(ref.encode("latin-1"), np.uint8).copy())
+    on_device = torch.empty(len(ref), dtype=torch.uint8, device="cuda")
+    out = {}
+    for i in range(args.repeats + 1):
+        _, st, _ = find(False)
+        shard, rst, _ = find(True)
+        with shard:
+            techs = (0, 1) if kind == "hybrid" else (0,)
+            counts = {t: shard.featurizer_counts(t) for t in techs}
+            buffers = {}
+            for t in techs:
+                n, nb, nc = counts[t]
+                want = dict(bases=nb, quals=nb, read_off=n + 1, cigars=nc, cigar_off=n + 1, ref_start=n, mapq=n, orientation=n, hp=n,
+                            site_of_read=n)
+                buffers[t] = {k: torch.empty(want[k] * sizes[k] + 16, dtype=torch.uint8, device="cuda") for k in GATHER_ARRAYS}
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            for t in techs:
+                shard.gather(t, {k: b.data_ptr() for k, b in buffers[t].items()}, stream=stream.cuda_stream)
+            e1.record(stream)
+            e1.synchronize()
+            kernel_ms = e0.elapsed_time(e1)
+            out = {"sites": shard.n_sites, "featurizer_reads": [counts[t][0] for t in techs], "gathered_bytes": [2 * counts[t][1] + 4 * counts[t][2] for t in techs]}
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        on_device.copy_(chromosome)
+        torch.cuda.synchronize()
+        upload_ms = (time.perf_counter() - t0) * 1e3
+        if i == 0:
+            continue
+        for k, v in (("host_gather_ms", st["gather_ms"]), ("host_route_call_ms", st["total_ms"]), ("gather_kernel_ms", kernel_ms),
+                     ("resident_call_ms", rst["total_ms"]), ("reference_upload_ms", upload_ms)):
+            times[k].append(v)
+    out.update({"resident": kind, "length": args.length, "reads": [len(r) for r in sets], "positions": int(len(positions)), "repeats": args.repeats})
+    out.update({k: spread(v) for k, v in times.items()})
+    print(json.dumps(out))
+
+
+def resident_call(args):
+    """Wall seconds of python -m hello_amd.call --from_bam on one synthetic chromosome through shard files and with --resident,
+    three runs each, interleaved; every run a child process under its own time limit."""
+    from hello_amd import loader, netspec as ns, weights
+    ref, reads = synthesize(args.call_length, args.coverage, args.read_length)
+    times = {"shard_files_s": [], "resident_s": []}
+    with tempfile.TemporaryDirectory() as d:
+        bam, fa, model = os.path.join(d, "x.bam"), os.path.join(d, "g.fa"), os.path.join(d, "model.hello.npz")
+        write_bam(bam, [("chr1", len(ref))], reads, index=True)
+        with open(fa, "w") as fh:
+            fh.write(">chr1\n" + "\n".join(ref[i:i + 60] for i in range(0, len(ref), 60)) + "\n")
+        loader.save_native(model, "single_tech", weights.synth_state(ns.build("single_tech"), seed=17))
+        vcfs = {}
+        for i in range(3):
+            for key, extra in (("shard_files_s", []), ("resident_s", ["--resident"])):
+                work = os.path.join(d, f"{key}{i}")
+                t0 = time.perf_counter()
+                done = subprocess.run(["timeout", "-k", "10", str(args.step_timeout), sys.executable, "-m", "hello_amd.call", "--ibam", bam,
+                                       "--ref", fa, "--workdir", work, "--network", model, "--from_bam"] + extra, cwd=ROOT,
+                                      capture_output=True, text=True)
+                times[key].append(time.perf_counter() - t0)
+                if done.returncode != 0:
+                    sys.stderr.write(done.stderr[-3000:])
+                    raise SystemExit(f"call {key} ended with status {done.returncode}")
+                vcfs[key] = open(os.path.join(work, "results.output.vcf"), "rb").read()
+                shard_bytes = sum(os.path.getsize(os.path.join(r, f)) for r, _, fs in os.walk(work) for f in fs if f.endswith(".hshard"))
+                if key == "shard_files_s":
+                    files_bytes = shard_bytes
+                else:
+                    assert shard_bytes == 0
+        assert vcfs["shard_files_s"] == vcfs["resident_s"]
+    out = {"resident": "call --from_bam", "length": args.call_length, "reads": len(reads), "hshard_bytes_of_the_file_route": files_bytes, "records": sum(1 for line in vcfs["resident_s"].splitlines() if not line.startswith(b"#"))}
     out.update({k: spread(v) for k, v in times.items()})
     print(json.dumps(out))
 
