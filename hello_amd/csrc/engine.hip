@@ -136,6 +136,7 @@ struct hello_engine {
     std::vector<int> lane_tail;                 // [n_lanes]: the last op of each lane
     hipEvent_t ev_lanes_go = nullptr;           // recorded on the call's stream once the inputs are staged: the other lanes start behind it
     DevBuf d_feat_in, d_feat_out;    // featurizer staging (host-pointer callers)
+    DevBuf d_support;                // hello_engine_allele_support staging (host-pointer callers): inputs | out
     hipStream_t own_stream = nullptr;
     hipStream_t last_stream = nullptr;
     hipEvent_t ev_staged = nullptr;  // H2D of the pinned CSR block finished
@@ -594,6 +595,7 @@ void hello_engine_destroy(hello_engine* e) {
     if (e->ev_lanes_go) (void)hipEventDestroy(e->ev_lanes_go);
     e->d_feat_in.release();
     e->d_feat_out.release();
+    e->d_support.release();
     e->d_debug.release();
     e->d_stamps.release();
     if (e->d_weights) (void)hipFree(e->d_weights);
@@ -1410,6 +1412,60 @@ int hello_engine_featurize(hello_engine* e, const uint8_t* bases, const uint8_t*
     return HELLO_OK;
 } catch (...) {
     return hello::exception_status("hello_engine_featurize");
+}
+
+
+int hello_engine_allele_support(hello_engine* e, const int64_t* cigar_offsets, const uint8_t* mapq, const int8_t* orientation,
+                                const int64_t* allele_read_offsets, int64_t n_reads, int64_t n_alleles, int64_t* out,
+                                int32_t flags, void* hip_stream) try {
+    if (!e) return fail(HELLO_ERR_ARG, "engine is NULL");
+    if (n_reads < 0 || n_alleles < 0) return fail(HELLO_ERR_ARG, "negative count");
+    if (n_alleles == 0) return HELLO_OK;
+    if (!cigar_offsets || !mapq || !orientation || !allele_read_offsets || !out) return fail(HELLO_ERR_ARG, "NULL pointer");
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t stream = hip_stream ? (hipStream_t)hip_stream : e->own_stream;
+    e->last_stream = stream;
+    const bool in_dev = flags & HELLO_IN_DEVICE, out_dev = flags & HELLO_OUT_DEVICE;
+    if (!in_dev) {
+        if (allele_read_offsets[0] != 0) return fail(HELLO_ERR_SHAPE, "allele_read_offsets must start at 0");
+        for (int64_t a = 0; a < n_alleles; ++a)
+            if (allele_read_offsets[a + 1] < allele_read_offsets[a])
+                return fail(HELLO_ERR_SHAPE, "allele_read_offsets decreases at allele %lld", (long long)a);
+        if (allele_read_offsets[n_alleles] != n_reads)
+            return fail(HELLO_ERR_SHAPE, "allele_read_offsets ends at %lld, n_reads = %lld", (long long)allele_read_offsets[n_alleles],
+                        (long long)n_reads);
+    }
+    hello::SupportArgs a{};
+    a.cigar_off = (const long long*)cigar_offsets; a.mapq = mapq; a.orientation = orientation;
+    a.allele_off = (const long long*)allele_read_offsets; a.n_reads = n_reads; a.n_alleles = n_alleles; a.out = (long long*)out;
+    const size_t out_bytes = (size_t)n_alleles * 4 * 8;
+    if (!in_dev || !out_dev) {
+        struct Part { const void* src; size_t bytes; size_t off; };
+        Part parts[4] = {{cigar_offsets, (size_t)(n_reads + 1) * 8, 0}, {allele_read_offsets, (size_t)(n_alleles + 1) * 8, 0},
+                         {mapq, (size_t)n_reads, 0}, {orientation, (size_t)n_reads, 0}};
+        size_t total = 0;
+        if (!in_dev)
+            for (auto& p : parts) { p.off = total; total += (p.bytes + 15) & ~size_t(15); }
+        const size_t out_off = total;
+        if (!out_dev) total += out_bytes;
+        HIP_TRY(hipStreamSynchronize(stream));        // the block may be replaced: nothing queued may still read it
+        if (e->d_support.ensure(total)) return fail(HELLO_ERR_HIP, "device allocation of %zu bytes failed", total);
+        char* base = (char*)e->d_support.p;
+        if (!in_dev) {
+            for (auto& p : parts)
+                if (p.bytes) HIP_TRY(hipMemcpyAsync(base + p.off, p.src, p.bytes, hipMemcpyHostToDevice, stream));
+            a.cigar_off = (const long long*)(base + parts[0].off); a.allele_off = (const long long*)(base + parts[1].off);
+            a.mapq = (const uint8_t*)(base + parts[2].off); a.orientation = (const int8_t*)(base + parts[3].off);
+        }
+        if (!out_dev) a.out = (long long*)(base + out_off);
+    }
+    HIP_TRY(hello::launch_allele_support(a, stream));
+    if (!out_dev) HIP_TRY(hipMemcpyAsync(out, a.out, out_bytes, hipMemcpyDeviceToHost, stream));
+    // host arrays were pageable: the copies above are complete only after this
+    if (!in_dev || !out_dev) HIP_TRY(hipStreamSynchronize(stream));
+    return HELLO_OK;
+} catch (...) {
+    return hello::exception_status("hello_engine_allele_support");
 }
 
 }  // extern "C"

@@ -187,4 +187,15 @@ struct FeaturizeArgs {
 };
 hipError_t launch_featurize(const FeaturizeArgs& a, hipStream_t stream);
 
+// ---- per-allele read support (support.hip) -----------------------------------------------------------
+struct SupportArgs {
+    const long long* cigar_off;      // [R+1] as the featurizer reads them: a read without operations is a dummy row
+    const uint8_t* mapq;             // [R]
+    const int8_t* orientation;       // [R] > 0 forward
+    const long long* allele_off;     // [A+1] exclusive scan of reads_per_allele
+    long long n_reads, n_alleles;
+    long long* out;                  // [A][4]: reads, forward reads, sum mapq, sum mapq^2
+};
+hipError_t launch_allele_support(const SupportArgs& a, hipStream_t stream);
+
 }  // namespace hello

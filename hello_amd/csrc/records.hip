@@ -8,6 +8,8 @@
 //   python/vcfFromContigs.py:139-227   fixEmptyAlleles / createVcfRecord normalisation
 // ALT alleles are emitted sorted (hello_amd/vcf.py explains why); ties between pair probabilities are broken the way
 // Python's ``sorted([(v, k)], reverse=True)[0]`` breaks them: by the pair of allele strings.
+// hello_site_records_annotated adds the read support of every allele (hello_engine_allele_support) to the same lines: GQ, DP, AD,
+// ADF and ADR in the sample column, MQ in INFO.  The reference writes none of them; DESIGN.md "Annotations" defines them.
 // No device code in this file.
 #include <algorithm>
 #include <cmath>
@@ -119,6 +121,10 @@ struct SiteCtx {
     Reference ref;
 };
 
+struct Support {                         // read support of the site's alleles, [n_alleles][4] per technology (second: or NULL)
+    const int64_t* tech[2];
+};
+
 struct RowCall {
     bool record = false;
     int64_t position = -1;               // 0-based, after normalisation
@@ -171,8 +177,9 @@ bool pad_left_if_empty(const SiteCtx& s, int64_t& pos, std::string& ref, std::ve
 }
 
 // callAlleles / caller_calling.vcfRecords for one row; appends the line (with '\n') to `out` when there is a record
+// With `support` the line carries the annotations: INFO gains ;MQ, the sample column GQ:DP:AD:ADF:ADR.
 template <class F>
-RowCall call_row(const SiteCtx& s, F value, const char* info, std::string& out, Failure& f) {
+RowCall call_row(const SiteCtx& s, F value, const char* info, const Support* support, std::string& out, Failure& f) {
     RowCall c;
     best_pair(s, value, c.best, c.p);
     c.qual = -10.0 * std::log10(1.0 - (c.p < QUAL_CAP ? c.p : QUAL_CAP));
@@ -235,7 +242,7 @@ RowCall call_row(const SiteCtx& s, F value, const char* info, std::string& out, 
     }
     c.record = true;
     c.position = pos;
-    char num[64];
+    char num[96];
     out.append(s.chromosome.p, s.chromosome.n);
     out.append(num, snprintf(num, sizeof(num), "\t%lld\t.\t", (long long)(pos + 1)));
     out.append(ref);
@@ -246,7 +253,42 @@ RowCall call_row(const SiteCtx& s, F value, const char* info, std::string& out, 
     }
     out.append(num, snprintf(num, sizeof(num), "\t%f\tPASS\t", c.qual));
     out.append(info);
-    out.append(num, snprintf(num, sizeof(num), "\tGT\t%d/%d\n", genotype[0], genotype[1]));
+    if (!support) {
+        out.append(num, snprintf(num, sizeof(num), "\tGT\t%d/%d\n", genotype[0], genotype[1]));
+        return c;
+    }
+    // DP and MQ over every read of the site, whichever allele it supports; AD / ADF per listed allele, found among the site's
+    // alleles by its string BEFORE normalisation (alt_views; the reference allele may not be one of them: 0)
+    long long depth = 0, squares = 0;
+    for (int t = 0; t < 2; ++t)
+        if (support->tech[t])
+            for (int a = 0; a < s.n_alleles; ++a) {
+                depth += support->tech[t][4 * a];
+                squares += support->tech[t][4 * a + 3];
+            }
+    std::vector<long long> ad(1 + alt_views.size(), 0), adf(1 + alt_views.size(), 0);
+    for (size_t x = 0; x <= alt_views.size(); ++x) {
+        const Str& text = x ? alt_views[x - 1] : ref_allele;
+        for (int a = 0; a < s.n_alleles; ++a)
+            if (s.names[a] == text) {
+                for (int t = 0; t < 2; ++t)
+                    if (support->tech[t]) {
+                        ad[x] += support->tech[t][4 * a];
+                        adf[x] += support->tech[t][4 * a + 1];
+                    }
+                break;
+            }
+    }
+    if (depth > 0) out.append(num, snprintf(num, sizeof(num), ";MQ=%.2f", std::sqrt((double)squares / (double)depth)));
+    else out.append(";MQ=.");
+    const double gq = std::floor(c.qual + 0.5);
+    out.append(num, snprintf(num, sizeof(num), "\tGT:GQ:DP:AD:ADF:ADR\t%d/%d:%d:%lld", genotype[0], genotype[1],
+                             gq < 99 ? (int)gq : 99, depth));
+    for (int field = 0; field < 3; ++field)
+        for (size_t x = 0; x < ad.size(); ++x)
+            out.append(num, snprintf(num, sizeof(num), "%c%lld", x ? ',' : ':',
+                                     field == 0 ? ad[x] : (field == 1 ? adf[x] : ad[x] - adf[x])));
+    out.push_back('\n');
     return c;
 }
 
@@ -326,13 +368,10 @@ struct Chunk {                           // what one worker produced for its con
     Failure failure;
 };
 
-}  // namespace
-
-extern "C" {
-
-int hello_site_records(const hello_site_table* t, const float* posteriors, int64_t n_pairs_total, const float* meta,
-                       const int32_t* shard_site_off, int32_t n_shards, const hello_features_format* fmt,
-                       int32_t n_threads, hello_records** out) try {
+// hello_site_records (support0 NULL) and hello_site_records_annotated
+int site_records(const hello_site_table* t, const int64_t* support0, const int64_t* support1, const float* posteriors,
+                 int64_t n_pairs_total, const float* meta, const int32_t* shard_site_off, int32_t n_shards,
+                 const hello_features_format* fmt, int32_t n_threads, hello_records** out) {
     using hello::set_last_error;
     if (!t || !posteriors || !out) return set_last_error(HELLO_ERR_ARG, "NULL pointer");
     const int32_t S = t->n_sites;
@@ -426,10 +465,12 @@ int hello_site_records(const hello_site_table* t, const float* posteriors, int64
             // prepareVcf.py:154-163: sum(float(e_i) * float(meta_i)), Python's sum from the int 0, in float64
             auto mean = [&](int k) { return (((double)row[1][k] * m[0]) + (double)row[2][k] * m[1]) + (double)row[3][k] * m[2]; };
             const bool keep = !t->keep || t->keep[s];
+            const Support support{{support0 ? support0 + 4 * aoff[s] : nullptr, support1 ? support1 + 4 * aoff[s] : nullptr}};
+            const Support* annotate = support0 ? &support : nullptr;
             RowCall calls[5];
             const size_t before = ch.shard_vcf.size();
             if (keep) {
-                calls[0] = call_row(cx, [&](int k) { return (double)row[0][k]; }, "MixtureOfExpertPrediction", ch.shard_vcf, ch.failure);
+                calls[0] = call_row(cx, [&](int k) { return (double)row[0][k]; }, "MixtureOfExpertPrediction", annotate, ch.shard_vcf, ch.failure);
             } else {
                 best_pair(cx, [&](int k) { return (double)row[0][k]; }, calls[0].best, calls[0].p);
                 calls[0].qual = -10.0 * std::log10(1.0 - (calls[0].p < QUAL_CAP ? calls[0].p : QUAL_CAP));
@@ -441,7 +482,7 @@ int hello_site_records(const hello_site_table* t, const float* posteriors, int64
             }
             if (calls[0].record) {                            // a site enters the final VCF through its .features entry
                 const size_t mb = ch.mean_vcf.size();
-                calls[4] = call_row(cx, mean, "HELLO", ch.mean_vcf, ch.failure);
+                calls[4] = call_row(cx, mean, "HELLO", annotate, ch.mean_vcf, ch.failure);
                 ch.mean_len[s - ch.lo] = (int32_t)(ch.mean_vcf.size() - mb);
                 if (calls[4].record) rec->mean_position[s] = calls[4].position;
             } else {
@@ -552,8 +593,27 @@ int hello_site_records(const hello_site_table* t, const float* posteriors, int64
     }
     *out = rec;
     return HELLO_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hello_site_records(const hello_site_table* t, const float* posteriors, int64_t n_pairs_total, const float* meta,
+                       const int32_t* shard_site_off, int32_t n_shards, const hello_features_format* fmt,
+                       int32_t n_threads, hello_records** out) try {
+    return site_records(t, nullptr, nullptr, posteriors, n_pairs_total, meta, shard_site_off, n_shards, fmt, n_threads, out);
 } catch (...) {
     return hello::exception_status("hello_site_records");
+}
+
+int hello_site_records_annotated(const hello_site_table* t, const int64_t* support0, const int64_t* support1, const float* posteriors,
+                                 int64_t n_pairs_total, const float* meta, const int32_t* shard_site_off, int32_t n_shards,
+                                 const hello_features_format* fmt, int32_t n_threads, hello_records** out) try {
+    if (!support0) return hello::set_last_error(HELLO_ERR_ARG, "support0 is NULL (hello_site_records writes the lines without annotations)");
+    return site_records(t, support0, support1, posteriors, n_pairs_total, meta, shard_site_off, n_shards, fmt, n_threads, out);
+} catch (...) {
+    return hello::exception_status("hello_site_records_annotated");
 }
 
 int hello_records_get(const hello_records* r, hello_records_view* v) try {

@@ -90,6 +90,9 @@ def load_library():
     if diagnostics:
         lib.hello_engine_debug_stamps.argtypes = [vp, i32]
         lib.hello_engine_debug_read_stamps.argtypes = [vp, vp, i64, C.POINTER(i64), C.POINTER(i32)]
+    if hasattr(lib, "hello_engine_allele_support"):      # likewise an addition within ABI version 2 (featurizer.allele_support)
+        lib.hello_engine_allele_support.argtypes = [vp, vp, vp, vp, vp, i64, i64, vp, i32, vp]
+        lib.hello_engine_allele_support.restype = C.c_int
     lib.hello_engine_stream.argtypes = [vp]
     lib.hello_engine_stream.restype = C.c_void_p
     lib.hello_engine_destroy.argtypes = [vp]

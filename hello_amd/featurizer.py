@@ -138,3 +138,57 @@ def featurize_device(engine: Engine, pointers: dict, n_reads: int, n_sites: int,
     fn.argtypes = [vp] * 16 + [C.c_int64, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, vp]
     _check(fn(engine.handle, *[pointers[k] for k in FEATURIZE_ARRAYS], n_reads, n_sites, feature_length, channels,
               out_pointer, HELLO_IN_DEVICE | HELLO_OUT_DEVICE, stream))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# per-allele read support (hello_engine_allele_support, hello_amd/csrc/support.hip)
+# ---------------------------------------------------------------------------------------------------------------------
+SUPPORT_ARRAYS = ("cigar_off", "mapq", "orientation", "allele_off")                   # hello_engine_allele_support's order
+SUPPORT_DTYPES = dict(cigar_off=np.int64, mapq=np.uint8, orientation=np.int8, allele_off=np.int64)
+
+
+def _support_fn(engine: Engine):
+    fn = getattr(engine.lib, "hello_engine_allele_support", None)
+    if fn is None:
+        raise RuntimeError("this libhello_mi355x.so has no hello_engine_allele_support: rebuild it (`make -C hello_amd/csrc`)")
+    return fn
+
+
+def allele_offsets(reads_per_allele) -> np.ndarray:
+    """int64 [A + 1]: the exclusive scan of the ``reads_per_allele`` the engine receives (dummy reads count as 1)."""
+    off = np.zeros(int(np.shape(reads_per_allele)[0]) + 1, np.int64)
+    np.cumsum(reads_per_allele, dtype=np.int64, out=off[1:])
+    return off
+
+
+def allele_support(engine: Engine, cigar_off, mapq, orientation, allele_off, device: bool = False):
+    """Per allele, over its reads with at least one CIGAR operation: [reads, forward reads, sum mapq, sum mapq^2], int64 [A, 4].
+    Host form: NumPy arrays in, a NumPy array out (staged through device memory, synchronous).  ``device``: the four arrays
+    are copied to the engine's GPU first and the call takes device pointers, ordered with the caller's current torch stream;
+    -> a torch CUDA tensor."""
+    fn = _support_fn(engine)
+    given = dict(cigar_off=cigar_off, mapq=mapq, orientation=orientation, allele_off=allele_off)
+    host = {k: np.ascontiguousarray(given[k], dtype=SUPPORT_DTYPES[k]) for k in SUPPORT_ARRAYS}
+    n_reads, n_alleles = int(host["mapq"].shape[0]), int(host["allele_off"].shape[0]) - 1
+    if host["cigar_off"].shape[0] != n_reads + 1 or host["orientation"].shape[0] != n_reads or n_alleles < 0:
+        raise ValueError("cigar_off [R + 1], mapq [R], orientation [R] and allele_off [A + 1] do not fit each other")
+    pad = lambda a: a if a.shape[0] else np.zeros(1, a.dtype)                           # noqa: E731 (a pointer is taken of each)
+    if not device:
+        out = np.zeros(4 * max(n_alleles, 1), np.int64)
+        held = {k: pad(v) for k, v in host.items()}
+        _check(fn(engine.handle, *[held[k].ctypes.data for k in SUPPORT_ARRAYS], n_reads, n_alleles, out.ctypes.data, 0, None))
+        return out[:4 * n_alleles].reshape(n_alleles, 4)
+    import torch
+    where = torch.device(f"cuda:{engine.device}")
+    dev = {k: torch.from_numpy(pad(v)).to(where) for k, v in host.items()}
+    out = torch.zeros(4 * max(n_alleles, 1), dtype=torch.int64, device=where)
+    with engine.on_stream(where) as handle:
+        allele_support_device(engine, {k: dev[k].data_ptr() for k in SUPPORT_ARRAYS}, n_reads, n_alleles, out.data_ptr(), handle)
+    return out[:4 * n_alleles].view(n_alleles, 4)
+
+
+def allele_support_device(engine: Engine, pointers: dict, n_reads: int, n_alleles: int, out_pointer: int, stream):
+    """``hello_engine_allele_support`` on arrays ALREADY in device memory (``pointers``: name of SUPPORT_ARRAYS -> device
+    address), asynchronous on ``stream``: what the shard pipeline launches behind each technology's featurizer."""
+    _check(_support_fn(engine)(engine.handle, *[pointers[k] for k in SUPPORT_ARRAYS], n_reads, n_alleles, out_pointer,
+                               HELLO_IN_DEVICE | HELLO_OUT_DEVICE, stream))

@@ -49,6 +49,10 @@ def _lib():
         lib.hello_site_records.argtypes = [C.POINTER(_SiteTable), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
                                            C.POINTER(_FeaturesFormat), C.c_int32, C.POINTER(C.c_void_p)]
         lib.hello_site_records.restype = C.c_int
+        lib.hello_site_records_annotated.argtypes = [C.POINTER(_SiteTable), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                                     C.c_void_p, C.c_int32, C.POINTER(_FeaturesFormat), C.c_int32,
+                                                     C.POINTER(C.c_void_p)]
+        lib.hello_site_records_annotated.restype = C.c_int
         lib.hello_records_get.argtypes = [C.c_void_p, C.POINTER(_View)]
         lib.hello_records_get.restype = C.c_int
         lib.hello_records_destroy.argtypes = [C.c_void_p]
@@ -187,8 +191,10 @@ class Records:
 
 
 def site_records(table: SiteTable, posteriors: np.ndarray, meta: Optional[np.ndarray], shard_site_off=None,
-                 features: bool = True, threads: int = 0) -> Records:
-    """posteriors float32 [4, P] and meta float32 [S, 3] | None on the host, as ``Engine.forward`` returns them."""
+                 features: bool = True, threads: int = 0, support=None) -> Records:
+    """posteriors float32 [4, P] and meta float32 [S, 3] | None on the host, as ``Engine.forward`` returns them.
+    ``support``: None, or one int64 [A, 4] array per technology as ``Engine.allele_support`` returns them -- then the lines
+    carry GQ / DP / AD / ADF / ADR and MQ (``hello_site_records_annotated``; ``hello_amd.vcf.annotate`` states the rules)."""
     lib = _lib()
     post = np.ascontiguousarray(posteriors, dtype=np.float32)
     if post.ndim != 2 or post.shape[0] != 4:
@@ -202,8 +208,18 @@ def site_records(table: SiteTable, posteriors: np.ndarray, meta: Optional[np.nda
         prefix, suffix = meta_pickle_format()
         fmt = _FeaturesFormat(prefix, len(prefix), suffix, len(suffix))
     handle = C.c_void_p()
-    _check(lib.hello_site_records(C.byref(table.struct), post.ctypes.data, int(post.shape[1]),
-                                  m.ctypes.data if m is not None else None,
-                                  off.ctypes.data if off is not None else None, int(off.shape[0]) - 1 if off is not None else 1,
-                                  C.byref(fmt) if fmt is not None else None, int(threads), C.byref(handle)))
+    tail = (post.ctypes.data, int(post.shape[1]), m.ctypes.data if m is not None else None,
+            off.ctypes.data if off is not None else None, int(off.shape[0]) - 1 if off is not None else 1,
+            C.byref(fmt) if fmt is not None else None, int(threads), C.byref(handle))
+    if support is None:
+        _check(lib.hello_site_records(C.byref(table.struct), *tail))
+        return Records(handle)
+    if isinstance(support, np.ndarray):
+        support = [support]
+    sup = [np.ascontiguousarray(t, dtype=np.int64) for t in support]
+    n_alleles = int(table.alleles_per_site.sum())
+    if not 1 <= len(sup) <= 2 or any(t.shape != (n_alleles, 4) for t in sup):
+        raise ValueError(f"support must hold one or two int64 [{n_alleles}, 4] arrays (one per technology)")
+    _check(lib.hello_site_records_annotated(C.byref(table.struct), sup[0].ctypes.data, sup[1].ctypes.data if len(sup) > 1 else None,
+                                            *tail))
     return Records(handle)

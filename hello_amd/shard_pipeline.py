@@ -8,7 +8,10 @@ python/caller_calling.py:859-900).  Here the unit of GPU work is decoupled from 
                         out in ONE pinned block (a single pass over the bytes), cross PCIe in ONE copy on a copy stream
                         into one of ``depth`` device slots, and ``hello_engine_featurize`` -> ``hello_engine_forward`` (+
                         posteriors) run on the compute stream while the next block is being laid out and copied; pair
-                        posteriors + meta weights return through pinned memory
+                        posteriors + meta weights return through pinned memory; with ``annotate`` one launch of
+                        ``hello_engine_allele_support`` per technology follows its featurizer on the same stream (the
+                        per-read arrays are in the block already; on the resident route they exist nowhere else) and the
+                        per-allele read support returns beside the posteriors
     ``RecordWriter``    ``hello_site_records`` (multi-threaded C, hello_amd/records.py) turns a launch's posteriors into
                         every shard's ``.vcf`` lines, ``.features`` pickle stream and final-VCF lines; Python only slices
                         the blobs per shard and writes files -- no per-site Python object anywhere
@@ -28,7 +31,7 @@ import numpy as np
 
 from . import records as rec
 from .engine import n_pairs
-from .featurizer import FEATURIZE_ARRAYS, featurize_device
+from .featurizer import FEATURIZE_ARRAYS, SUPPORT_ARRAYS, allele_support_device, featurize_device
 from .resident import GATHER_ARRAYS, ResidentShard
 from .shards import PackedShard
 
@@ -63,6 +66,7 @@ class Scored:
     posteriors: np.ndarray          # float32 [4, P]
     meta: Optional[np.ndarray]      # float32 [S, 3]
     seconds: float = 0.0
+    support: Optional[List[np.ndarray]] = None      # annotate: int64 [A, 4] per technology (reads, forward, sum mapq, sum mapq^2)
 
 
 class _Slot:
@@ -70,6 +74,7 @@ class _Slot:
         self.pinned = self.dev = None           # staging block (uint8) on both sides
         self.pile = [None, None]                # featurizer output per technology (device uint8)
         self.out_dev = self.out_pinned = None   # float32: logits | meta | posteriors
+        self.sup_dev = self.sup_pinned = None   # annotate: int64 read support [technologies][A][4]
         self.copied = self.done = None
         self.pending = None
 
@@ -84,7 +89,7 @@ def _grow(t, n, **kw):
 class ShardScorer:
     """Featurise + score coalesced shards on the GPU, ``depth`` launches in flight."""
 
-    def __init__(self, network, include_hp: bool = False, feature_length: int = 150, depth: int = 2):
+    def __init__(self, network, include_hp: bool = False, feature_length: int = 150, depth: int = 2, annotate: bool = False):
         import torch
         self.engine = eng = network.engine
         prog = eng.program
@@ -97,6 +102,7 @@ class ShardScorer:
         if prog.window != feature_length:
             raise ValueError(f"the model reads {prog.window} bp windows, the driver featurises {feature_length}")
         self.L = feature_length
+        self.annotate = bool(annotate)
         self.channels = [prog.channels0, prog.channels1]
         self.device = torch.device(f"cuda:{eng.device}")
         self.compute = torch.cuda.Stream(self.device)
@@ -134,6 +140,9 @@ class ShardScorer:
             place((name, None), np.int64, S)
         if self.uses_ref:
             place(("onehot", None), np.uint8, S * self.L * 5)
+        if getattr(self, "annotate", False):                      # behind the site arrays: resident launches stage it too
+            for t in techs:
+                place(("allele_off", t), np.int64, sum(sh.n_alleles for sh in shards) + 1)
         return parts, at, reads, S
 
     def _fill(self, shards, parts, block: np.ndarray, techs, origin: int = 0):
@@ -188,7 +197,7 @@ class ShardScorer:
 
     # -- pipeline ---------------------------------------------------------------------------------------------------
     def _harvest(self, slot: _Slot) -> Scored:
-        shards, tags, A, S, P, t0 = slot.pending
+        shards, tags, A, S, P, t0, n_support = slot.pending
         slot.pending = None
         slot.done.synchronize()
         _release(shards)                                          # the gather kernels that read their device memory have run
@@ -197,7 +206,10 @@ class ShardScorer:
         host = slot.out_pinned.numpy()
         meta = host[n_logits:n_logits + n_meta].reshape(S, 3).copy() if e.has_meta else None
         post = host[n_logits + n_meta:n_logits + n_meta + 4 * P].reshape(4, P).copy()
-        return Scored(shards, tags, post, meta, time.perf_counter() - t0)
+        support = None
+        if n_support:
+            support = [slot.sup_pinned.numpy()[4 * A * k:4 * A * (k + 1)].reshape(A, 4).copy() for k in range(n_support)]
+        return Scored(shards, tags, post, meta, time.perf_counter() - t0, support)
 
     def submit(self, shards: Sequence[PackedShard], tags: Optional[list] = None) -> List[Scored]:
         """Queue one launch over ``shards`` (coalesced in order); returns what finished meanwhile, oldest first."""
@@ -226,19 +238,31 @@ class ShardScorer:
         origin = parts[("ref", None)][0] if resident else 0
         slot.pinned = _grow(slot.pinned, nbytes - origin, dtype=torch.uint8, pin_memory=True)
         self._fill(scored, parts, slot.pinned.numpy(), () if resident else techs, origin)
+        rpa = None
+        if self.annotate:                                          # the exclusive scan of what the engine gets as reads_per_allele
+            rpa = [np.concatenate([_reads_per_allele(sh, t) for sh in scored]) for t in techs]
+            for t, counts in zip(techs, rpa):
+                at, dtype, count = parts[("allele_off", t)]
+                v = slot.pinned.numpy()[at - origin:at - origin + count * dtype.itemsize].view(dtype)
+                v[0] = 0
+                np.cumsum(counts, dtype=np.int64, out=v[1:])
         self.stage_seconds += time.perf_counter() - t0
         with torch.cuda.stream(self.copy):
             slot.dev = _grow(slot.dev, nbytes, dtype=torch.uint8, device=self.device)
             slot.dev[origin:nbytes].copy_(slot.pinned[:nbytes - origin], non_blocking=True)
             slot.copied.record(self.copy)
 
-        rpa = [np.concatenate([_reads_per_allele(sh, t) for sh in scored]) for t in techs]
+        if rpa is None:
+            rpa = [np.concatenate([_reads_per_allele(sh, t) for sh in scored]) for t in techs]
         aps = np.concatenate([sh.alleles_per_site for sh in scored]).astype(np.int32)
         A, P = int(rpa[0].shape[0]), n_pairs(aps)
         sizes = [e.n_experts * A, 3 * S if e.has_meta else 0, 4 * P]
         total = sum(sizes)
         slot.out_dev = _grow(slot.out_dev, total, dtype=torch.float32, device=self.device)
         slot.out_pinned = _grow(slot.out_pinned, total, dtype=torch.float32, pin_memory=True)
+        if self.annotate:
+            slot.sup_dev = _grow(slot.sup_dev, 4 * A * len(techs), dtype=torch.int64, device=self.device)
+            slot.sup_pinned = _grow(slot.sup_pinned, 4 * A * len(techs), dtype=torch.int64, pin_memory=True)
         base = slot.dev.data_ptr()
         with torch.cuda.stream(self.compute):
             self.compute.wait_event(slot.copied)
@@ -251,6 +275,9 @@ class ShardScorer:
                 ptr = {name: base + parts[(name, t if (name, t) in parts else None)][0] for name in FEATURIZE_ARRAYS}
                 featurize_device(e, ptr, reads[t], S, self.L, self.channels[t], slot.pile[t].data_ptr(), self.compute.cuda_stream)
                 pile.append(slot.pile[t][:n].view(reads[t], self.L, self.channels[t]))
+                if self.annotate:
+                    allele_support_device(e, {name: base + parts[(name, t)][0] for name in SUPPORT_ARRAYS}, reads[t], A,
+                                          slot.sup_dev.data_ptr() + 32 * A * t, self.compute.cuda_stream)
             seg = None
             if self.uses_ref:
                 at = parts[("onehot", None)][0]
@@ -261,8 +288,10 @@ class ShardScorer:
             e.forward(pile[0], rpa[0], aps, pile[1] if self.hybrid else None, rpa[1] if self.hybrid else None, seg,
                       stream=self.compute.cuda_stream, out=out, posteriors=True)
             slot.out_pinned[:total].copy_(slot.out_dev[:total], non_blocking=True)
+            if self.annotate:
+                slot.sup_pinned[:4 * A * len(techs)].copy_(slot.sup_dev[:4 * A * len(techs)], non_blocking=True)
             slot.done.record(self.compute)
-        slot.pending = (shards, tags, A, S, P, t0)
+        slot.pending = (shards, tags, A, S, P, t0, len(techs) if self.annotate else 0)
         return finished
 
     def _gather(self, shards: Sequence[ResidentShard], parts, dev, techs):
@@ -367,7 +396,8 @@ class RecordWriter:
         if live:
             table = site_table([sh for sh, _ in live], self.genomes, self.wanted)
             site_off = np.concatenate([[0], np.cumsum([sh.n_sites for sh, _ in live])]).astype(np.int32)
-            with rec.site_records(table, scored.posteriors, scored.meta, site_off, features=True, threads=self.threads) as r:
+            with rec.site_records(table, scored.posteriors, scored.meta, site_off, features=True, threads=self.threads,
+                                  support=scored.support) as r:
                 for k, (sh, tag) in enumerate(live):
                     lo, hi = int(site_off[k]), int(site_off[k + 1])
                     prefix = self.prefix_of(tag)
@@ -408,13 +438,14 @@ class RecordWriter:
 def run(network, shard_paths: Sequence[str], prefix_of, include_hp: bool = False, genomes=None, wanted=None,
         reader_threads: int = 4, record_threads: int = 0, sites_per_launch: int = 8192, reads_per_launch: int = 320_000,
         read_ahead: Optional[int] = None, depth: int = 2, tags: Optional[list] = None, loader=None, scorer=None,
-        writer_threads: int = 2, in_thread: bool = False) -> "RunStats":
+        writer_threads: int = 2, in_thread: bool = False, annotate: bool = False) -> "RunStats":
     """Score shard files in order with bounded read-ahead: at most ``read_ahead`` loaded shards wait for the GPU, at most
     ``depth`` launches are in flight and at most two scored launches wait for the record writer, whatever the number of
     shards -- host memory is flat over a run.  ``in_thread``: ``loader`` runs in the calling thread, one path at a time, when
-    its shard is due (resident shards: the loader uses the GPU and its result is released by the thread that made it)."""
+    its shard is due (resident shards: the loader uses the GPU and its result is released by the thread that made it).
+    ``annotate``: the record lines carry read support (GQ / DP / AD / ADF / ADR / MQ); a ``scorer`` passed in decides for itself."""
     from concurrent.futures import ThreadPoolExecutor
-    scorer = scorer or ShardScorer(network, include_hp, depth=depth)
+    scorer = scorer or ShardScorer(network, include_hp, depth=depth, annotate=annotate)
     writer = RecordWriter(prefix_of, genomes, wanted, record_threads)
     tags = list(tags) if tags is not None else list(range(len(shard_paths)))
     loader = loader or PackedShard.from_file

@@ -14,7 +14,7 @@ string work on the host; the posteriors themselves come from the GPU (hello_amd.
 from __future__ import annotations
 
 import math
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence, Tuple
 
 QUAL_CAP = 1 - 1e-8            # "Quality score restricted to value 80" (prepareVcf.py:61)
@@ -30,6 +30,9 @@ class Call:
     qual: float
     info: str = "HELLO"
     filter: str = "PASS"
+    # the reference allele and the ALTs as the site spells them, BEFORE normalisation (what ``annotate`` looks up); not part
+    # of a call's value
+    source: Tuple[str, ...] = field(default=(), compare=False, repr=False)
 
     def line(self) -> str:
         return "%s\t%d\t.\t%s\t%s\t%f\t%s\t%s\tGT\t%s" % (
@@ -87,8 +90,9 @@ def call_site(posteriors: Dict[Tuple[str, str], float], chromosome: str, start: 
     norm = normalise(start, ref_allele, alts, genome)
     if norm is None:
         return None
+    source = (ref_allele,) + tuple(alts)
     pos, ref, alts = norm
-    return Call(chromosome, pos, ref, tuple(alts), genotype, qual, info)
+    return Call(chromosome, pos, ref, tuple(alts), genotype, qual, info, source=source)
 
 
 def mean_posteriors(experts: Sequence[Dict], meta: Sequence[float]) -> Dict:
@@ -104,6 +108,59 @@ def call_from_prediction(prediction, chromosome: str, start: int, length: int, g
         return call_site(prediction, chromosome, start, length, genome)
     _, e0, e1, e2, meta = prediction
     return call_site(mean_posteriors((e0, e1, e2), meta), chromosome, start, length, genome)
+
+
+# --------------------------------------------------------------------------------------------
+# annotations (``--annotate``; the reference writes none: DESIGN.md "Annotations")
+# --------------------------------------------------------------------------------------------
+ANNOTATED_FORMAT = "GT:GQ:DP:AD:ADF:ADR"
+ANNOTATION_HEADER = (
+    '##INFO=<ID=MQ,Number=1,Type=Float,Description="Root mean square mapping quality of the reads supporting any allele of the site">\n'
+    '##FORMAT=<ID=GQ,Number=1,Type=Integer,Description="Genotype quality: QUAL rounded, at most 99">\n'
+    '##FORMAT=<ID=DP,Number=1,Type=Integer,Description="Reads supporting any allele of the site">\n'
+    '##FORMAT=<ID=AD,Number=R,Type=Integer,Description="Reads supporting each listed allele">\n'
+    '##FORMAT=<ID=ADF,Number=R,Type=Integer,Description="Reads supporting each listed allele on the forward strand">\n'
+    '##FORMAT=<ID=ADR,Number=R,Type=Integer,Description="Reads supporting each listed allele on the reverse strand">\n')
+
+
+def annotate(call: Call, site_alleles: Sequence[str], support0, support1=None) -> str:
+    """``call.line()`` with read support: the rules of ``hello_site_records_annotated`` (hello_amd/csrc/records.hip).
+    ``support0`` / ``support1``: per allele of the site, in ``site_alleles`` order, the four integers of
+    ``hello_engine_allele_support`` (reads, forward reads, sum mapq, sum mapq^2) for each technology; both are summed.
+
+      GQ   min(99, floor(QUAL + 0.5))
+      DP   reads over ALL alleles of the site, listed in the record or not
+      AD   REF, then each ALT in the record's order: the reads of the site allele whose string equals that allele before
+           normalisation (``call.source``), 0 when the site does not hold it; ADF the forward ones, ADR = AD - ADF
+      MQ   sqrt(sum mapq^2 / DP) in double, written %.2f; ``.`` when DP is 0
+    """
+    tables = [[[int(v) for v in row] for row in t] for t in (support0, support1) if t is not None]
+    names = list(site_alleles)
+    depth = sum(row[0] for t in tables for row in t)
+    squares = sum(row[3] for t in tables for row in t)
+    ad, adf = [], []
+    for allele in call.source:
+        a = names.index(allele) if allele in names else None
+        ad.append(sum(t[a][0] for t in tables) if a is not None else 0)
+        adf.append(sum(t[a][1] for t in tables) if a is not None else 0)
+    mq = "%.2f" % math.sqrt(float(squares) / float(depth)) if depth > 0 else "."
+    gq = min(99, int(math.floor(call.qual + 0.5)))
+    join = lambda values: ",".join(str(v) for v in values)                # noqa: E731
+    sample = ":".join(["/".join(str(g) for g in call.genotype), str(gq), str(depth), join(ad), join(adf),
+                       join(a - f for a, f in zip(ad, adf))])
+    return "%s\t%d\t.\t%s\t%s\t%f\t%s\t%s;MQ=%s\t%s\t%s" % (
+        call.chromosome, call.position + 1, call.ref, ",".join(call.alts), call.qual, call.filter, call.info, mq,
+        ANNOTATED_FORMAT, sample)
+
+
+def strip_annotations(line: str) -> str:
+    """An annotated record line without its annotations: the line the caller writes without ``--annotate``."""
+    cols = line.rstrip("\n").split("\t")
+    if len(cols) < 10 or cols[8] != ANNOTATED_FORMAT:
+        return line
+    cols[7] = cols[7][:cols[7].rindex(";MQ=")]
+    cols[8], cols[9] = "GT", cols[9].split(":")[0]
+    return "\t".join(cols) + ("\n" if line.endswith("\n") else "")
 
 
 # --------------------------------------------------------------------------------------------

@@ -252,6 +252,23 @@ int hello_engine_featurize(hello_engine* engine,
                            int64_t n_reads, int32_t n_sites, int32_t feature_length, int32_t channels,
                            uint8_t* out, int32_t flags, void* hip_stream);
 
+/* Per-allele read support of a launch (no counterpart in the reference, whose VCF carries GT and QUAL only): for every allele
+ * the reads that stand behind it, from the per-read arrays hello_engine_featurize reads.  An addition within ABI version 2.
+ *   cigar_offsets [R+1], mapq [R], orientation [R]   as passed to hello_engine_featurize
+ *   allele_read_offsets [A+1]                        exclusive scan of the reads_per_allele hello_engine_forward receives
+ *                                                    (the dummy read of an unsupported allele counts as 1)
+ *   out int64 [A][4]                                 over the reads r of allele a with cigar_offsets[r+1] > cigar_offsets[r] (a
+ *                                                    read with zero CIGAR operations is the dummy row and supports nothing):
+ *                                                    their number, those with orientation > 0, sum mapq, sum mapq^2
+ * One launch of allele_support_kernel, asynchronous on `hip_stream`; integers written by index, so two runs give the same bytes.
+ * `flags`: HELLO_IN_DEVICE when ALL input arrays are device pointers, HELLO_OUT_DEVICE for `out`; host pointers are staged
+ * through device memory of the engine and the call synchronises.  n_alleles == 0 launches nothing and leaves `out` untouched.
+ * Host offsets that do not start at 0, decrease or do not end at n_reads are refused (HELLO_ERR_SHAPE); device offsets cannot
+ * be read here: the kernel clamps them to [0, n_reads]. */
+int hello_engine_allele_support(hello_engine* engine, const int64_t* cigar_offsets, const uint8_t* mapq,
+                                const int8_t* orientation, const int64_t* allele_read_offsets,
+                                int64_t n_reads, int64_t n_alleles, int64_t* out, int32_t flags, void* hip_stream);
+
 /* ---- BAM input and candidate positions (host BAM reader + one GPU kernel; no engine, no model) ------------------------
  * Additions within ABI version 2.
  *
@@ -577,6 +594,21 @@ typedef struct hello_records_view {          /* pointers into a hello_records ob
 int hello_site_records(const hello_site_table* sites, const float* posteriors, int64_t n_pairs_total, const float* meta,
                        const int32_t* shard_site_off, int32_t n_shards, const hello_features_format* fmt,
                        int32_t n_threads, hello_records** out);
+/* hello_site_records with read support (an addition within ABI version 2): the same decisions and the same lines, with
+ * annotations on the shard lines and the final-VCF lines.  support0 / support1: int64 [A][4] per technology as
+ * hello_engine_allele_support writes them, HOST memory (support1 NULL = one technology); both technologies are summed.
+ *   FORMAT  GT:GQ:DP:AD:ADF:ADR
+ *           GQ   min(99, floor(QUAL + 0.5)) of the line's own QUAL
+ *           DP   reads over ALL alleles of the site, listed in the record or not
+ *           AD   one value for REF and one per ALT in the record's order, each taken from the site allele whose string equals
+ *                that allele before normalisation (0 when the reference allele is not among the site's alleles);
+ *                ADF those on the forward strand, ADR = AD - ADF
+ *   INFO    <as before>;MQ=%.2f with MQ = sqrt(sum mapq^2 / DP) over the reads of DP in double, MQ=. when DP is 0
+ * The `.features` streams, the view and every other field are those of hello_site_records. */
+int hello_site_records_annotated(const hello_site_table* sites, const int64_t* support0, const int64_t* support1,
+                                 const float* posteriors, int64_t n_pairs_total, const float* meta,
+                                 const int32_t* shard_site_off, int32_t n_shards, const hello_features_format* fmt,
+                                 int32_t n_threads, hello_records** out);
 int hello_records_get(const hello_records* records, hello_records_view* view);
 void hello_records_destroy(hello_records* records);
 

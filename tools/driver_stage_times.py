@@ -2,6 +2,7 @@
 final VCF, from ONE host process on one GPU, and where its host time goes.
 
     python tools/driver_stage_times.py [--sites 1048576] [--shard_sites 400,4000] [--coverage 30] [--threads 16]
+                                       [--annotate] [--support-kernel]
 
 A synthetic shard (30 reads per site, 150-base reads, two alleles per site) is replicated into enough ``.hshard`` files
 (16 distinct ones with shifted coordinates, the rest links to them; tmpfs: the page cache stands in for the upstream stage
@@ -9,7 +10,9 @@ handing shards over) for ``--sites`` sites, once as reference-sized shards (~400
 ``call.main`` runs end to end: per-shard .vcf / .features / .mean.vcf / .log files + results.output.vcf.  Printed: sites/s
 of the whole run and of the scoring loop, the loop's stage clocks (feeder waiting for readers, staging, record stage on
 its thread), the process's peak RSS -- at a quarter of the shards and at all of them, which is how "memory is flat in the
-number of shards" is checked -- and the record stage alone on 1 / 4 / N threads.
+number of shards" is checked -- and the record stage alone on 1 / 4 / N threads.  ``--annotate`` runs the driver and the record
+stage with read support in the lines; ``--support-kernel`` times ``hello_engine_allele_support`` alone (HIP events, device
+pointers) on the per-read arrays of one 8 192-site launch and prints the bytes it moves and the bandwidth that makes.
 """
 import argparse
 import logging
@@ -72,6 +75,45 @@ def write_shards(directory, payload, n_files, span, distinct=16):
         shards.write_flat(path, moved)
 
 
+def support_kernel_alone(rng, coverage, config, rounds=200):
+    """hello_engine_allele_support on one 8 192-site launch's arrays in device memory: microseconds per launch between two HIP
+    events around ``rounds`` back-to-back launches (after 20 unmeasured ones), bytes moved, bandwidth."""
+    import torch
+    from hello_amd import featurizer as fz
+    from hello_amd.engine import Engine
+    payload, n_reads = template_payload(rng, 8192, coverage)
+    fa = shards.PackedShard(dict(payload)).featurizer_core(0)
+    off = fz.allele_offsets(fa["reads_per_allele"])
+    n_alleles = int(off.shape[0]) - 1
+    spec = ns.build(config)
+    engine = Engine(spec, weights.synth_state(spec, seed=1), device=0)
+    try:
+        host = dict(cigar_off=fa["cigar_off"], mapq=fa["mapq"], orientation=fa["orientation"], allele_off=off)
+        dev = {k: torch.from_numpy(np.ascontiguousarray(host[k], fz.SUPPORT_DTYPES[k])).to("cuda:0") for k in fz.SUPPORT_ARRAYS}
+        out = torch.zeros((n_alleles, 4), dtype=torch.int64, device="cuda:0")
+        stream = torch.cuda.Stream()
+        pointers = {k: dev[k].data_ptr() for k in fz.SUPPORT_ARRAYS}
+        begin, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        with torch.cuda.stream(stream):
+            for k in range(20 + rounds):
+                if k == 20:
+                    begin.record(stream)
+                fz.allele_support_device(engine, pointers, n_reads, n_alleles, out.data_ptr(), stream.cuda_stream)
+            end.record(stream)
+        end.synchronize()
+        us = begin.elapsed_time(end) * 1e3 / rounds
+        want = fz.allele_support(engine, host["cigar_off"], host["mapq"], host["orientation"], off)
+        assert np.array_equal(out.cpu().numpy(), want) and int(want[:, 0].sum()) == n_reads
+        # distinct bytes: per read one CIGAR offset, mapq, orientation; per allele one offset in, four int64 out (the lanes load
+        # both ends of a read's CIGAR range, 18 bytes per read, of which 8 are the neighbour's and come from the cache)
+        moved = 10 * n_reads + 8 + 8 * (n_alleles + 1) + 32 * n_alleles
+        print(f"allele_support_kernel alone, 8 192 sites, {n_alleles} alleles, {n_reads} reads: {us:7.2f} us per launch ({rounds} "
+              f"back-to-back launches between two events, launch overhead included); {moved} distinct bytes moved (10 per read, "
+              f"40 per allele) = {moved / us / 1e3:6.1f} GB/s")
+    finally:
+        engine.close()
+
+
 def rss_mb():
     return resource.getrusage(resource.RUSAGE_SELF).ru_maxrss / 1024.0
 
@@ -86,16 +128,21 @@ def main():
     ap.add_argument("--arithmetic", default="fp32")
     ap.add_argument("--no-record-alone", action="store_true", help="skip the record stage's stand-alone timing at the end")
     ap.add_argument("--only-all", action="store_true", help="skip the quarter-of-the-shards run (the memory-flatness check)")
+    ap.add_argument("--annotate", action="store_true", help="the driver and the record stage write read support (call --annotate)")
+    ap.add_argument("--support-kernel", action="store_true", help="only time hello_engine_allele_support alone on one 8 192-site launch")
     args = ap.parse_args()
     logging.basicConfig(level=logging.WARNING)
     rng = np.random.default_rng(7)
+    if args.support_kernel:
+        support_kernel_alone(rng, args.coverage, args.config)
+        return
     base = tempfile.mkdtemp(dir="/dev/shm" if os.path.isdir("/dev/shm") else None, prefix="hello_driver_")
     try:
         spec = ns.build(args.config)
         model = os.path.join(base, "model.hello.npz")
         loader.save_native(model, args.config, weights.synth_state(spec, seed=1))
         print(f"# python tools/driver_stage_times.py --sites {args.sites} --shard_sites {args.shard_sites} --threads {args.threads} "
-              f"--arithmetic {args.arithmetic}   "
+              f"--arithmetic {args.arithmetic}{' --annotate' if args.annotate else ''}   "
               f"({args.config}, {args.coverage} reads per site, {len(os.sched_getaffinity(0))} CPUs visible)")
         for shard_sites in [int(x) for x in args.shard_sites.split(",")]:
             payload, n_reads = template_payload(rng, shard_sites, args.coverage)
@@ -105,7 +152,7 @@ def main():
                 os.makedirs(sdir)
                 write_shards(sdir, payload, count, 700 * shard_sites + 10_000)
                 argv = ["--network", model, "--workdir", work, "--shards", sdir, "--num_threads", str(args.threads),
-                        "--arithmetic", args.arithmetic]
+                        "--arithmetic", args.arithmetic] + (["--annotate"] if args.annotate else [])
                 captured = []
                 handler = logging.Handler()
                 handler.emit = lambda record, captured=captured: captured.append(record.getMessage())
@@ -133,11 +180,15 @@ def main():
         shard = shards.PackedShard(dict(payload))
         table = sp.site_table([shard])
         post = rng.random((4, 3 * 8192)).astype(np.float32)
+        support = None
+        if args.annotate:
+            n = shard.featurizer_core(0)["reads_per_allele"].astype(np.int64)
+            support = [np.stack([n, n // 2, 60 * n, 3600 * n], axis=1)]
         for threads in sorted({1, 4, args.threads}):
             best = 1e9
             for _ in range(5):
                 t0 = time.perf_counter()
-                records.site_records(table, post, None, threads=threads).close()
+                records.site_records(table, post, None, threads=threads, support=support).close()
                 best = min(best, time.perf_counter() - t0)
             print(f"record stage alone, 8 192 sites, {threads:2d} threads: {best * 1e3:6.2f} ms = {8192 / best:11,.0f} sites/s")
     finally:
