@@ -33,7 +33,9 @@ the features directory the way ``get_workdir`` does (call.py:40-48).
 
 ``--annotate`` (not in the reference, off by default) adds read support to every record line: GQ, DP, AD, ADF, ADR in the sample
 column and MQ in INFO, counted on the GPU from the launch's own per-read arrays (``hello_engine_allele_support``); without it
-every file is byte for byte what it is with the flag absent.
+every file is byte for byte what it is with the flag absent.  ``--annotate_evidence`` (implies the fields of ``--annotate``)
+adds genotype likelihoods and base-level evidence behind them: PL from the line's own posteriors, MBQ and MPOS in INFO, ADI / ADP
+with a two-technology model and AH1 / AH2 with ``--include_hp`` (``hello_engine_allele_evidence``; ``hello_amd.vcf.annotate_evidence``).
 """
 from __future__ import annotations
 
@@ -119,20 +121,22 @@ def _genome_bytes(genomes: Optional[Dict[str, str]]) -> Optional[Dict[str, bytes
 
 
 def score_shard(network, sites, include_hp: bool = False, genomes: Optional[Dict[str, str]] = None,
-                feature_length: int = FEATURE_LENGTH, keep=None, annotate: bool = False):
+                feature_length: int = FEATURE_LENGTH, keep=None, annotate: bool = False, evidence: bool = False):
     """Featurise and score every site of ONE shard in one launch, synchronously (the building block under test; the
     driver itself streams shards through ``shard_pipeline.run``).  -> [(record line | None, .features entry | None)] per
     site, in order -- what caller_calling.vcfRecords returns per site (:657-754).  ``sites``: a ``shards.PackedShard``
     or a list of ``shards.CandidateSite``; ``keep``: optional per-site booleans, sites marked False are scored but emit
-    nothing; ``annotate``: the record lines carry read support (``hello_amd.vcf.annotate``)."""
+    nothing; ``annotate``: the record lines carry read support (``hello_amd.vcf.annotate``); ``evidence``: also PL and the
+    base-level evidence (``hello_amd.vcf.annotate_evidence``; implies ``annotate``)."""
     from . import records as rec
     from .shard_pipeline import ShardScorer, prepare, site_table
     packed = sites if isinstance(sites, shard_io.PackedShard) else shard_io.PackedShard.from_sites(sites, feature_length)
     if packed.n_sites == 0:
         return []
     scorer = getattr(network, "_shard_scorer", None)
-    if scorer is None or scorer.L != feature_length or scorer.annotate != bool(annotate):
-        scorer = network._shard_scorer = ShardScorer(network, include_hp, feature_length, annotate=annotate)
+    annotate = bool(annotate) or bool(evidence)
+    if scorer is None or scorer.L != feature_length or scorer.annotate != annotate or scorer.evidence != bool(evidence):
+        scorer = network._shard_scorer = ShardScorer(network, include_hp, feature_length, annotate=annotate, evidence=evidence)
     elif scorer.channels[0] != (7 if include_hp else 6):
         raise ValueError(f"--include_hp {'set' if include_hp else 'not set'}: the featurizer would write {7 if include_hp else 6} "
                          f"channels, the model reads {scorer.channels[0]}")
@@ -140,7 +144,8 @@ def score_shard(network, sites, include_hp: bool = False, genomes: Optional[Dict
     done = scorer.submit([packed]) + scorer.flush()
     scored = done[-1]
     table = site_table([packed], _genome_bytes(genomes), keep=None if keep is None else np.asarray(keep, np.uint8))
-    with rec.site_records(table, scored.posteriors, scored.meta, None, features=True, support=scored.support) as r:
+    with rec.site_records(table, scored.posteriors, scored.meta, None, features=True, support=scored.support,
+                          evidence=scored.evidence, evidence_fields=scored.evidence_fields) as r:
         entries = iter(pickle.loads(bytes(r.features)))
         out = []
         for s in range(packed.n_sites):
@@ -162,15 +167,18 @@ def natural_key(path: str):
 # ------------------------------------------------------------------------------------------------
 # final VCF (prepareVcf.main)
 # ------------------------------------------------------------------------------------------------
-def header(chromosomes: Sequence[str], lengths: Dict[str, int], annotate: bool = False) -> str:
-    """prepareVcf.py:185-196; ``annotate``: plus the lines that declare MQ, GQ, DP, AD, ADF and ADR."""
+def header(chromosomes: Sequence[str], lengths: Dict[str, int], annotate: bool = False, evidence=None) -> str:
+    """prepareVcf.py:185-196; ``annotate``: plus the lines that declare MQ, GQ, DP, AD, ADF and ADR; ``evidence``: None, or
+    (two technologies, haplotags) of an ``--annotate_evidence`` run -- then ``vcf.evidence_header`` of them instead."""
     s = "##fileformat=VCFv4.1\n"
     for c in chromosomes:
         s += "##contig=<ID=%s,length=%d>\n" % (c, lengths[c]) if c in lengths else "##contig=<ID=%s>\n" % c
     s += '##INFO=<ID=HELLO,Number=1,Type=String,Description="Obtained from HELLO variant caller">\n'
     s += '##FORMAT=<ID=GT,Number=1,Type=String,Description="Genotype">\n'
     s += '##FILTER=<ID=FAIL,Description="Failed call">\n'
-    if annotate:
+    if evidence is not None:
+        s += vcf.evidence_header(*evidence)
+    elif annotate:
         s += vcf.ANNOTATION_HEADER
     s += "#" + "\t".join("CHROM  POS     ID      REF     ALT     QUAL    FILTER  INFO    FORMAT  SAMPLE1".split()) + "\n"
     return s
@@ -248,6 +256,10 @@ def parser() -> argparse.ArgumentParser:
     ap.add_argument("--annotate", action="store_true", default=False,
                     help="write read support into every record: GQ, DP, AD, ADF, ADR in the sample column and MQ in INFO, counted on "
                          "the GPU from the reads each launch scores (not in the reference; off: the files are the reference's)")
+    ap.add_argument("--annotate_evidence", action="store_true", default=False,
+                    help="the fields of --annotate plus PL from the record's own posteriors, mean base quality (MBQ) and read "
+                         "position (MPOS) per allele in INFO, ADI / ADP (depth per technology) with a two-technology model and "
+                         "AH1 / AH2 (depth per haplotag) with --include_hp, from the reads each launch scores (not in the reference)")
     ap.add_argument("--device", type=int, default=0, help="GPU of a single-process run")
     ap.add_argument("--gpus", type=int, default=1,
                     help="processes / GPUs of this node: > 1 re-launches this command under torch.distributed.run "
@@ -257,6 +269,13 @@ def parser() -> argparse.ArgumentParser:
                     help="fp32: exact fp32 everywhere (default).  bf16x3: the read convolver's 64-channel trunk on the bf16 matrix "
                          "cores as 3-term splits (~1.3x faster; posteriors move by ~1e-6)")
     return ap
+
+
+def _header_evidence(args, network):
+    """``header``'s ``evidence`` argument: None without --annotate_evidence, else (two-technology model, --include_hp)."""
+    if not getattr(args, "annotate_evidence", False):
+        return None
+    return bool(network.engine.program.channels1), bool(args.include_hp)
 
 
 def _argv_of(args) -> List[str]:
@@ -458,7 +477,8 @@ def run_resident(args) -> str:
     stats = sp.run(network, [name for _, name in files], lambda n: os.path.join(features_dir, "features%d" % n), args.include_hp,
                    _genome_bytes(genome), wanted, record_threads=max(1, threads - 1),
                    sites_per_launch=getattr(args, "sites_per_launch", 8192), tags=[n for n, _ in files], loader=candidates_of,
-                   in_thread=True, annotate=getattr(args, "annotate", False))
+                   in_thread=True, annotate=getattr(args, "annotate", False), evidence=getattr(args, "annotate_evidence", False))
+    evidence = _header_evidence(args, network)
     network.close()
     logger.info("%d shard files, %d sites, %d reads in %d launches, %.2f s (candidate stage %.2f s of it, %.1f ms in its kernels; "
                 "staging %.2f s, record stage %.2f s on its threads; resident set after the loop %.0f MB)", len(files), stats.sites,
@@ -470,7 +490,8 @@ def run_resident(args) -> str:
             raise ValueError("Did not run: log file %s doesn't have termination string" % (out.prefix + ".log"))
     result_path = os.path.join(args.workdir, "results.output.vcf")
     lengths = {c: len(g) for c, g in genome.items()}
-    n = sp.merge_final_vcf(stats.outputs, lambda names: header(names, lengths, getattr(args, "annotate", False)), result_path)
+    n = sp.merge_final_vcf(stats.outputs, lambda names: header(names, lengths, getattr(args, "annotate", False), evidence),
+                           result_path)
     logger.info("Completed runs in %.2f s. %d records in %s", time.perf_counter() - t0, n, result_path)
     return result_path
 
@@ -568,7 +589,8 @@ def main(args) -> str:
     stats = sp.run(network, shard_paths[lo:hi], lambda n: os.path.join(features_dir, "features%d" % n), args.include_hp,
                    _genome_bytes(genomes), wanted, reader_threads=readers, record_threads=max(1, threads - readers),
                    sites_per_launch=getattr(args, "sites_per_launch", 8192), tags=numbers[lo:hi],
-                   annotate=getattr(args, "annotate", False))
+                   annotate=getattr(args, "annotate", False), evidence=getattr(args, "annotate_evidence", False))
+    evidence = _header_evidence(args, network)
     network.close()
     logger.info("rank %d: %d shards, %d sites, %d reads in %d launches, %.2f s (%.0f sites/s; waiting for readers %.2f s, "
                 "staging %.2f s, record stage %.2f s on its threads; resident set after the loop %.0f MB)", rank, hi - lo,
@@ -586,7 +608,7 @@ def main(args) -> str:
             outputs = [o for r in range(world) for o in sp.load_index(os.path.join(features_dir, "mean_index.rank%d.npz" % r))]
     if rank == 0:
         lengths = {c: len(g) for c, g in genomes.items()}
-        n = sp.merge_final_vcf(outputs, lambda names: header(names, lengths, getattr(args, "annotate", False)), result_path)
+        n = sp.merge_final_vcf(outputs, lambda names: header(names, lengths, getattr(args, "annotate", False), evidence), result_path)
         logger.info("Completed runs in %.2f s. %d records in %s", time.perf_counter() - t0, n, result_path)
     if world > 1:
         import torch.distributed as dist

@@ -137,6 +137,7 @@ struct hello_engine {
     hipEvent_t ev_lanes_go = nullptr;           // recorded on the call's stream once the inputs are staged: the other lanes start behind it
     DevBuf d_feat_in, d_feat_out;    // featurizer staging (host-pointer callers)
     DevBuf d_support;                // hello_engine_allele_support staging (host-pointer callers): inputs | out
+    DevBuf d_evidence;               // hello_engine_allele_evidence staging (host-pointer callers): inputs | out
     hipStream_t own_stream = nullptr;
     hipStream_t last_stream = nullptr;
     hipEvent_t ev_staged = nullptr;  // H2D of the pinned CSR block finished
@@ -596,6 +597,7 @@ void hello_engine_destroy(hello_engine* e) {
     e->d_feat_in.release();
     e->d_feat_out.release();
     e->d_support.release();
+    e->d_evidence.release();
     e->d_debug.release();
     e->d_stamps.release();
     if (e->d_weights) (void)hipFree(e->d_weights);
@@ -1466,6 +1468,84 @@ int hello_engine_allele_support(hello_engine* e, const int64_t* cigar_offsets, c
     return HELLO_OK;
 } catch (...) {
     return hello::exception_status("hello_engine_allele_support");
+}
+
+int hello_engine_allele_evidence(hello_engine* e, const uint8_t* quals, const int64_t* read_offsets, const uint32_t* cigars,
+                                 const int64_t* cigar_offsets, const int64_t* ref_starts, const uint8_t* hp,
+                                 const int32_t* site_of_read, const int64_t* assembly_starts, const int64_t* assembly_stops,
+                                 const int64_t* allele_read_offsets, int64_t n_reads, int64_t n_sites, int64_t n_alleles,
+                                 int64_t* out, int32_t flags, void* hip_stream) try {
+    if (!e) return fail(HELLO_ERR_ARG, "engine is NULL");
+    if (n_reads < 0 || n_sites < 0 || n_alleles < 0) return fail(HELLO_ERR_ARG, "negative count");
+    if (n_alleles == 0) return HELLO_OK;
+    if (!quals || !read_offsets || !cigars || !cigar_offsets || !ref_starts || !hp || !site_of_read || !assembly_starts ||
+        !assembly_stops || !allele_read_offsets || !out)
+        return fail(HELLO_ERR_ARG, "NULL pointer");
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t stream = hip_stream ? (hipStream_t)hip_stream : e->own_stream;
+    e->last_stream = stream;
+    const bool in_dev = flags & HELLO_IN_DEVICE, out_dev = flags & HELLO_OUT_DEVICE;
+    if (!in_dev) {
+        if (read_offsets[0] != 0 || cigar_offsets[0] != 0 || allele_read_offsets[0] != 0)
+            return fail(HELLO_ERR_SHAPE, "offset arrays must start at 0");
+        for (int64_t r = 0; r < n_reads; ++r) {
+            if (read_offsets[r + 1] < read_offsets[r] || cigar_offsets[r + 1] < cigar_offsets[r])
+                return fail(HELLO_ERR_SHAPE, "offsets of read %lld decrease", (long long)r);
+            if (site_of_read[r] < 0 || site_of_read[r] >= n_sites)
+                return fail(HELLO_ERR_SHAPE, "site_of_read[%lld] = %d out of range", (long long)r, site_of_read[r]);
+        }
+        for (int64_t a = 0; a < n_alleles; ++a)
+            if (allele_read_offsets[a + 1] < allele_read_offsets[a])
+                return fail(HELLO_ERR_SHAPE, "allele_read_offsets decreases at allele %lld", (long long)a);
+        if (allele_read_offsets[n_alleles] != n_reads)
+            return fail(HELLO_ERR_SHAPE, "allele_read_offsets ends at %lld, n_reads = %lld", (long long)allele_read_offsets[n_alleles],
+                        (long long)n_reads);
+    }
+    hello::EvidenceArgs a{};
+    a.quals = quals; a.read_off = (const long long*)read_offsets; a.cigars = cigars; a.cigar_off = (const long long*)cigar_offsets;
+    a.ref_start = (const long long*)ref_starts; a.hp = hp; a.site_of_read = site_of_read;
+    a.asm_start = (const long long*)assembly_starts; a.asm_stop = (const long long*)assembly_stops;
+    a.allele_off = (const long long*)allele_read_offsets;
+    a.n_reads = n_reads; a.n_sites = n_sites; a.n_alleles = n_alleles; a.out = (long long*)out;
+    const size_t out_bytes = (size_t)n_alleles * 6 * 8;
+    if (!in_dev || !out_dev) {
+        struct Part { const void* src; size_t bytes; size_t off; };
+        Part parts[10] = {};
+        size_t total = 0;
+        if (!in_dev) {
+            // the bases and the CIGAR words end where their (validated) offsets end
+            const size_t n_bases = (size_t)read_offsets[n_reads], n_cig = (size_t)cigar_offsets[n_reads];
+            const Part host[10] = {{quals, n_bases, 0}, {read_offsets, (size_t)(n_reads + 1) * 8, 0}, {cigars, n_cig * 4, 0},
+                                   {cigar_offsets, (size_t)(n_reads + 1) * 8, 0}, {ref_starts, (size_t)n_reads * 8, 0},
+                                   {hp, (size_t)n_reads, 0}, {site_of_read, (size_t)n_reads * 4, 0},
+                                   {assembly_starts, (size_t)n_sites * 8, 0}, {assembly_stops, (size_t)n_sites * 8, 0},
+                                   {allele_read_offsets, (size_t)(n_alleles + 1) * 8, 0}};
+            for (int k = 0; k < 10; ++k) { parts[k] = host[k]; parts[k].off = total; total += (parts[k].bytes + 15) & ~size_t(15); }
+            total += 16;
+        }
+        const size_t out_off = total;
+        if (!out_dev) total += out_bytes;
+        HIP_TRY(hipStreamSynchronize(stream));        // the block may be replaced: nothing queued may still read it
+        if (e->d_evidence.ensure(total)) return fail(HELLO_ERR_HIP, "device allocation of %zu bytes failed", total);
+        char* base = (char*)e->d_evidence.p;
+        if (!in_dev) {
+            for (auto& p : parts)
+                if (p.bytes) HIP_TRY(hipMemcpyAsync(base + p.off, p.src, p.bytes, hipMemcpyHostToDevice, stream));
+            a.quals = (const uint8_t*)(base + parts[0].off); a.read_off = (const long long*)(base + parts[1].off);
+            a.cigars = (const uint32_t*)(base + parts[2].off); a.cigar_off = (const long long*)(base + parts[3].off);
+            a.ref_start = (const long long*)(base + parts[4].off); a.hp = (const uint8_t*)(base + parts[5].off);
+            a.site_of_read = (const int32_t*)(base + parts[6].off); a.asm_start = (const long long*)(base + parts[7].off);
+            a.asm_stop = (const long long*)(base + parts[8].off); a.allele_off = (const long long*)(base + parts[9].off);
+        }
+        if (!out_dev) a.out = (long long*)(base + out_off);
+    }
+    HIP_TRY(hello::launch_allele_evidence(a, stream));
+    if (!out_dev) HIP_TRY(hipMemcpyAsync(out, a.out, out_bytes, hipMemcpyDeviceToHost, stream));
+    // host arrays were pageable: the copies above are complete only after this
+    if (!in_dev || !out_dev) HIP_TRY(hipStreamSynchronize(stream));
+    return HELLO_OK;
+} catch (...) {
+    return hello::exception_status("hello_engine_allele_evidence");
 }
 
 }  // extern "C"

@@ -198,4 +198,21 @@ struct SupportArgs {
 };
 hipError_t launch_allele_support(const SupportArgs& a, hipStream_t stream);
 
+// ---- per-allele base-level read evidence (evidence.hip) ----------------------------------------------
+struct EvidenceArgs {
+    const uint8_t* quals;            // the featurizer's arrays: base qualities at read_off
+    const long long* read_off;       // [R+1]
+    const uint32_t* cigars;          // BAM packing: length << 4 | operation
+    const long long* cigar_off;      // [R+1]; a read without operations is a dummy row
+    const long long* ref_start;      // [R]
+    const uint8_t* hp;               // [R] haplotag 0 | 1 | 2
+    const int32_t* site_of_read;     // [R]
+    const long long* asm_start;      // [S] the span [asm_start, asm_stop) whose bases belong to the allele
+    const long long* asm_stop;       // [S]
+    const long long* allele_off;     // [A+1] exclusive scan of reads_per_allele
+    long long n_reads, n_sites, n_alleles;
+    long long* out;                  // [A][6]: reads with a span base, sum min quality, sum end distance, hp 1, hp 2, guarded
+};
+hipError_t launch_allele_evidence(const EvidenceArgs& a, hipStream_t stream);
+
 }  // namespace hello

@@ -10,6 +10,8 @@
 // Python's ``sorted([(v, k)], reverse=True)[0]`` breaks them: by the pair of allele strings.
 // hello_site_records_annotated adds the read support of every allele (hello_engine_allele_support) to the same lines: GQ, DP, AD,
 // ADF and ADR in the sample column, MQ in INFO.  The reference writes none of them; DESIGN.md "Annotations" defines them.
+// hello_site_records_evidence adds, behind those, PL from the line's own posterior row and the base-level evidence of every
+// listed allele (hello_engine_allele_evidence): ADI / ADP, AH1 / AH2, MBQ and MPOS (DESIGN.md "Evidence").
 // No device code in this file.
 #include <algorithm>
 #include <cmath>
@@ -123,6 +125,8 @@ struct SiteCtx {
 
 struct Support {                         // read support of the site's alleles, [n_alleles][4] per technology (second: or NULL)
     const int64_t* tech[2];
+    const int64_t* evidence[2] = {nullptr, nullptr};   // hello_site_records_evidence: [n_alleles][6] per technology, or both NULL
+    int32_t fields = 0;                                // HELLO_EVIDENCE_* bits
 };
 
 struct RowCall {
@@ -177,7 +181,8 @@ bool pad_left_if_empty(const SiteCtx& s, int64_t& pos, std::string& ref, std::ve
 }
 
 // callAlleles / caller_calling.vcfRecords for one row; appends the line (with '\n') to `out` when there is a record
-// With `support` the line carries the annotations: INFO gains ;MQ, the sample column GQ:DP:AD:ADF:ADR.
+// With `support` the line carries the annotations: INFO gains ;MQ, the sample column GQ:DP:AD:ADF:ADR; with its `evidence`
+// also ;MBQ;MPOS and PL[:ADI:ADP][:AH1:AH2].
 template <class F>
 RowCall call_row(const SiteCtx& s, F value, const char* info, const Support* support, std::string& out, Failure& f) {
     RowCall c;
@@ -267,10 +272,12 @@ RowCall call_row(const SiteCtx& s, F value, const char* info, const Support* sup
                 squares += support->tech[t][4 * a + 3];
             }
     std::vector<long long> ad(1 + alt_views.size(), 0), adf(1 + alt_views.size(), 0);
+    std::vector<int> found(1 + alt_views.size(), -1);         // the site allele behind each listed allele
     for (size_t x = 0; x <= alt_views.size(); ++x) {
         const Str& text = x ? alt_views[x - 1] : ref_allele;
         for (int a = 0; a < s.n_alleles; ++a)
             if (s.names[a] == text) {
+                found[x] = a;
                 for (int t = 0; t < 2; ++t)
                     if (support->tech[t]) {
                         ad[x] += support->tech[t][4 * a];
@@ -281,13 +288,74 @@ RowCall call_row(const SiteCtx& s, F value, const char* info, const Support* sup
     }
     if (depth > 0) out.append(num, snprintf(num, sizeof(num), ";MQ=%.2f", std::sqrt((double)squares / (double)depth)));
     else out.append(";MQ=.");
+    const bool evidence = support->evidence[0] != nullptr;
+    const bool two = support->tech[1] != nullptr, haplotags = (support->fields & HELLO_EVIDENCE_HP) != 0;
+    auto column = [&](int a, int k) {                         // evidence column k of site allele a, both technologies
+        long long v = 0;
+        for (int t = 0; t < 2; ++t)
+            if (support->evidence[t]) v += support->evidence[t][6 * a + k];
+        return v;
+    };
+    if (evidence)                                             // MBQ, MPOS: the mean over the reads with a span base, rounded
+        for (int k = 1; k <= 2; ++k) {
+            out.append(k == 1 ? ";MBQ=" : ";MPOS=");
+            for (size_t x = 0; x < found.size(); ++x) {
+                if (x) out.push_back(',');
+                const long long nq = found[x] >= 0 ? column(found[x], 0) : 0;
+                if (nq > 0) out.append(num, snprintf(num, sizeof(num), "%lld", (2 * column(found[x], k) + nq) / (2 * nq)));
+                else out.push_back('.');
+            }
+        }
     const double gq = std::floor(c.qual + 0.5);
-    out.append(num, snprintf(num, sizeof(num), "\tGT:GQ:DP:AD:ADF:ADR\t%d/%d:%d:%lld", genotype[0], genotype[1],
-                             gq < 99 ? (int)gq : 99, depth));
+    out.append("\tGT:GQ:DP:AD:ADF:ADR");
+    if (evidence) {
+        out.append(":PL");
+        if (two) out.append(":ADI:ADP");
+        if (haplotags) out.append(":AH1:AH2");
+    }
+    out.append(num, snprintf(num, sizeof(num), "\t%d/%d:%d:%lld", genotype[0], genotype[1], gq < 99 ? (int)gq : 99, depth));
     for (int field = 0; field < 3; ++field)
         for (size_t x = 0; x < ad.size(); ++x)
             out.append(num, snprintf(num, sizeof(num), "%c%lld", x ? ',' : ':',
                                      field == 0 ? ad[x] : (field == 1 ? adf[x] : ad[x] - adf[x])));
+    if (evidence) {
+        // PL in VCF order from the posteriors of the pairs of listed alleles, scaled to the largest of them
+        bool all_found = true;
+        for (int a : found) all_found = all_found && a >= 0;
+        auto pair_value = [&](int i, int j) {                 // the row's value for the pair of site alleles {i, j}
+            if (i > j) std::swap(i, j);
+            return (double)value(i * s.n_alleles - i * (i - 1) / 2 + (j - i));
+        };
+        double p_max = 0;
+        if (all_found)
+            for (size_t k = 0; k < found.size(); ++k)
+                for (size_t j = 0; j <= k; ++j) p_max = std::max(p_max, pair_value(found[j], found[k]));
+        if (!all_found || !(p_max > 0)) {
+            out.append(":.");
+        } else {
+            bool first = true;
+            for (size_t k = 0; k < found.size(); ++k)
+                for (size_t j = 0; j <= k; ++j) {
+                    const double p = pair_value(found[j], found[k]);
+                    int pl = 255;
+                    if (p > 0 && p / p_max > 0) {
+                        const double v = std::floor(-10.0 * std::log10(p / p_max) + 0.5);
+                        pl = v < 255 ? (int)v : 255;
+                    }
+                    out.append(num, snprintf(num, sizeof(num), "%c%d", first ? ':' : ',', pl));
+                    first = false;
+                }
+        }
+        if (two)                                              // AD of each technology alone
+            for (int t = 0; t < 2; ++t)
+                for (size_t x = 0; x < found.size(); ++x)
+                    out.append(num, snprintf(num, sizeof(num), "%c%lld", x ? ',' : ':',
+                                             found[x] >= 0 ? (long long)support->tech[t][4 * found[x]] : 0LL));
+        if (haplotags)
+            for (int k = 3; k <= 4; ++k)
+                for (size_t x = 0; x < found.size(); ++x)
+                    out.append(num, snprintf(num, sizeof(num), "%c%lld", x ? ',' : ':', found[x] >= 0 ? column(found[x], k) : 0LL));
+    }
     out.push_back('\n');
     return c;
 }
@@ -368,8 +436,9 @@ struct Chunk {                           // what one worker produced for its con
     Failure failure;
 };
 
-// hello_site_records (support0 NULL) and hello_site_records_annotated
-int site_records(const hello_site_table* t, const int64_t* support0, const int64_t* support1, const float* posteriors,
+// hello_site_records (support0 NULL), hello_site_records_annotated (evidence0 NULL) and hello_site_records_evidence
+int site_records(const hello_site_table* t, const int64_t* support0, const int64_t* support1, const int64_t* evidence0,
+                 const int64_t* evidence1, int32_t fields, const float* posteriors,
                  int64_t n_pairs_total, const float* meta, const int32_t* shard_site_off, int32_t n_shards,
                  const hello_features_format* fmt, int32_t n_threads, hello_records** out) {
     using hello::set_last_error;
@@ -465,7 +534,8 @@ int site_records(const hello_site_table* t, const int64_t* support0, const int64
             // prepareVcf.py:154-163: sum(float(e_i) * float(meta_i)), Python's sum from the int 0, in float64
             auto mean = [&](int k) { return (((double)row[1][k] * m[0]) + (double)row[2][k] * m[1]) + (double)row[3][k] * m[2]; };
             const bool keep = !t->keep || t->keep[s];
-            const Support support{{support0 ? support0 + 4 * aoff[s] : nullptr, support1 ? support1 + 4 * aoff[s] : nullptr}};
+            const Support support{{support0 ? support0 + 4 * aoff[s] : nullptr, support1 ? support1 + 4 * aoff[s] : nullptr},
+                                  {evidence0 ? evidence0 + 6 * aoff[s] : nullptr, evidence1 ? evidence1 + 6 * aoff[s] : nullptr}, fields};
             const Support* annotate = support0 ? &support : nullptr;
             RowCall calls[5];
             const size_t before = ch.shard_vcf.size();
@@ -602,7 +672,8 @@ extern "C" {
 int hello_site_records(const hello_site_table* t, const float* posteriors, int64_t n_pairs_total, const float* meta,
                        const int32_t* shard_site_off, int32_t n_shards, const hello_features_format* fmt,
                        int32_t n_threads, hello_records** out) try {
-    return site_records(t, nullptr, nullptr, posteriors, n_pairs_total, meta, shard_site_off, n_shards, fmt, n_threads, out);
+    return site_records(t, nullptr, nullptr, nullptr, nullptr, 0, posteriors, n_pairs_total, meta, shard_site_off, n_shards, fmt,
+                        n_threads, out);
 } catch (...) {
     return hello::exception_status("hello_site_records");
 }
@@ -611,9 +682,26 @@ int hello_site_records_annotated(const hello_site_table* t, const int64_t* suppo
                                  int64_t n_pairs_total, const float* meta, const int32_t* shard_site_off, int32_t n_shards,
                                  const hello_features_format* fmt, int32_t n_threads, hello_records** out) try {
     if (!support0) return hello::set_last_error(HELLO_ERR_ARG, "support0 is NULL (hello_site_records writes the lines without annotations)");
-    return site_records(t, support0, support1, posteriors, n_pairs_total, meta, shard_site_off, n_shards, fmt, n_threads, out);
+    return site_records(t, support0, support1, nullptr, nullptr, 0, posteriors, n_pairs_total, meta, shard_site_off, n_shards, fmt,
+                        n_threads, out);
 } catch (...) {
     return hello::exception_status("hello_site_records_annotated");
+}
+
+int hello_site_records_evidence(const hello_site_table* t, const int64_t* support0, const int64_t* support1, const int64_t* evidence0,
+                                const int64_t* evidence1, int32_t fields, const float* posteriors, int64_t n_pairs_total,
+                                const float* meta, const int32_t* shard_site_off, int32_t n_shards, const hello_features_format* fmt,
+                                int32_t n_threads, hello_records** out) try {
+    if (!support0 || !evidence0)
+        return hello::set_last_error(HELLO_ERR_ARG, "support0 or evidence0 is NULL (hello_site_records_annotated writes the lines "
+                                                    "without evidence)");
+    if ((support1 == nullptr) != (evidence1 == nullptr))
+        return hello::set_last_error(HELLO_ERR_ARG, "evidence1 must be NULL exactly when support1 is NULL");
+    if (fields & ~HELLO_EVIDENCE_HP) return hello::set_last_error(HELLO_ERR_ARG, "unknown bit in fields: %d", (int)fields);
+    return site_records(t, support0, support1, evidence0, evidence1, fields, posteriors, n_pairs_total, meta, shard_site_off, n_shards,
+                        fmt, n_threads, out);
+} catch (...) {
+    return hello::exception_status("hello_site_records_evidence");
 }
 
 int hello_records_get(const hello_records* r, hello_records_view* v) try {

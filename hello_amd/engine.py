@@ -93,6 +93,9 @@ def load_library():
     if hasattr(lib, "hello_engine_allele_support"):      # likewise an addition within ABI version 2 (featurizer.allele_support)
         lib.hello_engine_allele_support.argtypes = [vp, vp, vp, vp, vp, i64, i64, vp, i32, vp]
         lib.hello_engine_allele_support.restype = C.c_int
+    if hasattr(lib, "hello_engine_allele_evidence"):     # likewise (featurizer.allele_evidence)
+        lib.hello_engine_allele_evidence.argtypes = [vp] * 11 + [i64, i64, i64, vp, i32, vp]
+        lib.hello_engine_allele_evidence.restype = C.c_int
     lib.hello_engine_stream.argtypes = [vp]
     lib.hello_engine_stream.restype = C.c_void_p
     lib.hello_engine_destroy.argtypes = [vp]

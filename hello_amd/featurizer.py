@@ -192,3 +192,61 @@ def allele_support_device(engine: Engine, pointers: dict, n_reads: int, n_allele
     address), asynchronous on ``stream``: what the shard pipeline launches behind each technology's featurizer."""
     _check(_support_fn(engine)(engine.handle, *[pointers[k] for k in SUPPORT_ARRAYS], n_reads, n_alleles, out_pointer,
                                HELLO_IN_DEVICE | HELLO_OUT_DEVICE, stream))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# per-allele base-level read evidence (hello_engine_allele_evidence, hello_amd/csrc/evidence.hip)
+# ---------------------------------------------------------------------------------------------------------------------
+EVIDENCE_ARRAYS = ("quals", "read_off", "cigars", "cigar_off", "ref_start", "hp", "site_of_read", "asm_start", "asm_stop",
+                   "allele_off")                                                        # hello_engine_allele_evidence's order
+EVIDENCE_DTYPES = dict(quals=np.uint8, read_off=np.int64, cigars=np.uint32, cigar_off=np.int64, ref_start=np.int64, hp=np.uint8,
+                       site_of_read=np.int32, asm_start=np.int64, asm_stop=np.int64, allele_off=np.int64)
+
+
+def _evidence_fn(engine: Engine):
+    fn = getattr(engine.lib, "hello_engine_allele_evidence", None)
+    if fn is None:
+        raise RuntimeError("this libhello_mi355x.so has no hello_engine_allele_evidence: rebuild it (`make -C hello_amd/csrc`)")
+    return fn
+
+
+def allele_evidence(engine: Engine, arrays: dict, allele_off=None, device: bool = False):
+    """Per allele, over its reads with at least one CIGAR operation: [reads with a base inside the site's span, sum of their
+    lowest such quality, sum of their distance to the nearer read end, reads with hp == 1, reads with hp == 2, reads stopped
+    by the guard], int64 [A, 6] (include/hello_mi355x.h states the walk).  ``arrays``: the featurizer's arrays by name
+    (``pack_sites``) with ``allele_off`` among them or given.  Host form: NumPy in, NumPy out (staged, synchronous);
+    ``device``: the arrays are copied to the engine's GPU first and the call takes device pointers, ordered with the caller's
+    current torch stream; -> a torch CUDA tensor."""
+    fn = _evidence_fn(engine)
+    given = dict(arrays)
+    if allele_off is not None:
+        given["allele_off"] = allele_off
+    host = {k: np.ascontiguousarray(given[k], dtype=EVIDENCE_DTYPES[k]) for k in EVIDENCE_ARRAYS}
+    n_reads, n_sites, n_alleles = int(host["ref_start"].shape[0]), int(host["asm_start"].shape[0]), int(host["allele_off"].shape[0]) - 1
+    if (host["read_off"].shape[0] != n_reads + 1 or host["cigar_off"].shape[0] != n_reads + 1 or host["hp"].shape[0] != n_reads
+            or host["site_of_read"].shape[0] != n_reads or host["asm_stop"].shape[0] != n_sites or n_alleles < 0
+            or host["quals"].shape[0] < int(host["read_off"][-1]) or host["cigars"].shape[0] < int(host["cigar_off"][-1])):
+        raise ValueError("the per-read arrays [R] / [R + 1], the site arrays [S], allele_off [A + 1], quals and cigars do not fit "
+                         "each other")
+    pad = lambda a: a if a.shape[0] else np.zeros(1, a.dtype)                           # noqa: E731 (a pointer is taken of each)
+    if not device:
+        out = np.zeros(6 * max(n_alleles, 1), np.int64)
+        held = {k: pad(v) for k, v in host.items()}
+        _check(fn(engine.handle, *[held[k].ctypes.data for k in EVIDENCE_ARRAYS], n_reads, n_sites, n_alleles, out.ctypes.data, 0,
+                  None))
+        return out[:6 * n_alleles].reshape(n_alleles, 6)
+    import torch
+    where = torch.device(f"cuda:{engine.device}")
+    dev = {k: torch.from_numpy(pad(v)).to(where) for k, v in host.items()}
+    out = torch.zeros(6 * max(n_alleles, 1), dtype=torch.int64, device=where)
+    with engine.on_stream(where) as handle:
+        allele_evidence_device(engine, {k: dev[k].data_ptr() for k in EVIDENCE_ARRAYS}, n_reads, n_sites, n_alleles, out.data_ptr(),
+                               handle)
+    return out[:6 * n_alleles].view(n_alleles, 6)
+
+
+def allele_evidence_device(engine: Engine, pointers: dict, n_reads: int, n_sites: int, n_alleles: int, out_pointer: int, stream):
+    """``hello_engine_allele_evidence`` on arrays ALREADY in device memory (``pointers``: name of EVIDENCE_ARRAYS -> device
+    address), asynchronous on ``stream``: what the shard pipeline launches behind each technology's support kernel."""
+    _check(_evidence_fn(engine)(engine.handle, *[pointers[k] for k in EVIDENCE_ARRAYS], n_reads, n_sites, n_alleles, out_pointer,
+                                HELLO_IN_DEVICE | HELLO_OUT_DEVICE, stream))

@@ -53,6 +53,10 @@ def _lib():
                                                      C.c_void_p, C.c_int32, C.POINTER(_FeaturesFormat), C.c_int32,
                                                      C.POINTER(C.c_void_p)]
         lib.hello_site_records_annotated.restype = C.c_int
+        lib.hello_site_records_evidence.argtypes = [C.POINTER(_SiteTable)] + [C.c_void_p] * 4 + [C.c_int32, C.c_void_p, C.c_int64,
+                                                    C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(_FeaturesFormat), C.c_int32,
+                                                    C.POINTER(C.c_void_p)]
+        lib.hello_site_records_evidence.restype = C.c_int
         lib.hello_records_get.argtypes = [C.c_void_p, C.POINTER(_View)]
         lib.hello_records_get.restype = C.c_int
         lib.hello_records_destroy.argtypes = [C.c_void_p]
@@ -190,11 +194,17 @@ class Records:
             pass
 
 
+HELLO_EVIDENCE_HP = 1           # evidence_fields: write AH1 / AH2
+
+
 def site_records(table: SiteTable, posteriors: np.ndarray, meta: Optional[np.ndarray], shard_site_off=None,
-                 features: bool = True, threads: int = 0, support=None) -> Records:
+                 features: bool = True, threads: int = 0, support=None, evidence=None, evidence_fields: int = 0) -> Records:
     """posteriors float32 [4, P] and meta float32 [S, 3] | None on the host, as ``Engine.forward`` returns them.
     ``support``: None, or one int64 [A, 4] array per technology as ``Engine.allele_support`` returns them -- then the lines
-    carry GQ / DP / AD / ADF / ADR and MQ (``hello_site_records_annotated``; ``hello_amd.vcf.annotate`` states the rules)."""
+    carry GQ / DP / AD / ADF / ADR and MQ (``hello_site_records_annotated``; ``hello_amd.vcf.annotate`` states the rules).
+    ``evidence`` (with ``support``, one per technology as well): int64 [A, 6] arrays as ``featurizer.allele_evidence`` returns
+    them -- then the lines also carry PL, ADI / ADP, MBQ and MPOS, and AH1 / AH2 with ``HELLO_EVIDENCE_HP`` in
+    ``evidence_fields`` (``hello_site_records_evidence``; ``hello_amd.vcf.annotate_evidence``)."""
     lib = _lib()
     post = np.ascontiguousarray(posteriors, dtype=np.float32)
     if post.ndim != 2 or post.shape[0] != 4:
@@ -212,6 +222,8 @@ def site_records(table: SiteTable, posteriors: np.ndarray, meta: Optional[np.nda
             off.ctypes.data if off is not None else None, int(off.shape[0]) - 1 if off is not None else 1,
             C.byref(fmt) if fmt is not None else None, int(threads), C.byref(handle))
     if support is None:
+        if evidence is not None:
+            raise ValueError("evidence goes with support (the evidence lines are the annotated lines with more fields)")
         _check(lib.hello_site_records(C.byref(table.struct), *tail))
         return Records(handle)
     if isinstance(support, np.ndarray):
@@ -220,6 +232,15 @@ def site_records(table: SiteTable, posteriors: np.ndarray, meta: Optional[np.nda
     n_alleles = int(table.alleles_per_site.sum())
     if not 1 <= len(sup) <= 2 or any(t.shape != (n_alleles, 4) for t in sup):
         raise ValueError(f"support must hold one or two int64 [{n_alleles}, 4] arrays (one per technology)")
-    _check(lib.hello_site_records_annotated(C.byref(table.struct), sup[0].ctypes.data, sup[1].ctypes.data if len(sup) > 1 else None,
-                                            *tail))
+    second = lambda arrays: arrays[1].ctypes.data if len(arrays) > 1 else None          # noqa: E731
+    if evidence is None:
+        _check(lib.hello_site_records_annotated(C.byref(table.struct), sup[0].ctypes.data, second(sup), *tail))
+        return Records(handle)
+    if isinstance(evidence, np.ndarray):
+        evidence = [evidence]
+    evi = [np.ascontiguousarray(t, dtype=np.int64) for t in evidence]
+    if len(evi) != len(sup) or any(t.shape != (n_alleles, 6) for t in evi):
+        raise ValueError(f"evidence must hold one int64 [{n_alleles}, 6] array per technology of support ({len(sup)})")
+    _check(lib.hello_site_records_evidence(C.byref(table.struct), sup[0].ctypes.data, second(sup), evi[0].ctypes.data, second(evi),
+                                           int(evidence_fields), *tail))
     return Records(handle)

@@ -11,7 +11,9 @@ python/caller_calling.py:859-900).  Here the unit of GPU work is decoupled from 
                         posteriors + meta weights return through pinned memory; with ``annotate`` one launch of
                         ``hello_engine_allele_support`` per technology follows its featurizer on the same stream (the
                         per-read arrays are in the block already; on the resident route they exist nowhere else) and the
-                        per-allele read support returns beside the posteriors
+                        per-allele read support returns beside the posteriors; with ``evidence`` one launch of
+                        ``hello_engine_allele_evidence`` follows each support launch (base qualities, positions in the
+                        read and haplotags per allele) and returns the same way
     ``RecordWriter``    ``hello_site_records`` (multi-threaded C, hello_amd/records.py) turns a launch's posteriors into
                         every shard's ``.vcf`` lines, ``.features`` pickle stream and final-VCF lines; Python only slices
                         the blobs per shard and writes files -- no per-site Python object anywhere
@@ -31,7 +33,8 @@ import numpy as np
 
 from . import records as rec
 from .engine import n_pairs
-from .featurizer import FEATURIZE_ARRAYS, SUPPORT_ARRAYS, allele_support_device, featurize_device
+from .featurizer import (EVIDENCE_ARRAYS, FEATURIZE_ARRAYS, SUPPORT_ARRAYS, allele_evidence_device, allele_support_device,
+                         featurize_device)
 from .resident import GATHER_ARRAYS, ResidentShard
 from .shards import PackedShard
 
@@ -67,6 +70,8 @@ class Scored:
     meta: Optional[np.ndarray]      # float32 [S, 3]
     seconds: float = 0.0
     support: Optional[List[np.ndarray]] = None      # annotate: int64 [A, 4] per technology (reads, forward, sum mapq, sum mapq^2)
+    evidence: Optional[List[np.ndarray]] = None     # evidence: int64 [A, 6] per technology (hello_engine_allele_evidence)
+    evidence_fields: int = 0                        # evidence: HELLO_EVIDENCE_* bits for the record stage
 
 
 class _Slot:
@@ -75,6 +80,7 @@ class _Slot:
         self.pile = [None, None]                # featurizer output per technology (device uint8)
         self.out_dev = self.out_pinned = None   # float32: logits | meta | posteriors
         self.sup_dev = self.sup_pinned = None   # annotate: int64 read support [technologies][A][4]
+        self.evi_dev = self.evi_pinned = None   # evidence: int64 [technologies][A][6]
         self.copied = self.done = None
         self.pending = None
 
@@ -89,7 +95,8 @@ def _grow(t, n, **kw):
 class ShardScorer:
     """Featurise + score coalesced shards on the GPU, ``depth`` launches in flight."""
 
-    def __init__(self, network, include_hp: bool = False, feature_length: int = 150, depth: int = 2, annotate: bool = False):
+    def __init__(self, network, include_hp: bool = False, feature_length: int = 150, depth: int = 2, annotate: bool = False,
+                 evidence: bool = False):
         import torch
         self.engine = eng = network.engine
         prog = eng.program
@@ -102,7 +109,9 @@ class ShardScorer:
         if prog.window != feature_length:
             raise ValueError(f"the model reads {prog.window} bp windows, the driver featurises {feature_length}")
         self.L = feature_length
-        self.annotate = bool(annotate)
+        self.evidence = bool(evidence)
+        self.annotate = bool(annotate) or self.evidence           # the evidence lines are the annotated lines with more fields
+        self.evidence_fields = rec.HELLO_EVIDENCE_HP if include_hp else 0
         self.channels = [prog.channels0, prog.channels1]
         self.device = torch.device(f"cuda:{eng.device}")
         self.compute = torch.cuda.Stream(self.device)
@@ -197,7 +206,7 @@ class ShardScorer:
 
     # -- pipeline ---------------------------------------------------------------------------------------------------
     def _harvest(self, slot: _Slot) -> Scored:
-        shards, tags, A, S, P, t0, n_support = slot.pending
+        shards, tags, A, S, P, t0, n_support, n_evidence = slot.pending
         slot.pending = None
         slot.done.synchronize()
         _release(shards)                                          # the gather kernels that read their device memory have run
@@ -209,7 +218,10 @@ class ShardScorer:
         support = None
         if n_support:
             support = [slot.sup_pinned.numpy()[4 * A * k:4 * A * (k + 1)].reshape(A, 4).copy() for k in range(n_support)]
-        return Scored(shards, tags, post, meta, time.perf_counter() - t0, support)
+        evidence = None
+        if n_evidence:
+            evidence = [slot.evi_pinned.numpy()[6 * A * k:6 * A * (k + 1)].reshape(A, 6).copy() for k in range(n_evidence)]
+        return Scored(shards, tags, post, meta, time.perf_counter() - t0, support, evidence, self.evidence_fields if evidence else 0)
 
     def submit(self, shards: Sequence[PackedShard], tags: Optional[list] = None) -> List[Scored]:
         """Queue one launch over ``shards`` (coalesced in order); returns what finished meanwhile, oldest first."""
@@ -263,6 +275,9 @@ class ShardScorer:
         if self.annotate:
             slot.sup_dev = _grow(slot.sup_dev, 4 * A * len(techs), dtype=torch.int64, device=self.device)
             slot.sup_pinned = _grow(slot.sup_pinned, 4 * A * len(techs), dtype=torch.int64, pin_memory=True)
+        if self.evidence:
+            slot.evi_dev = _grow(slot.evi_dev, 6 * A * len(techs), dtype=torch.int64, device=self.device)
+            slot.evi_pinned = _grow(slot.evi_pinned, 6 * A * len(techs), dtype=torch.int64, pin_memory=True)
         base = slot.dev.data_ptr()
         with torch.cuda.stream(self.compute):
             self.compute.wait_event(slot.copied)
@@ -278,6 +293,10 @@ class ShardScorer:
                 if self.annotate:
                     allele_support_device(e, {name: base + parts[(name, t)][0] for name in SUPPORT_ARRAYS}, reads[t], A,
                                           slot.sup_dev.data_ptr() + 32 * A * t, self.compute.cuda_stream)
+                if self.evidence:
+                    allele_evidence_device(e, {name: base + parts[(name, t if (name, t) in parts else None)][0]
+                                               for name in EVIDENCE_ARRAYS}, reads[t], S, A,
+                                           slot.evi_dev.data_ptr() + 48 * A * t, self.compute.cuda_stream)
             seg = None
             if self.uses_ref:
                 at = parts[("onehot", None)][0]
@@ -290,8 +309,10 @@ class ShardScorer:
             slot.out_pinned[:total].copy_(slot.out_dev[:total], non_blocking=True)
             if self.annotate:
                 slot.sup_pinned[:4 * A * len(techs)].copy_(slot.sup_dev[:4 * A * len(techs)], non_blocking=True)
+            if self.evidence:
+                slot.evi_pinned[:6 * A * len(techs)].copy_(slot.evi_dev[:6 * A * len(techs)], non_blocking=True)
             slot.done.record(self.compute)
-        slot.pending = (shards, tags, A, S, P, t0, len(techs) if self.annotate else 0)
+        slot.pending = (shards, tags, A, S, P, t0, len(techs) if self.annotate else 0, len(techs) if self.evidence else 0)
         return finished
 
     def _gather(self, shards: Sequence[ResidentShard], parts, dev, techs):
@@ -397,7 +418,7 @@ class RecordWriter:
             table = site_table([sh for sh, _ in live], self.genomes, self.wanted)
             site_off = np.concatenate([[0], np.cumsum([sh.n_sites for sh, _ in live])]).astype(np.int32)
             with rec.site_records(table, scored.posteriors, scored.meta, site_off, features=True, threads=self.threads,
-                                  support=scored.support) as r:
+                                  support=scored.support, evidence=scored.evidence, evidence_fields=scored.evidence_fields) as r:
                 for k, (sh, tag) in enumerate(live):
                     lo, hi = int(site_off[k]), int(site_off[k + 1])
                     prefix = self.prefix_of(tag)
@@ -438,14 +459,16 @@ class RecordWriter:
 def run(network, shard_paths: Sequence[str], prefix_of, include_hp: bool = False, genomes=None, wanted=None,
         reader_threads: int = 4, record_threads: int = 0, sites_per_launch: int = 8192, reads_per_launch: int = 320_000,
         read_ahead: Optional[int] = None, depth: int = 2, tags: Optional[list] = None, loader=None, scorer=None,
-        writer_threads: int = 2, in_thread: bool = False, annotate: bool = False) -> "RunStats":
+        writer_threads: int = 2, in_thread: bool = False, annotate: bool = False, evidence: bool = False) -> "RunStats":
     """Score shard files in order with bounded read-ahead: at most ``read_ahead`` loaded shards wait for the GPU, at most
     ``depth`` launches are in flight and at most two scored launches wait for the record writer, whatever the number of
     shards -- host memory is flat over a run.  ``in_thread``: ``loader`` runs in the calling thread, one path at a time, when
     its shard is due (resident shards: the loader uses the GPU and its result is released by the thread that made it).
-    ``annotate``: the record lines carry read support (GQ / DP / AD / ADF / ADR / MQ); a ``scorer`` passed in decides for itself."""
+    ``annotate``: the record lines carry read support (GQ / DP / AD / ADF / ADR / MQ); ``evidence``: also PL and the base-level
+    evidence (MBQ / MPOS, ADI / ADP with two technologies, AH1 / AH2 with ``include_hp``); a ``scorer`` passed in decides for
+    itself."""
     from concurrent.futures import ThreadPoolExecutor
-    scorer = scorer or ShardScorer(network, include_hp, depth=depth, annotate=annotate)
+    scorer = scorer or ShardScorer(network, include_hp, depth=depth, annotate=annotate, evidence=evidence)
     writer = RecordWriter(prefix_of, genomes, wanted, record_threads)
     tags = list(tags) if tags is not None else list(range(len(shard_paths)))
     loader = loader or PackedShard.from_file

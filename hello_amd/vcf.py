@@ -164,6 +164,99 @@ def strip_annotations(line: str) -> str:
 
 
 # --------------------------------------------------------------------------------------------
+# genotype likelihoods and base-level evidence (``--annotate_evidence``: DESIGN.md "Evidence")
+# --------------------------------------------------------------------------------------------
+_EVIDENCE_DECLARATIONS = dict(
+    MBQ='##INFO=<ID=MBQ,Number=R,Type=Integer,Description="Mean over the supporting reads of the lowest base quality inside the allele">\n',
+    MPOS='##INFO=<ID=MPOS,Number=R,Type=Integer,Description="Mean over the supporting reads of the distance in read bases from the allele to the nearer read end">\n',
+    PL='##FORMAT=<ID=PL,Number=G,Type=Integer,Description="Phred-scaled genotype likelihoods from the pair posteriors, at most 255">\n',
+    ADI='##FORMAT=<ID=ADI,Number=R,Type=Integer,Description="Reads supporting each listed allele, first technology (Illumina)">\n',
+    ADP='##FORMAT=<ID=ADP,Number=R,Type=Integer,Description="Reads supporting each listed allele, second technology (PacBio)">\n',
+    AH1='##FORMAT=<ID=AH1,Number=R,Type=Integer,Description="Reads supporting each listed allele with haplotag 1">\n',
+    AH2='##FORMAT=<ID=AH2,Number=R,Type=Integer,Description="Reads supporting each listed allele with haplotag 2">\n')
+
+
+def evidence_format(two_technologies: bool, hp: bool) -> str:
+    """The FORMAT column of an evidence line."""
+    return ANNOTATED_FORMAT + ":PL" + (":ADI:ADP" if two_technologies else "") + (":AH1:AH2" if hp else "")
+
+
+def evidence_header(two_technologies: bool, hp: bool) -> str:
+    """The header lines an ``--annotate_evidence`` run adds: those of ``--annotate`` and one per field actually written."""
+    keys = ["MBQ", "MPOS", "PL"] + (["ADI", "ADP"] if two_technologies else []) + (["AH1", "AH2"] if hp else [])
+    return ANNOTATION_HEADER + "".join(_EVIDENCE_DECLARATIONS[k] for k in keys)
+
+
+def phred_likelihoods(call: Call, site_alleles: Sequence[str], posteriors: Dict[Tuple[str, str], float]) -> str:
+    """``PL`` of a record from the pair posteriors its QUAL comes from: in VCF order (for k: for j <= k) the posterior p_jk of
+    the pair of listed alleles {L_j, L_k} (``call.source``), min(255, floor(-10 log10(p_jk / p_max) + 0.5)) with p_max the
+    largest of them; 255 for p_jk <= 0; ``.`` when a listed allele is not among the site's alleles or p_max <= 0."""
+    names = list(site_alleles)
+    if any(allele not in names for allele in call.source):
+        return "."
+    def value(a, b):
+        return float(posteriors[(a, b)] if (a, b) in posteriors else posteriors[(b, a)])
+    listed = [value(call.source[j], call.source[k]) for k in range(len(call.source)) for j in range(k + 1)]
+    p_max = max(listed)
+    if not p_max > 0:
+        return "."
+    out = []
+    for p in listed:
+        ratio = p / p_max if p > 0 else 0.0
+        out.append(int(min(255.0, math.floor(-10.0 * math.log10(ratio) + 0.5))) if ratio > 0 else 255)
+    return ",".join(str(v) for v in out)
+
+
+def annotate_evidence(call: Call, site_alleles: Sequence[str], posteriors: Dict[Tuple[str, str], float], support0, evidence0,
+                      support1=None, evidence1=None, hp: bool = False) -> str:
+    """``annotate(call, ...)`` with genotype likelihoods and base-level evidence: the rules of ``hello_site_records_evidence``
+    (hello_amd/csrc/records.hip).  ``posteriors``: the {pair: p} the call was made from (``call_site``'s argument).
+    ``evidence0`` / ``evidence1``: per allele of the site the six integers of ``hello_engine_allele_evidence`` (reads with a
+    base inside the allele nq, sum of their lowest such quality, sum of their distance to the nearer read end, reads with
+    haplotag 1, with haplotag 2, guarded reads) for each technology; ``evidence1`` goes with ``support1``.
+
+      PL          ``phred_likelihoods``
+      ADI, ADP    AD from technology 0 alone, technology 1 alone (two technologies only)
+      AH1, AH2    haplotag 1 / 2 reads per listed allele, both technologies summed (``hp`` only)
+      MBQ, MPOS   per listed allele, sums and nq over both technologies: (2 sum + nq) // (2 nq); ``.`` when nq is 0 or the
+                  site does not hold the allele
+    """
+    if (support1 is None) != (evidence1 is None):
+        raise ValueError("evidence1 goes with support1")
+    base = annotate(call, site_alleles, support0, support1).split("\t")
+    support = [[[int(v) for v in row] for row in t] for t in (support0, support1) if t is not None]
+    evidence = [[[int(v) for v in row] for row in t] for t in (evidence0, evidence1) if t is not None]
+    names = list(site_alleles)
+    found = [names.index(allele) if allele in names else None for allele in call.source]
+    column = lambda a, k: sum(t[a][k] for t in evidence)                                     # noqa: E731
+    join = lambda values: ",".join(str(v) for v in values)                                   # noqa: E731
+
+    def mean(k):
+        nq = [column(a, 0) if a is not None else 0 for a in found]
+        return join((2 * column(a, k) + n) // (2 * n) if n > 0 else "." for a, n in zip(found, nq))
+    two = len(support) == 2
+    base[7] += ";MBQ=%s;MPOS=%s" % (mean(1), mean(2))
+    base[8] = evidence_format(two, hp)
+    sample = [base[9], phred_likelihoods(call, site_alleles, posteriors)]
+    if two:
+        sample += [join(t[a][0] if a is not None else 0 for a in found) for t in support]
+    if hp:
+        sample += [join(column(a, k) if a is not None else 0 for a in found) for k in (3, 4)]
+    base[9] = ":".join(sample)
+    return "\t".join(base)
+
+
+def strip_evidence(line: str) -> str:
+    """An evidence line without PL and the evidence fields: the line ``--annotate`` writes."""
+    cols = line.rstrip("\n").split("\t")
+    if len(cols) < 10 or not cols[8].startswith(ANNOTATED_FORMAT + ":PL"):
+        return line
+    cols[7] = cols[7][:cols[7].rindex(";MBQ=")]
+    cols[8], cols[9] = ANNOTATED_FORMAT, ":".join(cols[9].split(":")[:ANNOTATED_FORMAT.count(":") + 1])
+    return "\t".join(cols) + ("\n" if line.endswith("\n") else "")
+
+
+# --------------------------------------------------------------------------------------------
 # the per-shard ``.features`` records and what prepareVcf makes of them
 # --------------------------------------------------------------------------------------------
 def feature_record(prediction, chromosome: str, start: int, length: int) -> dict:

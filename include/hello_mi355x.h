@@ -269,6 +269,33 @@ int hello_engine_allele_support(hello_engine* engine, const int64_t* cigar_offse
                                 const int8_t* orientation, const int64_t* allele_read_offsets,
                                 int64_t n_reads, int64_t n_alleles, int64_t* out, int32_t flags, void* hip_stream);
 
+/* Per-allele base-level read evidence of a launch (no counterpart in the reference; an addition within ABI version 2): what the
+ * reads of every allele put inside their site's span [assembly_start, assembly_stop), from the arrays hello_engine_featurize
+ * reads plus the allele_read_offsets of hello_engine_allele_support.
+ * One read r, n = its bases, reference cursor p = ref_starts[r], read cursor i = 0, its operations in order:
+ *   M = X (0 7 8), length L   base i+j sits at p+j and BELONGS iff start <= p+j < stop;  p += L, i += L
+ *   I (1), length L           all L bases belong iff start <= p <= stop: the insertion joins the base on its left, so one right
+ *                             behind the last span base counts, and so does one at an empty span (start == stop);  i += L
+ *   S (4)  i += L, never belongs        D N (2 3)  p += L        H P (5 6) and any code >= 9  nothing
+ *   The walk stops in front of the first reference-consuming operation (M = X D N) that begins at p >= stop; what follows it
+ *   is not examined.  GUARD: an operation of the walk that would move i past n ends it -- the read counts in column 5 and in
+ *   no other column, and no quality outside the read's own is loaded; a site_of_read outside [0, n_sites) does the same.
+ *   A read with zero operations is the dummy row of an unsupported allele and counts in no column.
+ *   For a read with a belonging base: qmin = its lowest belonging quality; d = min(i0, n-1-i1), i0 / i1 its first / last
+ *   belonging read index (the distance in read bases, soft-clipped ones included, to the nearer read end).
+ *   out int64 [A][6]   per allele over its reads: 0 reads with a belonging base (nq), 1 sum qmin, 2 sum d,
+ *                      3 reads with hp == 1, 4 reads with hp == 2, 5 reads stopped by the guard (0 on valid input)
+ * One launch of allele_evidence_kernel, asynchronous on `hip_stream`; integers written by index, so two runs give the same bytes.
+ * `flags`: as hello_engine_allele_support.  Host arrays are validated (HELLO_ERR_SHAPE): the three offset arrays start at 0 and
+ * never decrease (read_offsets and cigar_offsets end at the sizes of quals and cigars, allele_read_offsets at n_reads) and
+ * site_of_read lies in [0, n_sites); device arrays cannot be read here: the kernel clamps allele offsets to [0, n_reads].
+ * n_alleles == 0 launches nothing and leaves `out` untouched. */
+int hello_engine_allele_evidence(hello_engine* engine, const uint8_t* quals, const int64_t* read_offsets, const uint32_t* cigars,
+                                 const int64_t* cigar_offsets, const int64_t* ref_starts, const uint8_t* hp,
+                                 const int32_t* site_of_read, const int64_t* assembly_starts, const int64_t* assembly_stops,
+                                 const int64_t* allele_read_offsets, int64_t n_reads, int64_t n_sites, int64_t n_alleles,
+                                 int64_t* out, int32_t flags, void* hip_stream);
+
 /* ---- BAM input and candidate positions (host BAM reader + one GPU kernel; no engine, no model) ------------------------
  * Additions within ABI version 2.
  *
@@ -609,6 +636,26 @@ int hello_site_records_annotated(const hello_site_table* sites, const int64_t* s
                                  const float* posteriors, int64_t n_pairs_total, const float* meta,
                                  const int32_t* shard_site_off, int32_t n_shards, const hello_features_format* fmt,
                                  int32_t n_threads, hello_records** out);
+/* hello_site_records_annotated with genotype likelihoods and base-level evidence (an addition within ABI version 2): the same
+ * decisions and the same lines, plus the fields below.  evidence0 / evidence1: int64 [A][6] per technology as
+ * hello_engine_allele_evidence writes them, HOST memory; evidence1 must be NULL exactly when support1 is NULL.  `fields`: a mask
+ * of HELLO_EVIDENCE_* bits.  "Listed alleles": REF, then the record's ALTs in its order, each found among the site's alleles by
+ * its string before normalisation, as AD finds it.
+ *   FORMAT  GT:GQ:DP:AD:ADF:ADR:PL  [:ADI:ADP with two technologies]  [:AH1:AH2 with HELLO_EVIDENCE_HP]
+ *           PL   in VCF order (for k: for j <= k) from the posterior p_jk of the pair of listed alleles {j, k} in the row the
+ *                line's QUAL comes from (mixture row on shard lines, meta-weighted mean on final-VCF lines), in double:
+ *                min(255, floor(-10 log10(p_jk / p_max) + 0.5)), p_max the largest over the listed pairs; 255 for p_jk <= 0;
+ *                the whole field is `.` when a listed allele is not among the site's alleles or p_max <= 0
+ *           ADI / ADP   AD from technology 0 alone / technology 1 alone
+ *           AH1 / AH2   columns 3 / 4 (reads with haplotag 1 / 2) per listed allele, both technologies summed
+ *   INFO    <as annotated>;MBQ=..;MPOS=..   per listed allele (comma separated), with the sum (column 1 for MBQ, column 2 for
+ *           MPOS) and nq (column 0) added over both technologies: (2 sum + nq) / (2 nq) in integer division -- the mean,
+ *           rounded; `.` when nq is 0 or the allele is not among the site's alleles */
+#define HELLO_EVIDENCE_HP 1          /* write AH1 / AH2 */
+int hello_site_records_evidence(const hello_site_table* sites, const int64_t* support0, const int64_t* support1,
+                                const int64_t* evidence0, const int64_t* evidence1, int32_t fields, const float* posteriors,
+                                int64_t n_pairs_total, const float* meta, const int32_t* shard_site_off, int32_t n_shards,
+                                const hello_features_format* fmt, int32_t n_threads, hello_records** out);
 int hello_records_get(const hello_records* records, hello_records_view* view);
 void hello_records_destroy(hello_records* records);
 

@@ -2,7 +2,7 @@
 final VCF, from ONE host process on one GPU, and where its host time goes.
 
     python tools/driver_stage_times.py [--sites 1048576] [--shard_sites 400,4000] [--coverage 30] [--threads 16]
-                                       [--annotate] [--support-kernel]
+                                       [--annotate] [--support-kernel] [--annotate_evidence] [--evidence-kernel]
 
 A synthetic shard (30 reads per site, 150-base reads, two alleles per site) is replicated into enough ``.hshard`` files
 (16 distinct ones with shifted coordinates, the rest links to them; tmpfs: the page cache stands in for the upstream stage
@@ -13,6 +13,8 @@ its thread), the process's peak RSS -- at a quarter of the shards and at all of 
 number of shards" is checked -- and the record stage alone on 1 / 4 / N threads.  ``--annotate`` runs the driver and the record
 stage with read support in the lines; ``--support-kernel`` times ``hello_engine_allele_support`` alone (HIP events, device
 pointers) on the per-read arrays of one 8 192-site launch and prints the bytes it moves and the bandwidth that makes.
+``--annotate_evidence`` runs the driver and the record stage with PL and the base-level evidence in the lines as well;
+``--evidence-kernel`` times ``hello_engine_allele_evidence`` and, beside it, ``hello_engine_featurize`` on the same launch.
 """
 import argparse
 import logging
@@ -114,6 +116,56 @@ def support_kernel_alone(rng, coverage, config, rounds=200):
         engine.close()
 
 
+def evidence_kernel_alone(rng, coverage, config, rounds=200):
+    """hello_engine_allele_evidence on one 8 192-site launch's arrays in device memory, and hello_engine_featurize on the same
+    arrays (the same per-read walk, plus ~900 bytes written per read) as the yardstick: microseconds per launch between two
+    HIP events around ``rounds`` back-to-back launches (after 20 unmeasured ones)."""
+    import torch
+    from hello_amd import featurizer as fz
+    from hello_amd.engine import Engine
+    payload, n_reads = template_payload(rng, 8192, coverage)
+    fa = shards.PackedShard(dict(payload)).featurizer_arrays(0)
+    off = fz.allele_offsets(fa["reads_per_allele"])
+    n_alleles, n_sites = int(off.shape[0]) - 1, 8192
+    spec = ns.build(config)
+    engine = Engine(spec, weights.synth_state(spec, seed=1), device=0)
+    try:
+        host = dict(fa, allele_off=off)
+        dtypes = dict(fz.EVIDENCE_DTYPES, bases=np.uint8, mapq=np.uint8, orientation=np.int8, ref=np.uint8, ref_off=np.int64,
+                      window_start=np.int64)
+        names = sorted(set(fz.EVIDENCE_ARRAYS) | set(fz.FEATURIZE_ARRAYS))
+        dev = {k: torch.from_numpy(np.ascontiguousarray(host[k], dtypes[k])).to("cuda:0") for k in names}
+        pointers = {k: dev[k].data_ptr() for k in names}
+        out = torch.zeros((n_alleles, 6), dtype=torch.int64, device="cuda:0")
+        pile = torch.zeros((n_reads, 150, 6), dtype=torch.uint8, device="cuda:0")
+        stream = torch.cuda.Stream()
+
+        def timed(launch):
+            begin, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            with torch.cuda.stream(stream):
+                for k in range(20 + rounds):
+                    if k == 20:
+                        begin.record(stream)
+                    launch()
+                end.record(stream)
+            end.synchronize()
+            return begin.elapsed_time(end) * 1e3 / rounds
+        us = timed(lambda: fz.allele_evidence_device(engine, pointers, n_reads, n_sites, n_alleles, out.data_ptr(), stream.cuda_stream))
+        us_feat = timed(lambda: fz.featurize_device(engine, pointers, n_reads, n_sites, 150, 6, pile.data_ptr(), stream.cuda_stream))
+        want = fz.allele_evidence(engine, host)
+        assert np.array_equal(out.cpu().numpy(), want) and int(want[:, 0].sum()) == n_reads and int(want[:, 5].sum()) == 0
+        # distinct bytes: per read two offsets (8 + 8), ref_start 8, site 4, hp 1, one CIGAR word 4 and the one quality inside
+        # the one-base span (its 64-byte line is what HBM delivers); per site 16; per allele one offset in, six int64 out
+        moved = 34 * n_reads + 16 + 16 * n_sites + 8 * (n_alleles + 1) + 48 * n_alleles
+        print(f"allele_evidence_kernel alone, 8 192 sites, {n_alleles} alleles, {n_reads} reads: {us:7.2f} us per launch ({rounds} "
+              f"back-to-back launches between two events, launch overhead included); {moved} distinct bytes moved (34 per read, "
+              f"16 per site, 56 per allele) = {moved / us / 1e3:6.1f} GB/s")
+        print(f"featurize_kernel on the same launch ({n_reads} reads x 150 x 6 bytes out):                {us_feat:7.2f} us per launch; "
+              f"evidence / featurize = {us / us_feat:.3f}")
+    finally:
+        engine.close()
+
+
 def rss_mb():
     return resource.getrusage(resource.RUSAGE_SELF).ru_maxrss / 1024.0
 
@@ -130,11 +182,18 @@ def main():
     ap.add_argument("--only-all", action="store_true", help="skip the quarter-of-the-shards run (the memory-flatness check)")
     ap.add_argument("--annotate", action="store_true", help="the driver and the record stage write read support (call --annotate)")
     ap.add_argument("--support-kernel", action="store_true", help="only time hello_engine_allele_support alone on one 8 192-site launch")
+    ap.add_argument("--annotate_evidence", action="store_true",
+                    help="the driver and the record stage write PL and base-level evidence too (call --annotate_evidence)")
+    ap.add_argument("--evidence-kernel", action="store_true",
+                    help="only time hello_engine_allele_evidence, and hello_engine_featurize beside it, on one 8 192-site launch")
     args = ap.parse_args()
     logging.basicConfig(level=logging.WARNING)
     rng = np.random.default_rng(7)
     if args.support_kernel:
         support_kernel_alone(rng, args.coverage, args.config)
+        return
+    if args.evidence_kernel:
+        evidence_kernel_alone(rng, args.coverage, args.config)
         return
     base = tempfile.mkdtemp(dir="/dev/shm" if os.path.isdir("/dev/shm") else None, prefix="hello_driver_")
     try:
@@ -142,7 +201,8 @@ def main():
         model = os.path.join(base, "model.hello.npz")
         loader.save_native(model, args.config, weights.synth_state(spec, seed=1))
         print(f"# python tools/driver_stage_times.py --sites {args.sites} --shard_sites {args.shard_sites} --threads {args.threads} "
-              f"--arithmetic {args.arithmetic}{' --annotate' if args.annotate else ''}   "
+              f"--arithmetic {args.arithmetic}{' --annotate' if args.annotate else ''}"
+              f"{' --annotate_evidence' if args.annotate_evidence else ''}   "
               f"({args.config}, {args.coverage} reads per site, {len(os.sched_getaffinity(0))} CPUs visible)")
         for shard_sites in [int(x) for x in args.shard_sites.split(",")]:
             payload, n_reads = template_payload(rng, shard_sites, args.coverage)
@@ -152,7 +212,8 @@ def main():
                 os.makedirs(sdir)
                 write_shards(sdir, payload, count, 700 * shard_sites + 10_000)
                 argv = ["--network", model, "--workdir", work, "--shards", sdir, "--num_threads", str(args.threads),
-                        "--arithmetic", args.arithmetic] + (["--annotate"] if args.annotate else [])
+                        "--arithmetic", args.arithmetic] + (["--annotate"] if args.annotate else []) + \
+                    (["--annotate_evidence"] if args.annotate_evidence else [])
                 captured = []
                 handler = logging.Handler()
                 handler.emit = lambda record, captured=captured: captured.append(record.getMessage())
@@ -180,15 +241,17 @@ def main():
         shard = shards.PackedShard(dict(payload))
         table = sp.site_table([shard])
         post = rng.random((4, 3 * 8192)).astype(np.float32)
-        support = None
-        if args.annotate:
+        support = evidence = None
+        if args.annotate or args.annotate_evidence:
             n = shard.featurizer_core(0)["reads_per_allele"].astype(np.int64)
             support = [np.stack([n, n // 2, 60 * n, 3600 * n], axis=1)]
+        if args.annotate_evidence:
+            evidence = [np.stack([n, 30 * n, 40 * n, n // 3, n // 3, 0 * n], axis=1)]
         for threads in sorted({1, 4, args.threads}):
             best = 1e9
             for _ in range(5):
                 t0 = time.perf_counter()
-                records.site_records(table, post, None, threads=threads, support=support).close()
+                records.site_records(table, post, None, threads=threads, support=support, evidence=evidence).close()
                 best = min(best, time.perf_counter() - t0)
             print(f"record stage alone, 8 192 sites, {threads:2d} threads: {best * 1e3:6.2f} ms = {8192 / best:11,.0f} sites/s")
     finally:
