@@ -36,6 +36,11 @@ column and MQ in INFO, counted on the GPU from the launch's own per-read arrays 
 every file is byte for byte what it is with the flag absent.  ``--annotate_evidence`` (implies the fields of ``--annotate``)
 adds genotype likelihoods and base-level evidence behind them: PL from the line's own posteriors, MBQ and MPOS in INFO, ADI / ADP
 with a two-technology model and AH1 / AH2 with ``--include_hp`` (``hello_engine_allele_evidence``; ``hello_amd.vcf.annotate_evidence``).
+
+``--gvcf`` (with ``--from_bam`` / ``--from_bams``, not in the reference, off by default) writes ``<workdir>/results.output.g.vcf``
+after ``results.output.vcf`` is complete: its records byte for byte, and reference-confidence blocks (``<NON_REF>``, ``END``,
+``MIN_DP``, ``GQ``, ``PL``) over every other position of the chromosomes called, counted on the GPU in a second pass over the BAM(s)
+(``hello_amd.gvcf``).
 """
 from __future__ import annotations
 
@@ -260,6 +265,12 @@ def parser() -> argparse.ArgumentParser:
                     help="the fields of --annotate plus PL from the record's own posteriors, mean base quality (MBQ) and read "
                          "position (MPOS) per allele in INFO, ADI / ADP (depth per technology) with a two-technology model and "
                          "AH1 / AH2 (depth per haplotag) with --include_hp, from the reads each launch scores (not in the reference)")
+    ap.add_argument("--gvcf", action="store_true", default=False,
+                    help="with --from_bam / --from_bams: also write <workdir>/results.output.g.vcf -- the records of results.output.vcf "
+                         "plus reference-confidence blocks (<NON_REF>, END, MIN_DP, GQ, PL) over every other position, counted on "
+                         "the GPU in a second pass over the BAM(s) (not in the reference; one GPU)")
+    ap.add_argument("--gvcf_gq_binsize", type=int, default=5,
+                    help="--gvcf: consecutive positions whose GQ falls into one band of this width share a block (at least 1)")
     ap.add_argument("--device", type=int, default=0, help="GPU of a single-process run")
     ap.add_argument("--gpus", type=int, default=1,
                     help="processes / GPUs of this node: > 1 re-launches this command under torch.distributed.run "
@@ -439,6 +450,41 @@ def check_resident(args) -> None:
                          "--resident (the shard files of --from_bam / --from_bams can be dealt to several GPUs)")
 
 
+def check_gvcf(args) -> None:
+    """The refusals of --gvcf, each naming the fix."""
+    if not getattr(args, "gvcf", False):
+        return
+    if not (getattr(args, "from_bam", False) or getattr(args, "from_bams", False)):
+        raise SystemExit("--gvcf counts the reads of the BAM(s) between the records, and the shard route has no BAM on its path: add "
+                         "--from_bam (one BAM) or --from_bams (--ibam and --pbam), or drop --gvcf (python -m hello_amd.gvcf writes a "
+                         "gVCF from a VCF that exists and its BAMs)")
+    if getattr(args, "gpus", 1) > 1 or ("RANK" in os.environ and "WORLD_SIZE" in os.environ):
+        raise SystemExit("--gvcf runs its pass over the BAM(s) in one process on one GPU: run it with --gpus 1 as a plain command, or "
+                         "drop --gvcf and run python -m hello_amd.gvcf on the finished results.output.vcf")
+    if getattr(args, "gvcf_gq_binsize", 5) < 1:
+        raise SystemExit("--gvcf_gq_binsize is the width of a GQ band: give 1 or more")
+
+
+def gvcf_pass(args, result_path: str, genome: Dict[str, str]) -> Optional[str]:
+    """--gvcf: ``results.output.g.vcf`` beside the finished ``result_path``, at the thresholds the route's own stages ran with."""
+    if not getattr(args, "gvcf", False):
+        return None
+    from . import candidates as cd, gvcf
+    if getattr(args, "from_bams", False):
+        bams, q, mq = [args.ibam, args.pbam], args.q_threshold, args.mapq_threshold
+    else:
+        bams, q, mq = [from_bam_route(args.ibam, args.pbam)[0]], cd.DEFAULT_Q_THRESHOLD, cd.DEFAULT_MIN_MAPQ
+    chromosomes = args.chromosomes.split(",") if args.chromosomes else list(genome)
+    out = result_path[:-len(".vcf")] + ".g.vcf"
+    t0 = time.perf_counter()
+    stats: dict = {}
+    gvcf.write_gvcf(result_path, bams, genome, out, chromosomes, q, mq, args.gvcf_gq_binsize, args.device, stats=stats)
+    logging.getLogger("hello_amd.call").info(
+        "gVCF pass: %d blocks in %s, %.2f s (BAM decode %.2f s, kernels %.1f ms)", int(stats.get("blocks", 0)), out,
+        time.perf_counter() - t0, stats.get("decode_s", 0.0), stats.get("kernel_ms", 0.0))
+    return out
+
+
 def run_resident(args) -> str:
     """--from_bam / --from_bams with --resident: hotspots and ``shard<N>.txt`` as ``shards_from_bam(s)`` write them, then ONE loop
     in this process: shard file -> candidate sites whose reads stay on the GPU (``candidates.resident_activity``) -> ``ShardScorer``
@@ -447,6 +493,7 @@ def run_resident(args) -> str:
     from . import candidates as cd, shard_pipeline as sp
     logger = logging.getLogger("hello_amd.call")
     check_resident(args)
+    check_gvcf(args)
     if args.from_bams:
         from . import hybrid as hy
         genome, ns, bam = _from_bams_stages(args)
@@ -493,11 +540,13 @@ def run_resident(args) -> str:
     n = sp.merge_final_vcf(stats.outputs, lambda names: header(names, lengths, getattr(args, "annotate", False), evidence),
                            result_path)
     logger.info("Completed runs in %.2f s. %d records in %s", time.perf_counter() - t0, n, result_path)
+    gvcf_pass(args, result_path, genome)
     return result_path
 
 
 def main(args) -> str:
     logger = logging.getLogger("hello_amd.call")
+    check_gvcf(args)
     if getattr(args, "resident", False):
         return run_resident(args)
     if getattr(args, "from_bams", False) and not args.shards:
@@ -610,6 +659,7 @@ def main(args) -> str:
         lengths = {c: len(g) for c, g in genomes.items()}
         n = sp.merge_final_vcf(outputs, lambda names: header(names, lengths, getattr(args, "annotate", False), evidence), result_path)
         logger.info("Completed runs in %.2f s. %d records in %s", time.perf_counter() - t0, n, result_path)
+        gvcf_pass(args, result_path, genomes)
     if world > 1:
         import torch.distributed as dist
         dist.barrier()

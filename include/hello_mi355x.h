@@ -723,6 +723,48 @@ int hello_site_server_get_stats(hello_site_server* server, hello_site_server_sta
 /* Closes the sockets, unmaps and unlinks the segment and the socket file. */
 void hello_site_server_destroy(hello_site_server* server);
 
+/* Reference-confidence blocks of a gVCF (not in the reference; DESIGN.md section 7f states the rules, hello_amd/gvcf.py restates
+ * them in Python).  Over the span [lo, hi) of one chromosome: per position the bases of the counted reads (n_total) and those that
+ * equal the reference case-insensitively (n_ref), then the called / no-call flag, GQ and band of the position, and the maximal
+ * runs of consecutive positions of one band that lie in no excluded interval.
+ *   reads: the arrays of hello_bam_fetch, `source` 0 / 1 as for hello_hotspots_find, each source coordinate-sorted.  A read counts
+ *          when it is usable (as for the hotspot stage), not QC-fail (0x200) and mapq >= mapq_threshold; no de-duplication, no cap.
+ *          A counted read whose CIGAR consumes more bases than it has is refused (HELLO_ERR_ARG).
+ *   reference: the chromosome's text (case kept), reference_length bytes; 0 <= lo <= hi <= reference_length.
+ *   excluded_starts / excluded_stops: n_excluded intervals [start, stop), sorted, not overlapping (they may touch).
+ *   gq_binsize >= 1: the band of a called position is GQ / gq_binsize; HELLO_REFBLOCKS_NO_CALL is the band of no-call positions.
+ *   options: 0, or HELLO_REFBLOCKS_KEEP_COUNTS (the per-position counters are copied back too).
+ * Two kernel launches on `device` (refblocks.hip): counting and the number of runs per tile; then, with exact offsets, the runs.
+ * Runs of one band that meet at a tile edge are joined on the host.  Host memory in and out. */
+#define HELLO_REFBLOCKS_KEEP_COUNTS 1
+#define HELLO_REFBLOCKS_NO_CALL (-1)
+#define HELLO_REFBLOCKS_STATS 7
+enum {
+    HELLO_REFBLOCKS_START = 0,      /* int64 [blocks] */
+    HELLO_REFBLOCKS_END = 1,        /* int64 [blocks], exclusive */
+    HELLO_REFBLOCKS_BAND = 2,       /* int32 [blocks] */
+    HELLO_REFBLOCKS_MIN_DP = 3,     /* int32 [blocks]: the smallest n_total */
+    HELLO_REFBLOCKS_GQ = 4,         /* int32 [blocks]: the smallest GQ */
+    HELLO_REFBLOCKS_N_REF = 5,      /* int32 [blocks]: n_ref of the first position with that GQ */
+    HELLO_REFBLOCKS_N_TOTAL = 6,    /* int32 [blocks]: n_total of that position */
+    HELLO_REFBLOCKS_COUNT_REF = 7,  /* int32 [hi - lo] with HELLO_REFBLOCKS_KEEP_COUNTS, else count 0 */
+    HELLO_REFBLOCKS_COUNT_TOTAL = 8 /* int32 [hi - lo] with HELLO_REFBLOCKS_KEEP_COUNTS, else count 0 */
+};
+typedef struct hello_refblocks hello_refblocks;
+int hello_refblocks_find(const uint8_t* bases, const uint8_t* quals, const int64_t* read_offsets,
+                         const uint32_t* cigars, const int64_t* cigar_offsets, const int64_t* ref_starts,
+                         const int64_t* ref_ends, const uint8_t* mapq, const uint16_t* flags, const uint64_t* name_hash,
+                         const uint8_t* source, int64_t n_reads, const uint8_t* reference, int64_t reference_length,
+                         int64_t lo, int64_t hi, const int64_t* excluded_starts, const int64_t* excluded_stops,
+                         int64_t n_excluded, int32_t q_threshold, int32_t mapq_threshold, int32_t gq_binsize, int32_t options,
+                         int32_t device, hello_refblocks** out);
+/* a pointer into `blocks` (valid until hello_refblocks_free) and its element count */
+int hello_refblocks_array(const hello_refblocks* blocks, int32_t which, const void** data, int64_t* count);
+/* stats[HELLO_REFBLOCKS_STATS]: tiles, reads counted, runs before joining, blocks after joining, kernel ms (HIP events, both
+ * launches), plan ms, total ms */
+int hello_refblocks_stats(const hello_refblocks* blocks, double* stats);
+void hello_refblocks_free(hello_refblocks* blocks);
+
 #ifdef __cplusplus
 }
 #endif
