@@ -41,6 +41,11 @@ with a two-technology model and AH1 / AH2 with ``--include_hp`` (``hello_engine_
 after ``results.output.vcf`` is complete: its records byte for byte, and reference-confidence blocks (``<NON_REF>``, ``END``,
 ``MIN_DP``, ``GQ``, ``PL``) over every other position of the chromosomes called, counted on the GPU in a second pass over the BAM(s)
 (``hello_amd.gvcf``).
+
+``--phase`` (with ``--from_bam`` / ``--from_bams``, not in the reference, off by default) writes ``<workdir>/results.output.phased.vcf``
+after ``results.output.vcf`` is complete: its lines in its order, the heterozygous records that the reads link rewritten as ``a|b``
+with a phase set (``PS``), observed, linked and tagged on the GPU in a pass of its own over the BAM(s) (``hello_amd.phase``;
+DESIGN.md section 7g).
 """
 from __future__ import annotations
 
@@ -271,6 +276,14 @@ def parser() -> argparse.ArgumentParser:
                          "the GPU in a second pass over the BAM(s) (not in the reference; one GPU)")
     ap.add_argument("--gvcf_gq_binsize", type=int, default=5,
                     help="--gvcf: consecutive positions whose GQ falls into one band of this width share a block (at least 1)")
+    ap.add_argument("--phase", action="store_true", default=False,
+                    help="with --from_bam / --from_bams: also write <workdir>/results.output.phased.vcf -- the lines of "
+                         "results.output.vcf, heterozygous records that the reads link rewritten as a|b with a phase set (PS), "
+                         "from a pass of its own over the BAM(s) on the GPU (not in the reference; one GPU)")
+    ap.add_argument("--phase_window", type=int, default=8,
+                    help="--phase: a record is linked to this many heterozygous records before it (1 to 32)")
+    ap.add_argument("--phase_min_margin", type=int, default=2,
+                    help="--phase: the smallest |cis - trans| read count that joins a record to a phase set (at least 1)")
     ap.add_argument("--device", type=int, default=0, help="GPU of a single-process run")
     ap.add_argument("--gpus", type=int, default=1,
                     help="processes / GPUs of this node: > 1 re-launches this command under torch.distributed.run "
@@ -485,6 +498,44 @@ def gvcf_pass(args, result_path: str, genome: Dict[str, str]) -> Optional[str]:
     return out
 
 
+def check_phase(args) -> None:
+    """The refusals of --phase, each naming the fix."""
+    if not getattr(args, "phase", False):
+        return
+    if not (getattr(args, "from_bam", False) or getattr(args, "from_bams", False)):
+        raise SystemExit("--phase reads the alleles of neighbouring records off the reads of the BAM(s), and the shard route has no BAM "
+                         "on its path: add --from_bam (one BAM) or --from_bams (--ibam and --pbam), or drop --phase (python -m "
+                         "hello_amd.phase phases a VCF that exists from its BAMs)")
+    if getattr(args, "gpus", 1) > 1 or ("RANK" in os.environ and "WORLD_SIZE" in os.environ):
+        raise SystemExit("--phase runs its pass over the BAM(s) in one process on one GPU: run it with --gpus 1 as a plain command, or "
+                         "drop --phase and run python -m hello_amd.phase on the finished results.output.vcf")
+    if not 1 <= getattr(args, "phase_window", 8) <= 32:
+        raise SystemExit("--phase_window is the number of records a record is linked back to: give 1 to 32")
+    if getattr(args, "phase_min_margin", 2) < 1:
+        raise SystemExit("--phase_min_margin is the smallest |cis - trans| that joins a phase set: give 1 or more")
+
+
+def phase_pass(args, result_path: str) -> Optional[str]:
+    """--phase: ``results.output.phased.vcf`` beside the finished ``result_path``, at the thresholds the route's own stages ran with."""
+    if not getattr(args, "phase", False):
+        return None
+    from . import candidates as cd, phase
+    if getattr(args, "from_bams", False):
+        bams, q, mq = [args.ibam, args.pbam], args.q_threshold, args.mapq_threshold
+    else:
+        bams, q, mq = [from_bam_route(args.ibam, args.pbam)[0]], cd.DEFAULT_Q_THRESHOLD, cd.DEFAULT_MIN_MAPQ
+    out = result_path[:-len(".vcf")] + ".phased.vcf"
+    t0 = time.perf_counter()
+    stats: dict = {}
+    phase.write_phased_vcf(result_path, bams, out, args.chromosomes.split(",") if args.chromosomes else None, q, mq,
+                           args.phase_window, args.phase_min_margin, args.device, stats=stats)
+    logging.getLogger("hello_amd.call").info(
+        "phase pass: %d slots of %d reads in %s, %.2f s (BAM decode %.2f s, kernels %.1f ms)", int(stats.get("slots", 0)),
+        int(stats.get("reads_counted", 0)), out, time.perf_counter() - t0, stats.get("decode_s", 0.0),
+        stats.get("observe_ms", 0.0) + stats.get("link_ms", 0.0) + stats.get("tag_ms", 0.0))
+    return out
+
+
 def run_resident(args) -> str:
     """--from_bam / --from_bams with --resident: hotspots and ``shard<N>.txt`` as ``shards_from_bam(s)`` write them, then ONE loop
     in this process: shard file -> candidate sites whose reads stay on the GPU (``candidates.resident_activity``) -> ``ShardScorer``
@@ -494,6 +545,7 @@ def run_resident(args) -> str:
     logger = logging.getLogger("hello_amd.call")
     check_resident(args)
     check_gvcf(args)
+    check_phase(args)
     if args.from_bams:
         from . import hybrid as hy
         genome, ns, bam = _from_bams_stages(args)
@@ -541,12 +593,14 @@ def run_resident(args) -> str:
                            result_path)
     logger.info("Completed runs in %.2f s. %d records in %s", time.perf_counter() - t0, n, result_path)
     gvcf_pass(args, result_path, genome)
+    phase_pass(args, result_path)
     return result_path
 
 
 def main(args) -> str:
     logger = logging.getLogger("hello_amd.call")
     check_gvcf(args)
+    check_phase(args)
     if getattr(args, "resident", False):
         return run_resident(args)
     if getattr(args, "from_bams", False) and not args.shards:
@@ -660,6 +714,7 @@ def main(args) -> str:
         n = sp.merge_final_vcf(outputs, lambda names: header(names, lengths, getattr(args, "annotate", False), evidence), result_path)
         logger.info("Completed runs in %.2f s. %d records in %s", time.perf_counter() - t0, n, result_path)
         gvcf_pass(args, result_path, genomes)
+        phase_pass(args, result_path)
     if world > 1:
         import torch.distributed as dist
         dist.barrier()

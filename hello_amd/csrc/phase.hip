@@ -1,0 +1,579 @@
+// Read-backed phasing (include/hello_mi355x.h: hello_phase_*): aligned reads + the heterozygous records of one chromosome -> what
+// every counted read shows at every record it spans (allele a, allele b or nothing), how often two records within a window were
+// seen together in cis and in trans, and, once the host has chained the records into phase sets, a haplotype for every read.  Not
+// in the reference; DESIGN.md section 7g states the rules and hello_amd/phase.py restates them in Python, integer for integer.
+//
+// Host: the read filter, the validation of every counted read (the kernel reads within its bases), per counted read its reference
+// end from the CIGAR, the contiguous range of records whose start it covers (two binary searches in the sorted record starts) and,
+// by an exclusive scan of those counts, the offset of its first slot.  Device, three kernels:
+//   observe: a wave per counted read.  The lanes hold the read's candidate records, 64 per round; the walk over the CIGAR is
+//     wave-uniform (one operation at a time, the same for all lanes, ended once every lane's record lies behind the cursor), and a
+//     lane only has work where an operation meets its own span -- it compares the bases it would append with both alleles as it
+//     goes, so no string is stored.  Each lane writes the slot of its own record: one writer per slot, no reduction across lanes.
+//     (The opposite assignment -- lanes over the bases of an operation, a loop over the records -- puts 64 lanes on spans that are
+//     one base long at most records and needs a cross-lane compare; section 7g.)
+//   link: a thread per slot.  Slot distance within a read is record-index distance, so the thread looks back at most `window`
+//     slots of its own read and adds 1 to link[t][k][cis | trans] in global memory with an integer atomic.
+//   tag: a thread per counted read, one pass over its slots with the sets and flips the host chained.
+// Slot capacity is exact, counters are integers and every slot and every tag has one writer: two runs give the same bytes.
+#include <algorithm>
+#include <chrono>
+#include <climits>
+#include <cstring>
+#include <memory>
+#include <vector>
+
+#include <hip/hip_runtime.h>
+
+#include "../../include/hello_mi355x.h"
+#include "differing.h"
+
+namespace hello {
+int set_last_error(int code, const char* fmt, ...);      // engine.hip
+int exception_status(const char* where) noexcept;         // engine.hip
+
+namespace {
+
+constexpr int kPhThreads = 256;
+constexpr int kPhWaves = kPhThreads / 64;
+
+struct PhObserveArgs {
+    const uint8_t* bases;
+    const uint8_t* quals;
+    const int64_t* read_off;
+    const uint32_t* cigars;
+    const int64_t* cigar_off;
+    const int64_t* ref_start;
+    const int64_t* list;         // the counted reads, in input order
+    const int64_t* list_end;     // reference end of list[k], from its CIGAR
+    const int64_t* first;        // [counted]: the first candidate record of list[k]
+    const int64_t* slot_off;     // [counted + 1]: exclusive scan of the candidate counts
+    const int64_t* rec_start;    // [records], sorted
+    const int64_t* rec_end;
+    const uint8_t* alleles;      // allele a then allele b of every record, upper case
+    const int64_t* allele_off;   // [2 records + 1]
+    int8_t* slots;
+    int64_t n_counted;
+    int q_threshold;
+};
+
+__global__ __launch_bounds__(kPhThreads) void phase_observe_kernel(PhObserveArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int64_t k = (int64_t)blockIdx.x * kPhWaves + (threadIdx.x >> 6);
+    if (k >= a.n_counted) return;
+    const int64_t s0 = a.slot_off[k], n_cand = a.slot_off[k + 1] - s0;
+    if (n_cand == 0) return;
+    const int64_t r = a.list[k], rs = a.ref_start[r], re = a.list_end[k], t0 = a.first[k];
+    const uint8_t* bases = a.bases + a.read_off[r];
+    const uint8_t* quals = a.quals + a.read_off[r];
+    const int64_t c0 = a.cigar_off[r], n_ops = a.cigar_off[r + 1] - c0;
+    for (int64_t round = 0; round < n_cand; round += 64) {
+        const int64_t j = round + lane;
+        const bool mine = j < n_cand;
+        int64_t A = 0, B = 0, la = 0, lb = 0;
+        const uint8_t* al_a = a.alleles;
+        const uint8_t* al_b = a.alleles;
+        if (mine) {
+            const int64_t t = t0 + j;
+            A = a.rec_start[t];
+            B = a.rec_end[t];
+            const int64_t o0 = a.allele_off[2 * t], o1 = a.allele_off[2 * t + 1], o2 = a.allele_off[2 * t + 2];
+            al_a += o0;
+            al_b += o1;
+            la = o1 - o0;
+            lb = o2 - o1;
+        }
+        bool dead = !mine || !(B < re);                                   // the base behind the span must be aligned
+        bool ma = true, mb = true;
+        int64_t len = 0;
+        int minq = 255;
+        auto append = [&](int64_t i) {
+            const unsigned char c = bases[i] & 0xDF;
+            const int q = quals[i];
+            ma = ma && len < la && al_a[len] == c;
+            mb = mb && len < lb && al_b[len] == c;
+            minq = q < minq ? q : minq;
+            ++len;
+        };
+        int64_t rf = rs, rd = 0;
+        for (int64_t ci = 0; ci < n_ops; ++ci) {
+            if (!__any(!dead && rf <= B)) break;                          // every lane's span lies behind the cursor
+            const unsigned c = a.cigars[c0 + ci];
+            const int op = c & 15u;
+            const int64_t n = c >> 4;
+            if (op == BAM_CMATCH || op == BAM_CEQUAL || op == BAM_CDIFF) {
+                if (!dead) {
+                    const int64_t j0 = A > rf ? A - rf : 0, j1 = B - rf < n ? B - rf : n;
+                    for (int64_t i = j0; i < j1 && (ma || mb); ++i) append(rd + i);
+                }
+                rf += n;
+                rd += n;
+            } else if (op == BAM_CINS) {
+                if (!dead && rf - 1 >= A && rf - 1 < B)
+                    for (int64_t i = 0; i < n && (ma || mb); ++i) append(rd + i);
+                rd += n;
+            } else if (op == BAM_CDEL) {
+                rf += n;
+            } else if (op == BAM_CREF_SKIP) {
+                if (rf < B && rf + n > A) dead = true;
+                rf += n;
+            } else if (op == BAM_CSOFT_CLIP) {
+                rd += n;
+            }
+        }
+        int o = -1;
+        if (!dead && minq >= a.q_threshold) {
+            if (ma && len == la) o = 0;
+            else if (mb && len == lb) o = 1;
+        }
+        if (mine) a.slots[s0 + j] = (int8_t)o;
+    }
+}
+
+struct PhLinkArgs {
+    const int8_t* slots;
+    const int64_t* slot_off;     // [counted + 1]
+    const int64_t* first;
+    int32_t* link;               // [records][window][2]
+    int64_t n_slots, n_counted;
+    int window;
+};
+
+__global__ __launch_bounds__(kPhThreads) void phase_link_kernel(PhLinkArgs a) {
+    const int64_t s = (int64_t)blockIdx.x * kPhThreads + threadIdx.x;
+    if (s >= a.n_slots) return;
+    const int o = a.slots[s];
+    if (o < 0) return;
+    int64_t x = 0, y = a.n_counted + 1;                                   // the last read whose first slot is at or before s
+    while (x < y) {
+        const int64_t mid = (x + y) >> 1;
+        if (a.slot_off[mid] <= s) x = mid + 1; else y = mid;
+    }
+    const int64_t k = x - 1, base = a.slot_off[k], t = a.first[k] + (s - base);
+    for (int d = 1; d <= a.window && s - d >= base; ++d) {
+        const int p = a.slots[s - d];
+        if (p < 0) continue;
+        atomicAdd(&a.link[(t * a.window + (d - 1)) * 2 + (p != o ? 1 : 0)], 1);
+    }
+}
+
+struct PhTagArgs {
+    const int8_t* slots;
+    const int64_t* slot_off;
+    const int64_t* first;
+    const int32_t* set;          // [records]: the record that opened the set
+    const uint8_t* flip;
+    const int64_t* set_pos;      // [records]: POS of the set's first record, 0 when the set has one member
+    uint8_t* hp;                 // [counted]
+    int64_t* ps;
+    int64_t n_counted;
+};
+
+__global__ __launch_bounds__(kPhThreads) void phase_tag_kernel(PhTagArgs a) {
+    const int64_t k = (int64_t)blockIdx.x * kPhThreads + threadIdx.x;
+    if (k >= a.n_counted) return;
+    const int64_t s0 = a.slot_off[k], s1 = a.slot_off[k + 1], t0 = a.first[k];
+    int mine = -1, n1 = 0, n2 = 0;
+    int64_t pos = 0;
+    for (int64_t s = s0; s < s1; ++s) {
+        const int o = a.slots[s];
+        const int64_t t = t0 + (s - s0);
+        if (o < 0 || a.set_pos[t] == 0) continue;
+        if (mine < 0) { mine = a.set[t]; pos = a.set_pos[t]; }
+        if (a.set[t] != mine) continue;
+        if ((o ^ (int)a.flip[t]) == 0) ++n1; else ++n2;
+    }
+    a.hp[k] = n1 > n2 ? 1 : n2 > n1 ? 2 : 0;
+    a.ps[k] = pos;
+}
+
+struct PhBatch {
+    int8_t* slots = nullptr;     // device
+    int64_t* slot_off = nullptr;
+    int64_t* first = nullptr;
+    int64_t n_counted = 0, n_slots = 0, read_base = 0;
+    std::vector<int64_t> reads;  // list[k] of the batch
+};
+
+template <class T> T* dev_put(const T* src, size_t n) {
+    void* p = nullptr;
+    HS_HIP(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)));
+    if (n && hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(p);
+        raise(HELLO_ERR_HIP, "hipMemcpy to the device failed");
+    }
+    return (T*)p;
+}
+
+}  // namespace
+}  // namespace hello
+
+struct hello_phase {
+    int device = 0, window = 0, q_threshold = 0, mapq_threshold = 0;
+    int64_t n_records = 0, n_reads = 0;
+    std::vector<int64_t> rec_start;
+    int64_t* d_rec_start = nullptr;
+    int64_t* d_rec_end = nullptr;
+    uint8_t* d_alleles = nullptr;
+    int64_t* d_allele_off = nullptr;
+    std::vector<hello::PhBatch> batches;
+    std::vector<int8_t> slots;
+    std::vector<int64_t> slot_offsets{0}, first, ps;
+    std::vector<int32_t> links;
+    std::vector<uint8_t> hp;
+    double stats[HELLO_PHASE_STATS] = {0};
+    ~hello_phase() {
+        for (auto& b : batches) { (void)hipFree(b.slots); (void)hipFree(b.slot_off); (void)hipFree(b.first); }
+        (void)hipFree(d_rec_start);
+        (void)hipFree(d_rec_end);
+        (void)hipFree(d_alleles);
+        (void)hipFree(d_allele_off);
+    }
+};
+
+namespace hello {
+namespace {
+
+void phase_open_device(int device) {
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) raise(HELLO_ERR_NOGPU, "no GPU visible");
+    if (device < 0 || device >= n_dev) raise(HELLO_ERR_ARG, "device %d of %d", device, n_dev);
+    hipDeviceProp_t prop;
+    HS_HIP(hipGetDeviceProperties(&prop, device));
+    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+        raise(HELLO_ERR_NOGPU, "device %d is %s; this library is built for gfx950 only", device, prop.gcnArchName);
+    HS_HIP(hipSetDevice(device));
+}
+
+struct Timer {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    Timer() {
+        HS_HIP(hipEventCreate(&e0));
+        HS_HIP(hipEventCreate(&e1));
+    }
+    ~Timer() {
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+    }
+    void start() { HS_HIP(hipEventRecord(e0, 0)); }
+    float stop() {
+        float ms = 0.0f;
+        HS_HIP(hipGetLastError());
+        HS_HIP(hipEventRecord(e1, 0));
+        HS_HIP(hipEventSynchronize(e1));
+        HS_HIP(hipEventElapsedTime(&ms, e0, e1));
+        return ms;
+    }
+};
+
+unsigned blocks_for(int64_t items, int per_block) {
+    const int64_t n = (items + per_block - 1) / per_block;
+    if (n > INT32_MAX) raise(HELLO_ERR_ARG, "%lld items in one launch", (long long)items);
+    return (unsigned)n;
+}
+
+}  // namespace
+}  // namespace hello
+
+extern "C" {
+
+int hello_phase_observe(const uint8_t* bases, const uint8_t* quals, const int64_t* read_offsets, const uint32_t* cigars,
+                        const int64_t* cigar_offsets, const int64_t* ref_starts, const int64_t* ref_ends, const uint8_t* mapq,
+                        const uint16_t* flags, const uint64_t* name_hash, const uint8_t* source, int64_t n_reads,
+                        const int64_t* record_starts, const int64_t* record_ends, const uint8_t* alleles,
+                        const int64_t* allele_offsets, int64_t n_records, int32_t q_threshold, int32_t mapq_threshold,
+                        int32_t window, int32_t device, hello_phase** handle) try {
+    using namespace hello;
+    using clock = std::chrono::steady_clock;
+    const auto t0 = clock::now();
+    if (!handle || !read_offsets || !cigar_offsets || (n_reads > 0 && (!bases || !quals || !cigars || !ref_starts || !ref_ends ||
+        !mapq || !flags || !name_hash || !source)))
+        return set_last_error(HELLO_ERR_ARG, "NULL pointer");
+    if (n_reads < 0 || n_records < 0) return set_last_error(HELLO_ERR_ARG, "negative count");
+    hello_phase* h = *handle;
+    std::unique_ptr<hello_phase> own;
+    if (!h) {
+        // ---- the first call of a chromosome: its records, validated and uploaded once
+        if (!allele_offsets || (n_records > 0 && (!record_starts || !record_ends || !alleles)))
+            return set_last_error(HELLO_ERR_ARG, "NULL pointer");
+        if (window < 1 || window > HELLO_PHASE_MAX_WINDOW)
+            return set_last_error(HELLO_ERR_ARG, "window %d: 1 to %d", window, HELLO_PHASE_MAX_WINDOW);
+        if (n_records > INT32_MAX / (2 * HELLO_PHASE_MAX_WINDOW))
+            return set_last_error(HELLO_ERR_ARG, "%lld records in one chromosome", (long long)n_records);
+        if (allele_offsets[0] != 0) return set_last_error(HELLO_ERR_ARG, "allele_offsets[0] is not 0");
+        for (int64_t t = 0; t < n_records; ++t) {
+            if (record_starts[t] < 0 || record_ends[t] <= record_starts[t])
+                return set_last_error(HELLO_ERR_ARG, "record %lld: span [%lld, %lld)", (long long)t, (long long)record_starts[t],
+                                      (long long)record_ends[t]);
+            if (t > 0 && record_starts[t] < record_starts[t - 1])
+                return set_last_error(HELLO_ERR_ARG, "record %lld: records are not sorted by position", (long long)t);
+            if (allele_offsets[2 * t + 1] < allele_offsets[2 * t] || allele_offsets[2 * t + 2] < allele_offsets[2 * t + 1])
+                return set_last_error(HELLO_ERR_SHAPE, "record %lld: allele offsets decrease", (long long)t);
+        }
+        own.reset(new hello_phase());
+        h = own.get();
+        phase_open_device(device);
+        h->device = device;
+        h->window = window;
+        h->q_threshold = q_threshold;
+        h->mapq_threshold = mapq_threshold;
+        h->n_records = n_records;
+        h->rec_start.assign(record_starts, record_starts + n_records);
+        h->links.assign((size_t)n_records * window * 2, 0);
+        h->d_rec_start = dev_put(record_starts, (size_t)n_records);
+        h->d_rec_end = dev_put(record_ends, (size_t)n_records);
+        h->d_alleles = dev_put(alleles, (size_t)allele_offsets[2 * n_records]);
+        h->d_allele_off = dev_put(allele_offsets, (size_t)(2 * n_records + 1));
+    } else {
+        if (n_records != h->n_records || window != h->window || q_threshold != h->q_threshold || mapq_threshold != h->mapq_threshold ||
+            device != h->device)
+            return set_last_error(HELLO_ERR_ARG, "a further call names other records, thresholds, window or device than the first");
+        HS_HIP(hipSetDevice(h->device));
+    }
+    if (!h->hp.empty() || !h->ps.empty()) return set_last_error(HELLO_ERR_ARG, "reads cannot be added after hello_phase_tag");
+
+    // ---- the counted reads, validated (the kernel reads within their bases), and the records each one's start-to-end covers
+    const int64_t n = h->n_records;
+    const int64_t* rec = h->rec_start.data();
+    PhBatch b;
+    struct Guard {                                                          // the batch's device memory, until the handle owns it
+        PhBatch* b;
+        ~Guard() {
+            if (b) { (void)hipFree(b->slots); (void)hipFree(b->slot_off); (void)hipFree(b->first); }
+        }
+    } guard{&b};
+    b.read_base = h->n_reads;
+    std::vector<int64_t> list_end, first, slot_off{0}, all_first((size_t)n_reads, 0), all_count((size_t)n_reads, 0);
+    for (int64_t r = 0; r < n_reads; ++r) {
+        if (source[r] > 1) return set_last_error(HELLO_ERR_ARG, "source[%lld] = %d: 0 or 1", (long long)r, (int)source[r]);
+        if (read_offsets[r + 1] < read_offsets[r] || cigar_offsets[r + 1] < cigar_offsets[r])
+            return set_last_error(HELLO_ERR_SHAPE, "read %lld: offsets decrease", (long long)r);
+        if (!usable(flags[r], mapq[r]) || (flags[r] & 0x200) || (int)mapq[r] < mapq_threshold) continue;
+        int64_t qlen = 0, rlen = 0;
+        for (int64_t c = cigar_offsets[r]; c < cigar_offsets[r + 1]; ++c) {
+            const int op = cigars[c] & 15;
+            const int64_t len = cigars[c] >> 4;
+            if (op == BAM_CMATCH || op == BAM_CINS || op == BAM_CSOFT_CLIP || op == BAM_CEQUAL || op == BAM_CDIFF) qlen += len;
+            if (op == BAM_CMATCH || op == BAM_CDEL || op == BAM_CREF_SKIP || op == BAM_CEQUAL || op == BAM_CDIFF) rlen += len;
+        }
+        if (qlen > read_offsets[r + 1] - read_offsets[r])
+            return set_last_error(HELLO_ERR_ARG, "read %lld: its CIGAR consumes %lld bases, it has %lld", (long long)r, (long long)qlen,
+                                  (long long)(read_offsets[r + 1] - read_offsets[r]));
+        const int64_t end = ref_starts[r] + rlen;
+        const int64_t f = std::lower_bound(rec, rec + n, ref_starts[r]) - rec;
+        const int64_t l = std::lower_bound(rec, rec + n, end) - rec;
+        const int64_t count = std::max<int64_t>(l - f, 0);
+        b.reads.push_back(r);
+        list_end.push_back(end);
+        first.push_back(f);
+        slot_off.push_back(slot_off.back() + count);                        // exclusive scan: the capacity is exact
+        all_first[r] = f;
+        all_count[r] = count;
+    }
+    b.n_counted = (int64_t)b.reads.size();
+    b.n_slots = slot_off.back();
+    const auto t1 = clock::now();
+
+    float observe_ms = 0.0f, link_ms = 0.0f;
+    std::vector<int8_t> slots((size_t)b.n_slots);
+    if (b.n_slots > 0) {
+        DevMem m;
+        PhObserveArgs a{};
+        const int64_t nb = read_offsets[n_reads], nc = cigar_offsets[n_reads];
+        a.bases = m.put(bases, (size_t)nb);
+        a.quals = m.put(quals, (size_t)nb);
+        a.read_off = m.put(read_offsets, (size_t)n_reads + 1);
+        a.cigars = m.put(cigars, (size_t)nc);
+        a.cigar_off = m.put(cigar_offsets, (size_t)n_reads + 1);
+        a.ref_start = m.put(ref_starts, (size_t)n_reads);
+        a.list = m.put(b.reads.data(), b.reads.size());
+        a.list_end = m.put(list_end.data(), list_end.size());
+        b.first = dev_put(first.data(), first.size());
+        b.slot_off = dev_put(slot_off.data(), slot_off.size());
+        void* p = nullptr;
+        HS_HIP(hipMalloc(&p, (size_t)b.n_slots));
+        b.slots = (int8_t*)p;
+        HS_HIP(hipMemset(p, 0xFF, (size_t)b.n_slots));
+        const PhBatch& kept = b;
+        a.first = kept.first;
+        a.slot_off = kept.slot_off;
+        a.rec_start = h->d_rec_start;
+        a.rec_end = h->d_rec_end;
+        a.alleles = h->d_alleles;
+        a.allele_off = h->d_allele_off;
+        a.slots = kept.slots;
+        a.n_counted = b.n_counted;
+        a.q_threshold = q_threshold;
+        Timer timer;
+        timer.start();
+        hipLaunchKernelGGL(phase_observe_kernel, dim3(blocks_for(b.n_counted, kPhWaves)), dim3(kPhThreads), 0, 0, a);
+        observe_ms = timer.stop();
+        PhLinkArgs l{};
+        l.slots = kept.slots;
+        l.slot_off = kept.slot_off;
+        l.first = kept.first;
+        l.link = m.zeros<int32_t>(h->links.size());
+        l.n_slots = b.n_slots;
+        l.n_counted = b.n_counted;
+        l.window = h->window;
+        timer.start();
+        hipLaunchKernelGGL(phase_link_kernel, dim3(blocks_for(b.n_slots, kPhThreads)), dim3(kPhThreads), 0, 0, l);
+        link_ms = timer.stop();
+        HS_HIP(hipMemcpy(slots.data(), kept.slots, slots.size(), hipMemcpyDeviceToHost));
+        std::vector<int32_t> link(h->links.size());
+        HS_HIP(hipMemcpy(link.data(), l.link, link.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < link.size(); ++i) h->links[i] += link[i];    // the spans' links are added on the host
+    }
+    h->batches.push_back(b);                                                // without a slot: nothing on the device, the tags are 0
+    guard.b = nullptr;
+    // ---- the host's view, aligned with the reads given so far
+    h->slots.insert(h->slots.end(), slots.begin(), slots.end());
+    for (int64_t r = 0; r < n_reads; ++r) {
+        h->first.push_back(all_first[r]);
+        h->slot_offsets.push_back(h->slot_offsets.back() + all_count[r]);
+    }
+    h->n_reads += n_reads;
+    h->stats[0] = (double)h->n_records;
+    h->stats[1] = (double)h->n_reads;
+    h->stats[2] += (double)b.n_counted;
+    h->stats[3] += (double)b.n_slots;
+    h->stats[4] += observe_ms;
+    h->stats[5] += link_ms;
+    h->stats[7] += std::chrono::duration<double, std::milli>(t1 - t0).count();
+    h->stats[8] += std::chrono::duration<double, std::milli>(clock::now() - t0).count();
+    if (own) *handle = own.release();
+    return HELLO_OK;
+} catch (const hello::Fail& f) {
+    return hello::set_last_error(f.code, "%s", f.msg.c_str());
+} catch (...) {
+    return hello::exception_status("hello_phase_observe");
+}
+
+int hello_phase_chain(const int32_t* link, const int32_t* chromosome, int64_t n_records, int32_t window, int32_t min_margin,
+                      int32_t* set, uint8_t* flip) try {
+    using namespace hello;
+    if (n_records < 0) return set_last_error(HELLO_ERR_ARG, "negative count");
+    if (n_records > 0 && (!link || !chromosome || !set || !flip)) return set_last_error(HELLO_ERR_ARG, "NULL pointer");
+    if (window < 1 || window > HELLO_PHASE_MAX_WINDOW) return set_last_error(HELLO_ERR_ARG, "window %d: 1 to %d", window, HELLO_PHASE_MAX_WINDOW);
+    if (min_margin < 1) return set_last_error(HELLO_ERR_ARG, "min_margin %d: at least 1", min_margin);
+    if (n_records > INT32_MAX) return set_last_error(HELLO_ERR_ARG, "%lld records", (long long)n_records);
+    for (int64_t t = 0; t < n_records; ++t) {
+        int32_t seen[HELLO_PHASE_MAX_WINDOW];                               // the sets met, in the order of k
+        int64_t same[HELLO_PHASE_MAX_WINDOW], opp[HELLO_PHASE_MAX_WINDOW];
+        int n_seen = 0;
+        for (int k = 1; k <= window && t - k >= 0; ++k) {
+            const int64_t s = t - k;
+            if (chromosome[s] != chromosome[t]) continue;
+            int64_t cis = link[(t * window + (k - 1)) * 2], trans = link[(t * window + (k - 1)) * 2 + 1];
+            if (flip[s]) std::swap(cis, trans);
+            int g = 0;
+            while (g < n_seen && seen[g] != set[s]) ++g;
+            if (g == n_seen) {
+                seen[g] = set[s];
+                same[g] = opp[g] = 0;
+                ++n_seen;
+            }
+            same[g] += cis;
+            opp[g] += trans;
+        }
+        int best = -1;
+        int64_t margin = -1;
+        for (int g = 0; g < n_seen; ++g) {
+            const int64_t m = same[g] > opp[g] ? same[g] - opp[g] : opp[g] - same[g];
+            if (m > margin) { margin = m; best = g; }                      // a tie stays with the set of the smaller k
+        }
+        if (best >= 0 && margin >= min_margin) {
+            set[t] = seen[best];
+            flip[t] = opp[best] > same[best] ? 1 : 0;
+        } else {
+            set[t] = (int32_t)t;
+            flip[t] = 0;
+        }
+    }
+    return HELLO_OK;
+} catch (...) {
+    return hello::exception_status("hello_phase_chain");
+}
+
+int hello_phase_tag(hello_phase* h, const int32_t* set, const uint8_t* flip) try {
+    using namespace hello;
+    using clock = std::chrono::steady_clock;
+    const auto t0 = clock::now();
+    if (!h || (h->n_records > 0 && (!set || !flip))) return set_last_error(HELLO_ERR_ARG, "NULL pointer");
+    const int64_t n = h->n_records;
+    std::vector<int64_t> members((size_t)n, 0), set_pos((size_t)n, 0);
+    for (int64_t t = 0; t < n; ++t) {
+        if (set[t] < 0 || set[t] > t || set[set[t]] != set[t])
+            return set_last_error(HELLO_ERR_ARG, "set[%lld] = %d: the record that opened the set, at or before it", (long long)t, set[t]);
+        if (flip[t] > 1) return set_last_error(HELLO_ERR_ARG, "flip[%lld] = %d: 0 or 1", (long long)t, (int)flip[t]);
+        ++members[set[t]];
+    }
+    for (int64_t t = 0; t < n; ++t) set_pos[t] = members[set[t]] >= 2 ? h->rec_start[set[t]] + 1 : 0;
+    h->hp.assign((size_t)h->n_reads, 0);
+    h->ps.assign((size_t)h->n_reads, 0);
+    h->stats[6] = 0.0;
+    bool any = false;
+    for (const PhBatch& b : h->batches) any = any || b.n_slots > 0;
+    if (any) {
+        HS_HIP(hipSetDevice(h->device));
+        DevMem m;
+        PhTagArgs a{};
+        a.set = m.put(set, (size_t)n);
+        a.flip = m.put(flip, (size_t)n);
+        a.set_pos = m.put(set_pos.data(), set_pos.size());
+        Timer timer;
+        for (const PhBatch& b : h->batches) {
+            if (b.n_slots == 0) continue;
+            a.slots = b.slots;
+            a.slot_off = b.slot_off;
+            a.first = b.first;
+            a.n_counted = b.n_counted;
+            a.hp = m.zeros<uint8_t>((size_t)b.n_counted);
+            a.ps = m.zeros<int64_t>((size_t)b.n_counted);
+            timer.start();
+            hipLaunchKernelGGL(phase_tag_kernel, dim3(blocks_for(b.n_counted, kPhThreads)), dim3(kPhThreads), 0, 0, a);
+            h->stats[6] += timer.stop();
+            std::vector<uint8_t> hp((size_t)b.n_counted);
+            std::vector<int64_t> ps((size_t)b.n_counted);
+            HS_HIP(hipMemcpy(hp.data(), a.hp, hp.size(), hipMemcpyDeviceToHost));
+            HS_HIP(hipMemcpy(ps.data(), a.ps, ps.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
+            for (int64_t k = 0; k < b.n_counted; ++k) {
+                h->hp[(size_t)(b.read_base + b.reads[k])] = hp[k];
+                h->ps[(size_t)(b.read_base + b.reads[k])] = ps[k];
+            }
+        }
+    }
+    h->stats[8] += std::chrono::duration<double, std::milli>(clock::now() - t0).count();
+    return HELLO_OK;
+} catch (const hello::Fail& f) {
+    return hello::set_last_error(f.code, "%s", f.msg.c_str());
+} catch (...) {
+    return hello::exception_status("hello_phase_tag");
+}
+
+int hello_phase_array(const hello_phase* h, int32_t which, const void** data, int64_t* count) {
+    if (!h || !data || !count) return hello::set_last_error(HELLO_ERR_ARG, "NULL pointer");
+    switch (which) {
+        case HELLO_PHASE_SLOTS: *data = h->slots.data(); *count = (int64_t)h->slots.size(); break;
+        case HELLO_PHASE_SLOT_OFFSETS: *data = h->slot_offsets.data(); *count = (int64_t)h->slot_offsets.size(); break;
+        case HELLO_PHASE_FIRST: *data = h->first.data(); *count = (int64_t)h->first.size(); break;
+        case HELLO_PHASE_LINKS: *data = h->links.data(); *count = (int64_t)h->links.size(); break;
+        case HELLO_PHASE_HP: *data = h->hp.data(); *count = (int64_t)h->hp.size(); break;
+        case HELLO_PHASE_PS: *data = h->ps.data(); *count = (int64_t)h->ps.size(); break;
+        default: return hello::set_last_error(HELLO_ERR_ARG, "array selector %d", which);
+    }
+    return HELLO_OK;
+}
+
+int hello_phase_stats(const hello_phase* h, double* stats) {
+    if (!h || !stats) return hello::set_last_error(HELLO_ERR_ARG, "NULL pointer");
+    std::copy(h->stats, h->stats + HELLO_PHASE_STATS, stats);
+    return HELLO_OK;
+}
+
+void hello_phase_free(hello_phase* h) {
+    if (h) (void)hipSetDevice(h->device);
+    delete h;
+}
+
+}  // extern "C"

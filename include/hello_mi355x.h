@@ -765,6 +765,48 @@ int hello_refblocks_array(const hello_refblocks* blocks, int32_t which, const vo
 int hello_refblocks_stats(const hello_refblocks* blocks, double* stats);
 void hello_refblocks_free(hello_refblocks* blocks);
 
+/* Read-backed phasing of heterozygous records (not in the reference; DESIGN.md section 7g states the rules, hello_amd/phase.py
+ * restates them in Python).  One handle per chromosome.
+ *   hello_phase_observe: with *handle NULL it creates the handle from the chromosome's phasable records -- record_starts /
+ *          record_ends [n_records] (the span [POS - 1, POS - 1 + len(REF)), sorted by start), and `alleles` with allele_offsets
+ *          [2 n_records + 1]: allele a then allele b of every record, upper case -- and adds the reads given; with *handle set it
+ *          adds a further batch of reads (one span of the chromosome) to it, and the record arguments are not read again.
+ *          reads: the arrays of hello_bam_fetch, `source` 0 / 1; a read counts by the rule of hello_refblocks_find, and a counted
+ *          read whose CIGAR consumes more bases than it has, or records that are not sorted, are refused (HELLO_ERR_ARG).
+ *          Per counted read one int8 slot (-1 none, 0 allele a, 1 allele b) per record whose start it covers (observe kernel),
+ *          and link[t][k - 1][0 cis | 1 trans], k = 1..window, counted over the slots of every read (link kernel, integer atomics).
+ *   hello_phase_chain: host only, opens no GPU.  link int32 [n_records][window][2], chromosome int32 [n_records] (records of
+ *          another chromosome are not linked) -> set [n_records] (the index of the record that opened the set of t) and flip.
+ *   hello_phase_tag: with the chained set / flip of the handle's records, hp (1, 2, or 0) and ps (the POS of the read's phase set,
+ *          or 0) of every read given to hello_phase_observe, in the order given (tag kernel over the slots kept on the device).
+ * Host memory in and out; phase.hip. */
+#define HELLO_PHASE_MAX_WINDOW 32
+#define HELLO_PHASE_STATS 9
+enum {
+    HELLO_PHASE_SLOTS = 0,         /* int8 [slots] */
+    HELLO_PHASE_SLOT_OFFSETS = 1,  /* int64 [reads + 1]: an uncounted read has no slot */
+    HELLO_PHASE_FIRST = 2,         /* int64 [reads]: the record of the read's first slot */
+    HELLO_PHASE_LINKS = 3,         /* int32 [n_records][window][2], summed over the batches */
+    HELLO_PHASE_HP = 4,            /* uint8 [reads], after hello_phase_tag */
+    HELLO_PHASE_PS = 5             /* int64 [reads], after hello_phase_tag */
+};
+typedef struct hello_phase hello_phase;
+int hello_phase_observe(const uint8_t* bases, const uint8_t* quals, const int64_t* read_offsets, const uint32_t* cigars,
+                        const int64_t* cigar_offsets, const int64_t* ref_starts, const int64_t* ref_ends, const uint8_t* mapq,
+                        const uint16_t* flags, const uint64_t* name_hash, const uint8_t* source, int64_t n_reads,
+                        const int64_t* record_starts, const int64_t* record_ends, const uint8_t* alleles,
+                        const int64_t* allele_offsets, int64_t n_records, int32_t q_threshold, int32_t mapq_threshold,
+                        int32_t window, int32_t device, hello_phase** handle);
+int hello_phase_chain(const int32_t* link, const int32_t* chromosome, int64_t n_records, int32_t window, int32_t min_margin,
+                      int32_t* set, uint8_t* flip);
+int hello_phase_tag(hello_phase* phase, const int32_t* set, const uint8_t* flip);
+/* a pointer into `phase` (valid until the next hello_phase_* call on it) and its element count */
+int hello_phase_array(const hello_phase* phase, int32_t which, const void** data, int64_t* count);
+/* stats[HELLO_PHASE_STATS]: records, reads given, reads counted, slots, observe / link / tag kernel ms (HIP events), plan ms,
+ * total ms of the calls */
+int hello_phase_stats(const hello_phase* phase, double* stats);
+void hello_phase_free(hello_phase* phase);
+
 #ifdef __cplusplus
 }
 #endif
