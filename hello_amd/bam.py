@@ -12,7 +12,7 @@ from typing import List, Optional, Tuple
 
 import numpy as np
 
-from .engine import load_library
+from ._abi import ARRAY_GETTER, bind, check as _check, handle_array, i32, i64, vp
 
 _ARRAYS = (  # (field, hello_bam_* selector, dtype)
     ("bases", 0, np.uint8), ("quals", 1, np.uint8), ("read_offsets", 2, np.int64), ("cigars", 3, np.uint32),
@@ -20,31 +20,20 @@ _ARRAYS = (  # (field, hello_bam_* selector, dtype)
     ("flags", 8, np.uint16), ("name_hash", 9, np.uint64), ("strand", 10, np.uint8), ("hp", 11, np.uint8),
 )
 
-_bound = None
+_PROTOTYPES = (
+    ("hello_bam_open", [C.c_char_p, i32, C.POINTER(vp)]),
+    ("hello_bam_n_references", [vp]),
+    ("hello_bam_reference", [vp, i32, C.POINTER(C.c_char_p), C.POINTER(i64)]),
+    ("hello_bam_fetch", [vp, C.c_char_p, i64, i64, i32, C.POINTER(vp)]),
+    ("hello_bam_reads_info", [vp, C.POINTER(i64), C.POINTER(i32), C.POINTER(i64)]),
+    ("hello_bam_reads_array", ARRAY_GETTER),
+    ("hello_bam_reads_free", [vp], None),
+    ("hello_bam_close", [vp], None),
+)
 
 
 def _lib():
-    global _bound
-    if _bound is None:
-        lib = load_library()
-        vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
-        lib.hello_bam_open.argtypes = [C.c_char_p, i32, C.POINTER(vp)]
-        lib.hello_bam_n_references.argtypes = [vp]
-        lib.hello_bam_reference.argtypes = [vp, i32, C.POINTER(C.c_char_p), C.POINTER(i64)]
-        lib.hello_bam_fetch.argtypes = [vp, C.c_char_p, i64, i64, i32, C.POINTER(vp)]
-        lib.hello_bam_reads_info.argtypes = [vp, C.POINTER(i64), C.POINTER(i32), C.POINTER(i64)]
-        lib.hello_bam_reads_array.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(i64)]
-        lib.hello_bam_reads_free.argtypes = [vp]
-        lib.hello_bam_reads_free.restype = None
-        lib.hello_bam_close.argtypes = [vp]
-        lib.hello_bam_close.restype = None
-        _bound = lib
-    return _bound
-
-
-def _check(rc: int) -> None:
-    if rc != 0:
-        raise RuntimeError(_lib().hello_last_error().decode(errors="replace"))
+    return bind(_PROTOTYPES)
 
 
 @dataclass
@@ -68,6 +57,11 @@ class Reads:
     @property
     def n_reads(self) -> int:
         return int(self.ref_starts.shape[0])
+
+    def pointers(self, extra: np.ndarray) -> List[int]:
+        """The eleven leading arguments of an entry point that takes a read set: the ten arrays, then ``extra`` (hp or source)."""
+        return [a.ctypes.data for a in (self.bases, self.quals, self.read_offsets, self.cigars, self.cigar_offsets, self.ref_starts,
+                                        self.ref_ends, self.mapq, self.flags, self.name_hash, extra)]
 
     def read(self, i: int) -> Tuple[str, List[Tuple[int, int]], np.ndarray]:
         """(bases, [(op, length)], qualities) of read i."""
@@ -116,16 +110,7 @@ class BamFile:
         try:
             n, used, blocks = C.c_int64(), C.c_int32(), C.c_int64()
             _check(self._lib.hello_bam_reads_info(r, C.byref(n), C.byref(used), C.byref(blocks)))
-            out = {}
-            for field, which, dtype in _ARRAYS:
-                ptr, count = C.c_void_p(), C.c_int64()
-                _check(self._lib.hello_bam_reads_array(r, which, C.byref(ptr), C.byref(count)))
-                k = int(count.value)
-                if k == 0:
-                    out[field] = np.zeros(0, dtype)
-                else:
-                    buf = (C.c_char * (k * np.dtype(dtype).itemsize)).from_address(ptr.value)
-                    out[field] = np.frombuffer(buf, dtype=dtype).copy()
+            out = {field: handle_array(self._lib.hello_bam_reads_array, r, which, dtype) for field, which, dtype in _ARRAYS}
             return Reads(**out, used_index=bool(used.value), n_blocks=int(blocks.value))
         finally:
             self._lib.hello_bam_reads_free(r)

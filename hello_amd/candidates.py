@@ -26,7 +26,7 @@ import numpy as np
 
 from . import shards
 from .bam import BamFile, Reads
-from .engine import load_library
+from ._abi import ARRAY_GETTER, READS, STATS_GETTER, bind, check, handle_array, handle_stats, i32, i64, vp
 
 DEFAULT_Q_THRESHOLD = 10
 DEFAULT_MIN_MAPQ = 10
@@ -49,21 +49,16 @@ REFUSAL = ("candidate sites are built from one Illumina BAM: two BAMs and --hybr
            "hello_amd does not have; one PacBio BAM goes through hello_amd.pacbio (python -m hello_amd.pacbio)")
 
 _log = logging.getLogger(__name__)
-_bound = None
+_PROTOTYPES = (
+    ("hello_candidates_find", READS + [i64, vp, i64, vp, i64, i32, i32, i32, i32, i32, C.POINTER(vp)]),
+    ("hello_candidates_array", ARRAY_GETTER),
+    ("hello_candidates_stats", STATS_GETTER),
+    ("hello_candidates_free", [vp], None),
+)
 
 
 def _lib():
-    global _bound
-    if _bound is None:
-        lib = load_library()
-        vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
-        lib.hello_candidates_find.argtypes = [vp] * 11 + [i64, vp, i64, vp, i64, i32, i32, i32, i32, i32, C.POINTER(vp)]
-        lib.hello_candidates_array.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(i64)]
-        lib.hello_candidates_stats.argtypes = [vp, C.POINTER(C.c_double)]
-        lib.hello_candidates_free.argtypes = [vp]
-        lib.hello_candidates_free.restype = None
-        _bound = lib
-    return _bound
+    return bind(_PROTOTYPES)
 
 
 def read_positions(path: str) -> Dict[str, List[int]]:
@@ -112,27 +107,15 @@ def find_sites(reads: Reads, reference: str, positions: Sequence[int], chromosom
     pos = np.ascontiguousarray(positions, dtype=np.int64)
     lib = _lib()
     h = C.c_void_p()
-    ptr = lambda a: a.ctypes.data  # noqa: E731
-    r = reads
-    rc = lib.hello_candidates_find(ptr(r.bases), ptr(r.quals), ptr(r.read_offsets), ptr(r.cigars), ptr(r.cigar_offsets),
-                                   ptr(r.ref_starts), ptr(r.ref_ends), ptr(r.mapq), ptr(r.flags), ptr(r.name_hash), ptr(r.hp),
-                                   int(r.n_reads), ptr(ref), int(ref.shape[0]), ptr(pos), int(pos.shape[0]),
-                                   int(options) | (rs.HELLO_CANDIDATES_RESIDENT if resident else 0),
-                                   int(feature_length), int(q_threshold), int(mapq_threshold), int(device), C.byref(h))
-    if rc != 0:
-        message = lib.hello_last_error().decode(errors="replace")
-        raise (ValueError if rc == -1 else RuntimeError)(message)
+    check(lib.hello_candidates_find(*reads.pointers(reads.hp), int(reads.n_reads), ref.ctypes.data, int(ref.shape[0]),
+                                    pos.ctypes.data, int(pos.shape[0]),
+                                    int(options) | (rs.HELLO_CANDIDATES_RESIDENT if resident else 0),
+                                    int(feature_length), int(q_threshold), int(mapq_threshold), int(device), C.byref(h)),
+          value_error_on_arg=True)
     keep = False
     try:
-        got = {}
-        for name, which, dtype in _ARRAYS:
-            p, n = C.c_void_p(), C.c_int64()
-            lib.hello_candidates_array(h, which, C.byref(p), C.byref(n))
-            k = int(n.value)
-            got[name] = np.zeros(0, dtype) if k == 0 else np.frombuffer(
-                (C.c_char * (k * np.dtype(dtype).itemsize)).from_address(p.value), dtype).copy()
-        st = (C.c_double * N_STATS)()
-        lib.hello_candidates_stats(h, st)
+        got = {name: handle_array(lib.hello_candidates_array, h, which, dtype) for name, which, dtype in _ARRAYS}
+        st = handle_stats(lib.hello_candidates_stats, h, STAT_NAMES)
         extra = {k: got.pop(k) for k in ("read_index", "regions_pass1", "regions_pass2")}
         got.update(chromosome_table(chromosome, got["start"].shape[0]), has_second=np.array(0))
         if resident:
@@ -144,7 +127,7 @@ def find_sites(reads: Reads, reference: str, positions: Sequence[int], chromosom
     finally:
         if not keep:
             lib.hello_candidates_free(h)
-    return shard, dict(zip(STAT_NAMES, list(st))), extra
+    return shard, st, extra
 
 
 def chromosome_table(chromosome: str, n_sites: int) -> Dict[str, np.ndarray]:

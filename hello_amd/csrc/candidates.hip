@@ -37,22 +37,13 @@
 // Resident (HELLO_CANDIDATES_RESIDENT): the host gather is skipped; the result keeps the pass-2 reads and a gather table per
 // technology on the device (keep_resident), and hello_candidates_gather has gather_reads_kernel write the featurizer's per-read
 // arrays straight into the scoring loop's launch block.
-#include <algorithm>
 #include <chrono>
 #include <memory>
 #include <thread>
 #include <unordered_set>
-#include <vector>
 
-#include <hip/hip_runtime.h>
-
-#include "../../include/hello_mi355x.h"
 #include "differing.h"
-
-namespace hello {
-int set_last_error(int code, const char* fmt, ...);      // engine.hip
-int exception_status(const char* where) noexcept;         // engine.hip
-}  // namespace hello
+#include "stage_host.h"
 
 namespace hello {
 namespace {
@@ -525,35 +516,6 @@ __global__ __launch_bounds__(64) void reassemble_kernel(ReassemblyArgs q) {
     }
 }
 
-struct KernelTimer {               // HIP events around a launch on the default stream; destroyed on every path
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    KernelTimer() = default;
-    void start() {
-        HS_HIP(hipEventCreate(&e0));
-        HS_HIP(hipEventCreate(&e1));
-        HS_HIP(hipEventRecord(e0, 0));
-    }
-    float stop() {
-        float ms = 0.0f;
-        HS_HIP(hipEventRecord(e1, 0));
-        HS_HIP(hipEventSynchronize(e1));
-        HS_HIP(hipEventElapsedTime(&ms, e0, e1));
-        return ms;
-    }
-    ~KernelTimer() {
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-    }
-    KernelTimer(const KernelTimer&) = delete;
-    KernelTimer& operator=(const KernelTimer&) = delete;
-};
-
-struct ReadsIn {
-    const uint8_t* bases; const uint8_t* quals; const int64_t* read_off; const uint32_t* cigars; const int64_t* cigar_off;
-    const int64_t* ref_start; const int64_t* ref_end; const uint8_t* mapq; const uint16_t* flags; const uint64_t* name_hash;
-    int64_t n;
-};
-
 struct Job {                       // one searcher: an active region (pass 1) or a cluster (pass 2)
     int64_t start, stop;           // the searcher's region
     int64_t fetch_lo, fetch_hi;    // the reads fetched for it
@@ -565,17 +527,11 @@ struct Job {                       // one searcher: an active region (pass 1) or
 struct JobStats { int64_t empty = 0, bounds = 0, capped = 0, counted = 0, tiles = 0, events = 0, clipped = 0; float ms = 0, clip_ms = 0; };
 
 // The reads every stage after the selection sees: the input reads themselves, or the clipped copies of one pass (PacBio).
-struct ReadSet {
-    const uint8_t* bases = nullptr; const uint8_t* quals = nullptr; const int64_t* read_off = nullptr;
-    const uint32_t* cigars = nullptr; const int64_t* cigar_off = nullptr; const int64_t* ref_start = nullptr;
-    const int64_t* ref_end = nullptr; const uint8_t* mapq = nullptr;
+// The view is the set's host arrays (`flags` only on input reads), the layout what strict_walk found in them.
+struct ReadSet : ReadsView, ReadLayout {
     const int64_t* origin = nullptr;          // the input read of every read; nullptr: these are the input reads
-    int64_t n = 0;
-    std::vector<int64_t> plant_off, plant, last_pos;    // planting positions of the I/D operations; last M/D position or -1
-    std::vector<uint8_t> pflags;                        // 1 partial_start, 2 partial_stop (Read.cpp:42-49)
     // on the device
-    const uint8_t* d_bases = nullptr; const uint8_t* d_quals = nullptr; const int64_t* d_read_off = nullptr;
-    const uint32_t* d_cigars = nullptr; const int64_t* d_cigar_off = nullptr; const int64_t* d_ref_start = nullptr;
+    DeviceReads d;
     const int64_t* d_ref_end = nullptr; const uint8_t* d_table = nullptr;
     DevMem mem;
     // storage of a derived set
@@ -584,66 +540,6 @@ struct ReadSet {
     std::vector<uint32_t> v_cigars;
     int64_t input(int64_t r) const { return origin ? origin[r] : r; }
 };
-
-inline bool is_query_op(int op) { return op == 0 || op == 1 || op == 4 || op == 7 || op == 8; }
-inline bool is_ref_op(int op) { return op == 0 || op == 2 || op == 3 || op == 7 || op == 8; }
-
-// Validation of every usable read (the kernels read within its bases), its planting positions, and what Read::_get_read_mapping
-// knows about it as a whole: last_position, partial_start, partial_stop.  `flags` == nullptr: every read is used (a derived
-// set).  `clip_input`: the reads are about to be clipped -- the refusal of a soft clip between aligned operations waits for the
-// clipped CIGARs, and what the clip kernels rely on is checked instead.  -> the longest reference span.
-int64_t describe_reads(ReadSet& s, const uint16_t* flags, bool clip_input) {
-    int64_t max_span = 0;
-    s.plant_off.assign((size_t)s.n + 1, 0);
-    s.plant.clear();
-    s.last_pos.assign((size_t)s.n, -1);
-    s.pflags.assign((size_t)s.n, 0);
-    for (int64_t r = 0; r < s.n; ++r) {
-        s.plant_off[r + 1] = s.plant_off[r];
-        if (flags && r > 0 && s.ref_start[r] < s.ref_start[r - 1])
-            raise(HELLO_ERR_ARG, "read %lld: reads are not coordinate-sorted (the BAM must be)", (long long)r);
-        if (s.read_off[r + 1] < s.read_off[r] || s.cigar_off[r + 1] < s.cigar_off[r])
-            raise(HELLO_ERR_SHAPE, "read %lld: offsets decrease", (long long)r);
-        if (flags && !usable(flags[r], s.mapq[r])) continue;
-        int64_t qlen = 0, rlen = 0;
-        const int64_t c0 = s.cigar_off[r], c1 = s.cigar_off[r + 1];
-        bool prev = false, aligned = false;
-        for (int64_t c = c0; c < c1; ++c) {
-            const int op = s.cigars[c] & 15;
-            const int64_t len = s.cigars[c] >> 4;
-            if (op > 8) raise(HELLO_ERR_ARG, "read %lld: CIGAR operation %d", (long long)r, op);
-            if (len == 0) raise(HELLO_ERR_ARG, "read %lld: zero-length CIGAR operation", (long long)r);
-            if (op == 1 || op == 2) s.plant.push_back(s.ref_start[r] + rlen - 1);
-            if (is_query_op(op)) qlen += len;
-            if (is_ref_op(op)) rlen += len;
-            if (op == 0 || op == 2 || op == 7 || op == 8) { s.last_pos[r] = s.ref_start[r] + rlen - 1; prev = true; aligned = true; }
-            else if (op == 3) prev = false;
-            else if (op == 1) {
-                if (!prev) s.pflags[r] |= 1;
-                else if (c == c1 - 1) s.pflags[r] |= 2;
-                prev = true;
-                aligned = true;
-            } else if (op == 4 && aligned && !clip_input) {        // a clip inside the alignment would split a region's read bytes
-                for (int64_t k = c + 1; k < c1; ++k)
-                    if ((s.cigars[k] & 15) != 4 && (s.cigars[k] & 15) != 5)
-                        raise(HELLO_ERR_ARG, "read %lld: a soft clip between aligned operations", (long long)s.input(r));
-            }
-        }
-        s.plant_off[r + 1] = (int64_t)s.plant.size();
-        if (clip_input && rlen == 0) raise(HELLO_ERR_ARG, "read %lld: no CIGAR operation on the reference", (long long)r);
-        if (qlen != s.read_off[r + 1] - s.read_off[r])
-            raise(HELLO_ERR_SHAPE, "read %lld: CIGAR query length %lld, %lld bases", (long long)r, (long long)qlen,
-                  (long long)(s.read_off[r + 1] - s.read_off[r]));
-        if (s.ref_start[r] < 0 || s.ref_end[r] != s.ref_start[r] + std::max<int64_t>(rlen, 1))
-            raise(HELLO_ERR_SHAPE, "read %lld: ref_end does not match its CIGAR", (long long)r);
-        if (flags)
-            for (int64_t i = s.read_off[r]; i < s.read_off[r + 1]; ++i)
-                if (!strchr("=ACMGRSVTWYHKDBN", s.bases[i]) || !s.bases[i])
-                    raise(HELLO_ERR_ARG, "read %lld: base '%c' is not a BAM base code", (long long)r, s.bases[i]);
-        max_span = std::max(max_span, s.ref_end[r] - s.ref_start[r]);
-    }
-    return max_span;
-}
 
 // ---- strict clipping (python/PileupContainerLite.py: strictClipFn :255-363, strictClipRead :366-468, __get_reads :554-573)
 //
@@ -822,7 +718,7 @@ __global__ __launch_bounds__(256) void clip_write_kernel(ClipArgs a) {
 
 // The kept reads of every job (PileupContainerLite.__get_reads :526-570 under the cap of ReadSampler.__call__,
 // PileupDataTools.py:139-146), on the original alignments.
-void select_reads(std::vector<Job>& jobs, const ReadsIn& in, int64_t max_span, bool pacbio, JobStats& st) {
+void select_reads(std::vector<Job>& jobs, const ReadsView& in, int64_t max_span, bool pacbio, JobStats& st) {
     std::unordered_set<std::pair<uint64_t, int>, PairHash> seen;
     for (Job& job : jobs) {
         const int64_t span = job.fetch_hi - job.fetch_lo;
@@ -842,7 +738,7 @@ void select_reads(std::vector<Job>& jobs, const ReadsIn& in, int64_t max_span, b
 }
 
 // PacBio: the clipped copy of every (job, kept read) pair as the reads of `out`; job.reads become indices into it.
-void clip_reads(std::vector<Job>& jobs, const ReadsIn& in, const ReadSet& input, ReadSet& out, JobStats& st) {
+void clip_reads(std::vector<Job>& jobs, const ReadsView& in, const ReadSet& input, ReadSet& out, JobStats& st) {
     std::vector<int64_t> pair_read, pair_lo, pair_hi;
     for (Job& job : jobs)
         for (int64_t& r : job.reads) {
@@ -862,8 +758,8 @@ void clip_reads(std::vector<Job>& jobs, const ReadsIn& in, const ReadSet& input,
     if (n > 0) {
         DevMem m;
         ClipArgs c{};
-        c.bases = input.d_bases; c.quals = input.d_quals; c.read_off = input.d_read_off; c.cigars = input.d_cigars;
-        c.cigar_off = input.d_cigar_off; c.ref_start = input.d_ref_start; c.ref_end = input.d_ref_end;
+        c.bases = input.d.bases; c.quals = input.d.quals; c.read_off = input.d.read_off; c.cigars = input.d.cigars;
+        c.cigar_off = input.d.cigar_off; c.ref_start = input.d.ref_start; c.ref_end = input.d_ref_end;
         c.pair_read = m.put(pair_read.data(), pair_read.size());
         c.pair_lo = m.put(pair_lo.data(), pair_lo.size());
         c.pair_hi = m.put(pair_hi.data(), pair_hi.size());
@@ -871,11 +767,10 @@ void clip_reads(std::vector<Job>& jobs, const ReadsIn& in, const ReadSet& input,
         c.flank = kClipFlank;
         c.rec = m.zeros<ClipRec>((size_t)n);
         const dim3 grid((unsigned)((n + 3) / 4));
-        KernelTimer t1;
-        t1.start();
+        KernelTimer timer;
+        timer.start();
         hipLaunchKernelGGL(clip_plan_kernel, grid, dim3(256), 0, 0, c);
-        HS_HIP(hipGetLastError());
-        st.clip_ms = t1.stop();
+        st.clip_ms = timer.stop();
         std::vector<ClipRec> rec((size_t)n);
         HS_HIP(hipMemcpy(rec.data(), c.rec, rec.size() * sizeof(ClipRec), hipMemcpyDeviceToHost));
         for (int64_t p = 0; p < n; ++p) {                      // the second launch writes within these: checked before it runs
@@ -893,23 +788,21 @@ void clip_reads(std::vector<Job>& jobs, const ReadsIn& in, const ReadSet& input,
             st.clipped += o.clipped ? 1 : 0;
         }
         const size_t nb = (size_t)out.v_read_off[n], nc = (size_t)out.v_cigar_off[n];
-        out.d_read_off = c.out_read_off = out.mem.put(out.v_read_off.data(), out.v_read_off.size());
-        out.d_cigar_off = c.out_cigar_off = out.mem.put(out.v_cigar_off.data(), out.v_cigar_off.size());
-        out.d_bases = c.out_bases = out.mem.zeros<uint8_t>(nb);
-        out.d_quals = c.out_quals = out.mem.zeros<uint8_t>(nb);
-        out.d_cigars = c.out_cigars = out.mem.zeros<uint32_t>(nc);
-        KernelTimer t2;
-        t2.start();
+        out.d.read_off = c.out_read_off = out.mem.put(out.v_read_off.data(), out.v_read_off.size());
+        out.d.cigar_off = c.out_cigar_off = out.mem.put(out.v_cigar_off.data(), out.v_cigar_off.size());
+        out.d.bases = c.out_bases = out.mem.zeros<uint8_t>(nb);
+        out.d.quals = c.out_quals = out.mem.zeros<uint8_t>(nb);
+        out.d.cigars = c.out_cigars = out.mem.zeros<uint32_t>(nc);
+        timer.start();
         hipLaunchKernelGGL(clip_write_kernel, grid, dim3(256), 0, 0, c);
-        HS_HIP(hipGetLastError());
-        st.clip_ms += t2.stop();
+        st.clip_ms += timer.stop();
         out.v_bases.resize(nb);
         out.v_quals.resize(nb);
         out.v_cigars.resize(nc);
         if (nb) HS_HIP(hipMemcpy(out.v_bases.data(), c.out_bases, nb, hipMemcpyDeviceToHost));
         if (nb) HS_HIP(hipMemcpy(out.v_quals.data(), c.out_quals, nb, hipMemcpyDeviceToHost));
         if (nc) HS_HIP(hipMemcpy(out.v_cigars.data(), c.out_cigars, nc * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        out.d_ref_start = out.mem.put(out.v_ref_start.data(), out.v_ref_start.size());
+        out.d.ref_start = out.mem.put(out.v_ref_start.data(), out.v_ref_start.size());
         out.d_ref_end = out.mem.put(out.v_ref_end.data(), out.v_ref_end.size());
         const std::vector<uint8_t> table((size_t)n, 1);             // every read counts in the PacBio table, increment 1
         out.d_table = out.mem.put(table.data(), table.size());
@@ -917,7 +810,7 @@ void clip_reads(std::vector<Job>& jobs, const ReadsIn& in, const ReadSet& input,
     out.bases = out.v_bases.data(); out.quals = out.v_quals.data(); out.read_off = out.v_read_off.data();
     out.cigars = out.v_cigars.data(); out.cigar_off = out.v_cigar_off.data(); out.ref_start = out.v_ref_start.data();
     out.ref_end = out.v_ref_end.data(); out.mapq = out.v_mapq.data(); out.origin = out.v_origin.data();
-    describe_reads(out, nullptr, false);
+    strict_walk(out, kStrictRegions, out, out.origin);
 }
 
 // The window and differing regions of every job with reads (AlleleSearcherLite.__init__ + determineDifferingRegions(strict = True)).
@@ -928,8 +821,8 @@ void differing_regions(std::vector<Job>& jobs, const ReadSet& in, int64_t refere
     std::vector<int64_t> flo, fhi, bit_base, creads_off{0}, creads, tile_lo, tile_ev_off{0};
     std::vector<int32_t> tile_chunk, chunk_job;
     int64_t bits = 0;
-    a.bases = in.d_bases; a.quals = in.d_quals; a.read_off = in.d_read_off; a.cigars = in.d_cigars; a.cigar_off = in.d_cigar_off;
-    a.ref_start = in.d_ref_start; a.ref_end = in.d_ref_end; a.table = in.d_table;
+    a.bases = in.d.bases; a.quals = in.d.quals; a.read_off = in.d.read_off; a.cigars = in.d.cigars; a.cigar_off = in.d.cigar_off;
+    a.ref_start = in.d.ref_start; a.ref_end = in.d_ref_end; a.table = in.d_table;
     for (size_t j = 0; j < jobs.size(); ++j) {
         Job& job = jobs[j];
         const bool capped = job.capped;
@@ -991,7 +884,6 @@ void differing_regions(std::vector<Job>& jobs, const ReadSet& in, int64_t refere
         KernelTimer timer;
         timer.start();
         hipLaunchKernelGGL(hotspot_kernel, dim3((unsigned)tile_lo.size()), dim3(256), 0, 0, a);
-        HS_HIP(hipGetLastError());
         st.ms = timer.stop();
     }
     std::vector<unsigned> bitsv((size_t)words);
@@ -1067,17 +959,6 @@ std::vector<Job> cluster_jobs(const std::vector<std::pair<int64_t, int64_t>>& lo
     return jobs2;
 }
 
-void use_device(int device) {
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) raise(HELLO_ERR_NOGPU, "no GPU visible");
-    if (device < 0 || device >= n_dev) raise(HELLO_ERR_ARG, "device %d of %d", device, n_dev);
-    hipDeviceProp_t prop;
-    HS_HIP(hipGetDeviceProperties(&prop, device));
-    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        raise(HELLO_ERR_NOGPU, "device %d is %s; this library is built for gfx950 only", device, prop.gcnArchName);
-    HS_HIP(hipSetDevice(device));
-}
-
 // The allele stage's plan: record slots = reads x the regions they overlap, counted exactly.
 struct AllelePlan {
     std::vector<int64_t> cl_read_off{0}, cl_reads, cl_reg_off{0}, cl_job, reg_start, reg_stop, rd_rec_off{0}, slot_g, slot_x;
@@ -1125,8 +1006,8 @@ struct AllelePlan {
     AlleleArgs upload(DevMem& m, const ReadSet& rs2, const uint8_t* d_ref, int64_t reference_length, int q_threshold,
                       int mapq_threshold) const {
         AlleleArgs b{};
-        b.bases = rs2.d_bases; b.quals = rs2.d_quals; b.read_off = rs2.d_read_off; b.cigars = rs2.d_cigars;
-        b.cigar_off = rs2.d_cigar_off; b.ref_start = rs2.d_ref_start;
+        b.bases = rs2.d.bases; b.quals = rs2.d.quals; b.read_off = rs2.d.read_off; b.cigars = rs2.d.cigars;
+        b.cigar_off = rs2.d.cigar_off; b.ref_start = rs2.d.ref_start;
         b.mapq = m.put(rs2.mapq, (size_t)rs2.n);
         b.last_pos = m.put(rs2.last_pos.data(), rs2.last_pos.size());
         b.pflags = m.put(rs2.pflags.data(), rs2.pflags.size());
@@ -1351,12 +1232,12 @@ void keep_resident(hello_candidates& o, const ReadSet& rs2, int64_t n_first, con
         auto res = std::make_unique<Resident>();
         DevMem& m = res->mem;
         const size_t n = (size_t)rs2.n;
-        res->bases = device_copy(m, rs2.d_bases, (size_t)rs2.read_off[n]);
-        res->quals = device_copy(m, rs2.d_quals, (size_t)rs2.read_off[n]);
-        res->read_off = device_copy(m, rs2.d_read_off, n + 1);
-        res->cigars = device_copy(m, rs2.d_cigars, (size_t)rs2.cigar_off[n]);
-        res->cigar_off = device_copy(m, rs2.d_cigar_off, n + 1);
-        res->ref_start = device_copy(m, rs2.d_ref_start, n);
+        res->bases = device_copy(m, rs2.d.bases, (size_t)rs2.read_off[n]);
+        res->quals = device_copy(m, rs2.d.quals, (size_t)rs2.read_off[n]);
+        res->read_off = device_copy(m, rs2.d.read_off, n + 1);
+        res->cigars = device_copy(m, rs2.d.cigars, (size_t)rs2.cigar_off[n]);
+        res->cigar_off = device_copy(m, rs2.d.cigar_off, n + 1);
+        res->ref_start = device_copy(m, rs2.d.ref_start, n);
         res->mapq = m.put(rs2.mapq, n);
         std::vector<int8_t> orientation(n);
         std::vector<uint8_t> hp(n);
@@ -1427,12 +1308,7 @@ void join_sets(const ReadSet& ill, const ReadSet& clipped, ReadSet& out) {
     out.ref_end = out.v_ref_end.data(); out.mapq = out.v_mapq.data(); out.origin = out.v_origin.data();
     std::vector<uint8_t> table((size_t)(ni + np), 0);
     std::fill(table.begin() + ni, table.end(), (uint8_t)1);
-    out.d_bases = out.mem.put(out.bases, out.v_bases.size());
-    out.d_quals = out.mem.put(out.quals, out.v_quals.size());
-    out.d_read_off = out.mem.put(out.read_off, out.v_read_off.size());
-    out.d_cigars = out.mem.put(out.cigars, out.v_cigars.size());
-    out.d_cigar_off = out.mem.put(out.cigar_off, out.v_cigar_off.size());
-    out.d_ref_start = out.mem.put(out.ref_start, out.v_ref_start.size());
+    out.d = upload_reads(out.mem, out);
     out.d_ref_end = out.mem.put(out.ref_end, out.v_ref_end.size());
     out.d_table = out.mem.put(table.data(), table.size());
 }
@@ -1440,10 +1316,10 @@ void join_sets(const ReadSet& ill, const ReadSet& clipped, ReadSet& out) {
 // The coverage gate of a cluster (python/AlleleSearcherLite.py:264-266: container 0's average_coverage > 14; DESIGN.md "Two
 // BAMs" defines the rule): over the Illumina reads that overlap [lo, hi) and are mapped, primary, not QC-fail, not duplicate and
 // a proper pair if paired -- before de-duplication and the cap -- sum of counts > 14 * columns.
-bool coverage_gate(const ReadsIn& in, int64_t max_span, int64_t lo, int64_t hi) {
+bool coverage_gate(const ReadsView& in, int64_t max_span, int64_t lo, int64_t hi) {
     const int64_t* begin = in.ref_start;
     const int64_t first = std::lower_bound(begin, begin + in.n, lo - max_span) - begin;
-    // first walk: the reads that count, checked once (they include reads the searchers skip and describe_reads did not look
+    // first walk: the reads that count, checked once (they include reads the searchers skip and strict_walk did not look
     // at), and the span of their columns
     std::vector<int64_t> counted;
     int64_t c_lo = INT64_MAX, c_hi = INT64_MIN;
@@ -1522,11 +1398,11 @@ int hello_candidates_find(const uint8_t* bases, const uint8_t* quals, const int6
     for (int64_t i = 1; i < n_positions; ++i)
         if (positions[i] < positions[i - 1]) return set_last_error(HELLO_ERR_ARG, "position %lld: positions are not sorted", (long long)i);
 
-    ReadSet input;                                     // describe_reads: validation, planting positions, last_position, partials
-    input.bases = bases; input.quals = quals; input.read_off = read_offsets; input.cigars = cigars; input.cigar_off = cigar_offsets;
-    input.ref_start = ref_starts; input.ref_end = ref_ends; input.mapq = mapq; input.n = n_reads;
-    const int64_t max_span = describe_reads(input, flags, pacbio);
-    const ReadsIn in{bases, quals, read_offsets, cigars, cigar_offsets, ref_starts, ref_ends, mapq, flags, name_hash, n_reads};
+    const ReadsView in{bases, quals, read_offsets, cigars, cigar_offsets, ref_starts, ref_ends, mapq, flags, name_hash, n_reads};
+    ReadSet input;                                     // strict_walk: validation, planting positions, last_position, partials
+    static_cast<ReadsView&>(input) = in;
+    strict_walk(in, pacbio ? kStrictClipInput : kStrictRegions, input);
+    const int64_t max_span = input.max_span[0];
 
     std::vector<Job> jobs1 = active_region_jobs(positions, n_positions);
     auto res = std::make_unique<hello_candidates>();
@@ -1537,17 +1413,11 @@ int hello_candidates_find(const uint8_t* bases, const uint8_t* quals, const int6
     int64_t n_slots = 0, n_clusters = 0, sites_oob = 0;
     if (n_reads == 0) st1.empty = (int64_t)jobs1.size();
     if (!jobs1.empty() && n_reads > 0) {
-        use_device(device);
+        open_device(device);
         DevMem m;
         HotspotArgs a{};
-        const int64_t nb = read_offsets[n_reads], nc = cigar_offsets[n_reads];
         std::vector<uint8_t> table(n_reads, 0);                      // every read counts in the Illumina table
-        input.d_bases = m.put(bases, (size_t)nb);
-        input.d_quals = m.put(quals, (size_t)nb);
-        input.d_read_off = m.put(read_offsets, (size_t)n_reads + 1);
-        input.d_cigars = m.put(cigars, (size_t)nc);
-        input.d_cigar_off = m.put(cigar_offsets, (size_t)n_reads + 1);
-        input.d_ref_start = m.put(ref_starts, (size_t)n_reads);
+        input.d = upload_reads(m, in);
         input.d_ref_end = m.put(ref_ends, (size_t)n_reads);
         input.d_table = m.put(table.data(), table.size());
         ReadSet clipped1, clipped2;                                  // PacBio: the clipped reads of pass 1 and of pass 2
@@ -1579,7 +1449,6 @@ int hello_candidates_find(const uint8_t* bases, const uint8_t* quals, const int6
                 KernelTimer timer;
                 timer.start();
                 hipLaunchKernelGGL(allele_kernel, dim3((unsigned)plan.n_cl), dim3(256), 0, 0, b);
-                HS_HIP(hipGetLastError());
                 allele_ms = timer.stop();
             }
             got.download(b);
@@ -1604,11 +1473,7 @@ int hello_candidates_find(const uint8_t* bases, const uint8_t* quals, const int6
     std::copy(st, st + HELLO_CANDIDATES_STATS, res->stats);
     *out = res.release();
     return HELLO_OK;
-} catch (const hello::Fail& f) {
-    return hello::set_last_error(f.code, "%s", f.msg.c_str());
-} catch (...) {
-    return hello::exception_status("hello_candidates_find");
-}
+} HS_ENTRY_END("hello_candidates_find")
 
 int hello_candidates_find_hybrid(
     const uint8_t* bases0, const uint8_t* quals0, const int64_t* read_offsets0, const uint32_t* cigars0, const int64_t* cigar_offsets0,
@@ -1638,16 +1503,16 @@ int hello_candidates_find_hybrid(
     for (int64_t i = 1; i < n_positions; ++i)
         if (positions[i] < positions[i - 1]) return set_last_error(HELLO_ERR_ARG, "position %lld: positions are not sorted", (long long)i);
 
+    const ReadsView in0{bases0, quals0, read_offsets0, cigars0, cigar_offsets0, ref_starts0, ref_ends0, mapq0, flags0, name_hash0, n_reads0};
+    const ReadsView in1{bases1, quals1, read_offsets1, cigars1, cigar_offsets1, ref_starts1, ref_ends1, mapq1, flags1, name_hash1, n_reads1};
     ReadSet input0, input1;
-    input0.bases = bases0; input0.quals = quals0; input0.read_off = read_offsets0; input0.cigars = cigars0; input0.cigar_off = cigar_offsets0;
-    input0.ref_start = ref_starts0; input0.ref_end = ref_ends0; input0.mapq = mapq0; input0.n = n_reads0;
-    input1.bases = bases1; input1.quals = quals1; input1.read_off = read_offsets1; input1.cigars = cigars1; input1.cigar_off = cigar_offsets1;
-    input1.ref_start = ref_starts1; input1.ref_end = ref_ends1; input1.mapq = mapq1; input1.n = n_reads1;
-    const int64_t max_span0 = describe_reads(input0, flags0, false), max_span1 = describe_reads(input1, flags1, true);
+    static_cast<ReadsView&>(input0) = in0;
+    static_cast<ReadsView&>(input1) = in1;
+    strict_walk(in0, kStrictRegions, input0);
+    strict_walk(in1, kStrictClipInput, input1);
+    const int64_t max_span0 = input0.max_span[0], max_span1 = input1.max_span[0];
     int64_t max_span_all0 = 0;                         // the coverage gate looks at reads the searchers do not use
     for (int64_t r = 0; r < n_reads0; ++r) max_span_all0 = std::max(max_span_all0, ref_ends0[r] - ref_starts0[r]);
-    const ReadsIn in0{bases0, quals0, read_offsets0, cigars0, cigar_offsets0, ref_starts0, ref_ends0, mapq0, flags0, name_hash0, n_reads0};
-    const ReadsIn in1{bases1, quals1, read_offsets1, cigars1, cigar_offsets1, ref_starts1, ref_ends1, mapq1, flags1, name_hash1, n_reads1};
 
     std::vector<Job> jobs1 = active_region_jobs(positions, n_positions);
     auto res = std::make_unique<hello_candidates>();
@@ -1660,15 +1525,10 @@ int hello_candidates_find_hybrid(
     int64_t gate_passed = 0, reassembled = 0, eligible = 0, reassigned = 0, by_tie = 0, illumina_sites = 0;
     if (n_reads0 + n_reads1 == 0) st1.empty = (int64_t)jobs1.size();
     if (!jobs1.empty() && n_reads0 + n_reads1 > 0) {
-        use_device(device);
+        open_device(device);
         DevMem m;
         HotspotArgs a{};
-        input1.d_bases = m.put(bases1, (size_t)read_offsets1[n_reads1]);          // what the clip kernels read
-        input1.d_quals = m.put(quals1, (size_t)read_offsets1[n_reads1]);
-        input1.d_read_off = m.put(read_offsets1, (size_t)n_reads1 + 1);
-        input1.d_cigars = m.put(cigars1, (size_t)cigar_offsets1[n_reads1]);
-        input1.d_cigar_off = m.put(cigar_offsets1, (size_t)n_reads1 + 1);
-        input1.d_ref_start = m.put(ref_starts1, (size_t)n_reads1);
+        input1.d = upload_reads(m, in1);                                          // what the clip kernels read
         input1.d_ref_end = m.put(ref_ends1, (size_t)n_reads1);
         a.ref_lo = 0;
         a.ref_len = reference_length;
@@ -1724,7 +1584,6 @@ int hello_candidates_find_hybrid(
                 KernelTimer timer;
                 timer.start();
                 hipLaunchKernelGGL(hybrid_records_kernel, dim3((unsigned)plan.n_cl), dim3(256), 0, 0, b);
-                HS_HIP(hipGetLastError());
                 allele_ms = timer.stop();
             }
 
@@ -1783,7 +1642,6 @@ int hello_candidates_find_hybrid(
                 KernelTimer timer;
                 timer.start();
                 hipLaunchKernelGGL(hybrid_alleles_kernel, dim3((unsigned)plan.n_cl), dim3(256), 0, 0, b);
-                HS_HIP(hipGetLastError());
                 allele_ms += timer.stop();
             }
             got.download(b);
@@ -1816,11 +1674,7 @@ int hello_candidates_find_hybrid(
     std::copy(hst, hst + (HELLO_CANDIDATES_HYBRID_STATS - HELLO_CANDIDATES_STATS), res->hybrid_stats);
     *out = res.release();
     return HELLO_OK;
-} catch (const hello::Fail& f) {
-    return hello::set_last_error(f.code, "%s", f.msg.c_str());
-} catch (...) {
-    return hello::exception_status("hello_candidates_find_hybrid");
-}
+} HS_ENTRY_END("hello_candidates_find_hybrid")
 
 int hello_candidates_array(const hello_candidates* c, int32_t which, const void** data, int64_t* count) {
     if (!c || !data || !count) return hello::set_last_error(HELLO_ERR_ARG, "NULL pointer");
@@ -1916,11 +1770,7 @@ int hello_candidates_gather(const hello_candidates* c, int32_t tech, uint8_t* ba
     hipLaunchKernelGGL(gather_reads_kernel, dim3((unsigned)((n_reads + 3) / 4)), dim3(256), 0, (hipStream_t)hip_stream, a);
     HS_HIP(hipGetLastError());
     return HELLO_OK;
-} catch (const hello::Fail& f) {
-    return hello::set_last_error(f.code, "%s", f.msg.c_str());
-} catch (...) {
-    return hello::exception_status("hello_candidates_gather");
-}
+} HS_ENTRY_END("hello_candidates_gather")
 
 int hello_candidates_gather_table(const int32_t* reads_per_allele, int64_t n_alleles, const int64_t* read_off, const int64_t* cigar_off,
                                   int64_t capacity, int64_t* source, int64_t* out_read_off, int64_t* out_cigar_off, int64_t* n_reads) try {
@@ -1939,10 +1789,6 @@ int hello_candidates_gather_table(const int32_t* reads_per_allele, int64_t n_all
     std::copy(t.base_off.begin(), t.base_off.end(), out_read_off);
     std::copy(t.cigar_off.begin(), t.cigar_off.end(), out_cigar_off);
     return HELLO_OK;
-} catch (const hello::Fail& f) {
-    return hello::set_last_error(f.code, "%s", f.msg.c_str());
-} catch (...) {
-    return hello::exception_status("hello_candidates_gather_table");
-}
+} HS_ENTRY_END("hello_candidates_gather_table")
 
 }  // extern "C"

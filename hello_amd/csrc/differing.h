@@ -1,5 +1,5 @@
 // Differing positions of a set of reads against the reference: the counting, partial-resolution and flagging kernel that the
-// hotspot stage (hotspots.hip) and the candidate stage (candidates.hip) share, with the host helpers both need.  A "chunk" is any
+// hotspot stage (hotspots.hip) and the candidate stage (candidates.hip) share; the host layer is stage_host.h.  A "chunk" is any
 // region with its own read list; the kernel keeps the flagged positions of a chunk on [flag_lo, flag_hi) in the chunk's own bits.
 //
 // Device: one workgroup per tile of kTile genome positions.  Its four waves walk the chunk's reads, one read per wave, CIGAR
@@ -11,23 +11,15 @@
 // float32 thresholds of the reference, and sets the flagged positions in a bitmap with atomicOr.  All counts are integers and the
 // bitmap is an OR, so the result does not depend on the order of any atomic: two runs give the same bytes.
 #pragma once
-#include <algorithm>
-#include <cstdarg>
-#include <cstdio>
-#include <cstring>
-#include <string>
-#include <vector>
-
 #include <hip/hip_runtime.h>
 
-#include "../../include/hello_mi355x.h"
+#include "cigar.h"
 
 namespace hello {
 namespace {
 
 constexpr int kTile = 256;                 // genome positions per workgroup
 constexpr int kCodes = 16;                 // BAM read base codes "=ACMGRSVTWYHKDBN"
-constexpr int BAM_CMATCH = 0, BAM_CINS = 1, BAM_CDEL = 2, BAM_CREF_SKIP = 3, BAM_CSOFT_CLIP = 4, BAM_CEQUAL = 7, BAM_CDIFF = 8;
 constexpr int kFull = 0, kLeft = 1, kRight = 2;
 
 struct HsEvent {
@@ -277,54 +269,6 @@ __global__ __launch_bounds__(256) void hotspot_kernel(HotspotArgs a) {
             if (total != 0.0f && (vi + vp) / total >= indel_threshold && vi / 2 + vp >= min_count) flag(p, p + k.ref_len);
         }
     }
-}
-
-struct Fail {
-    int code;
-    std::string msg;
-};
-[[noreturn]] void raise(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    throw Fail{code, buf};
-}
-
-#define HS_HIP(expr)                                                                                       \
-    do {                                                                                                   \
-        hipError_t e_ = (expr);                                                                            \
-        if (e_ != hipSuccess) raise(HELLO_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));         \
-    } while (0)
-
-struct DevMem {
-    std::vector<void*> ptrs;
-    template <class T> T* put(const T* src, size_t n) {
-        void* p = nullptr;
-        HS_HIP(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)));
-        ptrs.push_back(p);
-        if (n) HS_HIP(hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice));
-        return (T*)p;
-    }
-    template <class T> T* zeros(size_t n) {
-        void* p = nullptr;
-        HS_HIP(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)));
-        ptrs.push_back(p);
-        HS_HIP(hipMemset(p, 0, std::max<size_t>(n, 1) * sizeof(T)));
-        return (T*)p;
-    }
-    ~DevMem() { for (void* p : ptrs) (void)hipFree(p); }
-};
-
-struct PairHash {
-    size_t operator()(const std::pair<uint64_t, int>& k) const { return (size_t)(k.first * 0x9E3779B97F4A7C15ull) ^ (size_t)k.second; }
-};
-
-inline bool usable(uint16_t flag, uint8_t mapq) {                  // is_usable_read, python/PileupContainer.py:33-41
-    if (flag & (0x4 | 0x100 | 0x800 | 0x400)) return false;       // unmapped, secondary, supplementary, duplicate
-    if ((flag & 0x1) && !(flag & 0x2)) return false;               // paired but not a proper pair
-    return mapq > 0;                                               // QC-fail reads stay
 }
 
 }  // namespace

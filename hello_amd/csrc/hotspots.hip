@@ -10,25 +10,12 @@
 // kTile genome positions over the span its counted reads touch.  Device: the counting, partial-resolution and flagging kernel of
 // differing.h (shared with candidates.hip), one workgroup per tile; here a chunk's flags are clipped to the chunk and its bits sit
 // at the chunk's offset in one bitmap over the regions' span.
-#include <algorithm>
 #include <chrono>
-#include <cstdarg>
-#include <cstdio>
-#include <cstring>
 #include <memory>
-#include <string>
 #include <unordered_set>
-#include <vector>
 
-#include <hip/hip_runtime.h>
-
-#include "../../include/hello_mi355x.h"
 #include "differing.h"
-
-namespace hello {
-int set_last_error(int code, const char* fmt, ...);      // engine.hip
-int exception_status(const char* where) noexcept;         // engine.hip
-}  // namespace hello
+#include "stage_host.h"
 
 struct hello_hotspots {
     std::vector<int64_t> positions;
@@ -61,41 +48,14 @@ int hello_hotspots_find(const uint8_t* bases, const uint8_t* quals, const int64_
     const uint8_t table_of[2] = {(uint8_t)(pacbio ? 1 : 0), 1};
 
     // ---- validation of every usable read: the kernel reads within its bases and within the reference
+    const ReadsView in{bases, quals, read_offsets, cigars, cigar_offsets, ref_starts, ref_ends, mapq, flags, name_hash, n_reads};
+    ReadLayout layout;                                       // planting positions (pos - 1) of every I/D operation of a usable read
+    strict_walk(in, kStrictPlain, layout, nullptr, source, two ? 2 : 1);
+    const std::vector<int64_t>& plant_off = layout.plant_off;
+    const std::vector<int64_t>& plant = layout.plant;
+    const int64_t* max_span = layout.max_span;
     std::vector<int64_t> order[2];
-    int64_t max_span[2] = {0, 0};
-    std::vector<int64_t> plant_off(n_reads + 1, 0), plant;   // planting positions (pos - 1) of every I/D operation of a usable read
-    for (int64_t r = 0; r < n_reads; ++r) {
-        plant_off[r + 1] = plant_off[r];
-        if (source[r] > (two ? 1 : 0))
-            return set_last_error(HELLO_ERR_ARG, "source[%lld] = %d with %d read set(s)", (long long)r, source[r], two ? 2 : 1);
-        auto& o = order[source[r]];
-        if (!o.empty() && ref_starts[r] < ref_starts[o.back()])
-            return set_last_error(HELLO_ERR_ARG, "read %lld: reads are not coordinate-sorted (the BAM must be)", (long long)r);
-        o.push_back(r);
-        if (read_offsets[r + 1] < read_offsets[r] || cigar_offsets[r + 1] < cigar_offsets[r])
-            return set_last_error(HELLO_ERR_SHAPE, "read %lld: offsets decrease", (long long)r);
-        if (!usable(flags[r], mapq[r])) continue;
-        int64_t qlen = 0, rlen = 0;
-        for (int64_t c = cigar_offsets[r]; c < cigar_offsets[r + 1]; ++c) {
-            const int op = cigars[c] & 15;
-            const int64_t len = cigars[c] >> 4;
-            if (op > 8) return set_last_error(HELLO_ERR_ARG, "read %lld: CIGAR operation %d", (long long)r, op);
-            if (len == 0) return set_last_error(HELLO_ERR_ARG, "read %lld: zero-length CIGAR operation", (long long)r);
-            if (op == 1 || op == 2) plant.push_back(ref_starts[r] + rlen - 1);   // rfcounter - 1 (:221,247)
-            if (op == 0 || op == 1 || op == 4 || op == 7 || op == 8) qlen += len;
-            if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) rlen += len;
-        }
-        plant_off[r + 1] = (int64_t)plant.size();
-        if (qlen != read_offsets[r + 1] - read_offsets[r])
-            return set_last_error(HELLO_ERR_SHAPE, "read %lld: CIGAR query length %lld, %lld bases", (long long)r, (long long)qlen,
-                                  (long long)(read_offsets[r + 1] - read_offsets[r]));
-        if (ref_starts[r] < 0 || ref_ends[r] != ref_starts[r] + std::max<int64_t>(rlen, 1))
-            return set_last_error(HELLO_ERR_SHAPE, "read %lld: ref_end does not match its CIGAR", (long long)r);
-        for (int64_t i = read_offsets[r]; i < read_offsets[r + 1]; ++i)
-            if (!strchr("=ACMGRSVTWYHKDBN", bases[i]) || !bases[i])
-                return set_last_error(HELLO_ERR_ARG, "read %lld: base '%c' is not a BAM base code", (long long)r, bases[i]);
-        max_span[source[r]] = std::max(max_span[source[r]], ref_ends[r] - ref_starts[r]);
-    }
+    for (int64_t r = 0; r < n_reads; ++r) order[source[r]].push_back(r);
 
     // ---- chunk plan
     auto* res = new hello_hotspots();
@@ -171,23 +131,12 @@ int hello_hotspots_find(const uint8_t* bases, const uint8_t* quals, const int64_
     const int64_t n_tiles = (int64_t)tile_lo.size();
     float kernel_ms = 0.0f;
     if (n_tiles > 0) {
-        int n_dev = 0;
-        if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) return set_last_error(HELLO_ERR_NOGPU, "no GPU visible");
-        if (device < 0 || device >= n_dev) return set_last_error(HELLO_ERR_ARG, "device %d of %d", device, n_dev);
-        hipDeviceProp_t prop;
-        HS_HIP(hipGetDeviceProperties(&prop, device));
-        if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-            return set_last_error(HELLO_ERR_NOGPU, "device %d is %s; this library is built for gfx950 only", device, prop.gcnArchName);
-        HS_HIP(hipSetDevice(device));
+        open_device(device);
         DevMem m;
         HotspotArgs a{};
-        const int64_t nb = n_reads ? read_offsets[n_reads] : 0, nc = n_reads ? cigar_offsets[n_reads] : 0;
-        a.bases = m.put(bases, (size_t)nb);
-        a.quals = m.put(quals, (size_t)nb);
-        a.read_off = m.put(read_offsets, (size_t)n_reads + 1);
-        a.cigars = m.put(cigars, (size_t)nc);
-        a.cigar_off = m.put(cigar_offsets, (size_t)n_reads + 1);
-        a.ref_start = m.put(ref_starts, (size_t)n_reads);
+        const DeviceReads d = upload_reads(m, in);
+        a.bases = d.bases; a.quals = d.quals; a.read_off = d.read_off; a.cigars = d.cigars; a.cigar_off = d.cigar_off;
+        a.ref_start = d.ref_start;
         a.ref_end = m.put(ref_ends, (size_t)n_reads);
         a.table = m.put(table.data(), table.size());
         a.chunk_reads = m.put(creads.data(), creads.size());
@@ -208,17 +157,10 @@ int hello_hotspots_find(const uint8_t* bases, const uint8_t* quals, const int64_
         a.bitmap = m.zeros<unsigned>((size_t)words);
         a.q_threshold = q_threshold;
         a.hybrid = hybrid ? 1 : 0;
-        hipEvent_t e0, e1;
-        HS_HIP(hipEventCreate(&e0));
-        HS_HIP(hipEventCreate(&e1));
-        HS_HIP(hipEventRecord(e0, 0));
+        KernelTimer timer;
+        timer.start();
         hipLaunchKernelGGL(hotspot_kernel, dim3((unsigned)n_tiles), dim3(256), 0, 0, a);
-        HS_HIP(hipGetLastError());
-        HS_HIP(hipEventRecord(e1, 0));
-        HS_HIP(hipEventSynchronize(e1));
-        HS_HIP(hipEventElapsedTime(&kernel_ms, e0, e1));
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
+        kernel_ms = timer.stop();
         std::vector<unsigned> bits((size_t)words);
         HS_HIP(hipMemcpy(bits.data(), a.bitmap, bits.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
         for (int64_t w = 0; w < words; ++w)
@@ -232,11 +174,7 @@ int hello_hotspots_find(const uint8_t* bases, const uint8_t* quals, const int64_
     std::copy(st, st + HELLO_HOTSPOTS_STATS, res->stats);
     *out = own.release();
     return HELLO_OK;
-} catch (const hello::Fail& f) {
-    return hello::set_last_error(f.code, "%s", f.msg.c_str());
-} catch (...) {
-    return hello::exception_status("hello_hotspots_find");
-}
+} HS_ENTRY_END("hello_hotspots_find")
 
 int hello_hotspots_positions(const hello_hotspots* h, const int64_t** positions, int64_t* n_positions) {
     if (!h || !positions || !n_positions) return hello::set_last_error(HELLO_ERR_ARG, "NULL pointer");

@@ -16,22 +16,13 @@
 //     slots of its own read and adds 1 to link[t][k][cis | trans] in global memory with an integer atomic.
 //   tag: a thread per counted read, one pass over its slots with the sets and flips the host chained.
 // Slot capacity is exact, counters are integers and every slot and every tag has one writer: two runs give the same bytes.
-#include <algorithm>
 #include <chrono>
 #include <climits>
-#include <cstring>
 #include <memory>
-#include <vector>
 
-#include <hip/hip_runtime.h>
-
-#include "../../include/hello_mi355x.h"
-#include "differing.h"
+#include "stage_host.h"
 
 namespace hello {
-int set_last_error(int code, const char* fmt, ...);      // engine.hip
-int exception_status(const char* where) noexcept;         // engine.hip
-
 namespace {
 
 constexpr int kPhThreads = 256;
@@ -195,16 +186,6 @@ struct PhBatch {
     std::vector<int64_t> reads;  // list[k] of the batch
 };
 
-template <class T> T* dev_put(const T* src, size_t n) {
-    void* p = nullptr;
-    HS_HIP(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)));
-    if (n && hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(p);
-        raise(HELLO_ERR_HIP, "hipMemcpy to the device failed");
-    }
-    return (T*)p;
-}
-
 }  // namespace
 }  // namespace hello
 
@@ -233,38 +214,6 @@ struct hello_phase {
 
 namespace hello {
 namespace {
-
-void phase_open_device(int device) {
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) raise(HELLO_ERR_NOGPU, "no GPU visible");
-    if (device < 0 || device >= n_dev) raise(HELLO_ERR_ARG, "device %d of %d", device, n_dev);
-    hipDeviceProp_t prop;
-    HS_HIP(hipGetDeviceProperties(&prop, device));
-    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        raise(HELLO_ERR_NOGPU, "device %d is %s; this library is built for gfx950 only", device, prop.gcnArchName);
-    HS_HIP(hipSetDevice(device));
-}
-
-struct Timer {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    Timer() {
-        HS_HIP(hipEventCreate(&e0));
-        HS_HIP(hipEventCreate(&e1));
-    }
-    ~Timer() {
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-    }
-    void start() { HS_HIP(hipEventRecord(e0, 0)); }
-    float stop() {
-        float ms = 0.0f;
-        HS_HIP(hipGetLastError());
-        HS_HIP(hipEventRecord(e1, 0));
-        HS_HIP(hipEventSynchronize(e1));
-        HS_HIP(hipEventElapsedTime(&ms, e0, e1));
-        return ms;
-    }
-};
 
 unsigned blocks_for(int64_t items, int per_block) {
     const int64_t n = (items + per_block - 1) / per_block;
@@ -312,7 +261,7 @@ int hello_phase_observe(const uint8_t* bases, const uint8_t* quals, const int64_
         }
         own.reset(new hello_phase());
         h = own.get();
-        phase_open_device(device);
+        open_device(device);
         h->device = device;
         h->window = window;
         h->q_threshold = q_threshold;
@@ -320,10 +269,11 @@ int hello_phase_observe(const uint8_t* bases, const uint8_t* quals, const int64_
         h->n_records = n_records;
         h->rec_start.assign(record_starts, record_starts + n_records);
         h->links.assign((size_t)n_records * window * 2, 0);
-        h->d_rec_start = dev_put(record_starts, (size_t)n_records);
-        h->d_rec_end = dev_put(record_ends, (size_t)n_records);
-        h->d_alleles = dev_put(alleles, (size_t)allele_offsets[2 * n_records]);
-        h->d_allele_off = dev_put(allele_offsets, (size_t)(2 * n_records + 1));
+        DevMem m;                                                           // each upload leaves to the handle at once
+        h->d_rec_start = m.release(m.put(record_starts, (size_t)n_records));
+        h->d_rec_end = m.release(m.put(record_ends, (size_t)n_records));
+        h->d_alleles = m.release(m.put(alleles, (size_t)allele_offsets[2 * n_records]));
+        h->d_allele_off = m.release(m.put(allele_offsets, (size_t)(2 * n_records + 1)));
     } else {
         if (n_records != h->n_records || window != h->window || q_threshold != h->q_threshold || mapq_threshold != h->mapq_threshold ||
             device != h->device)
@@ -344,21 +294,11 @@ int hello_phase_observe(const uint8_t* bases, const uint8_t* quals, const int64_
     } guard{&b};
     b.read_base = h->n_reads;
     std::vector<int64_t> list_end, first, slot_off{0}, all_first((size_t)n_reads, 0), all_count((size_t)n_reads, 0);
+    const ReadsView in{bases, quals, read_offsets, cigars, cigar_offsets, ref_starts, ref_ends, mapq, flags, name_hash, n_reads};
     for (int64_t r = 0; r < n_reads; ++r) {
         if (source[r] > 1) return set_last_error(HELLO_ERR_ARG, "source[%lld] = %d: 0 or 1", (long long)r, (int)source[r]);
-        if (read_offsets[r + 1] < read_offsets[r] || cigar_offsets[r + 1] < cigar_offsets[r])
-            return set_last_error(HELLO_ERR_SHAPE, "read %lld: offsets decrease", (long long)r);
-        if (!usable(flags[r], mapq[r]) || (flags[r] & 0x200) || (int)mapq[r] < mapq_threshold) continue;
-        int64_t qlen = 0, rlen = 0;
-        for (int64_t c = cigar_offsets[r]; c < cigar_offsets[r + 1]; ++c) {
-            const int op = cigars[c] & 15;
-            const int64_t len = cigars[c] >> 4;
-            if (op == BAM_CMATCH || op == BAM_CINS || op == BAM_CSOFT_CLIP || op == BAM_CEQUAL || op == BAM_CDIFF) qlen += len;
-            if (op == BAM_CMATCH || op == BAM_CDEL || op == BAM_CREF_SKIP || op == BAM_CEQUAL || op == BAM_CDIFF) rlen += len;
-        }
-        if (qlen > read_offsets[r + 1] - read_offsets[r])
-            return set_last_error(HELLO_ERR_ARG, "read %lld: its CIGAR consumes %lld bases, it has %lld", (long long)r, (long long)qlen,
-                                  (long long)(read_offsets[r + 1] - read_offsets[r]));
+        int64_t qlen, rlen;
+        if (!counted_walk(in, r, mapq_threshold, qlen, rlen)) continue;
         const int64_t end = ref_starts[r] + rlen;
         const int64_t f = std::lower_bound(rec, rec + n, ref_starts[r]) - rec;
         const int64_t l = std::lower_bound(rec, rec + n, end) - rec;
@@ -379,17 +319,13 @@ int hello_phase_observe(const uint8_t* bases, const uint8_t* quals, const int64_
     if (b.n_slots > 0) {
         DevMem m;
         PhObserveArgs a{};
-        const int64_t nb = read_offsets[n_reads], nc = cigar_offsets[n_reads];
-        a.bases = m.put(bases, (size_t)nb);
-        a.quals = m.put(quals, (size_t)nb);
-        a.read_off = m.put(read_offsets, (size_t)n_reads + 1);
-        a.cigars = m.put(cigars, (size_t)nc);
-        a.cigar_off = m.put(cigar_offsets, (size_t)n_reads + 1);
-        a.ref_start = m.put(ref_starts, (size_t)n_reads);
+        const DeviceReads d = upload_reads(m, in);
+        a.bases = d.bases; a.quals = d.quals; a.read_off = d.read_off; a.cigars = d.cigars; a.cigar_off = d.cigar_off;
+        a.ref_start = d.ref_start;
         a.list = m.put(b.reads.data(), b.reads.size());
         a.list_end = m.put(list_end.data(), list_end.size());
-        b.first = dev_put(first.data(), first.size());
-        b.slot_off = dev_put(slot_off.data(), slot_off.size());
+        b.first = m.release(m.put(first.data(), first.size()));
+        b.slot_off = m.release(m.put(slot_off.data(), slot_off.size()));
         void* p = nullptr;
         HS_HIP(hipMalloc(&p, (size_t)b.n_slots));
         b.slots = (int8_t*)p;
@@ -404,7 +340,7 @@ int hello_phase_observe(const uint8_t* bases, const uint8_t* quals, const int64_
         a.slots = kept.slots;
         a.n_counted = b.n_counted;
         a.q_threshold = q_threshold;
-        Timer timer;
+        KernelTimer timer;
         timer.start();
         hipLaunchKernelGGL(phase_observe_kernel, dim3(blocks_for(b.n_counted, kPhWaves)), dim3(kPhThreads), 0, 0, a);
         observe_ms = timer.stop();
@@ -443,11 +379,7 @@ int hello_phase_observe(const uint8_t* bases, const uint8_t* quals, const int64_
     h->stats[8] += std::chrono::duration<double, std::milli>(clock::now() - t0).count();
     if (own) *handle = own.release();
     return HELLO_OK;
-} catch (const hello::Fail& f) {
-    return hello::set_last_error(f.code, "%s", f.msg.c_str());
-} catch (...) {
-    return hello::exception_status("hello_phase_observe");
-}
+} HS_ENTRY_END("hello_phase_observe")
 
 int hello_phase_chain(const int32_t* link, const int32_t* chromosome, int64_t n_records, int32_t window, int32_t min_margin,
                       int32_t* set, uint8_t* flip) try {
@@ -491,9 +423,7 @@ int hello_phase_chain(const int32_t* link, const int32_t* chromosome, int64_t n_
         }
     }
     return HELLO_OK;
-} catch (...) {
-    return hello::exception_status("hello_phase_chain");
-}
+} HS_ENTRY_END("hello_phase_chain")
 
 int hello_phase_tag(hello_phase* h, const int32_t* set, const uint8_t* flip) try {
     using namespace hello;
@@ -521,7 +451,7 @@ int hello_phase_tag(hello_phase* h, const int32_t* set, const uint8_t* flip) try
         a.set = m.put(set, (size_t)n);
         a.flip = m.put(flip, (size_t)n);
         a.set_pos = m.put(set_pos.data(), set_pos.size());
-        Timer timer;
+        KernelTimer timer;
         for (const PhBatch& b : h->batches) {
             if (b.n_slots == 0) continue;
             a.slots = b.slots;
@@ -545,11 +475,7 @@ int hello_phase_tag(hello_phase* h, const int32_t* set, const uint8_t* flip) try
     }
     h->stats[8] += std::chrono::duration<double, std::milli>(clock::now() - t0).count();
     return HELLO_OK;
-} catch (const hello::Fail& f) {
-    return hello::set_last_error(f.code, "%s", f.msg.c_str());
-} catch (...) {
-    return hello::exception_status("hello_phase_tag");
-}
+} HS_ENTRY_END("hello_phase_tag")
 
 int hello_phase_array(const hello_phase* h, int32_t which, const void** data, int64_t* count) {
     if (!h || !data || !count) return hello::set_last_error(HELLO_ERR_ARG, "NULL pointer");

@@ -14,23 +14,14 @@
 //     atomics, and the thread that owns the run's first position writes the record.
 // The output capacity is exact, so no run can be dropped.  Counters are integers, minima are order-free and every record is written
 // by its owner: two runs give the same bytes.  Runs of one key that meet at a tile edge are joined on the host.
-#include <algorithm>
 #include <chrono>
 #include <climits>
 #include <cmath>
-#include <cstring>
 #include <memory>
-#include <vector>
 
-#include <hip/hip_runtime.h>
-
-#include "../../include/hello_mi355x.h"
-#include "differing.h"
+#include "stage_host.h"
 
 namespace hello {
-int set_last_error(int code, const char* fmt, ...);      // engine.hip
-int exception_status(const char* where) noexcept;         // engine.hip
-
 namespace {
 
 // Two int32 counters per position live in LDS, so a tile is four times kTile: 8 KB of counters, 8 KB of keys and GQs and 12 KB of
@@ -271,25 +262,15 @@ int hello_refblocks_find(const uint8_t* bases, const uint8_t* quals, const int64
     // ---- the counted reads of each source, validated: the kernel reads within their bases
     std::vector<int64_t> list[2], list_end[2], max_end[2], starts[2];
     int64_t last_start[2] = {INT64_MIN, INT64_MIN};
+    const ReadsView in{bases, quals, read_offsets, cigars, cigar_offsets, ref_starts, ref_ends, mapq, flags, name_hash, n_reads};
     for (int64_t r = 0; r < n_reads; ++r) {
         const int s = source[r];
         if (s > 1) return set_last_error(HELLO_ERR_ARG, "source[%lld] = %d: 0 or 1", (long long)r, s);
         if (ref_starts[r] < last_start[s])
             return set_last_error(HELLO_ERR_ARG, "read %lld: reads are not coordinate-sorted (the BAM must be)", (long long)r);
         last_start[s] = ref_starts[r];
-        if (read_offsets[r + 1] < read_offsets[r] || cigar_offsets[r + 1] < cigar_offsets[r])
-            return set_last_error(HELLO_ERR_SHAPE, "read %lld: offsets decrease", (long long)r);
-        if (!usable(flags[r], mapq[r]) || (flags[r] & 0x200) || (int)mapq[r] < mapq_threshold) continue;
-        int64_t qlen = 0, rlen = 0;
-        for (int64_t c = cigar_offsets[r]; c < cigar_offsets[r + 1]; ++c) {
-            const int op = cigars[c] & 15;
-            const int64_t len = cigars[c] >> 4;
-            if (op == BAM_CMATCH || op == BAM_CINS || op == BAM_CSOFT_CLIP || op == BAM_CEQUAL || op == BAM_CDIFF) qlen += len;
-            if (op == BAM_CMATCH || op == BAM_CDEL || op == BAM_CREF_SKIP || op == BAM_CEQUAL || op == BAM_CDIFF) rlen += len;
-        }
-        if (qlen > read_offsets[r + 1] - read_offsets[r])
-            return set_last_error(HELLO_ERR_ARG, "read %lld: its CIGAR consumes %lld bases, it has %lld", (long long)r, (long long)qlen,
-                                  (long long)(read_offsets[r + 1] - read_offsets[r]));
+        int64_t qlen, rlen;
+        if (!counted_walk(in, r, mapq_threshold, qlen, rlen)) continue;
         const int64_t end = ref_starts[r] + rlen;
         if (end <= lo || ref_starts[r] >= hi) continue;
         list[s].push_back(r);
@@ -328,23 +309,12 @@ int hello_refblocks_find(const uint8_t* bases, const uint8_t* quals, const int64
     float kernel_ms = 0.0f;
     int64_t n_runs = 0;
     if (n_tiles > 0) {
-        int n_dev = 0;
-        if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) return set_last_error(HELLO_ERR_NOGPU, "no GPU visible");
-        if (device < 0 || device >= n_dev) return set_last_error(HELLO_ERR_ARG, "device %d of %d", device, n_dev);
-        hipDeviceProp_t prop;
-        HS_HIP(hipGetDeviceProperties(&prop, device));
-        if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-            return set_last_error(HELLO_ERR_NOGPU, "device %d is %s; this library is built for gfx950 only", device, prop.gcnArchName);
-        HS_HIP(hipSetDevice(device));
+        open_device(device);
         DevMem m;
         RbArgs a{};
-        const int64_t nb = n_reads ? read_offsets[n_reads] : 0, nc = n_reads ? cigar_offsets[n_reads] : 0;
-        a.bases = m.put(bases, (size_t)nb);
-        a.quals = m.put(quals, (size_t)nb);
-        a.read_off = m.put(read_offsets, (size_t)n_reads + 1);
-        a.cigars = m.put(cigars, (size_t)nc);
-        a.cigar_off = m.put(cigar_offsets, (size_t)n_reads + 1);
-        a.ref_start = m.put(ref_starts, (size_t)n_reads);
+        const DeviceReads d = upload_reads(m, in);
+        a.bases = d.bases; a.quals = d.quals; a.read_off = d.read_off; a.cigars = d.cigars; a.cigar_off = d.cigar_off;
+        a.ref_start = d.ref_start;
         a.list = m.put(list[0].data(), list[0].size());
         a.list_end = m.put(list_end[0].data(), list_end[0].size());
         a.tile_reads = m.put(tile_reads.data(), tile_reads.size());
@@ -363,17 +333,10 @@ int hello_refblocks_find(const uint8_t* bases, const uint8_t* quals, const int64
         a.c = -10.0 * std::log10(0.5);
         a.q_threshold = q_threshold;
         a.gq_binsize = gq_binsize;
-        hipEvent_t e0, e1;
-        HS_HIP(hipEventCreate(&e0));
-        HS_HIP(hipEventCreate(&e1));
-        float ms = 0.0f;
-        HS_HIP(hipEventRecord(e0, 0));
+        KernelTimer timer;
+        timer.start();
         hipLaunchKernelGGL(refblocks_kernel<false>, dim3((unsigned)n_tiles), dim3(kRbThreads), 0, 0, a);
-        HS_HIP(hipGetLastError());
-        HS_HIP(hipEventRecord(e1, 0));
-        HS_HIP(hipEventSynchronize(e1));
-        HS_HIP(hipEventElapsedTime(&ms, e0, e1));
-        kernel_ms += ms;
+        kernel_ms += timer.stop();
         std::vector<int32_t> tile_runs((size_t)n_tiles);
         HS_HIP(hipMemcpy(tile_runs.data(), a.tile_runs, tile_runs.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
         std::vector<int64_t> run_off((size_t)n_tiles);
@@ -384,15 +347,9 @@ int hello_refblocks_find(const uint8_t* bases, const uint8_t* quals, const int64
         }
         a.run_off = m.put(run_off.data(), run_off.size());
         a.runs = m.zeros<RbRun>((size_t)n_runs);
-        HS_HIP(hipEventRecord(e0, 0));
+        timer.start();
         hipLaunchKernelGGL(refblocks_kernel<true>, dim3((unsigned)n_tiles), dim3(kRbThreads), 0, 0, a);
-        HS_HIP(hipGetLastError());
-        HS_HIP(hipEventRecord(e1, 0));
-        HS_HIP(hipEventSynchronize(e1));
-        HS_HIP(hipEventElapsedTime(&ms, e0, e1));
-        kernel_ms += ms;
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
+        kernel_ms += timer.stop();
         std::vector<RbRun> runs((size_t)n_runs);
         if (n_runs) HS_HIP(hipMemcpy(runs.data(), a.runs, runs.size() * sizeof(RbRun), hipMemcpyDeviceToHost));
         if (options & HELLO_REFBLOCKS_KEEP_COUNTS) {
@@ -429,11 +386,7 @@ int hello_refblocks_find(const uint8_t* bases, const uint8_t* quals, const int64
     std::copy(st, st + HELLO_REFBLOCKS_STATS, res->stats);
     *out = own.release();
     return HELLO_OK;
-} catch (const hello::Fail& f) {
-    return hello::set_last_error(f.code, "%s", f.msg.c_str());
-} catch (...) {
-    return hello::exception_status("hello_refblocks_find");
-}
+} HS_ENTRY_END("hello_refblocks_find")
 
 int hello_refblocks_array(const hello_refblocks* h, int32_t which, const void** data, int64_t* count) {
     if (!h || !data || !count) return hello::set_last_error(HELLO_ERR_ARG, "NULL pointer");

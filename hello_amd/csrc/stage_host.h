@@ -1,0 +1,107 @@
+// The HIP host layer under the BAM-side stages (hotspots.hip, candidates.hip, refblocks.hip, phase.hip): opening the device,
+// owned device memory, the upload of a read set, timing a launch, and the tail of an entry point.  No kernel lives here.
+#pragma once
+#include <utility>
+
+#include <hip/hip_runtime.h>
+
+#include "cigar.h"
+
+namespace hello {
+int set_last_error(int code, const char* fmt, ...);      // engine.hip
+int exception_status(const char* where) noexcept;         // engine.hip
+
+namespace {
+
+#define HS_HIP(expr)                                                                                       \
+    do {                                                                                                   \
+        hipError_t e_ = (expr);                                                                            \
+        if (e_ != hipSuccess) raise(HELLO_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));         \
+    } while (0)
+
+// The tail of every entry point that can refuse or allocate: `int hello_x(...) try { ... } HS_ENTRY_END("hello_x")`.
+#define HS_ENTRY_END(name)                                                                                 \
+    catch (const hello::Fail& f) { return hello::set_last_error(f.code, "%s", f.msg.c_str()); }            \
+    catch (...) { return hello::exception_status(name); }
+
+void open_device(int device) {
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) raise(HELLO_ERR_NOGPU, "no GPU visible");
+    if (device < 0 || device >= n_dev) raise(HELLO_ERR_ARG, "device %d of %d", device, n_dev);
+    hipDeviceProp_t prop;
+    HS_HIP(hipGetDeviceProperties(&prop, device));
+    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+        raise(HELLO_ERR_NOGPU, "device %d is %s; this library is built for gfx950 only", device, prop.gcnArchName);
+    HS_HIP(hipSetDevice(device));
+}
+
+struct DevMem {
+    std::vector<void*> ptrs;
+    template <class T> T* put(const T* src, size_t n) {
+        void* p = nullptr;
+        HS_HIP(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)));
+        ptrs.push_back(p);
+        if (n) HS_HIP(hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice));
+        return (T*)p;
+    }
+    template <class T> T* zeros(size_t n) {
+        void* p = nullptr;
+        HS_HIP(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)));
+        ptrs.push_back(p);
+        HS_HIP(hipMemset(p, 0, std::max<size_t>(n, 1) * sizeof(T)));
+        return (T*)p;
+    }
+    template <class T> T* release(T* p) {                          // p leaves: a longer-lived owner frees it
+        ptrs.erase(std::find(ptrs.begin(), ptrs.end(), (void*)p));
+        return p;
+    }
+    ~DevMem() { for (void* p : ptrs) (void)hipFree(p); }
+};
+
+struct DeviceReads {
+    const uint8_t* bases = nullptr; const uint8_t* quals = nullptr; const int64_t* read_off = nullptr;
+    const uint32_t* cigars = nullptr; const int64_t* cigar_off = nullptr; const int64_t* ref_start = nullptr;
+};
+
+DeviceReads upload_reads(DevMem& m, const ReadsView& s) {
+    const size_t n = (size_t)s.n, nb = n ? (size_t)s.read_off[n] : 0, nc = n ? (size_t)s.cigar_off[n] : 0;
+    DeviceReads d;
+    d.bases = m.put(s.bases, nb);
+    d.quals = m.put(s.quals, nb);
+    d.read_off = m.put(s.read_off, n + 1);
+    d.cigars = m.put(s.cigars, nc);
+    d.cigar_off = m.put(s.cigar_off, n + 1);
+    d.ref_start = m.put(s.ref_start, n);
+    return d;
+}
+
+struct KernelTimer {               // HIP events around a launch on the default stream; destroyed on every path
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    KernelTimer() = default;
+    void start() {
+        if (!e0) HS_HIP(hipEventCreate(&e0));
+        if (!e1) HS_HIP(hipEventCreate(&e1));
+        HS_HIP(hipEventRecord(e0, 0));
+    }
+    float stop() {                 // after the launch: its error, if any, is the refusal
+        float ms = 0.0f;
+        HS_HIP(hipGetLastError());
+        HS_HIP(hipEventRecord(e1, 0));
+        HS_HIP(hipEventSynchronize(e1));
+        HS_HIP(hipEventElapsedTime(&ms, e0, e1));
+        return ms;
+    }
+    ~KernelTimer() {
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    }
+    KernelTimer(const KernelTimer&) = delete;
+    KernelTimer& operator=(const KernelTimer&) = delete;
+};
+
+struct PairHash {                                                  // (name hash, strand): a read pair's two mates stay distinct
+    size_t operator()(const std::pair<uint64_t, int>& k) const { return (size_t)(k.first * 0x9E3779B97F4A7C15ull) ^ (size_t)k.second; }
+};
+
+}  // namespace
+}  // namespace hello

@@ -21,6 +21,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from ._abi import ARRAY_GETTER, READS, STATS_GETTER, bind, check, handle_array, handle_stats, i32, i64, vp
 from .bam import BamFile, Reads
 
 ERROR_RATE = 0.001
@@ -44,14 +45,13 @@ FORMAT_HEADER = dict(
 
 Blocks = Dict[str, np.ndarray]
 _log = logging.getLogger(__name__)
-_bound = None
 
 
 # ------------------------------------------------------------------------------------------------
 # the rules, restated
 # ------------------------------------------------------------------------------------------------
 def usable(flag: int, mapq: int) -> bool:
-    """``usable`` of hello_amd/csrc/differing.h: mapped, primary, not a duplicate, a proper pair if paired, mapq > 0."""
+    """``usable`` of hello_amd/csrc/cigar.h: mapped, primary, not a duplicate, a proper pair if paired, mapq > 0."""
     if flag & (0x4 | 0x100 | 0x800 | 0x400):
         return False
     if (flag & 0x1) and not (flag & 0x2):
@@ -228,19 +228,16 @@ def excluded_intervals(records: Sequence[Tuple[int, int]]) -> List[Tuple[int, in
 # ------------------------------------------------------------------------------------------------
 # the GPU
 # ------------------------------------------------------------------------------------------------
+_PROTOTYPES = (
+    ("hello_refblocks_find", READS + [i64, vp, i64, i64, i64, vp, vp, i64, i32, i32, i32, i32, i32, C.POINTER(vp)]),
+    ("hello_refblocks_array", ARRAY_GETTER),
+    ("hello_refblocks_stats", STATS_GETTER),
+    ("hello_refblocks_free", [vp], None),
+)
+
+
 def _lib():
-    global _bound
-    if _bound is None:
-        from .engine import load_library
-        lib = load_library()
-        vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
-        lib.hello_refblocks_find.argtypes = [vp] * 11 + [i64, vp, i64, i64, i64, vp, vp, i64, i32, i32, i32, i32, i32, C.POINTER(vp)]
-        lib.hello_refblocks_array.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(i64)]
-        lib.hello_refblocks_stats.argtypes = [vp, C.POINTER(C.c_double)]
-        lib.hello_refblocks_free.argtypes = [vp]
-        lib.hello_refblocks_free.restype = None
-        _bound = lib
-    return _bound
+    return bind(_PROTOTYPES)
 
 
 def find_blocks(reads: Sequence[Reads], reference, lo: int, hi: int, excluded: Sequence[Tuple[int, int]] = (),
@@ -257,27 +254,15 @@ def find_blocks(reads: Sequence[Reads], reference, lo: int, hi: int, excluded: S
     lib = _lib()
     h = C.c_void_p()
     ptr = lambda a: a.ctypes.data  # noqa: E731
-    rc = lib.hello_refblocks_find(ptr(r.bases), ptr(r.quals), ptr(r.read_offsets), ptr(r.cigars), ptr(r.cigar_offsets),
-                                  ptr(r.ref_starts), ptr(r.ref_ends), ptr(r.mapq), ptr(r.flags), ptr(r.name_hash), ptr(source),
-                                  int(r.n_reads), ptr(ref), int(ref.shape[0]), int(lo), int(hi), ptr(starts), ptr(stops),
-                                  int(starts.shape[0]), int(q_threshold), int(mapq_threshold), int(gq_binsize),
-                                  KEEP_COUNTS if keep_counts else 0, int(device), C.byref(h))
-    if rc != 0:
-        raise RuntimeError(lib.hello_last_error().decode(errors="replace"))
+    check(lib.hello_refblocks_find(*r.pointers(source), int(r.n_reads), ptr(ref), int(ref.shape[0]), int(lo), int(hi), ptr(starts),
+                                   ptr(stops), int(starts.shape[0]), int(q_threshold), int(mapq_threshold), int(gq_binsize),
+                                   KEEP_COUNTS if keep_counts else 0, int(device), C.byref(h)))
     try:
         def array(which, dtype):
-            p, n = C.c_void_p(), C.c_int64()
-            if lib.hello_refblocks_array(h, which, C.byref(p), C.byref(n)) != 0:
-                raise RuntimeError(lib.hello_last_error().decode(errors="replace"))
-            k = int(n.value)
-            if k == 0:
-                return np.zeros(0, dtype)
-            return np.frombuffer((C.c_char * (k * np.dtype(dtype).itemsize)).from_address(p.value), dtype).copy()
+            return handle_array(lib.hello_refblocks_array, h, which, dtype)
         blocks = {name: array(which, dtype) for name, which, dtype in FIELDS}
         counts = (array(COUNT_REF, np.int32), array(COUNT_TOTAL, np.int32)) if keep_counts else None
-        st = (C.c_double * len(STAT_NAMES))()
-        lib.hello_refblocks_stats(h, st)
-        return blocks, dict(zip(STAT_NAMES, list(st))), counts
+        return blocks, handle_stats(lib.hello_refblocks_stats, h, STAT_NAMES), counts
     finally:
         lib.hello_refblocks_free(h)
 

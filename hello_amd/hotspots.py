@@ -21,7 +21,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from .bam import BamFile, Reads
-from .engine import load_library
+from ._abi import READS, STATS_GETTER, bind, check, handle_array, handle_stats, i32, i64, vp
 
 CHUNK_SIZE_ILLUMINA = 400          # HotspotDetectorDVFiltered.py:14-17
 CHUNK_SIZE_PACBIO = 10000
@@ -36,21 +36,16 @@ STAT_NAMES = ("chunks", "chunks_without_reads", "chunks_out_of_bounds", "chunks_
 MAX_LAUNCH_BASES = 16_000_000      # --workdir: regions of at most this many positions share a launch
 
 _log = logging.getLogger(__name__)
-_bound = None
+_PROTOTYPES = (
+    ("hello_hotspots_find", READS + [i64, vp, i64, vp, vp, i32, i32, i32, i32, i32, C.POINTER(vp)]),
+    ("hello_hotspots_positions", [vp, C.POINTER(vp), C.POINTER(i64)]),
+    ("hello_hotspots_stats", STATS_GETTER),
+    ("hello_hotspots_free", [vp], None),
+)
 
 
 def _lib():
-    global _bound
-    if _bound is None:
-        lib = load_library()
-        vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
-        lib.hello_hotspots_find.argtypes = [vp] * 11 + [i64, vp, i64, vp, vp, i32, i32, i32, i32, i32, C.POINTER(vp)]
-        lib.hello_hotspots_positions.argtypes = [vp, C.POINTER(vp), C.POINTER(i64)]
-        lib.hello_hotspots_stats.argtypes = [vp, C.POINTER(C.c_double)]
-        lib.hello_hotspots_free.argtypes = [vp]
-        lib.hello_hotspots_free.restype = None
-        _bound = lib
-    return _bound
+    return bind(_PROTOTYPES)
 
 
 def get_chunks(length: int, n_jobs: int) -> List[Tuple[int, int]]:
@@ -103,23 +98,14 @@ def find_positions(reads: Sequence[Reads], reference: str, regions: Sequence[Tup
     lib = _lib()
     h = C.c_void_p()
     ptr = lambda a: a.ctypes.data  # noqa: E731
-    rc = lib.hello_hotspots_find(ptr(r.bases), ptr(r.quals), ptr(r.read_offsets), ptr(r.cigars), ptr(r.cigar_offsets),
-                                 ptr(r.ref_starts), ptr(r.ref_ends), ptr(r.mapq), ptr(r.flags), ptr(r.name_hash), ptr(source),
-                                 int(r.n_reads), ptr(ref), int(ref.shape[0]), ptr(starts), ptr(stops), int(starts.shape[0]),
-                                 (HOTSPOTS_PACBIO if pacbio else 0) | (HOTSPOTS_HYBRID if hybrid_hotspot else 0)
-                                 | (HOTSPOTS_TWO_BAMS if len(reads) == 2 else 0),    # even when the second set is empty
-                                 int(q_threshold), int(mapq_threshold), int(device), C.byref(h))
-    if rc != 0:
-        raise RuntimeError(lib.hello_last_error().decode(errors="replace"))
+    check(lib.hello_hotspots_find(*r.pointers(source), int(r.n_reads), ptr(ref), int(ref.shape[0]), ptr(starts), ptr(stops),
+                                  int(starts.shape[0]),
+                                  (HOTSPOTS_PACBIO if pacbio else 0) | (HOTSPOTS_HYBRID if hybrid_hotspot else 0)
+                                  | (HOTSPOTS_TWO_BAMS if len(reads) == 2 else 0),    # even when the second set is empty
+                                  int(q_threshold), int(mapq_threshold), int(device), C.byref(h)))
     try:
-        p, n = C.c_void_p(), C.c_int64()
-        lib.hello_hotspots_positions(h, C.byref(p), C.byref(n))
-        k = int(n.value)
-        positions = np.zeros(0, np.int64) if k == 0 else np.frombuffer(
-            (C.c_char * (8 * k)).from_address(p.value), np.int64).copy()
-        st = (C.c_double * N_STATS)()
-        lib.hello_hotspots_stats(h, st)
-        return positions, dict(zip(STAT_NAMES, list(st)))
+        positions = handle_array(lambda h_, _, p, n: lib.hello_hotspots_positions(h_, p, n), h, 0, np.int64)   # one array, no selector
+        return positions, handle_stats(lib.hello_hotspots_stats, h, STAT_NAMES)
     finally:
         lib.hello_hotspots_free(h)
 

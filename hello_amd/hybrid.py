@@ -23,7 +23,7 @@ import numpy as np
 from . import candidates as cd
 from . import shards
 from .bam import BamFile, Reads
-from .engine import load_library
+from ._abi import ARRAY_GETTER, READS, STATS_GETTER, bind, check, handle_array, handle_stats, i32, i64, vp
 from .hotspots import HOTSPOTS_HYBRID
 
 DEFAULT_REASSEMBLY_SIZE = 10       # call.py: --reconcilement_size
@@ -33,26 +33,18 @@ STAT_NAMES = cd.STAT_NAMES + ("clusters_gate_passed", "clusters_reassembled", "p
 _SITE_ARRAYS = tuple(a for a in cd._ARRAYS if a[1] < 8)                       # start ... allele_text_off
 _READ_ARRAYS = tuple(a for a in cd._ARRAYS if 8 <= a[1] <= 18)                # reads_per_allele0 ... hp0, read_index
 _REGION_ARRAYS = tuple(a for a in cd._ARRAYS if a[1] > 18)
-_READ_SET_FIELDS = ("bases", "quals", "read_offsets", "cigars", "cigar_offsets", "ref_starts", "ref_ends", "mapq", "flags",
-                    "name_hash", "hp")
-
-_bound = None
+_READ_SET = READS + [i64]
+_PROTOTYPES = (
+    ("hello_candidates_find_hybrid", _READ_SET + _READ_SET + [vp, i64, vp, i64, i32, i32, i32, i32, i32, i32, C.POINTER(vp)]),
+    ("hello_candidates_array", ARRAY_GETTER),
+    ("hello_candidates_array_tech", [vp, i32] + ARRAY_GETTER[1:]),
+    ("hello_candidates_hybrid_stats", STATS_GETTER),
+    ("hello_candidates_free", [vp], None),
+)
 
 
 def _lib():
-    global _bound
-    if _bound is None:
-        lib = load_library()
-        vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
-        read_set = [vp] * 11 + [i64]
-        lib.hello_candidates_find_hybrid.argtypes = read_set + read_set + [vp, i64, vp, i64, i32, i32, i32, i32, i32, i32, C.POINTER(vp)]
-        lib.hello_candidates_array.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(i64)]
-        lib.hello_candidates_array_tech.argtypes = [vp, i32, i32, C.POINTER(vp), C.POINTER(i64)]
-        lib.hello_candidates_hybrid_stats.argtypes = [vp, C.POINTER(C.c_double)]
-        lib.hello_candidates_free.argtypes = [vp]
-        lib.hello_candidates_free.restype = None
-        _bound = lib
-    return _bound
+    return bind(_PROTOTYPES)
 
 
 def find_sites(illumina: Reads, pacbio: Reads, reference: str, positions: Sequence[int], chromosome: str = "chr",
@@ -67,23 +59,14 @@ def find_sites(illumina: Reads, pacbio: Reads, reference: str, positions: Sequen
     pos = np.ascontiguousarray(positions, dtype=np.int64)
     lib = _lib()
     h = C.c_void_p()
-    sets = []
-    for r in (illumina, pacbio):
-        sets += [getattr(r, f).ctypes.data for f in _READ_SET_FIELDS] + [int(r.n_reads)]
-    rc = lib.hello_candidates_find_hybrid(*sets, ref.ctypes.data, int(ref.shape[0]), pos.ctypes.data, int(pos.shape[0]),
-                                          (HOTSPOTS_HYBRID if hybrid_hotspot else 0) | (rs.HELLO_CANDIDATES_RESIDENT if resident else 0),
-                                          int(reassembly_size), int(feature_length),
-                                          int(q_threshold), int(mapq_threshold), int(device), C.byref(h))
-    if rc != 0:
-        message = lib.hello_last_error().decode(errors="replace")
-        raise (ValueError if rc == -1 else RuntimeError)(message)
+    sets = illumina.pointers(illumina.hp) + [int(illumina.n_reads)] + pacbio.pointers(pacbio.hp) + [int(pacbio.n_reads)]
+    check(lib.hello_candidates_find_hybrid(*sets, ref.ctypes.data, int(ref.shape[0]), pos.ctypes.data, int(pos.shape[0]),
+                                           (HOTSPOTS_HYBRID if hybrid_hotspot else 0) | (rs.HELLO_CANDIDATES_RESIDENT if resident else 0),
+                                           int(reassembly_size), int(feature_length),
+                                           int(q_threshold), int(mapq_threshold), int(device), C.byref(h)), value_error_on_arg=True)
 
     def array(tech, which, dtype):
-        p, n = C.c_void_p(), C.c_int64()
-        if lib.hello_candidates_array_tech(h, tech, which, C.byref(p), C.byref(n)) != 0:
-            raise RuntimeError(lib.hello_last_error().decode(errors="replace"))
-        k = int(n.value)
-        return np.zeros(0, dtype) if k == 0 else np.frombuffer((C.c_char * (k * np.dtype(dtype).itemsize)).from_address(p.value), dtype).copy()
+        return handle_array(lib.hello_candidates_array_tech, h, which, dtype, tech)
     keep = False
     try:
         got = {name: array(0, which, dtype) for name, which, dtype in _SITE_ARRAYS}
@@ -94,8 +77,7 @@ def find_sites(illumina: Reads, pacbio: Reads, reference: str, positions: Sequen
                     extra[f"read_index{tech}"] = array(tech, which, dtype)
                 else:
                     got[name[:-1] + str(tech)] = array(tech, which, dtype)
-        st = (C.c_double * N_STATS)()
-        lib.hello_candidates_hybrid_stats(h, st)
+        st = handle_stats(lib.hello_candidates_hybrid_stats, h, STAT_NAMES)
         got.update(cd.chromosome_table(chromosome, got["start"].shape[0]), has_second=np.array(1))
         if resident:
             extra.update({f"{k}{t}": got[f"{k}{t}"] for k in ("read_off", "cigar_off") for t in (0, 1)})
@@ -106,7 +88,7 @@ def find_sites(illumina: Reads, pacbio: Reads, reference: str, positions: Sequen
     finally:
         if not keep:
             lib.hello_candidates_free(h)
-    return shard, dict(zip(STAT_NAMES, list(st))), extra
+    return shard, st, extra
 
 
 def split_bams(bam) -> Tuple[str, str]:

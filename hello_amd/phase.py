@@ -21,6 +21,7 @@ from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
+from ._abi import ARRAY_GETTER, READS, STATS_GETTER, bind, check, handle_array, handle_stats, i32, i64, vp
 from .bam import BamFile, Reads
 from .gvcf import counted
 
@@ -33,7 +34,6 @@ SLOTS, SLOT_OFFSETS, FIRST, LINKS, HP, PS = range(6)
 STAT_NAMES = ("records", "reads", "reads_counted", "slots", "observe_ms", "link_ms", "tag_ms", "plan_ms", "total_ms")
 
 _log = logging.getLogger(__name__)
-_bound = None
 _ACGT = frozenset(b"ACGT")
 
 
@@ -261,25 +261,18 @@ def phased_header(header: str) -> str:
 # ------------------------------------------------------------------------------------------------
 # the GPU
 # ------------------------------------------------------------------------------------------------
+_PROTOTYPES = (
+    ("hello_phase_observe", READS + [i64, vp, vp, vp, vp, i64, i32, i32, i32, i32, C.POINTER(vp)]),
+    ("hello_phase_chain", [vp, vp, i64, i32, i32, vp, vp]),
+    ("hello_phase_tag", [vp, vp, vp]),
+    ("hello_phase_array", ARRAY_GETTER),
+    ("hello_phase_stats", STATS_GETTER),
+    ("hello_phase_free", [vp], None),
+)
+
+
 def _lib():
-    global _bound
-    if _bound is None:
-        from .engine import load_library
-        lib = load_library()
-        vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
-        lib.hello_phase_observe.argtypes = [vp] * 11 + [i64, vp, vp, vp, vp, i64, i32, i32, i32, i32, C.POINTER(vp)]
-        lib.hello_phase_chain.argtypes = [vp, vp, i64, i32, i32, vp, vp]
-        lib.hello_phase_tag.argtypes = [vp, vp, vp]
-        lib.hello_phase_array.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(i64)]
-        lib.hello_phase_stats.argtypes = [vp, C.POINTER(C.c_double)]
-        lib.hello_phase_free.argtypes = [vp]
-        lib.hello_phase_free.restype = None
-        _bound = lib
-    return _bound
-
-
-def _fail(lib):
-    raise RuntimeError(lib.hello_last_error().decode(errors="replace"))
+    return bind(_PROTOTYPES)
 
 
 class Phaser:
@@ -302,21 +295,11 @@ class Phaser:
             raise ValueError("one or two read sets (BAM files)")
         r, source = Reads.concat(list(reads))
         ptr = lambda a: a.ctypes.data  # noqa: E731
-        rc = self._lib.hello_phase_observe(ptr(r.bases), ptr(r.quals), ptr(r.read_offsets), ptr(r.cigars), ptr(r.cigar_offsets),
-                                           ptr(r.ref_starts), ptr(r.ref_ends), ptr(r.mapq), ptr(r.flags), ptr(r.name_hash), ptr(source),
-                                           int(r.n_reads), ptr(self._starts), ptr(self._ends), ptr(self._alleles), ptr(self._offsets),
-                                           self.n_records, *self._tail, C.byref(self._h))
-        if rc != 0:
-            _fail(self._lib)
+        check(self._lib.hello_phase_observe(*r.pointers(source), int(r.n_reads), ptr(self._starts), ptr(self._ends),
+                                            ptr(self._alleles), ptr(self._offsets), self.n_records, *self._tail, C.byref(self._h)))
 
     def _array(self, which: int, dtype) -> np.ndarray:
-        p, n = C.c_void_p(), C.c_int64()
-        if self._lib.hello_phase_array(self._h, which, C.byref(p), C.byref(n)) != 0:
-            _fail(self._lib)
-        k = int(n.value)
-        if k == 0:
-            return np.zeros(0, dtype)
-        return np.frombuffer((C.c_char * (k * np.dtype(dtype).itemsize)).from_address(p.value), dtype).copy()
+        return handle_array(self._lib.hello_phase_array, self._h, which, dtype)
 
     def arrays(self) -> Dict[str, np.ndarray]:
         return dict(slots=self._array(SLOTS, np.int8), slot_offsets=self._array(SLOT_OFFSETS, np.int64),
@@ -326,15 +309,11 @@ class Phaser:
         sets, flip = np.ascontiguousarray(sets, np.int32), np.ascontiguousarray(flip, np.uint8)
         if sets.shape != (self.n_records,) or flip.shape != (self.n_records,):
             raise ValueError("set and flip: one entry per record")
-        if self._lib.hello_phase_tag(self._h, sets.ctypes.data, flip.ctypes.data) != 0:
-            _fail(self._lib)
+        check(self._lib.hello_phase_tag(self._h, sets.ctypes.data, flip.ctypes.data))
         return self._array(HP, np.uint8), self._array(PS, np.int64)
 
     def stats(self) -> Dict[str, float]:
-        st = (C.c_double * len(STAT_NAMES))()
-        if self._lib.hello_phase_stats(self._h, st) != 0:
-            _fail(self._lib)
-        return dict(zip(STAT_NAMES, list(st)))
+        return handle_stats(self._lib.hello_phase_stats, self._h, STAT_NAMES)
 
     def close(self) -> None:
         if self._h:
@@ -366,9 +345,8 @@ def chain_native(link, window: int = DEFAULT_WINDOW, min_margin: int = DEFAULT_M
         raise ValueError("chromosome: one entry per record")
     sets, flip = np.zeros(n, np.int32), np.zeros(n, np.uint8)
     lib = _lib()
-    if lib.hello_phase_chain(link.ctypes.data, chromosome.ctypes.data, n, int(window), int(min_margin), sets.ctypes.data,
-                             flip.ctypes.data) != 0:
-        _fail(lib)
+    check(lib.hello_phase_chain(link.ctypes.data, chromosome.ctypes.data, n, int(window), int(min_margin), sets.ctypes.data,
+                                flip.ctypes.data))
     return sets, flip
 
 

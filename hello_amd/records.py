@@ -15,7 +15,8 @@ from typing import Dict, Optional, Sequence
 
 import numpy as np
 
-from .engine import _check, load_library
+from ._abi import bind, i32, i64, vp
+from .engine import _check
 
 
 class _SiteTable(C.Structure):
@@ -39,30 +40,18 @@ class _View(C.Structure):
                 ("best_pair", C.c_void_p), ("best_p", C.c_void_p), ("qual", C.c_void_p)]
 
 
-_bound = None
+_TAIL = [vp, vp, i32, C.POINTER(_FeaturesFormat), i32, C.POINTER(vp)]
+_PROTOTYPES = (
+    ("hello_site_records", [C.POINTER(_SiteTable), vp, i64] + _TAIL),
+    ("hello_site_records_annotated", [C.POINTER(_SiteTable), vp, vp, vp, i64] + _TAIL),
+    ("hello_site_records_evidence", [C.POINTER(_SiteTable)] + [vp] * 4 + [i32, vp, i64] + _TAIL),
+    ("hello_records_get", [vp, C.POINTER(_View)]),
+    ("hello_records_destroy", [vp], None),
+)
 
 
 def _lib():
-    global _bound
-    if _bound is None:
-        lib = load_library()
-        lib.hello_site_records.argtypes = [C.POINTER(_SiteTable), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
-                                           C.POINTER(_FeaturesFormat), C.c_int32, C.POINTER(C.c_void_p)]
-        lib.hello_site_records.restype = C.c_int
-        lib.hello_site_records_annotated.argtypes = [C.POINTER(_SiteTable), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
-                                                     C.c_void_p, C.c_int32, C.POINTER(_FeaturesFormat), C.c_int32,
-                                                     C.POINTER(C.c_void_p)]
-        lib.hello_site_records_annotated.restype = C.c_int
-        lib.hello_site_records_evidence.argtypes = [C.POINTER(_SiteTable)] + [C.c_void_p] * 4 + [C.c_int32, C.c_void_p, C.c_int64,
-                                                    C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(_FeaturesFormat), C.c_int32,
-                                                    C.POINTER(C.c_void_p)]
-        lib.hello_site_records_evidence.restype = C.c_int
-        lib.hello_records_get.argtypes = [C.c_void_p, C.POINTER(_View)]
-        lib.hello_records_get.restype = C.c_int
-        lib.hello_records_destroy.argtypes = [C.c_void_p]
-        lib.hello_records_destroy.restype = None
-        _bound = lib
-    return _bound
+    return bind(_PROTOTYPES)
 
 
 _meta_format = None

@@ -16,7 +16,7 @@ from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .engine import load_library
+from ._abi import bind, check, i32, i64, vp
 from .shards import SiteShard
 
 HELLO_CANDIDATES_RESIDENT = 64
@@ -24,26 +24,16 @@ GATHER_ARRAYS = ("bases", "quals", "read_off", "cigars", "cigar_off", "ref_start
 NOT_WRITABLE = ("a resident shard keeps its reads on the GPU and cannot be written as a .hshard file or read as host arrays: build "
                 "the candidates without resident=True for that")
 
-_bound = None
+_PROTOTYPES = (
+    ("hello_candidates_featurizer_counts", [vp, i32] + [C.POINTER(i64)] * 3),
+    ("hello_candidates_gather", [vp, i32] + [vp] * 10 + [i64] * 4 + [vp]),
+    ("hello_candidates_gather_table", [vp, i64, vp, vp, i64, vp, vp, vp, C.POINTER(i64)]),
+    ("hello_candidates_free", [vp], None),
+)
 
 
 def _lib():
-    global _bound
-    if _bound is None:
-        lib = load_library()
-        vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
-        lib.hello_candidates_featurizer_counts.argtypes = [vp, i32] + [C.POINTER(i64)] * 3
-        lib.hello_candidates_gather.argtypes = [vp, i32] + [vp] * 10 + [i64] * 4 + [vp]
-        lib.hello_candidates_gather_table.argtypes = [vp, i64, vp, vp, i64, vp, vp, vp, C.POINTER(i64)]
-        lib.hello_candidates_free.argtypes = [vp]
-        lib.hello_candidates_free.restype = None
-        _bound = lib
-    return _bound
-
-
-def _raise(lib, rc: int):
-    message = lib.hello_last_error().decode(errors="replace")
-    raise (ValueError if rc == -1 else RuntimeError)(message)
+    return bind(_PROTOTYPES)
 
 
 def gather_table(reads_per_allele: Sequence[int], read_off: Sequence[int], cigar_off: Sequence[int]) -> Dict[str, np.ndarray]:
@@ -57,16 +47,13 @@ def gather_table(reads_per_allele: Sequence[int], read_off: Sequence[int], cigar
     if read_off.shape[0] != real + 1 or cigar_off.shape[0] != real + 1:
         raise ValueError(f"read_off and cigar_off must hold {real + 1} offsets for {real} supporting reads")
     n = C.c_int64()
-    rc = lib.hello_candidates_gather_table(counts.ctypes.data, counts.shape[0], read_off.ctypes.data, cigar_off.ctypes.data, 0,
-                                           None, None, None, C.byref(n))
-    if rc != 0:
-        _raise(lib, rc)
+    check(lib.hello_candidates_gather_table(counts.ctypes.data, counts.shape[0], read_off.ctypes.data, cigar_off.ctypes.data, 0,
+                                            None, None, None, C.byref(n)), value_error_on_arg=True)
     k = int(n.value)
     source, out_read, out_cigar = np.zeros(k, np.int64), np.zeros(k + 1, np.int64), np.zeros(k + 1, np.int64)
-    rc = lib.hello_candidates_gather_table(counts.ctypes.data, counts.shape[0], read_off.ctypes.data, cigar_off.ctypes.data, k,
-                                           source.ctypes.data, out_read.ctypes.data, out_cigar.ctypes.data, C.byref(n))
-    if rc != 0:
-        _raise(lib, rc)
+    check(lib.hello_candidates_gather_table(counts.ctypes.data, counts.shape[0], read_off.ctypes.data, cigar_off.ctypes.data, k,
+                                            source.ctypes.data, out_read.ctypes.data, out_cigar.ctypes.data, C.byref(n)),
+          value_error_on_arg=True)
     return dict(source=source, read_off=out_read, cigar_off=out_cigar)
 
 
@@ -113,9 +100,7 @@ class ResidentShard(SiteShard):
 
     def _featurizer_counts(self, tech: int) -> Tuple[int, int, int]:
         n = [C.c_int64(), C.c_int64(), C.c_int64()]
-        rc = self._lib.hello_candidates_featurizer_counts(self.handle, tech, *[C.byref(x) for x in n])
-        if rc != 0:
-            _raise(self._lib, rc)
+        check(self._lib.hello_candidates_featurizer_counts(self.handle, tech, *[C.byref(x) for x in n]), value_error_on_arg=True)
         return tuple(int(x.value) for x in n)
 
     # -- the device side --------------------------------------------------------------------------------------------
@@ -125,10 +110,9 @@ class ResidentShard(SiteShard):
         address).  The shard must stay open until the stream has passed the launch."""
         if self.handle is None:
             raise ValueError("this resident shard is closed: its device memory was released")
-        rc = self._lib.hello_candidates_gather(self.handle, tech, *[pointers[k] for k in GATHER_ARRAYS], int(read_shift),
-                                               int(base_shift), int(cigar_shift), int(site_shift), stream or None)
-        if rc != 0:
-            _raise(self._lib, rc)
+        check(self._lib.hello_candidates_gather(self.handle, tech, *[pointers[k] for k in GATHER_ARRAYS], int(read_shift),
+                                                int(base_shift), int(cigar_shift), int(site_shift), stream or None),
+              value_error_on_arg=True)
 
     def close(self) -> None:
         if getattr(self, "handle", None) is not None:
