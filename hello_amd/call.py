@@ -46,10 +46,17 @@ after ``results.output.vcf`` is complete: its records byte for byte, and referen
 after ``results.output.vcf`` is complete: its lines in its order, the heterozygous records that the reads link rewritten as ``a|b``
 with a phase set (``PS``), observed, linked and tagged on the GPU in a pass of its own over the BAM(s) (``hello_amd.phase``;
 DESIGN.md section 7g).
+
+``--haplotag_vcf V`` (with ``--from_bam`` / ``--from_bams`` and ``--include_hp``, not in the reference, off by default) gives every
+read the candidate stage fetches a haplotag from the phased VCF ``V`` (``a|b`` records with ``PS``) in place of the BAM's own ``HP``
+tag, on the GPU (``hello_amd.haplotag``) -- the reference's workflow for its haplotagged PacBio model, without
+the outside tool that writes a tagged BAM.  ``--haplotag`` needs no phased VCF: pass 1 is this command with ``--phase`` in
+``<workdir>/haplotag_pass1``, pass 2 is this command with ``--haplotag_vcf`` on pass 1's ``results.output.phased.vcf``.
 """
 from __future__ import annotations
 
 import argparse
+import functools
 import glob
 import logging
 import os
@@ -284,6 +291,14 @@ def parser() -> argparse.ArgumentParser:
                     help="--phase: a record is linked to this many heterozygous records before it (1 to 32)")
     ap.add_argument("--phase_min_margin", type=int, default=2,
                     help="--phase: the smallest |cis - trans| read count that joins a record to a phase set (at least 1)")
+    ap.add_argument("--haplotag_vcf",
+                    help="with --from_bam / --from_bams and --include_hp: a phased VCF (a|b records with PS); every read the candidate "
+                         "stage fetches gets its haplotag from it on the GPU, in place of the BAM's own HP tag (not in the reference; "
+                         "one GPU)")
+    ap.add_argument("--haplotag", action="store_true", default=False,
+                    help="with --from_bam / --from_bams and --include_hp: two passes -- this command with --phase in "
+                         "<workdir>/haplotag_pass1, then this command with --haplotag_vcf on the phased VCF of pass 1 (not in the "
+                         "reference; one GPU)")
     ap.add_argument("--device", type=int, default=0, help="GPU of a single-process run")
     ap.add_argument("--gpus", type=int, default=1,
                     help="processes / GPUs of this node: > 1 re-launches this command under torch.distributed.run "
@@ -420,11 +435,14 @@ def shards_from_bam(args) -> str:
     from . import candidates as cd
     logger = logging.getLogger("hello_amd.call")
     genome, ns, bam, find = _from_bam_stages(args)
+    tagger = haplotagger_of(args)
+    find = _tagged(find, tagger)
     out_dir = os.path.join(args.workdir, "shards")
     os.makedirs(out_dir, exist_ok=True)
     for n, name in _shard_files(ns):
         _, st = cd.run_activity(bam, args.ref, name, os.path.join(out_dir, "shard%d" % n), device=args.device, genome=genome, find=find)
         logger.info("%s: %d sites", name, st.get("sites", 0))
+    _close_haplotagger(tagger)
     return out_dir
 
 
@@ -436,13 +454,15 @@ def shards_from_bams(args) -> str:
     from . import hybrid as hy
     logger = logging.getLogger("hello_amd.call")
     genome, ns, bams = _from_bams_stages(args)
+    tagger = haplotagger_of(args)
     out_dir = os.path.join(args.workdir, "shards")
     os.makedirs(out_dir, exist_ok=True)
     for n, name in _shard_files(ns):
         _, st = hy.run_activity(bams, args.ref, name, os.path.join(out_dir, "shard%d" % n), args.hybrid_hotspot,
                                 args.reconcilement_size, q_threshold=args.q_threshold, mapq_threshold=args.mapq_threshold,
-                                device=args.device, genome=genome)
+                                device=args.device, genome=genome, find=_tagged(None, tagger))
         logger.info("%s: %d sites, %d PacBio reads reassigned", name, st.get("sites", 0), st.get("pacbio_reads_reassigned", 0))
+    _close_haplotagger(tagger)
     return out_dir
 
 
@@ -536,6 +556,73 @@ def phase_pass(args, result_path: str) -> Optional[str]:
     return out
 
 
+def check_haplotag(args) -> None:
+    """The refusals of --haplotag_vcf and --haplotag, each naming the fix."""
+    vcf_given, two_passes = bool(getattr(args, "haplotag_vcf", None)), bool(getattr(args, "haplotag", False))
+    if not (vcf_given or two_passes):
+        return
+    flag = "--haplotag_vcf" if vcf_given else "--haplotag"
+    if vcf_given and two_passes:
+        raise SystemExit("--haplotag_vcf tags the reads from a phased VCF that exists, --haplotag from one it makes in a first pass: "
+                         "give one of the two")
+    if not (getattr(args, "from_bam", False) or getattr(args, "from_bams", False)) or args.shards:
+        raise SystemExit(f"{flag} tags the reads the candidate stage fetches from the BAM(s), and shard files hold reads that were "
+                         f"fetched before: add --from_bam (one BAM) or --from_bams (--ibam and --pbam) and drop --shards, or drop {flag}")
+    if not getattr(args, "include_hp", False):
+        raise SystemExit(f"{flag} without --include_hp: the model would not read the haplotags (six pileup channels); add --include_hp "
+                         f"with a model of seven channels, or drop {flag}")
+    if getattr(args, "gpus", 1) > 1 or ("RANK" in os.environ and "WORLD_SIZE" in os.environ):
+        raise SystemExit(f"{flag} tags the reads in the process that builds the candidate sites, on one GPU: run it with --gpus 1 as a "
+                         f"plain command, or drop {flag}")
+
+
+def haplotagger_of(args):
+    """--haplotag_vcf: one ``haplotag.Haplotagger`` over the file, at the thresholds the route's own stages run with (the choice of
+    ``phase_pass``); None without the flag."""
+    if not getattr(args, "haplotag_vcf", None):
+        return None
+    from . import candidates as cd, haplotag
+    q, mq = (args.q_threshold, args.mapq_threshold) if getattr(args, "from_bams", False) else (cd.DEFAULT_Q_THRESHOLD, cd.DEFAULT_MIN_MAPQ)
+    return haplotag.Haplotagger(args.haplotag_vcf, args.chromosomes.split(",") if args.chromosomes else None, q, mq, args.device)
+
+
+def _tagged(find, tagger):
+    """``find`` (None: ``hybrid.find_hybrid_candidates``) with the tagger bound, or ``find`` itself without one."""
+    if tagger is None:
+        return find
+    if find is None:
+        from .hybrid import find_hybrid_candidates as find
+    return functools.partial(find, tagger=tagger)
+
+
+def _close_haplotagger(tagger) -> None:
+    if tagger is None:
+        return
+    st = tagger.stats
+    tagger.close()
+    logging.getLogger("hello_amd.call").info(
+        "haplotags from %d phased records: %d reads tagged 1, %d tagged 2, %d tagged 0 in %d calls (kernel %.1f ms of %.1f ms)",
+        int(st["records"]), int(st["reads_hp1"]), int(st["reads_hp2"]), int(st["reads"] - st["reads_hp1"] - st["reads_hp2"]),
+        int(st["calls"]), st["kernel_ms"], st["total_ms"])
+
+
+def haplotag_passes(args) -> str:
+    """--haplotag: pass 1 is this command without --haplotag, --gvcf, --annotate and --annotate_evidence and with --phase, in
+    ``<workdir>/haplotag_pass1``; pass 2 is this command with --haplotag_vcf on pass 1's phased VCF, in ``<workdir>``.  Both run in
+    this process, each as the command would run alone (the hotspot stage runs twice)."""
+    logger = logging.getLogger("hello_amd.call")
+    first = argparse.Namespace(**vars(args))
+    first.haplotag = first.gvcf = first.annotate = first.annotate_evidence = False
+    first.phase = True
+    first.workdir = os.path.join(args.workdir, "haplotag_pass1")
+    phased_path = main(first)[:-len(".vcf")] + ".phased.vcf"
+    logger.info("--haplotag: pass 1 wrote %s; pass 2 tags the reads from it", phased_path)
+    second = argparse.Namespace(**vars(args))
+    second.haplotag = False
+    second.haplotag_vcf = phased_path
+    return main(second)
+
+
 def run_resident(args) -> str:
     """--from_bam / --from_bams with --resident: hotspots and ``shard<N>.txt`` as ``shards_from_bam(s)`` write them, then ONE loop
     in this process: shard file -> candidate sites whose reads stay on the GPU (``candidates.resident_activity``) -> ``ShardScorer``
@@ -546,6 +633,7 @@ def run_resident(args) -> str:
     check_resident(args)
     check_gvcf(args)
     check_phase(args)
+    check_haplotag(args)
     if args.from_bams:
         from . import hybrid as hy
         genome, ns, bam = _from_bams_stages(args)
@@ -554,6 +642,8 @@ def run_resident(args) -> str:
     else:
         genome, ns, bam, find = _from_bam_stages(args)
         kw = {}
+    tagger = haplotagger_of(args)
+    find = _tagged(find, tagger)
     files = list(_shard_files(ns))
     features_dir = os.path.join(args.workdir, features_dir_name(args.ibam, args.pbam))
     os.makedirs(features_dir, exist_ok=True)
@@ -579,6 +669,7 @@ def run_resident(args) -> str:
                    in_thread=True, annotate=getattr(args, "annotate", False), evidence=getattr(args, "annotate_evidence", False))
     evidence = _header_evidence(args, network)
     network.close()
+    _close_haplotagger(tagger)
     logger.info("%d shard files, %d sites, %d reads in %d launches, %.2f s (candidate stage %.2f s of it, %.1f ms in its kernels; "
                 "staging %.2f s, record stage %.2f s on its threads; resident set after the loop %.0f MB)", len(files), stats.sites,
                 stats.reads, stats.launches, stats.seconds, stats.wait_read,
@@ -601,6 +692,9 @@ def main(args) -> str:
     logger = logging.getLogger("hello_amd.call")
     check_gvcf(args)
     check_phase(args)
+    check_haplotag(args)
+    if getattr(args, "haplotag", False):
+        return haplotag_passes(args)
     if getattr(args, "resident", False):
         return run_resident(args)
     if getattr(args, "from_bams", False) and not args.shards:

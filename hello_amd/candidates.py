@@ -141,11 +141,12 @@ def chromosome_table(chromosome: str, n_sites: int) -> Dict[str, np.ndarray]:
 def find_candidates(bam, fasta: Optional[str], chromosome: str, positions: Sequence[int], q_threshold: int = DEFAULT_Q_THRESHOLD,
                     mapq_threshold: int = DEFAULT_MIN_MAPQ, device: int = 0, feature_length: int = 150, pacbio: bool = False,
                     hybrid_hotspot: bool = False, reference: Optional[str] = None,
-                    stats: Optional[dict] = None, resident: bool = False) -> shards.PackedShard:
+                    stats: Optional[dict] = None, resident: bool = False, tagger=None) -> shards.PackedShard:
     """The candidate sites of the sorted hotspot ``positions`` of ``chromosome`` as a validated ``PackedShard``: sites, alleles
     (reference allele first, then ascending byte order) and every allele's supporting reads (file order).  ``bam``: one path
     (a list of two, ``pacbio`` and ``hybrid_hotspot`` are refused).  ``stats``: filled with the statistics of the call.
-    ``resident``: a ``resident.ResidentShard`` whose reads stay on the GPU."""
+    ``resident``: a ``resident.ResidentShard`` whose reads stay on the GPU.  ``tagger``: a ``haplotag.Haplotagger``; the reads
+    fetched get its haplotags in place of the BAM's HP tags before the sites are looked for."""
     paths = [bam] if isinstance(bam, str) else list(bam)
     if len(paths) != 1 or pacbio or hybrid_hotspot:
         raise ValueError(REFUSAL)
@@ -160,6 +161,8 @@ def find_candidates(bam, fasta: Optional[str], chromosome: str, positions: Seque
         hi = int(positions.max()) + MIN_DISTANCE // 2 + FLANKING_BASES
     with BamFile(paths[0]) as b:
         reads = b.fetch(chromosome, lo, max(hi, lo))
+    if tagger is not None:
+        reads = tagger.retag(chromosome, reads)
     shard, st, extra = find_sites(reads, reference, positions, chromosome, feature_length, q_threshold, mapq_threshold, device,
                                   resident=resident)
     if stats is not None:

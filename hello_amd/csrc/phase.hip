@@ -6,8 +6,9 @@
 // Host: the read filter, the validation of every counted read (the kernel reads within its bases), per counted read its reference
 // end from the CIGAR, the contiguous range of records whose start it covers (two binary searches in the sorted record starts) and,
 // by an exclusive scan of those counts, the offset of its first slot.  Device, three kernels:
-//   observe: a wave per counted read.  The lanes hold the read's candidate records, 64 per round; the walk over the CIGAR is
-//     wave-uniform (one operation at a time, the same for all lanes, ended once every lane's record lies behind the cursor), and a
+//   observe: a wave per counted read.  The lanes hold the read's candidate records, 64 per round; the walk over the CIGAR
+//     (phase_walk.h, which haplotag.hip includes too) is wave-uniform
+//     (one operation at a time, the same for all lanes, ended once every lane's record lies behind the cursor), and a
 //     lane only has work where an operation meets its own span -- it compares the bases it would append with both alleles as it
 //     goes, so no string is stored.  Each lane writes the slot of its own record: one writer per slot, no reduction across lanes.
 //     (The opposite assignment -- lanes over the bases of an operation, a loop over the records -- puts 64 lanes on spans that are
@@ -20,6 +21,7 @@
 #include <climits>
 #include <memory>
 
+#include "phase_walk.h"
 #include "stage_host.h"
 
 namespace hello {
@@ -54,69 +56,14 @@ __global__ __launch_bounds__(kPhThreads) void phase_observe_kernel(PhObserveArgs
     if (k >= a.n_counted) return;
     const int64_t s0 = a.slot_off[k], n_cand = a.slot_off[k + 1] - s0;
     if (n_cand == 0) return;
-    const int64_t r = a.list[k], rs = a.ref_start[r], re = a.list_end[k], t0 = a.first[k];
-    const uint8_t* bases = a.bases + a.read_off[r];
-    const uint8_t* quals = a.quals + a.read_off[r];
-    const int64_t c0 = a.cigar_off[r], n_ops = a.cigar_off[r + 1] - c0;
+    const int64_t r = a.list[k], t0 = a.first[k], c0 = a.cigar_off[r];
+    const PhWalkRead rd{a.bases + a.read_off[r], a.quals + a.read_off[r], a.cigars + c0, a.cigar_off[r + 1] - c0, a.ref_start[r],
+                        a.list_end[k]};
+    const PhWalkTable tb{a.rec_start, a.rec_end, a.alleles, a.allele_off};
     for (int64_t round = 0; round < n_cand; round += 64) {
         const int64_t j = round + lane;
         const bool mine = j < n_cand;
-        int64_t A = 0, B = 0, la = 0, lb = 0;
-        const uint8_t* al_a = a.alleles;
-        const uint8_t* al_b = a.alleles;
-        if (mine) {
-            const int64_t t = t0 + j;
-            A = a.rec_start[t];
-            B = a.rec_end[t];
-            const int64_t o0 = a.allele_off[2 * t], o1 = a.allele_off[2 * t + 1], o2 = a.allele_off[2 * t + 2];
-            al_a += o0;
-            al_b += o1;
-            la = o1 - o0;
-            lb = o2 - o1;
-        }
-        bool dead = !mine || !(B < re);                                   // the base behind the span must be aligned
-        bool ma = true, mb = true;
-        int64_t len = 0;
-        int minq = 255;
-        auto append = [&](int64_t i) {
-            const unsigned char c = bases[i] & 0xDF;
-            const int q = quals[i];
-            ma = ma && len < la && al_a[len] == c;
-            mb = mb && len < lb && al_b[len] == c;
-            minq = q < minq ? q : minq;
-            ++len;
-        };
-        int64_t rf = rs, rd = 0;
-        for (int64_t ci = 0; ci < n_ops; ++ci) {
-            if (!__any(!dead && rf <= B)) break;                          // every lane's span lies behind the cursor
-            const unsigned c = a.cigars[c0 + ci];
-            const int op = c & 15u;
-            const int64_t n = c >> 4;
-            if (op == BAM_CMATCH || op == BAM_CEQUAL || op == BAM_CDIFF) {
-                if (!dead) {
-                    const int64_t j0 = A > rf ? A - rf : 0, j1 = B - rf < n ? B - rf : n;
-                    for (int64_t i = j0; i < j1 && (ma || mb); ++i) append(rd + i);
-                }
-                rf += n;
-                rd += n;
-            } else if (op == BAM_CINS) {
-                if (!dead && rf - 1 >= A && rf - 1 < B)
-                    for (int64_t i = 0; i < n && (ma || mb); ++i) append(rd + i);
-                rd += n;
-            } else if (op == BAM_CDEL) {
-                rf += n;
-            } else if (op == BAM_CREF_SKIP) {
-                if (rf < B && rf + n > A) dead = true;
-                rf += n;
-            } else if (op == BAM_CSOFT_CLIP) {
-                rd += n;
-            }
-        }
-        int o = -1;
-        if (!dead && minq >= a.q_threshold) {
-            if (ma && len == la) o = 0;
-            else if (mb && len == lb) o = 1;
-        }
+        const int o = phase_walk_observe(rd, tb, t0 + j, mine, a.q_threshold);     // every lane: the walk votes across the wave
         if (mine) a.slots[s0 + j] = (int8_t)o;
     }
 }

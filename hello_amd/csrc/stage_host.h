@@ -1,4 +1,4 @@
-// The HIP host layer under the BAM-side stages (hotspots.hip, candidates.hip, refblocks.hip, phase.hip): opening the device,
+// The HIP host layer under the BAM-side stages (hotspots.hip, candidates.hip, refblocks.hip, phase.hip, haplotag.hip): opening the device,
 // owned device memory, the upload of a read set, timing a launch, and the tail of an entry point.  No kernel lives here.
 #pragma once
 #include <utility>
@@ -42,6 +42,12 @@ struct DevMem {
         HS_HIP(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)));
         ptrs.push_back(p);
         if (n) HS_HIP(hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice));
+        return (T*)p;
+    }
+    template <class T> T* room(size_t n) {                         // not initialised: for what a kernel writes in full
+        void* p = nullptr;
+        HS_HIP(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)));
+        ptrs.push_back(p);
         return (T*)p;
     }
     template <class T> T* zeros(size_t n) {

@@ -104,11 +104,13 @@ def find_hybrid_candidates(bams, fasta: Optional[str], chromosome: str, position
                            reassembly_size: int = DEFAULT_REASSEMBLY_SIZE, q_threshold: int = cd.DEFAULT_Q_THRESHOLD,
                            mapq_threshold: int = cd.DEFAULT_MIN_MAPQ, device: int = 0, feature_length: int = 150,
                            reference: Optional[str] = None, stats: Optional[dict] = None,
-                           resident: bool = False) -> shards.PackedShard:
+                           resident: bool = False, tagger=None) -> shards.PackedShard:
     """The candidate sites of the sorted hotspot ``positions`` of ``chromosome`` from ``bams`` = [Illumina BAM, PacBio BAM] as a
     validated hybrid ``PackedShard``: alleles in the order of ``candidates.find_candidates``, every allele's supporting reads
     per technology in file order, the PacBio reads clipped.  ``stats``: filled with the statistics of the call.  ``resident``: a
-    ``resident.ResidentShard`` whose reads of both technologies stay on the GPU."""
+    ``resident.ResidentShard`` whose reads of both technologies stay on the GPU.  ``tagger``: a ``haplotag.Haplotagger``; the reads
+    fetched from each BAM get its haplotags in place of the BAM's HP tags, on the full alignments, before any clipping or
+    reconciliation."""
     ibam, pbam = split_bams(bams)
     if reference is None:
         from .hotspots import _read_reference
@@ -123,6 +125,8 @@ def find_hybrid_candidates(bams, fasta: Optional[str], chromosome: str, position
         illumina = b.fetch(chromosome, lo, max(hi, lo))
     with BamFile(pbam) as b:
         pacbio = b.fetch(chromosome, lo, max(hi, lo))
+    if tagger is not None:
+        illumina, pacbio = tagger.retag(chromosome, illumina), tagger.retag(chromosome, pacbio)
     shard, st, extra = find_sites(illumina, pacbio, reference, positions, chromosome, hybrid_hotspot, reassembly_size, feature_length,
                                   q_threshold, mapq_threshold, device, resident=resident)
     if stats is not None:
@@ -153,8 +157,11 @@ def concat_payloads(parts: Sequence[shards.PackedShard]) -> dict:
 
 def run_activity(bams, fasta: str, activity: str, output_prefix: str, hybrid_hotspot: bool = False,
                  reassembly_size: int = DEFAULT_REASSEMBLY_SIZE, feature_length: int = 150, q_threshold: int = cd.DEFAULT_Q_THRESHOLD,
-                 mapq_threshold: int = cd.DEFAULT_MIN_MAPQ, device: int = 0, genome: Optional[Dict[str, str]] = None) -> Tuple[str, Dict[str, float]]:
-    """One activity file -> ``<output_prefix>.hshard`` (both technologies) and the summed statistics."""
+                 mapq_threshold: int = cd.DEFAULT_MIN_MAPQ, device: int = 0, genome: Optional[Dict[str, str]] = None,
+                 find=None) -> Tuple[str, Dict[str, float]]:
+    """One activity file -> ``<output_prefix>.hshard`` (both technologies) and the summed statistics.  ``find``: the function with
+    ``find_hybrid_candidates``' signature that builds one chromosome's shard (default: ``find_hybrid_candidates``)."""
+    find = find or find_hybrid_candidates
     from .call import read_fasta
     by_chromosome = cd.read_positions(activity)
     if genome is None:
@@ -164,8 +171,8 @@ def run_activity(bams, fasta: str, activity: str, output_prefix: str, hybrid_hot
         if chromosome not in genome:
             raise ValueError(f"{fasta}: no sequence named {chromosome!r}")
         st: dict = {}
-        parts.append(find_hybrid_candidates(bams, fasta, chromosome, positions, hybrid_hotspot, reassembly_size, q_threshold,
-                                            mapq_threshold, device, feature_length, reference=genome[chromosome], stats=st))
+        parts.append(find(bams, fasta, chromosome, positions, hybrid_hotspot, reassembly_size, q_threshold, mapq_threshold, device,
+                          feature_length, reference=genome[chromosome], stats=st))
         for k in STAT_NAMES:
             total[k] = total.get(k, 0.0) + st[k]
     path = output_prefix + ".hshard"

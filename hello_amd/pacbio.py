@@ -26,11 +26,12 @@ from .hotspots import HOTSPOTS_PACBIO
 def find_pacbio_candidates(bam, fasta: Optional[str], chromosome: str, positions: Sequence[int],
                            q_threshold: int = cd.DEFAULT_Q_THRESHOLD, mapq_threshold: int = cd.DEFAULT_MIN_MAPQ, device: int = 0,
                            feature_length: int = 150, reference: Optional[str] = None,
-                           stats: Optional[dict] = None, resident: bool = False) -> shards.PackedShard:
+                           stats: Optional[dict] = None, resident: bool = False, tagger=None) -> shards.PackedShard:
     """The candidate sites of the sorted hotspot ``positions`` of ``chromosome`` from one PacBio BAM as a validated
     ``PackedShard``; alleles and supporting reads in the orders of ``candidates.find_candidates``, the reads clipped.  ``bam``:
     one path.  ``stats``: filled with the statistics of the call.  ``resident``: a ``resident.ResidentShard`` whose reads (the
-    clipped copies) stay on the GPU where the clip kernel wrote them."""
+    clipped copies) stay on the GPU where the clip kernel wrote them.  ``tagger``: a ``haplotag.Haplotagger``; the reads fetched
+    get its haplotags in place of the BAM's HP tags, on the full alignments, before anything is clipped."""
     paths = [bam] if isinstance(bam, str) else list(bam)
     if len(paths) != 1 or "," in paths[0]:
         raise ValueError(cd.REFUSAL)
@@ -45,6 +46,8 @@ def find_pacbio_candidates(bam, fasta: Optional[str], chromosome: str, positions
         hi = int(positions.max()) + cd.MIN_DISTANCE // 2 + cd.FLANKING_BASES
     with BamFile(paths[0]) as b:
         reads = b.fetch(chromosome, lo, max(hi, lo))
+    if tagger is not None:
+        reads = tagger.retag(chromosome, reads)
     shard, st, extra = cd.find_sites(reads, reference, positions, chromosome, feature_length, q_threshold, mapq_threshold, device,
                                      options=HOTSPOTS_PACBIO, resident=resident)
     if stats is not None:

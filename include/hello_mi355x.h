@@ -807,6 +807,36 @@ int hello_phase_array(const hello_phase* phase, int32_t which, const void** data
 int hello_phase_stats(const hello_phase* phase, double* stats);
 void hello_phase_free(hello_phase* phase);
 
+/* Haplotags from a phased VCF (not in the reference; DESIGN.md section 7h states the rule, hello_amd/haplotag.py restates it in
+ * Python).  One handle per chromosome; it keeps the record table on the device.
+ *   hello_haplotag_create: the chromosome's phased records -- record_starts / record_ends [n_records] (the span [POS - 1,
+ *          POS - 1 + len(REF)), sorted by start), `alleles` with allele_offsets [2 n_records + 1]: the haplotype-1 then the
+ *          haplotype-2 allele of every record, upper case, and ps [n_records], the records' positive phase sets -- validated and
+ *          uploaded once.  NULL pointers, n_records < 0, records that are not sorted and a phase set below 1 are refused
+ *          (HELLO_ERR_ARG) before the device is opened; n_records == 0 opens none.
+ *   hello_haplotag_reads: reads: the arrays of hello_bam_fetch (`source` is not read and may be NULL: a read is tagged alike
+ *          whichever BAM it came from); a read counts by the rule of hello_refblocks_find, and a counted read whose CIGAR consumes
+ *          more bases than it has is refused (HELLO_ERR_ARG) before any launch.  One fused launch, a wave per read: the read's
+ *          candidate records by two searches in the table, the walk of hello_phase_observe at each, and across the wave the phase
+ *          set of the read's first observation and the counts n1 / n2 of its observations in that set.  hp [n_reads]: 1, 2, or 0
+ *          (a tie, no observation, an uncounted read); ps [n_reads]: that set, also at a tie, or 0.  n_records == 0 or
+ *          n_reads == 0 launches nothing and gives zeros.  Any number of calls, in any order: the result of a read depends on
+ *          that read and the table alone.
+ * Host memory in and out; haplotag.hip. */
+#define HELLO_HAPLOTAG_STATS 9
+typedef struct hello_haplotag hello_haplotag;
+int hello_haplotag_create(const int64_t* record_starts, const int64_t* record_ends, const uint8_t* alleles,
+                          const int64_t* allele_offsets, const int64_t* ps, int64_t n_records, int32_t device,
+                          hello_haplotag** handle);
+int hello_haplotag_reads(hello_haplotag* haplotag, const uint8_t* bases, const uint8_t* quals, const int64_t* read_offsets,
+                         const uint32_t* cigars, const int64_t* cigar_offsets, const int64_t* ref_starts, const int64_t* ref_ends,
+                         const uint8_t* mapq, const uint16_t* flags, const uint64_t* name_hash, const uint8_t* source, int64_t n_reads,
+                         int32_t q_threshold, int32_t mapq_threshold, uint8_t* hp, int64_t* ps);
+/* stats[HELLO_HAPLOTAG_STATS]: records, calls, reads given, reads counted, reads with hp 1, reads with hp 2, kernel ms (HIP
+ * events), plan ms (the host's walk over the reads), total ms of create and the calls */
+int hello_haplotag_stats(const hello_haplotag* haplotag, double* stats);
+void hello_haplotag_free(hello_haplotag* haplotag);
+
 #ifdef __cplusplus
 }
 #endif
