@@ -8,10 +8,12 @@ shard in a process pool -- one site at a time: featurise (C++), score (torch CPU
 ``.features`` entry (caller_calling.py:859-900) -- checks every shard log for the sentinel ``Completed running the
 script`` (:225-229) and lets ``prepareVcf.main`` build the final VCF from the ``.features`` files (:233-241).
 
-This driver keeps that contract from the point where a shard's candidate sites exist (``hello_amd.shards``: BAM /
-FASTA ingestion, hotspot detection and allele assembly need pysam and the C++ searcher and stay upstream), and runs
-everything after it at the engine's rate (``hello_amd.shard_pipeline``): reader threads load shards with bounded
-read-ahead; several shards are coalesced into one GPU launch
+This driver keeps that contract.  ``--shards`` starts where a shard's candidate sites exist (``hello_amd.shards``);
+``--from_bam`` / ``--from_bams`` start from the BAM(s) and build them on the GPU first (``hello_amd.hotspots``, then
+``hello_amd.candidates`` / ``hello_amd.pacbio`` / ``hello_amd.hybrid``; ``hello_amd.route`` says which BAMs, options and
+thresholds every stage of a route runs with).  Everything after the candidate sites runs at the engine's rate
+(``hello_amd.shard_pipeline``): reader threads load shards with bounded read-ahead; several shards are coalesced into one
+GPU launch
 
     reads + CIGARs --hello_engine_featurize--> uint8 pileups (device) --hello_engine_forward--> logits, meta, pair
     posteriors --hello_site_records (host threads)--> record lines (caller_calling.py:698-743), ``.features`` entries
@@ -27,9 +29,10 @@ to the ranks as contiguous runs balanced by read count (``hello_amd.shard.partit
 totals), every rank writes its shards' files, and after ONE barrier rank 0 merges the final VCF from the files and the
 ranks' key indexes -- the ranks exchange no pileup or posterior data (the reference's pool does not either,
 call.py:215-221).
-Flags of the reference that configure upstream stages (--hybrid_hotspot, --q_threshold, --mapq_threshold,
---reconcilement_size, --chromosomes) are accepted so existing command lines keep working; --ibam / --pbam only name
-the features directory the way ``get_workdir`` does (call.py:40-48).
+The reference's flags for the stages before the candidate sites (--hybrid_hotspot, --q_threshold, --mapq_threshold,
+--reconcilement_size) reach those stages with ``--from_bams``; ``--from_bam`` runs them at the defaults, and with ``--shards``
+they are accepted so existing command lines keep working.  --ibam / --pbam are the BAM(s) of a BAM route, and always name the
+features directory the way ``get_workdir`` does (call.py:40-48).
 
 ``--annotate`` (not in the reference, off by default) adds read support to every record line: GQ, DP, AD, ADF, ADR in the sample
 column and MQ in INFO, counted on the GPU from the launch's own per-read arrays (``hello_engine_allele_support``); without it
@@ -56,7 +59,6 @@ the outside tool that writes a tagged BAM.  ``--haplotag`` needs no phased VCF: 
 from __future__ import annotations
 
 import argparse
-import functools
 import glob
 import logging
 import os
@@ -71,6 +73,7 @@ import numpy as np
 
 from . import shards as shard_io
 from . import vcf
+from .route import Route, chromosome_list, from_bam_route                   # noqa: F401 -- from_bam_route: an entry point here too
 from .wrapper import pair_keys
 
 from .shard_pipeline import SENTINEL                 # caller_calling.py:902, checked by call.py:225-229  # noqa: E402
@@ -243,8 +246,8 @@ def features_dir_name(ibam: Optional[str], pbam: Optional[str]) -> str:
 
 def parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description="HELLO variant scoring on MI355X, with call.py's command line")
-    ap.add_argument("--ibam", help="Illumina BAM file (names the features directory; BAM ingestion is upstream)")
-    ap.add_argument("--pbam", help="PacBio BAM file (names the features directory; BAM ingestion is upstream)")
+    ap.add_argument("--ibam", help="Illumina BAM file (names the features directory; read by --from_bam / --from_bams)")
+    ap.add_argument("--pbam", help="PacBio BAM file (names the features directory; read by --from_bam / --from_bams)")
     ap.add_argument("--ref", help="Reference FASTA (optional when the shards carry their reference windows)")
     ap.add_argument("--workdir", required=True, help="Working directory")
     ap.add_argument("--chromosomes", help="Chromosomes to use (comma-separated): shards' sites elsewhere are skipped")
@@ -369,18 +372,6 @@ def shard_read_totals(paths: Sequence[str], threads: int = 4) -> np.ndarray:
         return np.array(list(pool.map(total, paths)), np.int64)
 
 
-def from_bam_route(ibam: Optional[str], pbam: Optional[str]):
-    """python/call.py:90-109 for --from_bam: one Illumina BAM, or one PacBio BAM (``pacbio = pbam and not ibam``).  -> (the BAM,
-    pacbio, the function that builds a chromosome's candidate sites).  Both BAMs and comma lists are refused."""
-    from . import candidates as cd
-    if (ibam and pbam) or not (ibam or pbam) or "," in (ibam or pbam):
-        raise ValueError(cd.REFUSAL)
-    if pbam:
-        from .pacbio import find_pacbio_candidates
-        return pbam, True, find_pacbio_candidates
-    return ibam, False, cd.find_candidates
-
-
 def _shard_files(ns):
     """The hotspot stage per chromosome (``hotspots.txt`` in the reference's ``hotspots_<chrom>_<bam>`` directory), then
     ``shard<N>.txt`` beside it (shardHotspots): yields (N, the shard file) as each is written."""
@@ -397,80 +388,58 @@ def _shard_files(ns):
         raise SystemExit("no hotspot was found: nothing to call")
 
 
-def _from_bam_stages(args):
-    """--from_bam: -> (genome, the hotspot stage's arguments, the BAM, the function that builds a chromosome's candidate sites).
-    Both stages run at the default thresholds."""
+def _shards_of(args, two_bams: bool) -> str:
+    """python/call.py:111-221 up to the per-shard caller, on the GPU, for the route of ``args`` (``hello_amd.route``): per
+    chromosome hotspots.txt in the reference's ``hotspots_<chrom>_<bam(s)>`` directory, ``shard<N>.txt`` files beside it
+    (shardHotspots) and one ``shard<N>.hshard`` per shard file in ``<workdir>/shards``.  Returns that directory."""
     from . import candidates as cd
-    bam, pacbio, find = from_bam_route(args.ibam, args.pbam)
-    if not args.ref:
-        raise SystemExit("--from_bam needs --ref")
-    chromosomes = args.chromosomes.split(",") if args.chromosomes else None
-    genome = read_fasta(args.ref, chromosomes)
-    ns = argparse.Namespace(bam=bam, ref=args.ref, pacbio=pacbio, hybrid_hotspot=False, workdir=args.workdir,
-                            chromosomes=",".join(chromosomes or list(genome)), q_threshold=cd.DEFAULT_Q_THRESHOLD,
-                            mapq_threshold=cd.DEFAULT_MIN_MAPQ, device=args.device)
-    return genome, ns, bam, find
-
-
-def _from_bams_stages(args):
-    """--from_bams: -> (genome, the hotspot stage's arguments, [ibam, pbam]).  ``--hybrid_hotspot``, ``--reconcilement_size``,
-    ``--q_threshold`` and ``--mapq_threshold`` reach both stages, as they reach the reference's (python/call.py passes them on)."""
-    if not (args.ibam and args.pbam) or "," in args.ibam or "," in args.pbam:
-        raise ValueError("--from_bams needs one --ibam and one --pbam (one BAM: --from_bam)")
-    if not args.ref:
-        raise SystemExit("--from_bams needs --ref")
-    chromosomes = args.chromosomes.split(",") if args.chromosomes else None
-    genome = read_fasta(args.ref, chromosomes)
-    bams = [args.ibam, args.pbam]
-    ns = argparse.Namespace(bam=",".join(bams), ref=args.ref, pacbio=False, hybrid_hotspot=args.hybrid_hotspot, workdir=args.workdir,
-                            chromosomes=",".join(chromosomes or list(genome)), q_threshold=args.q_threshold,
-                            mapq_threshold=args.mapq_threshold, device=args.device)
-    return genome, ns, bams
+    logger = logging.getLogger("hello_amd.call")
+    route = Route.from_args(args, two_bams)
+    genome = read_fasta(route.ref, route.chromosomes)
+    tagger = haplotagger_of(args, route)
+    find, kw = route.finder(tagger)
+    out_dir = os.path.join(args.workdir, "shards")
+    os.makedirs(out_dir, exist_ok=True)
+    for n, name in _shard_files(route.hotspot_args(args.workdir, genome)):
+        _, st = cd.run_activity(list(route.bams), route.ref, name, os.path.join(out_dir, "shard%d" % n), genome=genome, find=find, **kw)
+        if two_bams:
+            logger.info("%s: %d sites, %d PacBio reads reassigned", name, st.get("sites", 0), st.get("pacbio_reads_reassigned", 0))
+        else:
+            logger.info("%s: %d sites", name, st.get("sites", 0))
+    _close_haplotagger(tagger)
+    return out_dir
 
 
 def shards_from_bam(args) -> str:
-    """python/call.py:111-221 up to the per-shard caller, on the GPU: per chromosome hotspots.txt in the reference's
-    ``hotspots_<chrom>_<bam>`` directory, ``shard<N>.txt`` files beside it (shardHotspots) and one ``shard<N>.hshard`` per
-    shard file in ``<workdir>/shards``.  Returns that directory."""
-    from . import candidates as cd
-    logger = logging.getLogger("hello_amd.call")
-    genome, ns, bam, find = _from_bam_stages(args)
-    tagger = haplotagger_of(args)
-    find = _tagged(find, tagger)
-    out_dir = os.path.join(args.workdir, "shards")
-    os.makedirs(out_dir, exist_ok=True)
-    for n, name in _shard_files(ns):
-        _, st = cd.run_activity(bam, args.ref, name, os.path.join(out_dir, "shard%d" % n), device=args.device, genome=genome, find=find)
-        logger.info("%s: %d sites", name, st.get("sites", 0))
-    _close_haplotagger(tagger)
-    return out_dir
+    """``<workdir>/shards`` of --from_bam: one Illumina BAM or one PacBio BAM, every stage at the default thresholds."""
+    return _shards_of(args, False)
 
 
 def shards_from_bams(args) -> str:
-    """``shards_from_bam`` for the hybrid caller (python/call.py:111-221 with both BAMs): hotspots over the Illumina and the
-    PacBio BAM together in the reference's ``hotspots_<chrom>_<ibam>_<pbam>`` directory, ``shard<N>.txt`` beside them and one
-    two-technology ``shard<N>.hshard`` per shard file in ``<workdir>/shards`` (hello_amd.hybrid).  Returns that directory.
-    ``shards_from_bam`` runs its stages at the default thresholds and stays as it is."""
-    from . import hybrid as hy
-    logger = logging.getLogger("hello_amd.call")
-    genome, ns, bams = _from_bams_stages(args)
-    tagger = haplotagger_of(args)
-    out_dir = os.path.join(args.workdir, "shards")
-    os.makedirs(out_dir, exist_ok=True)
-    for n, name in _shard_files(ns):
-        _, st = hy.run_activity(bams, args.ref, name, os.path.join(out_dir, "shard%d" % n), args.hybrid_hotspot,
-                                args.reconcilement_size, q_threshold=args.q_threshold, mapq_threshold=args.mapq_threshold,
-                                device=args.device, genome=genome, find=_tagged(None, tagger))
-        logger.info("%s: %d sites, %d PacBio reads reassigned", name, st.get("sites", 0), st.get("pacbio_reads_reassigned", 0))
-    _close_haplotagger(tagger)
-    return out_dir
+    """``<workdir>/shards`` of --from_bams, the hybrid caller (python/call.py:111-221 with both BAMs): two-technology shards
+    (hello_amd.hybrid), every stage with ``--hybrid_hotspot``, ``--reconcilement_size`` and the two thresholds of the command line."""
+    return _shards_of(args, True)
+
+
+def _bam_route(args) -> bool:
+    """A BAM route is selected: --from_bam or --from_bams."""
+    return bool(getattr(args, "from_bam", False) or getattr(args, "from_bams", False))
+
+
+def _under_launcher() -> bool:
+    return "RANK" in os.environ and "WORLD_SIZE" in os.environ
+
+
+def _several_processes(args) -> bool:
+    """Not one process on one GPU: --gpus above 1, or a launch under torch.distributed.run."""
+    return getattr(args, "gpus", 1) > 1 or _under_launcher()
 
 
 def check_resident(args) -> None:
     """The refusals of --resident, each naming the fix."""
     if not getattr(args, "resident", False):
         return
-    if not (getattr(args, "from_bam", False) or getattr(args, "from_bams", False)):
+    if not _bam_route(args):
         raise SystemExit("--resident keeps the candidate sites of --from_bam / --from_bams on the GPU: add --from_bam (one BAM) or "
                          "--from_bams (--ibam and --pbam), or drop --resident")
     if getattr(args, "from_bam", False) and getattr(args, "from_bams", False):
@@ -478,7 +447,7 @@ def check_resident(args) -> None:
     if args.shards:
         raise SystemExit("--resident builds its candidate sites itself and reads no shard files: drop --shards, or drop --resident to "
                          "score the shard files")
-    if getattr(args, "gpus", 1) > 1 or ("RANK" in os.environ and "WORLD_SIZE" in os.environ):
+    if _several_processes(args):
         raise SystemExit("--resident builds candidate sites on one GPU in one process: run it with --gpus 1 as a plain command, or drop "
                          "--resident (the shard files of --from_bam / --from_bams can be dealt to several GPUs)")
 
@@ -487,11 +456,11 @@ def check_gvcf(args) -> None:
     """The refusals of --gvcf, each naming the fix."""
     if not getattr(args, "gvcf", False):
         return
-    if not (getattr(args, "from_bam", False) or getattr(args, "from_bams", False)):
+    if not _bam_route(args):
         raise SystemExit("--gvcf counts the reads of the BAM(s) between the records, and the shard route has no BAM on its path: add "
                          "--from_bam (one BAM) or --from_bams (--ibam and --pbam), or drop --gvcf (python -m hello_amd.gvcf writes a "
                          "gVCF from a VCF that exists and its BAMs)")
-    if getattr(args, "gpus", 1) > 1 or ("RANK" in os.environ and "WORLD_SIZE" in os.environ):
+    if _several_processes(args):
         raise SystemExit("--gvcf runs its pass over the BAM(s) in one process on one GPU: run it with --gpus 1 as a plain command, or "
                          "drop --gvcf and run python -m hello_amd.gvcf on the finished results.output.vcf")
     if getattr(args, "gvcf_gq_binsize", 5) < 1:
@@ -502,16 +471,13 @@ def gvcf_pass(args, result_path: str, genome: Dict[str, str]) -> Optional[str]:
     """--gvcf: ``results.output.g.vcf`` beside the finished ``result_path``, at the thresholds the route's own stages ran with."""
     if not getattr(args, "gvcf", False):
         return None
-    from . import candidates as cd, gvcf
-    if getattr(args, "from_bams", False):
-        bams, q, mq = [args.ibam, args.pbam], args.q_threshold, args.mapq_threshold
-    else:
-        bams, q, mq = [from_bam_route(args.ibam, args.pbam)[0]], cd.DEFAULT_Q_THRESHOLD, cd.DEFAULT_MIN_MAPQ
-    chromosomes = args.chromosomes.split(",") if args.chromosomes else list(genome)
+    from . import gvcf
+    route = Route.from_args(args, need_ref=False)
     out = result_path[:-len(".vcf")] + ".g.vcf"
     t0 = time.perf_counter()
     stats: dict = {}
-    gvcf.write_gvcf(result_path, bams, genome, out, chromosomes, q, mq, args.gvcf_gq_binsize, args.device, stats=stats)
+    gvcf.write_gvcf(result_path, list(route.bams), genome, out, route.chromosomes or list(genome), route.q_threshold,
+                    route.mapq_threshold, args.gvcf_gq_binsize, route.device, stats=stats)
     logging.getLogger("hello_amd.call").info(
         "gVCF pass: %d blocks in %s, %.2f s (BAM decode %.2f s, kernels %.1f ms)", int(stats.get("blocks", 0)), out,
         time.perf_counter() - t0, stats.get("decode_s", 0.0), stats.get("kernel_ms", 0.0))
@@ -522,11 +488,11 @@ def check_phase(args) -> None:
     """The refusals of --phase, each naming the fix."""
     if not getattr(args, "phase", False):
         return
-    if not (getattr(args, "from_bam", False) or getattr(args, "from_bams", False)):
+    if not _bam_route(args):
         raise SystemExit("--phase reads the alleles of neighbouring records off the reads of the BAM(s), and the shard route has no BAM "
                          "on its path: add --from_bam (one BAM) or --from_bams (--ibam and --pbam), or drop --phase (python -m "
                          "hello_amd.phase phases a VCF that exists from its BAMs)")
-    if getattr(args, "gpus", 1) > 1 or ("RANK" in os.environ and "WORLD_SIZE" in os.environ):
+    if _several_processes(args):
         raise SystemExit("--phase runs its pass over the BAM(s) in one process on one GPU: run it with --gpus 1 as a plain command, or "
                          "drop --phase and run python -m hello_amd.phase on the finished results.output.vcf")
     if not 1 <= getattr(args, "phase_window", 8) <= 32:
@@ -539,16 +505,13 @@ def phase_pass(args, result_path: str) -> Optional[str]:
     """--phase: ``results.output.phased.vcf`` beside the finished ``result_path``, at the thresholds the route's own stages ran with."""
     if not getattr(args, "phase", False):
         return None
-    from . import candidates as cd, phase
-    if getattr(args, "from_bams", False):
-        bams, q, mq = [args.ibam, args.pbam], args.q_threshold, args.mapq_threshold
-    else:
-        bams, q, mq = [from_bam_route(args.ibam, args.pbam)[0]], cd.DEFAULT_Q_THRESHOLD, cd.DEFAULT_MIN_MAPQ
+    from . import phase
+    route = Route.from_args(args, need_ref=False)
     out = result_path[:-len(".vcf")] + ".phased.vcf"
     t0 = time.perf_counter()
     stats: dict = {}
-    phase.write_phased_vcf(result_path, bams, out, args.chromosomes.split(",") if args.chromosomes else None, q, mq,
-                           args.phase_window, args.phase_min_margin, args.device, stats=stats)
+    phase.write_phased_vcf(result_path, list(route.bams), out, route.chromosomes, route.q_threshold,
+                           route.mapq_threshold, args.phase_window, args.phase_min_margin, route.device, stats=stats)
     logging.getLogger("hello_amd.call").info(
         "phase pass: %d slots of %d reads in %s, %.2f s (BAM decode %.2f s, kernels %.1f ms)", int(stats.get("slots", 0)),
         int(stats.get("reads_counted", 0)), out, time.perf_counter() - t0, stats.get("decode_s", 0.0),
@@ -565,34 +528,25 @@ def check_haplotag(args) -> None:
     if vcf_given and two_passes:
         raise SystemExit("--haplotag_vcf tags the reads from a phased VCF that exists, --haplotag from one it makes in a first pass: "
                          "give one of the two")
-    if not (getattr(args, "from_bam", False) or getattr(args, "from_bams", False)) or args.shards:
+    if not _bam_route(args) or args.shards:
         raise SystemExit(f"{flag} tags the reads the candidate stage fetches from the BAM(s), and shard files hold reads that were "
                          f"fetched before: add --from_bam (one BAM) or --from_bams (--ibam and --pbam) and drop --shards, or drop {flag}")
     if not getattr(args, "include_hp", False):
         raise SystemExit(f"{flag} without --include_hp: the model would not read the haplotags (six pileup channels); add --include_hp "
                          f"with a model of seven channels, or drop {flag}")
-    if getattr(args, "gpus", 1) > 1 or ("RANK" in os.environ and "WORLD_SIZE" in os.environ):
+    if _several_processes(args):
         raise SystemExit(f"{flag} tags the reads in the process that builds the candidate sites, on one GPU: run it with --gpus 1 as a "
                          f"plain command, or drop {flag}")
 
 
-def haplotagger_of(args):
-    """--haplotag_vcf: one ``haplotag.Haplotagger`` over the file, at the thresholds the route's own stages run with (the choice of
-    ``phase_pass``); None without the flag."""
+def haplotagger_of(args, route: Optional[Route] = None):
+    """--haplotag_vcf: one ``haplotag.Haplotagger`` over the file, at the thresholds of ``route`` (default: the route of ``args``);
+    None without the flag."""
     if not getattr(args, "haplotag_vcf", None):
         return None
-    from . import candidates as cd, haplotag
-    q, mq = (args.q_threshold, args.mapq_threshold) if getattr(args, "from_bams", False) else (cd.DEFAULT_Q_THRESHOLD, cd.DEFAULT_MIN_MAPQ)
-    return haplotag.Haplotagger(args.haplotag_vcf, args.chromosomes.split(",") if args.chromosomes else None, q, mq, args.device)
-
-
-def _tagged(find, tagger):
-    """``find`` (None: ``hybrid.find_hybrid_candidates``) with the tagger bound, or ``find`` itself without one."""
-    if tagger is None:
-        return find
-    if find is None:
-        from .hybrid import find_hybrid_candidates as find
-    return functools.partial(find, tagger=tagger)
+    from . import haplotag
+    route = route or Route.from_args(args, need_ref=False)
+    return haplotag.Haplotagger(args.haplotag_vcf, route.chromosomes, route.q_threshold, route.mapq_threshold, route.device)
 
 
 def _close_haplotagger(tagger) -> None:
@@ -634,20 +588,14 @@ def run_resident(args) -> str:
     check_gvcf(args)
     check_phase(args)
     check_haplotag(args)
-    if args.from_bams:
-        from . import hybrid as hy
-        genome, ns, bam = _from_bams_stages(args)
-        find, kw = hy.find_hybrid_candidates, dict(hybrid_hotspot=args.hybrid_hotspot, reassembly_size=args.reconcilement_size,
-                                                   q_threshold=args.q_threshold, mapq_threshold=args.mapq_threshold)
-    else:
-        genome, ns, bam, find = _from_bam_stages(args)
-        kw = {}
-    tagger = haplotagger_of(args)
-    find = _tagged(find, tagger)
-    files = list(_shard_files(ns))
+    route = Route.from_args(args)
+    genome = read_fasta(route.ref, route.chromosomes)
+    tagger = haplotagger_of(args, route)
+    find, kw = route.finder(tagger)
+    files = list(_shard_files(route.hotspot_args(args.workdir, genome)))
     features_dir = os.path.join(args.workdir, features_dir_name(args.ibam, args.pbam))
     os.makedirs(features_dir, exist_ok=True)
-    wanted = set(args.chromosomes.split(",")) if args.chromosomes else None
+    wanted = set(route.chromosomes) if route.chromosomes else None
     threads = max(2, min(args.num_threads, len(os.sched_getaffinity(0))))
 
     from .loader import load
@@ -657,7 +605,7 @@ def run_resident(args) -> str:
     total: dict = {}
 
     def candidates_of(name):
-        found = list(cd.resident_activity(bam, args.ref, name, genome=genome, find=find, total=total, device=args.device, **kw))
+        found = list(cd.resident_activity(list(route.bams), route.ref, name, genome=genome, find=find, total=total, **kw))
         if len(found) != 1:                             # _shard_files writes one chromosome per file
             raise ValueError(f"{name}: positions on {len(found)} chromosomes; a shard file holds one")
         logger.info("%s: %d sites", name, found[0].n_sites)
@@ -697,44 +645,30 @@ def main(args) -> str:
         return haplotag_passes(args)
     if getattr(args, "resident", False):
         return run_resident(args)
-    if getattr(args, "from_bams", False) and not args.shards:
-        if getattr(args, "from_bam", False):
+    if _bam_route(args) and not args.shards:
+        flag, build = ("--from_bams", shards_from_bams) if getattr(args, "from_bams", False) else ("--from_bam", shards_from_bam)
+        if getattr(args, "from_bam", False) and getattr(args, "from_bams", False):
             raise SystemExit("--from_bam (one BAM) and --from_bams (an Illumina and a PacBio BAM) exclude each other")
-        if "RANK" in os.environ and "WORLD_SIZE" in os.environ:
-            raise SystemExit("--from_bams under an external launcher would build the same shards in every rank: start it as a plain "
-                             "command with --gpus N, or build the shards first and pass --shards")
-        if getattr(args, "gpus", 1) > 1:
-            # as --from_bam: the ranks must start before this process touches the GPU, so the BAM stages run in a child of their own
-            import multiprocessing
-            child = multiprocessing.get_context("spawn").Process(target=shards_from_bams, args=(args,))
-            child.start()
-            child.join()
-            if child.exitcode != 0:
-                raise SystemExit(f"the BAM stages of --from_bams failed (exit status {child.exitcode})")
-            args.shards = os.path.join(args.workdir, "shards")
-        else:
-            args.shards = shards_from_bams(args)
-    if getattr(args, "from_bam", False) and not args.shards:
-        if "RANK" in os.environ and "WORLD_SIZE" in os.environ:
-            raise SystemExit("--from_bam under an external launcher would build the same shards in every rank: start it as a plain "
+        if _under_launcher():
+            raise SystemExit(f"{flag} under an external launcher would build the same shards in every rank: start it as a plain "
                              "command with --gpus N, or build the shards first and pass --shards")
         if getattr(args, "gpus", 1) > 1:
             # the ranks must start before this process touches the GPU (_launch_ranks): the BAM stages run in a child of their own
             import multiprocessing
-            child = multiprocessing.get_context("spawn").Process(target=shards_from_bam, args=(args,))
+            child = multiprocessing.get_context("spawn").Process(target=build, args=(args,))
             child.start()
             child.join()
             if child.exitcode != 0:
-                raise SystemExit(f"the BAM stages of --from_bam failed (exit status {child.exitcode})")
+                raise SystemExit(f"the BAM stages of {flag} failed (exit status {child.exitcode})")
             args.shards = os.path.join(args.workdir, "shards")
         else:
-            args.shards = shards_from_bam(args)
+            args.shards = build(args)
     if not args.shards:
         raise SystemExit("--shards is required: BAM / FASTA ingestion, hotspot detection and allele assembly are upstream of "
                          "this engine (SURVEY.md section 2, rows 9-13); extract candidate-site shards with the reference's "
                          "searcher and hello_amd.shards.write_shard")
     result_path = os.path.join(args.workdir, "results.output.vcf")
-    under_launcher = "RANK" in os.environ and "WORLD_SIZE" in os.environ
+    under_launcher = _under_launcher()
     if getattr(args, "gpus", 1) > 1 and not under_launcher:
         rc = _launch_ranks(args)
         if rc != 0:
@@ -752,7 +686,8 @@ def main(args) -> str:
         numbers = list(range(len(shard_paths)))
     features_dir = os.path.join(args.workdir, features_dir_name(args.ibam, args.pbam))
     os.makedirs(features_dir, exist_ok=True)
-    wanted = set(args.chromosomes.split(",")) if args.chromosomes else None
+    names = chromosome_list(args.chromosomes)
+    wanted = set(names) if names else None
     genomes = read_fasta(args.ref, wanted) if args.ref else {}
 
     import torch

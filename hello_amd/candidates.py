@@ -37,7 +37,7 @@ STAT_NAMES = ("active_regions", "regions_without_reads", "regions_out_of_bounds"
               "clusters", "clusters_without_reads", "clusters_out_of_bounds", "clusters_at_read_cap", "differing_regions_pass2",
               "sites", "sites_out_of_bounds", "alleles", "reads_gathered", "record_slots", "pass1_kernel_ms", "pass2_kernel_ms",
               "allele_kernel_ms", "gather_ms", "total_ms", "clip_kernel_ms", "reads_clipped")
-_ARRAYS = (  # (name, hello_candidates_array selector, dtype)
+_ARRAYS = (  # (name, hello_candidates_array_tech selector, dtype; the read arrays carry technology 0's name)
     ("start", 0, np.int64), ("stop", 1, np.int64), ("window_start", 2, np.int64), ("ref_off", 3, np.int64), ("ref", 4, np.uint8),
     ("alleles_per_site", 5, np.int32), ("allele_text", 6, np.uint8), ("allele_text_off", 7, np.int64),
     ("reads_per_allele0", 8, np.int32), ("bases0", 9, np.uint8), ("quals0", 10, np.uint8), ("read_off0", 11, np.int64),
@@ -51,7 +51,7 @@ REFUSAL = ("candidate sites are built from one Illumina BAM: two BAMs and --hybr
 _log = logging.getLogger(__name__)
 _PROTOTYPES = (
     ("hello_candidates_find", READS + [i64, vp, i64, vp, i64, i32, i32, i32, i32, i32, C.POINTER(vp)]),
-    ("hello_candidates_array", ARRAY_GETTER),
+    ("hello_candidates_array_tech", [vp, i32] + ARRAY_GETTER[1:]),
     ("hello_candidates_stats", STATS_GETTER),
     ("hello_candidates_free", [vp], None),
 )
@@ -112,22 +112,38 @@ def find_sites(reads: Reads, reference: str, positions: Sequence[int], chromosom
                                     int(options) | (rs.HELLO_CANDIDATES_RESIDENT if resident else 0),
                                     int(feature_length), int(q_threshold), int(mapq_threshold), int(device), C.byref(h)),
           value_error_on_arg=True)
-    keep = False
+    return read_handle(lib, h, 1, lib.hello_candidates_stats, STAT_NAMES, chromosome, feature_length, resident)
+
+
+def read_handle(lib, h, technologies: int, stats_getter, stat_names, chromosome: str, feature_length: int, resident: bool):
+    """The arrays and statistics of the ``hello_candidates`` handle ``h`` of one or two technologies -> (``PackedShard``, or a
+    ``ResidentShard`` that owns the handle from here on, also when it raises; statistics; the extra arrays).  The read index is
+    ``read_index`` for one technology and ``read_index0`` / ``read_index1`` for two.  The handle is freed unless the shard owns it."""
+    from . import resident as rs
     try:
-        got = {name: handle_array(lib.hello_candidates_array, h, which, dtype) for name, which, dtype in _ARRAYS}
-        st = handle_stats(lib.hello_candidates_stats, h, STAT_NAMES)
-        extra = {k: got.pop(k) for k in ("read_index", "regions_pass1", "regions_pass2")}
-        got.update(chromosome_table(chromosome, got["start"].shape[0]), has_second=np.array(0))
+        got, extra = {}, {}
+        for name, which, dtype in _ARRAYS:
+            if which < 8:                                   # start ... allele_text_off: the sites
+                got[name] = handle_array(lib.hello_candidates_array_tech, h, which, dtype, 0)
+            elif which > 18:                                # regions_pass1, regions_pass2
+                extra[name] = handle_array(lib.hello_candidates_array_tech, h, which, dtype, 0)
+            else:                                           # reads_per_allele0 ... hp0, read_index: per technology
+                for tech in range(technologies):
+                    a = handle_array(lib.hello_candidates_array_tech, h, which, dtype, tech)
+                    if name == "read_index":
+                        extra[name + (str(tech) if technologies == 2 else "")] = a
+                    else:
+                        got[name[:-1] + str(tech)] = a
+        st = handle_stats(stats_getter, h, stat_names)
+        got.update(chromosome_table(chromosome, got["start"].shape[0]), has_second=np.array(technologies - 1))
         if resident:
-            extra.update(read_off0=got["read_off0"], cigar_off0=got["cigar_off0"])
-            shard = rs.ResidentShard(h.value, got, feature_length)          # owns the handle from here on, also when it raises
-            keep = True
-        else:
-            shard = shards.PackedShard(got, feature_length)
+            extra.update({f"{k}{t}": got[f"{k}{t}"] for k in ("read_off", "cigar_off") for t in range(technologies)})
+            owned, h = h, None
+            return rs.ResidentShard(owned.value, got, feature_length, hybrid=technologies == 2), st, extra
+        return shards.PackedShard(got, feature_length), st, extra
     finally:
-        if not keep:
+        if h is not None:
             lib.hello_candidates_free(h)
-    return shard, st, extra
 
 
 def chromosome_table(chromosome: str, n_sites: int) -> Dict[str, np.ndarray]:
@@ -136,6 +152,45 @@ def chromosome_table(chromosome: str, n_sites: int) -> Dict[str, np.ndarray]:
     return dict(chromosome_text=name if n_sites else np.zeros(0, np.uint8),
                 chromosome_text_off=np.array([0, name.shape[0]] if n_sites else [0], np.int64),
                 chromosome_of_site=np.zeros(n_sites, np.int32))
+
+
+def fetch_interval(positions: np.ndarray) -> Tuple[int, int]:
+    """The interval whose reads the candidate stage needs: pass 1 fetches [start - 75, stop + 75) around [first - 15, last + 15]
+    (long reads reach far outside it)."""
+    if positions.shape[0] == 0:
+        return 0, 0
+    lo = max(0, int(positions.min()) - MIN_DISTANCE // 2 - FLANKING_BASES)
+    return lo, max(int(positions.max()) + MIN_DISTANCE // 2 + FLANKING_BASES, lo)
+
+
+def find_from_bams(paths: Sequence[str], fasta: Optional[str], chromosome: str, positions: Sequence[int], q_threshold: int,
+                   mapq_threshold: int, device: int, feature_length: int, reference: Optional[str], stats: Optional[dict],
+                   resident: bool, tagger, options: int = 0, hybrid_hotspot: bool = False, reassembly_size: int = 0) -> shards.PackedShard:
+    """What the three finders share: the reads of ``fetch_interval`` from every BAM of ``paths``, retagged by ``tagger`` if there
+    is one, through ``find_sites`` with ``options`` (one BAM) or ``hybrid.find_sites`` (two: Illumina, PacBio); ``stats`` is filled
+    with the statistics and the extra arrays of the call."""
+    if reference is None:
+        from .hotspots import _read_reference
+        reference = _read_reference(fasta, chromosome)
+    positions = np.asarray(positions, np.int64)
+    lo, hi = fetch_interval(positions)
+    sets = []
+    for path in paths:
+        with BamFile(path) as b:
+            sets.append(b.fetch(chromosome, lo, hi))
+    if tagger is not None:
+        sets = [tagger.retag(chromosome, reads) for reads in sets]
+    if len(sets) == 2:
+        from . import hybrid
+        shard, st, extra = hybrid.find_sites(sets[0], sets[1], reference, positions, chromosome, hybrid_hotspot, reassembly_size,
+                                             feature_length, q_threshold, mapq_threshold, device, resident=resident)
+    else:
+        shard, st, extra = find_sites(sets[0], reference, positions, chromosome, feature_length, q_threshold, mapq_threshold, device,
+                                      options=options, resident=resident)
+    if stats is not None:
+        stats.update(st)
+        stats.update(extra)
+    return shard
 
 
 def find_candidates(bam, fasta: Optional[str], chromosome: str, positions: Sequence[int], q_threshold: int = DEFAULT_Q_THRESHOLD,
@@ -150,25 +205,8 @@ def find_candidates(bam, fasta: Optional[str], chromosome: str, positions: Seque
     paths = [bam] if isinstance(bam, str) else list(bam)
     if len(paths) != 1 or pacbio or hybrid_hotspot:
         raise ValueError(REFUSAL)
-    if reference is None:
-        from .hotspots import _read_reference
-        reference = _read_reference(fasta, chromosome)
-    positions = np.asarray(positions, np.int64)
-    if positions.shape[0] == 0:
-        lo = hi = 0
-    else:       # pass 1 fetches [start - 75, stop + 75) around [first - 15, last + 15]
-        lo = max(0, int(positions.min()) - MIN_DISTANCE // 2 - FLANKING_BASES)
-        hi = int(positions.max()) + MIN_DISTANCE // 2 + FLANKING_BASES
-    with BamFile(paths[0]) as b:
-        reads = b.fetch(chromosome, lo, max(hi, lo))
-    if tagger is not None:
-        reads = tagger.retag(chromosome, reads)
-    shard, st, extra = find_sites(reads, reference, positions, chromosome, feature_length, q_threshold, mapq_threshold, device,
-                                  resident=resident)
-    if stats is not None:
-        stats.update(st)
-        stats.update(extra)
-    return shard
+    return find_from_bams(paths, fasta, chromosome, positions, q_threshold, mapq_threshold, device, feature_length, reference, stats,
+                          resident, tagger)
 
 
 def write_packed(path: str, shard: shards.PackedShard) -> str:
@@ -177,7 +215,8 @@ def write_packed(path: str, shard: shards.PackedShard) -> str:
 
 
 def concat_payloads(parts: Sequence[shards.PackedShard]) -> dict:
-    """The arrays of several single-chromosome shards as one shard's arrays (a shard file may span chromosomes)."""
+    """The arrays of several single-chromosome shards as one shard's arrays (a shard file may span chromosomes); technology 1's
+    arrays too, and ``has_second`` = 1, when the parts are hybrid shards."""
     def cat(name):
         return np.concatenate([np.asarray(p.z[name]) for p in parts])
 
@@ -188,57 +227,85 @@ def concat_payloads(parts: Sequence[shards.PackedShard]) -> dict:
             out.append(o[1:] + base)
             base += int(o[-1])
         return np.concatenate(out)
+    per_read = ("reads_per_allele", "bases", "quals", "cigars", "ref_start", "mapq", "orientation", "hp")
     names = [p.chromosome_names[0] for p in parts if p.n_sites]
-    out = {k: cat(k) for k in ("start", "stop", "window_start", "ref", "alleles_per_site", "allele_text", "reads_per_allele0", "bases0",
-                               "quals0", "cigars0", "ref_start0", "mapq0", "orientation0", "hp0")}
+    out = {k: cat(k) for k in ("start", "stop", "window_start", "ref", "alleles_per_site", "allele_text") + tuple(k + "0" for k in per_read)}
     for k in ("ref_off", "allele_text_off", "read_off0", "cigar_off0"):
         out[k] = offsets(k)
     out["chromosome_text"], out["chromosome_text_off"] = shards.text_table(np.array(names, dtype="U")) if names else (
         np.zeros(0, np.uint8), np.zeros(1, np.int64))
     out["chromosome_of_site"] = np.concatenate([np.full(p.n_sites, i, np.int32) for i, p in enumerate(q for q in parts if q.n_sites)]
                                                + [np.zeros(0, np.int32)])
-    out["has_second"] = np.array(0)
+    second = all(p.hybrid for p in parts)
+    out["has_second"] = np.array(int(second))
+    if second:
+        out.update({k + "1": cat(k + "1") for k in per_read})
+        out.update({k: offsets(k) for k in ("read_off1", "cigar_off1")})
     return out
 
 
-def parser() -> argparse.ArgumentParser:
-    p = argparse.ArgumentParser(description="Candidate sites of a hotspot shard on the GPU (caller_calling.py's flags where they apply)")
-    p.add_argument("--bam", required=True, help="The Illumina BAM file (one file)")
-    p.add_argument("--ref", required=True, help="Reference FASTA")
-    p.add_argument("--activity", required=True, help="Hotspot / shard file: one {'chromosome', 'position'} line per position")
-    p.add_argument("--outputPrefix", required=True, help="The shard is written to <outputPrefix>.hshard")
-    p.add_argument("--featureLength", type=int, default=150, help="Length of the feature window")
-    p.add_argument("--q_threshold", type=int, default=DEFAULT_Q_THRESHOLD, help="Quality score threshold")
-    p.add_argument("--mapq_threshold", type=int, default=DEFAULT_MIN_MAPQ, help="Mapping quality threshold")
-    p.add_argument("--include_hp", action="store_true", default=False, help="Accepted for the reference's command line: the reads' HP tags are always stored; the scoring "
-                        "driver's --include_hp decides whether they are used")
-    p.add_argument("--pacbio", action="store_true", default=False, help="Refused: use python -m hello_amd.pacbio for one PacBio BAM")
-    p.add_argument("--hybrid_hotspot", action="store_true", default=False, help="Refused: needs two BAMs")
-    p.add_argument("--debug", action="store_true", default=False, help="Display debug messages")
-    p.add_argument("--device", type=int, default=0, help="GPU index")
+FLAG = dict(action="store_true", default=False)
+HP_HELP = "Accepted for the reference's command line: the reads' HP tags are always stored"
+
+
+def stage_parser(description: str, bam_help: str, hp_help: str = HP_HELP, after_output=(), after_hp=()) -> argparse.ArgumentParser:
+    """The command line the three candidate modules share; ``after_output`` / ``after_hp``: a module's own (flag, keywords) at the
+    two places where the modules' lists differ."""
+    p = argparse.ArgumentParser(description=description)
+    for name, kw in (("--bam", dict(required=True, help=bam_help)),
+                     ("--ref", dict(required=True, help="Reference FASTA")),
+                     ("--activity", dict(required=True, help="Hotspot / shard file: one {'chromosome', 'position'} line per position")),
+                     ("--outputPrefix", dict(required=True, help="The shard is written to <outputPrefix>.hshard")),
+                     *after_output,
+                     ("--featureLength", dict(type=int, default=150, help="Length of the feature window")),
+                     ("--q_threshold", dict(type=int, default=DEFAULT_Q_THRESHOLD, help="Quality score threshold")),
+                     ("--mapq_threshold", dict(type=int, default=DEFAULT_MIN_MAPQ, help="Mapping quality threshold")),
+                     ("--include_hp", dict(FLAG, help=hp_help)),
+                     *after_hp,
+                     ("--debug", dict(FLAG, help="Display debug messages")),
+                     ("--device", dict(type=int, default=0, help="GPU index"))):
+        p.add_argument(name, **kw)
     return p
 
 
-def run_activity(bam: str, fasta: str, activity: str, output_prefix: str, feature_length: int = 150,
-                 q_threshold: int = DEFAULT_Q_THRESHOLD, mapq_threshold: int = DEFAULT_MIN_MAPQ, device: int = 0, genome: Optional[Dict[str, str]] = None,
-                 find=None) -> Tuple[str, Dict[str, float]]:
-    """One activity file -> ``<output_prefix>.hshard`` and the summed statistics.  ``find``: the function with
-    ``find_candidates``' signature that builds one chromosome's shard (default: ``find_candidates``)."""
+def parser() -> argparse.ArgumentParser:
+    return stage_parser("Candidate sites of a hotspot shard on the GPU (caller_calling.py's flags where they apply)",
+                        "The Illumina BAM file (one file)",
+                        HP_HELP + "; the scoring driver's --include_hp decides whether they are used",
+                        after_hp=(("--pacbio", dict(FLAG, help="Refused: use python -m hello_amd.pacbio for one PacBio BAM")),
+                                  ("--hybrid_hotspot", dict(FLAG, help="Refused: needs two BAMs"))))
+
+
+def activity_shards(bam, fasta: str, activity: str, genome: Optional[Dict[str, str]] = None, find=None, total: Optional[dict] = None,
+                    **kw):
+    """One shard per chromosome of the activity file, in file order.  ``find``: ``find_candidates`` (default),
+    ``pacbio.find_pacbio_candidates`` or ``hybrid.find_hybrid_candidates``; ``kw``: its thresholds and options (``resident``
+    among them); ``total``: the statistics are summed into it."""
     find = find or find_candidates
     from .call import read_fasta
     by_chromosome = read_positions(activity)
     if genome is None:
         genome = read_fasta(fasta, list(by_chromosome))
-    parts, total = [], {}
     for chromosome, positions in by_chromosome.items():
         if chromosome not in genome:
             raise ValueError(f"{fasta}: no sequence named {chromosome!r}")
         st: dict = {}
-        shard = find(bam, fasta, chromosome, positions, q_threshold, mapq_threshold, device, feature_length,
-                     reference=genome[chromosome], stats=st)
-        for k in STAT_NAMES:
-            total[k] = total.get(k, 0.0) + st[k]
-        parts.append(shard)
+        shard = find(bam, fasta, chromosome, positions, reference=genome[chromosome], stats=st, **kw)
+        if total is not None:
+            for k, v in st.items():
+                if not isinstance(v, np.ndarray):
+                    total[k] = total.get(k, 0.0) + v
+        yield shard
+
+
+def run_activity(bam, fasta: str, activity: str, output_prefix: str, feature_length: int = 150,
+                 q_threshold: int = DEFAULT_Q_THRESHOLD, mapq_threshold: int = DEFAULT_MIN_MAPQ, device: int = 0, genome: Optional[Dict[str, str]] = None,
+                 find=None, **kw) -> Tuple[str, Dict[str, float]]:
+    """One activity file -> ``<output_prefix>.hshard`` and the summed statistics.  ``bam``, ``find`` and ``kw`` (a hybrid
+    finder's ``hybrid_hotspot`` and ``reassembly_size``, a ``tagger``) as for ``activity_shards``."""
+    total: dict = {}
+    parts = list(activity_shards(bam, fasta, activity, genome, find, total, q_threshold=q_threshold, mapq_threshold=mapq_threshold,
+                                 device=device, feature_length=feature_length, **kw))
     path = output_prefix + ".hshard"
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     shards.write_flat(path, concat_payloads(parts))
@@ -247,43 +314,39 @@ def run_activity(bam: str, fasta: str, activity: str, output_prefix: str, featur
 
 def resident_activity(bam, fasta: str, activity: str, genome: Optional[Dict[str, str]] = None, find=None, total: Optional[dict] = None,
                       **kw):
-    """``run_activity`` without the file: yields one ``ResidentShard`` per chromosome of the activity file, in file order (the
-    caller closes them or hands them to ``ShardScorer.submit``).  ``find``: ``find_candidates`` (default),
-    ``pacbio.find_pacbio_candidates`` or ``hybrid.find_hybrid_candidates``; ``kw``: its thresholds and options; ``total``: the
-    statistics are summed into it."""
-    find = find or find_candidates
-    from .call import read_fasta
-    by_chromosome = read_positions(activity)
-    if genome is None:
-        genome = read_fasta(fasta, list(by_chromosome))
-    for chromosome, positions in by_chromosome.items():
-        if chromosome not in genome:
-            raise ValueError(f"{fasta}: no sequence named {chromosome!r}")
-        st: dict = {}
-        shard = find(bam, fasta, chromosome, positions, reference=genome[chromosome], stats=st, resident=True, **kw)
+    """``run_activity`` without the file: yields one ``ResidentShard`` per chromosome of the activity file, each naming the file
+    (the caller closes them or hands them to ``ShardScorer.submit``)."""
+    for shard in activity_shards(bam, fasta, activity, genome, find, total, resident=True, **kw):
         shard.path = activity
-        if total is not None:
-            for k, v in st.items():
-                if not isinstance(v, np.ndarray):
-                    total[k] = total.get(k, 0.0) + v
         yield shard
 
 
-def main(argv=None) -> str:
-    args = parser().parse_args(argv)
+def start_main(parser: argparse.ArgumentParser, argv) -> argparse.Namespace:
+    args = parser.parse_args(argv)
     logging.basicConfig(level=logging.DEBUG if args.debug else logging.INFO, format="%(asctime)-15s %(message)s")
-    if args.pacbio or args.hybrid_hotspot or len(args.bam.split(",")) != 1:
-        raise ValueError(REFUSAL)
-    logging.info("Started script")
-    path, st = run_activity(args.bam, args.ref, args.activity, args.outputPrefix, args.featureLength, args.q_threshold,
-                            args.mapq_threshold, args.device)
-    logging.info("%d active regions -> %d sites, %d alleles, %d reads in %s", st.get("active_regions", 0), st.get("sites", 0),
-                 st.get("alleles", 0), st.get("reads_gathered", 0), path)
+    return args
+
+
+def finish_main(path: str, st: Dict[str, float], detail: str = "") -> str:
+    """The summary line of a module's command line (``detail``: what the module adds in brackets), the read-cap warnings and the
+    sentinel."""
+    logging.info("%d active regions -> %d sites, %d alleles, %d reads in %s%s", st.get("active_regions", 0), st.get("sites", 0),
+                 st.get("alleles", 0), st.get("reads_gathered", 0), path, detail)
     for key in ("regions_at_read_cap", "clusters_at_read_cap"):
         if st.get(key):
             logging.warning("%d %s: their first reads in file order were kept", st[key], key.replace("_", " "))
     logging.info("Completed running the script")
     return path
+
+
+def main(argv=None) -> str:
+    args = start_main(parser(), argv)
+    if args.pacbio or args.hybrid_hotspot or len(args.bam.split(",")) != 1:
+        raise ValueError(REFUSAL)
+    logging.info("Started script")
+    path, st = run_activity(args.bam, args.ref, args.activity, args.outputPrefix, args.featureLength, args.q_threshold,
+                            args.mapq_threshold, args.device)
+    return finish_main(path, st)
 
 
 if __name__ == "__main__":

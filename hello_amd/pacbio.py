@@ -15,11 +15,8 @@ import logging
 import sys
 from typing import Optional, Sequence
 
-import numpy as np
-
 from . import candidates as cd
 from . import shards
-from .bam import BamFile
 from .hotspots import HOTSPOTS_PACBIO
 
 
@@ -35,57 +32,22 @@ def find_pacbio_candidates(bam, fasta: Optional[str], chromosome: str, positions
     paths = [bam] if isinstance(bam, str) else list(bam)
     if len(paths) != 1 or "," in paths[0]:
         raise ValueError(cd.REFUSAL)
-    if reference is None:
-        from .hotspots import _read_reference
-        reference = _read_reference(fasta, chromosome)
-    positions = np.asarray(positions, np.int64)
-    if positions.shape[0] == 0:
-        lo = hi = 0
-    else:       # the interval of find_candidates: long reads reach far outside it
-        lo = max(0, int(positions.min()) - cd.MIN_DISTANCE // 2 - cd.FLANKING_BASES)
-        hi = int(positions.max()) + cd.MIN_DISTANCE // 2 + cd.FLANKING_BASES
-    with BamFile(paths[0]) as b:
-        reads = b.fetch(chromosome, lo, max(hi, lo))
-    if tagger is not None:
-        reads = tagger.retag(chromosome, reads)
-    shard, st, extra = cd.find_sites(reads, reference, positions, chromosome, feature_length, q_threshold, mapq_threshold, device,
-                                     options=HOTSPOTS_PACBIO, resident=resident)
-    if stats is not None:
-        stats.update(st)
-        stats.update(extra)
-    return shard
+    return cd.find_from_bams(paths, fasta, chromosome, positions, q_threshold, mapq_threshold, device, feature_length, reference, stats,
+                             resident, tagger, options=HOTSPOTS_PACBIO)
 
 
 def parser() -> argparse.ArgumentParser:
-    p = argparse.ArgumentParser(description="Candidate sites of a hotspot shard from one PacBio BAM on the GPU")
-    p.add_argument("--bam", required=True, help="The PacBio BAM file (one file)")
-    p.add_argument("--ref", required=True, help="Reference FASTA")
-    p.add_argument("--activity", required=True, help="Hotspot / shard file: one {'chromosome', 'position'} line per position")
-    p.add_argument("--outputPrefix", required=True, help="The shard is written to <outputPrefix>.hshard")
-    p.add_argument("--featureLength", type=int, default=150, help="Length of the feature window")
-    p.add_argument("--q_threshold", type=int, default=cd.DEFAULT_Q_THRESHOLD, help="Quality score threshold")
-    p.add_argument("--mapq_threshold", type=int, default=cd.DEFAULT_MIN_MAPQ, help="Mapping quality threshold")
-    p.add_argument("--include_hp", action="store_true", default=False, help="Accepted for the reference's command line: the reads' HP tags are always stored")
-    p.add_argument("--debug", action="store_true", default=False, help="Display debug messages")
-    p.add_argument("--device", type=int, default=0, help="GPU index")
-    return p
+    return cd.stage_parser("Candidate sites of a hotspot shard from one PacBio BAM on the GPU", "The PacBio BAM file (one file)")
 
 
 def main(argv=None) -> str:
-    args = parser().parse_args(argv)
-    logging.basicConfig(level=logging.DEBUG if args.debug else logging.INFO, format="%(asctime)-15s %(message)s")
+    args = cd.start_main(parser(), argv)
     if len(args.bam.split(",")) != 1:
         raise ValueError(cd.REFUSAL)
     logging.info("Started script")
     path, st = cd.run_activity(args.bam, args.ref, args.activity, args.outputPrefix, args.featureLength, args.q_threshold,
                                args.mapq_threshold, args.device, find=find_pacbio_candidates)
-    logging.info("%d active regions -> %d sites, %d alleles, %d reads in %s (%d reads clipped)", st.get("active_regions", 0),
-                 st.get("sites", 0), st.get("alleles", 0), st.get("reads_gathered", 0), path, st.get("reads_clipped", 0))
-    for key in ("regions_at_read_cap", "clusters_at_read_cap"):
-        if st.get(key):
-            logging.warning("%d %s: their first reads in file order were kept", st[key], key.replace("_", " "))
-    logging.info("Completed running the script")
-    return path
+    return cd.finish_main(path, st, " (%d reads clipped)" % st.get("reads_clipped", 0))
 
 
 if __name__ == "__main__":

@@ -175,8 +175,9 @@ def test_without_the_flags_nothing_is_checked_made_or_written(tmp_path, monkeypa
     assert args.haplotag is False and args.haplotag_vcf is None
     call.check_haplotag(args)                                                                    # no --from_bam, no --include_hp: not its business
     assert call.haplotagger_of(args) is None
-    find = object()
-    assert call._tagged(find, None) is find and call._tagged(None, None) is None
+    from hello_amd import pacbio
+    find, kw = call.Route.from_args(_args(*BAM)).finder(None)                                    # no tagger: the finder itself, nothing bound
+    assert find is pacbio.find_pacbio_candidates and "tagger" not in kw
     call._close_haplotagger(None)
     assert os.listdir(tmp_path) == []
     call.check_haplotag(call.argparse.Namespace(shards="s"))                                     # an args object from before the flags
