@@ -48,7 +48,8 @@ after ``results.output.vcf`` is complete: its records byte for byte, and referen
 ``--phase`` (with ``--from_bam`` / ``--from_bams``, not in the reference, off by default) writes ``<workdir>/results.output.phased.vcf``
 after ``results.output.vcf`` is complete: its lines in its order, the heterozygous records that the reads link rewritten as ``a|b``
 with a phase set (``PS``), observed, linked and tagged on the GPU in a pass of its own over the BAM(s) (``hello_amd.phase``;
-DESIGN.md section 7g).
+DESIGN.md section 7g).  ``--phase_fragments`` (with ``--phase`` or ``--haplotag``, off by default) makes the two mates of a read
+pair one fragment in that pass: joined by name on the GPU, linked over their merged observations, tagged alike (section 7i).
 
 ``--haplotag_vcf V`` (with ``--from_bam`` / ``--from_bams`` and ``--include_hp``, not in the reference, off by default) gives every
 read the candidate stage fetches a haplotag from the phased VCF ``V`` (``a|b`` records with ``PS``) in place of the BAM's own ``HP``
@@ -294,6 +295,9 @@ def parser() -> argparse.ArgumentParser:
                     help="--phase: a record is linked to this many heterozygous records before it (1 to 32)")
     ap.add_argument("--phase_min_margin", type=int, default=2,
                     help="--phase: the smallest |cis - trans| read count that joins a record to a phase set (at least 1)")
+    ap.add_argument("--phase_fragments", action="store_true", default=False,
+                    help="--phase / --haplotag: the two mates of a read pair act as one fragment -- joined by name on the GPU, "
+                         "linked over their merged observations and given one haplotag (not in the reference; DESIGN.md 7i)")
     ap.add_argument("--haplotag_vcf",
                     help="with --from_bam / --from_bams and --include_hp: a phased VCF (a|b records with PS); every read the candidate "
                          "stage fetches gets its haplotag from it on the GPU, in place of the BAM's own HP tag (not in the reference; "
@@ -485,7 +489,10 @@ def gvcf_pass(args, result_path: str, genome: Dict[str, str]) -> Optional[str]:
 
 
 def check_phase(args) -> None:
-    """The refusals of --phase, each naming the fix."""
+    """The refusals of --phase and --phase_fragments, each naming the fix."""
+    if getattr(args, "phase_fragments", False) and not (getattr(args, "phase", False) or getattr(args, "haplotag", False)):
+        raise SystemExit("--phase_fragments is a mode of the phasing pass and there is none in this run: add --phase (a phased VCF "
+                         "beside the result) or --haplotag (its pass 1 phases), or drop --phase_fragments")
     if not getattr(args, "phase", False):
         return
     if not _bam_route(args):
@@ -510,12 +517,17 @@ def phase_pass(args, result_path: str) -> Optional[str]:
     out = result_path[:-len(".vcf")] + ".phased.vcf"
     t0 = time.perf_counter()
     stats: dict = {}
+    fragments = bool(getattr(args, "phase_fragments", False))
     phase.write_phased_vcf(result_path, list(route.bams), out, route.chromosomes, route.q_threshold,
-                           route.mapq_threshold, args.phase_window, args.phase_min_margin, route.device, stats=stats)
+                           route.mapq_threshold, args.phase_window, args.phase_min_margin, route.device, stats=stats,
+                           **({"fragments": True} if fragments else {}))           # without the flag: the call of 7g, as it was
     logging.getLogger("hello_amd.call").info(
         "phase pass: %d slots of %d reads in %s, %.2f s (BAM decode %.2f s, kernels %.1f ms)", int(stats.get("slots", 0)),
         int(stats.get("reads_counted", 0)), out, time.perf_counter() - t0, stats.get("decode_s", 0.0),
-        stats.get("observe_ms", 0.0) + stats.get("link_ms", 0.0) + stats.get("tag_ms", 0.0))
+        sum(stats.get(k, 0.0) for k in ("observe_ms", "link_ms", "tag_ms", "pair_ms", "fragment_link_ms", "fragment_tag_ms")))
+    if fragments:
+        logging.getLogger("hello_amd.call").info("--phase_fragments: %d pairs joined, %d groups of reads with one name left apart",
+                                                 int(stats.get("pairs", 0)), int(stats.get("groups_refused", 0)))
     return out
 
 
@@ -563,7 +575,8 @@ def _close_haplotagger(tagger) -> None:
 def haplotag_passes(args) -> str:
     """--haplotag: pass 1 is this command without --haplotag, --gvcf, --annotate and --annotate_evidence and with --phase, in
     ``<workdir>/haplotag_pass1``; pass 2 is this command with --haplotag_vcf on pass 1's phased VCF, in ``<workdir>``.  Both run in
-    this process, each as the command would run alone (the hotspot stage runs twice)."""
+    this process, each as the command would run alone (the hotspot stage runs twice).  --phase_fragments goes to pass 1, and to
+    pass 2 only where --phase was given as well."""
     logger = logging.getLogger("hello_amd.call")
     first = argparse.Namespace(**vars(args))
     first.haplotag = first.gvcf = first.annotate = first.annotate_evidence = False
@@ -573,6 +586,7 @@ def haplotag_passes(args) -> str:
     logger.info("--haplotag: pass 1 wrote %s; pass 2 tags the reads from it", phased_path)
     second = argparse.Namespace(**vars(args))
     second.haplotag = False
+    second.phase_fragments = bool(getattr(args, "phase_fragments", False) and getattr(args, "phase", False))   # else pass 1's alone
     second.haplotag_vcf = phased_path
     return main(second)
 

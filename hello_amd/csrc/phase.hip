@@ -17,6 +17,21 @@
 //     slots of its own read and adds 1 to link[t][k][cis | trans] in global memory with an integer atomic.
 //   tag: a thread per counted read, one pass over its slots with the sets and flips the host chained.
 // Slot capacity is exact, counters are integers and every slot and every tag has one writer: two runs give the same bytes.
+//
+// Fragments (hello_phase_fragments, hello_phase_tag_fragments): the two mates of a read pair act as one
+// fragment.  After the last observe the handle's slots are joined into one device array and three more launches run over the
+// counted reads of ALL batches, indexed c = 0..counted-1 in the order given:
+//   pair (two kernels): an open-addressing table of 2^k >= 2 counted slots in global memory.  Insert: a thread per counted read
+//     claims the slot of its (name_hash, source) with atomicCAS on an int32 owner (-1 empty, else the claiming read) or finds the
+//     slot whose owner has its key -- keys are compared in the input arrays, so no key value is reserved -- and counts itself
+//     into the slot: reads, first mates, second mates, the smallest index of each kind (atomicAdd / atomicMin, the result does
+//     not depend on arrival order; which read owns a slot does, and nothing reads the owner but the probe).  Look-up: a thread
+//     per counted read finds its slot again and writes mate[c]; the slot's owner counts the group into pairs / groups_refused.
+//   fragment link: a thread per slot.  Exactly one thread answers for a (fragment, record): the slot of the only read that
+//     covers it or, where both mates do, the slot of the mate with the smaller index.  It evaluates F(t), looks back d = 1..window
+//     and evaluates F(t - d) from at most two slot loads, one atomicAdd on int32 per link.
+//   fragment tag: a thread per counted read, one pass over its range and its mate's in record order; both mates compute the same
+//     answer and each writes its own.
 #include <chrono>
 #include <climits>
 #include <memory>
@@ -125,6 +140,160 @@ __global__ __launch_bounds__(kPhThreads) void phase_tag_kernel(PhTagArgs a) {
     a.ps[k] = pos;
 }
 
+// ---- fragments: pairing ------------------------------------------------------------------------------------------------------
+struct PhPairArgs {
+    const uint64_t* name;        // [counted]: name_hash, flags and source of the counted reads, gathered on the host
+    const uint16_t* flags;
+    const uint8_t* source;
+    int32_t* owner;              // [mask + 1]: -1 empty, else the counted read that claimed the slot
+    int32_t* count;              // reads of the slot's group
+    int32_t* n_first;            // those with flag 0x1 and flag & 0xC0 == 0x40
+    int32_t* n_second;           // ... == 0x80
+    int32_t* min_first;          // the smallest counted index of each kind
+    int32_t* min_second;
+    int32_t* mate;               // [counted]
+    int32_t* totals;             // pairs, groups_refused
+    int64_t n_counted;
+    uint32_t mask;
+};
+
+// The first slot probed for a key (phase.pair_table_slot restates it): every bit of the name reaches the slot.
+__host__ __device__ inline uint32_t pair_slot(uint64_t name, uint32_t source, uint32_t mask) {
+    uint64_t x = name ^ (name >> 29);
+    x *= 0xBF58476D1CE4E5B9ull;
+    x ^= x >> 32;
+    return ((uint32_t)x + source) & mask;
+}
+
+// The slot of c's group.  claim: an empty slot on the way becomes c's.  The table holds at least twice the counted reads, so a
+// probe ends at an empty slot or at its group's before it has come round; it wraps at the table's end.
+template <bool claim> __device__ inline uint32_t pair_probe(const PhPairArgs& a, int32_t c) {
+    const uint64_t name = a.name[c];
+    const uint32_t source = a.source[c];
+    uint32_t slot = pair_slot(name, source, a.mask);
+    for (uint32_t tried = 0; tried <= a.mask; ++tried) {
+        const int32_t o = claim ? atomicCAS(&a.owner[slot], -1, c) : a.owner[slot];
+        if (o < 0 || o == c) break;                                       // claimed just now (or, looking up, not there: never)
+        if (a.name[o] == name && a.source[o] == source) break;
+        slot = (slot + 1) & a.mask;
+    }
+    return slot;
+}
+
+__global__ __launch_bounds__(kPhThreads) void phase_pair_insert_kernel(PhPairArgs a) {
+    const int64_t i = (int64_t)blockIdx.x * kPhThreads + threadIdx.x;
+    if (i >= a.n_counted) return;
+    const int32_t c = (int32_t)i;
+    const uint32_t slot = pair_probe<true>(a, c);
+    atomicAdd(&a.count[slot], 1);
+    const int f = a.flags[c];
+    if ((f & 0x1) && (f & 0xC0) == 0x40) { atomicAdd(&a.n_first[slot], 1); atomicMin(&a.min_first[slot], c); }
+    if ((f & 0x1) && (f & 0xC0) == 0x80) { atomicAdd(&a.n_second[slot], 1); atomicMin(&a.min_second[slot], c); }
+}
+
+__global__ __launch_bounds__(kPhThreads) void phase_pair_lookup_kernel(PhPairArgs a) {
+    const int64_t i = (int64_t)blockIdx.x * kPhThreads + threadIdx.x;
+    bool joined = false, refused = false;                                               // of the group this thread owns
+    if (i < a.n_counted) {
+        const int32_t c = (int32_t)i;
+        const uint32_t slot = pair_probe<false>(a, c);
+        const int n = a.count[slot];
+        const bool pair = n == 2 && a.n_first[slot] == 1 && a.n_second[slot] == 1;
+        a.mate[c] = !pair ? -1 : a.min_first[slot] == c ? a.min_second[slot] : a.min_first[slot];
+        joined = a.owner[slot] == c && pair;                                            // a group is counted once, by its owner
+        refused = a.owner[slot] == c && !pair && n >= 2;
+    }
+    // one add per wave and counter instead of one per group: every lane reaches the ballots
+    const unsigned long long j = __ballot(joined), r = __ballot(refused);
+    if ((threadIdx.x & 63) == 0) {
+        if (j) atomicAdd(&a.totals[0], __popcll(j));
+        if (r) atomicAdd(&a.totals[1], __popcll(r));
+    }
+}
+
+// ---- fragments: links and tags -----------------------------------------------------------------------------------------------
+struct PhFragArgs {
+    const int8_t* slots;         // the batches' slots, joined
+    const int64_t* slot_off;     // [counted + 1]
+    const int64_t* first;        // [counted]
+    const int32_t* mate;         // [counted]: the mate's counted index or -1
+    int32_t* link;               // [records][window][2]
+    int64_t n_slots, n_counted;
+    int window;
+    const int32_t* set;          // the tag launch: as PhTagArgs
+    const uint8_t* flip;
+    const int64_t* set_pos;
+    uint8_t* hp;
+    int64_t* ps;
+};
+
+struct PhRange { int64_t first, slot, n; };      // a read's candidate records [first, first + n) and its first slot
+
+__device__ inline PhRange range_of(const PhFragArgs& a, int64_t k) {
+    if (k < 0) return PhRange{0, 0, 0};
+    const int64_t s = a.slot_off[k];
+    return PhRange{a.first[k], s, a.slot_off[k + 1] - s};
+}
+
+__device__ inline bool covers(const PhRange& r, int64_t t) { return t >= r.first && t < r.first + r.n; }
+
+// F(t) of the fragment whose reads have the ranges x and y: the value of the only slot that covers t; with two, the common
+// value, the observed one where only one observed, none where they disagree.
+__device__ inline int fragment_at(const int8_t* slots, const PhRange& x, const PhRange& y, int64_t t) {
+    int o = -1;
+    if (covers(x, t)) o = slots[x.slot + (t - x.first)];
+    if (covers(y, t)) {
+        const int p = slots[y.slot + (t - y.first)];
+        if (o < 0) o = p;
+        else if (p >= 0 && p != o) o = -1;
+    }
+    return o;
+}
+
+__global__ __launch_bounds__(kPhThreads) void phase_fragment_link_kernel(PhFragArgs a) {
+    const int64_t s = (int64_t)blockIdx.x * kPhThreads + threadIdx.x;
+    if (s >= a.n_slots) return;
+    int64_t x = 0, y = a.n_counted + 1;                                   // the last read whose first slot is at or before s
+    while (x < y) {
+        const int64_t mid = (x + y) >> 1;
+        if (a.slot_off[mid] <= s) x = mid + 1; else y = mid;
+    }
+    const int64_t k = x - 1, m = a.mate[k];
+    const PhRange own = range_of(a, k), other = range_of(a, m);
+    const int64_t t = own.first + (s - own.slot);
+    if (m >= 0 && m < k && covers(other, t)) return;                      // the mate's slot answers for this record
+    const int o = fragment_at(a.slots, own, other, t);
+    if (o < 0) return;
+    for (int d = 1; d <= a.window && t - d >= 0; ++d) {
+        const int p = fragment_at(a.slots, own, other, t - d);
+        if (p < 0) continue;
+        atomicAdd(&a.link[(t * a.window + (d - 1)) * 2 + (p != o ? 1 : 0)], 1);
+    }
+}
+
+__global__ __launch_bounds__(kPhThreads) void phase_fragment_tag_kernel(PhFragArgs a) {
+    const int64_t k = (int64_t)blockIdx.x * kPhThreads + threadIdx.x;
+    if (k >= a.n_counted) return;
+    PhRange lo = range_of(a, k), hi = range_of(a, a.mate[k]);
+    if (lo.n == 0 || (hi.n > 0 && hi.first < lo.first)) { const PhRange z = lo; lo = hi; hi = z; }      // record order
+    int mine = -1, n1 = 0, n2 = 0;
+    int64_t pos = 0;
+    const auto visit = [&](int64_t t) {
+        const int o = fragment_at(a.slots, lo, hi, t);
+        if (o < 0 || a.set_pos[t] == 0) return;
+        if (mine < 0) { mine = a.set[t]; pos = a.set_pos[t]; }
+        if (a.set[t] != mine) return;
+        if ((o ^ (int)a.flip[t]) == 0) ++n1; else ++n2;
+    };
+    // lo's records, then what hi adds behind them: the records in a gap between the mates have no observation
+    const int64_t end = lo.first + lo.n;
+    for (int64_t t = lo.first; t < end; ++t) visit(t);
+    if (hi.n > 0)
+        for (int64_t t = hi.first > end ? hi.first : end; t < hi.first + hi.n; ++t) visit(t);
+    a.hp[k] = n1 > n2 ? 1 : n2 > n1 ? 2 : 0;
+    a.ps[k] = pos;
+}
+
 struct PhBatch {
     int8_t* slots = nullptr;     // device
     int64_t* slot_off = nullptr;
@@ -150,8 +319,22 @@ struct hello_phase {
     std::vector<int32_t> links;
     std::vector<uint8_t> hp;
     double stats[HELLO_PHASE_STATS] = {0};
+    // fragments (hello_phase_fragments): the counted reads of all batches as one set, on the device until the handle goes
+    bool fragments = false;
+    int64_t n_counted = 0, n_slots = 0;
+    std::vector<int64_t> counted_reads, mate;       // [counted]: the read of c in the order given; [reads]: the mate or -1
+    std::vector<int32_t> fragment_links;
+    int8_t* d_frag_slots = nullptr;
+    int64_t* d_frag_slot_off = nullptr;
+    int64_t* d_frag_first = nullptr;
+    int32_t* d_frag_mate = nullptr;
+    double fragment_stats[HELLO_PHASE_FRAGMENT_STATS] = {0};
     ~hello_phase() {
         for (auto& b : batches) { (void)hipFree(b.slots); (void)hipFree(b.slot_off); (void)hipFree(b.first); }
+        (void)hipFree(d_frag_slots);
+        (void)hipFree(d_frag_slot_off);
+        (void)hipFree(d_frag_first);
+        (void)hipFree(d_frag_mate);
         (void)hipFree(d_rec_start);
         (void)hipFree(d_rec_end);
         (void)hipFree(d_alleles);
@@ -166,6 +349,20 @@ unsigned blocks_for(int64_t items, int per_block) {
     const int64_t n = (items + per_block - 1) / per_block;
     if (n > INT32_MAX) raise(HELLO_ERR_ARG, "%lld items in one launch", (long long)items);
     return (unsigned)n;
+}
+
+// The chained set / flip a tag call is given, validated -> per record the POS of its set's first record, 0 for a set of one.
+std::vector<int64_t> set_positions(const hello_phase* h, const int32_t* set, const uint8_t* flip) {
+    const int64_t n = h->n_records;
+    std::vector<int64_t> members((size_t)n, 0), set_pos((size_t)n, 0);
+    for (int64_t t = 0; t < n; ++t) {
+        if (set[t] < 0 || set[t] > t || set[set[t]] != set[t])
+            raise(HELLO_ERR_ARG, "set[%lld] = %d: the record that opened the set, at or before it", (long long)t, set[t]);
+        if (flip[t] > 1) raise(HELLO_ERR_ARG, "flip[%lld] = %d: 0 or 1", (long long)t, (int)flip[t]);
+        ++members[set[t]];
+    }
+    for (int64_t t = 0; t < n; ++t) set_pos[t] = members[set[t]] >= 2 ? h->rec_start[set[t]] + 1 : 0;
+    return set_pos;
 }
 
 }  // namespace
@@ -228,6 +425,7 @@ int hello_phase_observe(const uint8_t* bases, const uint8_t* quals, const int64_
         HS_HIP(hipSetDevice(h->device));
     }
     if (!h->hp.empty() || !h->ps.empty()) return set_last_error(HELLO_ERR_ARG, "reads cannot be added after hello_phase_tag");
+    if (h->fragments) return set_last_error(HELLO_ERR_ARG, "reads cannot be added after hello_phase_fragments");
 
     // ---- the counted reads, validated (the kernel reads within their bases), and the records each one's start-to-end covers
     const int64_t n = h->n_records;
@@ -378,14 +576,7 @@ int hello_phase_tag(hello_phase* h, const int32_t* set, const uint8_t* flip) try
     const auto t0 = clock::now();
     if (!h || (h->n_records > 0 && (!set || !flip))) return set_last_error(HELLO_ERR_ARG, "NULL pointer");
     const int64_t n = h->n_records;
-    std::vector<int64_t> members((size_t)n, 0), set_pos((size_t)n, 0);
-    for (int64_t t = 0; t < n; ++t) {
-        if (set[t] < 0 || set[t] > t || set[set[t]] != set[t])
-            return set_last_error(HELLO_ERR_ARG, "set[%lld] = %d: the record that opened the set, at or before it", (long long)t, set[t]);
-        if (flip[t] > 1) return set_last_error(HELLO_ERR_ARG, "flip[%lld] = %d: 0 or 1", (long long)t, (int)flip[t]);
-        ++members[set[t]];
-    }
-    for (int64_t t = 0; t < n; ++t) set_pos[t] = members[set[t]] >= 2 ? h->rec_start[set[t]] + 1 : 0;
+    const std::vector<int64_t> set_pos = set_positions(h, set, flip);
     h->hp.assign((size_t)h->n_reads, 0);
     h->ps.assign((size_t)h->n_reads, 0);
     h->stats[6] = 0.0;
@@ -424,6 +615,157 @@ int hello_phase_tag(hello_phase* h, const int32_t* set, const uint8_t* flip) try
     return HELLO_OK;
 } HS_ENTRY_END("hello_phase_tag")
 
+int hello_phase_fragments(hello_phase* h, const uint64_t* name_hash, const uint16_t* flags, const uint8_t* source,
+                          int64_t n_reads) try {
+    using namespace hello;
+    if (!h) return set_last_error(HELLO_ERR_ARG, "NULL pointer");
+    if (n_reads != h->n_reads)
+        return set_last_error(HELLO_ERR_ARG, "n_reads %lld: the handle holds %lld reads", (long long)n_reads, (long long)h->n_reads);
+    if (n_reads > 0 && (!name_hash || !flags || !source)) return set_last_error(HELLO_ERR_ARG, "NULL pointer");
+    if (!h->hp.empty() || !h->ps.empty()) return set_last_error(HELLO_ERR_ARG, "mates cannot be joined after a tag call");
+    if (h->fragments) return set_last_error(HELLO_ERR_ARG, "hello_phase_fragments is called once, after the last hello_phase_observe");
+    for (int64_t r = 0; r < n_reads; ++r)
+        if (source[r] > 1) return set_last_error(HELLO_ERR_ARG, "source[%lld] = %d: 0 or 1", (long long)r, (int)source[r]);
+
+    // ---- the counted reads of all batches as one set, c = 0..n-1 in the order given, and their slots in the joined array
+    std::vector<int64_t> reads;
+    for (const PhBatch& b : h->batches)
+        for (int64_t r : b.reads) reads.push_back(b.read_base + r);
+    const int64_t n = (int64_t)reads.size(), n_slots = (int64_t)h->slots.size();
+    if (n > (1 << 29)) return set_last_error(HELLO_ERR_ARG, "%lld counted reads in one chromosome", (long long)n);
+    std::vector<uint64_t> name((size_t)n);
+    std::vector<uint16_t> fl((size_t)n);
+    std::vector<uint8_t> src((size_t)n);
+    std::vector<int64_t> first((size_t)n), slot_off((size_t)n + 1, n_slots);
+    for (int64_t c = 0; c < n; ++c) {
+        const size_t r = (size_t)reads[c];
+        name[c] = name_hash[r];
+        fl[c] = flags[r];
+        src[c] = source[r];
+        first[c] = h->first[r];
+        slot_off[c] = h->slot_offsets[r];                                  // an uncounted read has no slot: c's slots end where
+    }                                                                       // those of c + 1 begin
+    uint32_t table = 2;
+    while ((int64_t)table < 2 * n) table <<= 1;
+
+    std::vector<int32_t> mate((size_t)n, -1), link(h->links.size(), 0);
+    int32_t totals[2] = {0, 0};
+    float pair_ms = 0.0f, link_ms = 0.0f;
+    if (n > 0) {
+        HS_HIP(hipSetDevice(h->device));
+        DevMem m;
+        for (void* p : {(void*)h->d_frag_slot_off, (void*)h->d_frag_first, (void*)h->d_frag_mate, (void*)h->d_frag_slots})
+            (void)hipFree(p);                                              // what a refused earlier call left
+        h->d_frag_slot_off = h->d_frag_first = nullptr;
+        h->d_frag_mate = nullptr;
+        h->d_frag_slots = nullptr;
+        const auto take = [&m](auto* p) { return m.release(p); };         // to the handle at once, as in hello_phase_observe
+        h->d_frag_slot_off = take(m.put(slot_off.data(), slot_off.size()));
+        h->d_frag_first = take(m.put(first.data(), first.size()));
+        h->d_frag_mate = take(m.room<int32_t>((size_t)n));
+        h->d_frag_slots = take(m.room<int8_t>((size_t)n_slots));
+        int64_t at = 0;
+        for (const PhBatch& b : h->batches) {                              // the slots stay on the device: joined there
+            if (b.n_slots > 0) HS_HIP(hipMemcpy(h->d_frag_slots + at, b.slots, (size_t)b.n_slots, hipMemcpyDeviceToDevice));
+            at += b.n_slots;
+        }
+        if (at != n_slots) raise(HELLO_ERR_SHAPE, "the batches hold %lld slots, the handle %lld", (long long)at, (long long)n_slots);
+        PhPairArgs p{};
+        p.name = m.put(name.data(), name.size());
+        p.flags = m.put(fl.data(), fl.size());
+        p.source = m.put(src.data(), src.size());
+        p.owner = m.room<int32_t>(table);
+        HS_HIP(hipMemset(p.owner, 0xFF, (size_t)table * sizeof(int32_t)));
+        p.count = m.zeros<int32_t>(table);
+        p.n_first = m.zeros<int32_t>(table);
+        p.n_second = m.zeros<int32_t>(table);
+        p.min_first = m.room<int32_t>(table);
+        p.min_second = m.room<int32_t>(table);
+        HS_HIP(hipMemset(p.min_first, 0x7F, (size_t)table * sizeof(int32_t)));      // above every index
+        HS_HIP(hipMemset(p.min_second, 0x7F, (size_t)table * sizeof(int32_t)));
+        p.mate = h->d_frag_mate;
+        p.totals = m.zeros<int32_t>(2);
+        p.n_counted = n;
+        p.mask = table - 1;
+        KernelTimer timer;
+        timer.start();
+        hipLaunchKernelGGL(phase_pair_insert_kernel, dim3(blocks_for(n, kPhThreads)), dim3(kPhThreads), 0, 0, p);
+        hipLaunchKernelGGL(phase_pair_lookup_kernel, dim3(blocks_for(n, kPhThreads)), dim3(kPhThreads), 0, 0, p);
+        pair_ms = timer.stop();
+        HS_HIP(hipMemcpy(mate.data(), p.mate, mate.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HS_HIP(hipMemcpy(totals, p.totals, sizeof(totals), hipMemcpyDeviceToHost));
+        if (n_slots > 0) {
+            PhFragArgs a{};
+            a.slots = h->d_frag_slots;
+            a.slot_off = h->d_frag_slot_off;
+            a.first = h->d_frag_first;
+            a.mate = h->d_frag_mate;
+            a.link = m.zeros<int32_t>(link.size());
+            a.n_slots = n_slots;
+            a.n_counted = n;
+            a.window = h->window;
+            timer.start();
+            hipLaunchKernelGGL(phase_fragment_link_kernel, dim3(blocks_for(n_slots, kPhThreads)), dim3(kPhThreads), 0, 0, a);
+            link_ms = timer.stop();
+            HS_HIP(hipMemcpy(link.data(), a.link, link.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        }
+    }
+    h->mate.assign((size_t)n_reads, -1);
+    for (int64_t c = 0; c < n; ++c)
+        if (mate[c] >= 0) h->mate[(size_t)reads[c]] = reads[mate[c]];
+    h->fragment_links.swap(link);
+    h->counted_reads.swap(reads);
+    h->n_counted = n;
+    h->n_slots = n_slots;
+    h->fragment_stats[0] = (double)totals[0];
+    h->fragment_stats[1] = (double)totals[1];
+    h->fragment_stats[2] = pair_ms;
+    h->fragment_stats[3] = link_ms;
+    h->fragments = true;
+    return HELLO_OK;
+} HS_ENTRY_END("hello_phase_fragments")
+
+int hello_phase_tag_fragments(hello_phase* h, const int32_t* set, const uint8_t* flip) try {
+    using namespace hello;
+    if (!h || (h->n_records > 0 && (!set || !flip))) return set_last_error(HELLO_ERR_ARG, "NULL pointer");
+    if (!h->fragments) return set_last_error(HELLO_ERR_ARG, "hello_phase_tag_fragments needs hello_phase_fragments before it");
+    const std::vector<int64_t> set_pos = set_positions(h, set, flip);
+    h->hp.assign((size_t)h->n_reads, 0);
+    h->ps.assign((size_t)h->n_reads, 0);
+    h->fragment_stats[4] = 0.0;
+    if (h->n_slots > 0) {
+        HS_HIP(hipSetDevice(h->device));
+        DevMem m;
+        const size_t n = (size_t)h->n_counted;
+        PhFragArgs a{};
+        a.slots = h->d_frag_slots;
+        a.slot_off = h->d_frag_slot_off;
+        a.first = h->d_frag_first;
+        a.mate = h->d_frag_mate;
+        a.n_slots = h->n_slots;
+        a.n_counted = h->n_counted;
+        a.window = h->window;
+        a.set = m.put(set, (size_t)h->n_records);
+        a.flip = m.put(flip, (size_t)h->n_records);
+        a.set_pos = m.put(set_pos.data(), set_pos.size());
+        a.hp = m.room<uint8_t>(n);
+        a.ps = m.room<int64_t>(n);
+        KernelTimer timer;
+        timer.start();
+        hipLaunchKernelGGL(phase_fragment_tag_kernel, dim3(blocks_for(h->n_counted, kPhThreads)), dim3(kPhThreads), 0, 0, a);
+        h->fragment_stats[4] = timer.stop();
+        std::vector<uint8_t> hp(n);
+        std::vector<int64_t> ps(n);
+        HS_HIP(hipMemcpy(hp.data(), a.hp, n, hipMemcpyDeviceToHost));
+        HS_HIP(hipMemcpy(ps.data(), a.ps, n * sizeof(int64_t), hipMemcpyDeviceToHost));
+        for (size_t c = 0; c < n; ++c) {
+            h->hp[(size_t)h->counted_reads[c]] = hp[c];
+            h->ps[(size_t)h->counted_reads[c]] = ps[c];
+        }
+    }
+    return HELLO_OK;
+} HS_ENTRY_END("hello_phase_tag_fragments")
+
 int hello_phase_array(const hello_phase* h, int32_t which, const void** data, int64_t* count) {
     if (!h || !data || !count) return hello::set_last_error(HELLO_ERR_ARG, "NULL pointer");
     switch (which) {
@@ -433,6 +775,8 @@ int hello_phase_array(const hello_phase* h, int32_t which, const void** data, in
         case HELLO_PHASE_LINKS: *data = h->links.data(); *count = (int64_t)h->links.size(); break;
         case HELLO_PHASE_HP: *data = h->hp.data(); *count = (int64_t)h->hp.size(); break;
         case HELLO_PHASE_PS: *data = h->ps.data(); *count = (int64_t)h->ps.size(); break;
+        case HELLO_PHASE_MATE: *data = h->mate.data(); *count = (int64_t)h->mate.size(); break;
+        case HELLO_PHASE_FRAGMENT_LINKS: *data = h->fragment_links.data(); *count = (int64_t)h->fragment_links.size(); break;
         default: return hello::set_last_error(HELLO_ERR_ARG, "array selector %d", which);
     }
     return HELLO_OK;
@@ -441,6 +785,12 @@ int hello_phase_array(const hello_phase* h, int32_t which, const void** data, in
 int hello_phase_stats(const hello_phase* h, double* stats) {
     if (!h || !stats) return hello::set_last_error(HELLO_ERR_ARG, "NULL pointer");
     std::copy(h->stats, h->stats + HELLO_PHASE_STATS, stats);
+    return HELLO_OK;
+}
+
+int hello_phase_fragment_stats(const hello_phase* h, double* stats) {
+    if (!h || !stats) return hello::set_last_error(HELLO_ERR_ARG, "NULL pointer");
+    std::copy(h->fragment_stats, h->fragment_stats + HELLO_PHASE_FRAGMENT_STATS, stats);
     return HELLO_OK;
 }
 

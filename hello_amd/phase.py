@@ -9,6 +9,12 @@ Not in the reference; DESIGN.md section 7g defines the rules.  ``phasable``, ``o
 integer; ``write_phased_vcf`` is the driver pass: its own walk over the BAM(s) after scoring, one batch of reads per span of at
 most ``hotspots.MAX_LAUNCH_BASES`` positions (a read belongs to the span that holds its start), the spans' links added on the
 host, one chain per chromosome.
+
+``--phase_fragments`` (off by default) makes the two mates of a read pair one fragment: ``join_mates`` /
+``mates_of``, ``fragment_observations`` and the ``mate`` argument of ``links_of`` and ``haplotags_of`` restate the rules;
+``Phaser.fragments`` binds ``hello_phase_fragments`` (the pair and fragment-link kernels), ``Phaser.tag(..., fragments=True)``
+``hello_phase_tag_fragments``.  The driver collects name_hash, flags and source span after span and joins once per chromosome, so
+mates in different spans are joined too.
 """
 from __future__ import annotations
 
@@ -31,7 +37,9 @@ DEFAULT_WINDOW = 8
 DEFAULT_MIN_MARGIN = 2
 PS_HEADER = '##FORMAT=<ID=PS,Number=1,Type=Integer,Description="Phase set: POS of its first record">\n'
 SLOTS, SLOT_OFFSETS, FIRST, LINKS, HP, PS = range(6)
+MATE, FRAGMENT_LINKS = 6, 7
 STAT_NAMES = ("records", "reads", "reads_counted", "slots", "observe_ms", "link_ms", "tag_ms", "plan_ms", "total_ms")
+FRAGMENT_STAT_NAMES = ("pairs", "groups_refused", "pair_ms", "fragment_link_ms", "fragment_tag_ms")
 
 _log = logging.getLogger(__name__)
 _ACGT = frozenset(b"ACGT")
@@ -164,10 +172,85 @@ def slots_of(reads: Sequence[Reads], records: Sequence[Record], q_threshold: int
     return np.array(slots, np.int8), np.array(offsets, np.int64), np.array(first, np.int64)
 
 
-def links_of(slots, slot_offsets, first, n_records: int, window: int = DEFAULT_WINDOW) -> np.ndarray:
-    """int32 [n_records, window, 2]: link[t][k - 1][0] counts the reads with equal observations at t and t - k, [1] with unequal."""
-    link = np.zeros((n_records, window, 2), np.int32)
+def join_mates(name_hash, flags, source, is_counted):
+    """(mate int64 [reads], {pairs, groups_refused}) -- section 7i: the counted reads grouped by (source, name_hash); a group of
+    exactly two reads that both have flag 0x1, one with ``flag & 0xC0 == 0x40`` and one with ``== 0x80``, is a pair and each
+    read's mate is the other's index; every other read has -1.  ``groups_refused``: the groups of two or more left apart."""
+    groups: Dict[Tuple[int, int], List[int]] = {}
+    for r in range(len(flags)):
+        if is_counted[r]:
+            groups.setdefault((int(source[r]), int(name_hash[r])), []).append(r)
+    mate = np.full(len(flags), -1, np.int64)
+    pairs = refused = 0
+    for members in groups.values():
+        kinds = sorted(int(flags[r]) & 0xC0 if int(flags[r]) & 0x1 else 0 for r in members)
+        if kinds == [0x40, 0x80]:
+            mate[members[0]], mate[members[1]] = members[1], members[0]
+            pairs += 1
+        elif len(members) >= 2:
+            refused += 1
+    return mate, dict(pairs=pairs, groups_refused=refused)
+
+
+def mates_of(reads: Sequence[Reads], mapq_threshold: int = 10, details: Optional[dict] = None) -> np.ndarray:
+    """int64 [reads]: ``join_mates`` over the read sets one after the other, a read's source being its set.  ``details``: filled
+    with pairs and groups_refused."""
+    if not 1 <= len(reads) <= 2:
+        raise ValueError("one or two read sets (BAM files)")
+    rd, source = Reads.concat(list(reads))
+    mate, counts = join_mates(rd.name_hash, rd.flags, source, counted_mask(rd, mapq_threshold))
+    if details is not None:
+        details.update(counts)
+    return mate
+
+
+def fragment_observations(slots, slot_offsets, first, mate):
+    """(slots int8, slot_offsets int64 [reads + 1], first int64 [reads]) of every read's FRAGMENT -- itself, or itself and its
+    mate: one value F(t) per record from the first to the last candidate record of either read.  F(t) is none where no slot
+    covers t (the gap between the mates), the slot's value where one read covers t, and with two the common value, the observed
+    one where only one observed, none where they disagree.  Both mates of a pair get the same arrays."""
+    out: List[int] = []
+    offsets, lows = [0], []
     for r in range(len(first)):
+        ranges = [(int(first[x]), int(slot_offsets[x]), int(slot_offsets[x + 1] - slot_offsets[x]))
+                  for x in ((r,) if mate[r] < 0 else (r, int(mate[r])))]
+        ranges = [x for x in ranges if x[2] > 0]
+        lo = min((f for f, _, _ in ranges), default=int(first[r]))
+        hi = max((f + k for f, _, k in ranges), default=lo)
+        for t in range(lo, hi):
+            seen = {int(slots[s + t - f]) for f, s, k in ranges if f <= t < f + k} - {NONE}
+            out.append(seen.pop() if len(seen) == 1 else NONE)
+        lows.append(lo)
+        offsets.append(offsets[-1] + hi - lo)
+    return np.array(out, np.int8), np.array(offsets, np.int64), np.array(lows, np.int64)
+
+
+def pair_table_size(n_counted: int) -> int:
+    """Slots of the pair kernels' open-addressing table: the power of two that is at least twice the counted reads (and 2)."""
+    size = 2
+    while size < 2 * n_counted:
+        size <<= 1
+    return size
+
+
+def pair_table_slot(name_hash, source, size: int) -> np.ndarray:
+    """uint32: the first slot the pair kernels probe for (name_hash, source) in a table of ``size`` slots (phase.hip: pair_slot)."""
+    x = np.asarray(name_hash, np.uint64)
+    x = x ^ (x >> np.uint64(29))
+    x = x * np.uint64(0xBF58476D1CE4E5B9)
+    x = x ^ (x >> np.uint64(32))
+    return (((x & np.uint64(0xFFFFFFFF)) + np.asarray(source, np.uint64)) & np.uint64(size - 1)).astype(np.uint32)
+
+
+def links_of(slots, slot_offsets, first, n_records: int, window: int = DEFAULT_WINDOW, mate=None) -> np.ndarray:
+    """int32 [n_records, window, 2]: link[t][k - 1][0] counts the reads with equal observations at t and t - k, [1] with unequal.
+    ``mate`` (section 7i): the fragments are counted instead, a pair once over its ``fragment_observations``."""
+    link = np.zeros((n_records, window, 2), np.int32)
+    if mate is not None:
+        slots, slot_offsets, first = fragment_observations(slots, slot_offsets, first, mate)
+    for r in range(len(first)):
+        if mate is not None and 0 <= mate[r] < r:
+            continue                                    # the pair was counted at its first read
         s0, s1 = int(slot_offsets[r]), int(slot_offsets[r + 1])
         for s in range(s0, s1):
             if slots[s] < 0:
@@ -217,9 +300,12 @@ def set_positions(sets, positions) -> np.ndarray:
     return np.where(members[sets] >= 2, positions[sets], 0).astype(np.int64)
 
 
-def haplotags_of(slots, slot_offsets, first, sets, flip, positions):
+def haplotags_of(slots, slot_offsets, first, sets, flip, positions, mate=None):
     """(hp uint8 [reads], ps int64 [reads]): a read's set is that of its first observation at a phased record; over its observations
-    in that set, ``o xor flip`` counts into n1 / n2; hp 1, 2 or 0 (tie, or no set), ps the set's POS or 0."""
+    in that set, ``o xor flip`` counts into n1 / n2; hp 1, 2 or 0 (tie, or no set), ps the set's POS or 0.  ``mate`` (section 7i):
+    the rule runs over the ``fragment_observations`` instead, so both mates of a pair get one tag."""
+    if mate is not None:
+        slots, slot_offsets, first = fragment_observations(slots, slot_offsets, first, mate)
     set_pos = set_positions(sets, positions)
     n = len(first)
     hp, ps = np.zeros(n, np.uint8), np.zeros(n, np.int64)
@@ -267,6 +353,9 @@ _PROTOTYPES = (
     ("hello_phase_tag", [vp, vp, vp]),
     ("hello_phase_array", ARRAY_GETTER),
     ("hello_phase_stats", STATS_GETTER),
+    ("hello_phase_fragments", [vp, vp, vp, vp, i64]),
+    ("hello_phase_tag_fragments", [vp, vp, vp]),
+    ("hello_phase_fragment_stats", STATS_GETTER),
     ("hello_phase_free", [vp], None),
 )
 
@@ -277,7 +366,9 @@ def _lib():
 
 class Phaser:
     """One chromosome's ``hello_phase`` handle: ``observe`` adds a batch of read sets, ``arrays`` gives the slots and the links so
-    far, ``tag`` the haplotype of every read given, in the order given."""
+    far, ``tag`` the haplotype of every read given, in the order given.  ``fragments`` (once, after the last ``observe``) joins
+    the mates of all batches; ``arrays`` then holds ``mate`` and ``fragment_links`` too, and ``tag(..., fragments=True)`` tags both
+    mates of a pair alike."""
 
     def __init__(self, records: Sequence[Record], q_threshold: int = 10, mapq_threshold: int = 10, window: int = DEFAULT_WINDOW,
                  device: int = 0):
@@ -289,6 +380,21 @@ class Phaser:
         self._offsets = np.concatenate([[0], np.cumsum([len(x) for x in text])]).astype(np.int64)
         self._tail = (int(q_threshold), int(mapq_threshold), int(window), int(device))
         self._lib, self._h = _lib(), C.c_void_p()
+        self._joined = False
+
+    def fragments(self, name_hash, flags, source) -> np.ndarray:
+        """``hello_phase_fragments`` with name_hash / flags / source of every read observed, in the order given -> mate int64."""
+        name_hash, flags = np.ascontiguousarray(name_hash, np.uint64), np.ascontiguousarray(flags, np.uint16)
+        source = np.ascontiguousarray(source, np.uint8)
+        if not name_hash.shape == flags.shape == source.shape or name_hash.ndim != 1:
+            raise ValueError("name_hash, flags and source: one entry per read")
+        check(self._lib.hello_phase_fragments(self._h, name_hash.ctypes.data, flags.ctypes.data, source.ctypes.data,
+                                              int(name_hash.shape[0])))
+        self._joined = True
+        return self._array(MATE, np.int64)
+
+    def fragment_stats(self) -> Dict[str, float]:
+        return handle_stats(self._lib.hello_phase_fragment_stats, self._h, FRAGMENT_STAT_NAMES)
 
     def observe(self, reads: Sequence[Reads]) -> None:
         if not 1 <= len(reads) <= 2:
@@ -302,14 +408,19 @@ class Phaser:
         return handle_array(self._lib.hello_phase_array, self._h, which, dtype)
 
     def arrays(self) -> Dict[str, np.ndarray]:
-        return dict(slots=self._array(SLOTS, np.int8), slot_offsets=self._array(SLOT_OFFSETS, np.int64),
-                    first=self._array(FIRST, np.int64), links=self._array(LINKS, np.int32).reshape(self.n_records, self.window, 2))
+        shape = (self.n_records, self.window, 2)
+        out = dict(slots=self._array(SLOTS, np.int8), slot_offsets=self._array(SLOT_OFFSETS, np.int64),
+                   first=self._array(FIRST, np.int64), links=self._array(LINKS, np.int32).reshape(shape))
+        if self._joined:
+            out.update(mate=self._array(MATE, np.int64), fragment_links=self._array(FRAGMENT_LINKS, np.int32).reshape(shape))
+        return out
 
-    def tag(self, sets, flip) -> Tuple[np.ndarray, np.ndarray]:
+    def tag(self, sets, flip, fragments: bool = False) -> Tuple[np.ndarray, np.ndarray]:
         sets, flip = np.ascontiguousarray(sets, np.int32), np.ascontiguousarray(flip, np.uint8)
         if sets.shape != (self.n_records,) or flip.shape != (self.n_records,):
             raise ValueError("set and flip: one entry per record")
-        check(self._lib.hello_phase_tag(self._h, sets.ctypes.data, flip.ctypes.data))
+        tag = self._lib.hello_phase_tag_fragments if fragments else self._lib.hello_phase_tag
+        check(tag(self._h, sets.ctypes.data, flip.ctypes.data))
         return self._array(HP, np.uint8), self._array(PS, np.int64)
 
     def stats(self) -> Dict[str, float]:
@@ -351,16 +462,22 @@ def chain_native(link, window: int = DEFAULT_WINDOW, min_margin: int = DEFAULT_M
 
 
 def find_haplotags(reads: Sequence[Reads], records: Sequence[Record], q_threshold: int = 10, mapq_threshold: int = 10,
-                   window: int = DEFAULT_WINDOW, min_margin: int = DEFAULT_MIN_MARGIN, device: int = 0, details: Optional[dict] = None):
+                   window: int = DEFAULT_WINDOW, min_margin: int = DEFAULT_MIN_MARGIN, device: int = 0, details: Optional[dict] = None,
+                   fragments: bool = False):
     """Observe, chain and tag in one go -> (hp uint8, ps int64), aligned with the reads of the sets one after the other.
-    ``details``: filled with the arrays of ``find_observations``, ``set``, ``flip`` and ``stats``."""
+    ``details``: filled with the arrays of ``find_observations``, ``set``, ``flip`` and ``stats``.  ``fragments`` (section 7i): the
+    mates of a pair are joined, the chain runs on the fragment links and both mates get one tag; ``details`` also holds ``mate``,
+    ``fragment_links`` and the fragment statistics."""
     with Phaser(records, q_threshold, mapq_threshold, window, device) as ph:
         ph.observe(reads)
+        if fragments:
+            rd, source = Reads.concat(list(reads))
+            ph.fragments(rd.name_hash, rd.flags, source)
         got = ph.arrays()
-        sets, flip = chain_native(got["links"], window, min_margin)
-        hp, ps = ph.tag(sets, flip)
+        sets, flip = chain_native(got["fragment_links" if fragments else "links"], window, min_margin)
+        hp, ps = ph.tag(sets, flip, fragments)
         if details is not None:
-            details.update(got, set=sets, flip=flip, stats=ph.stats())
+            details.update(got, set=sets, flip=flip, stats=dict(ph.stats(), **(ph.fragment_stats() if fragments else {})))
         return hp, ps
 
 
@@ -396,9 +513,11 @@ def _from(rd: Reads, lo: int) -> Reads:
 
 def chromosome_phase(handles: Sequence[BamFile], chromosome: str, length: int, records: Sequence[Record], q_threshold: int = 10,
                      mapq_threshold: int = 10, window: int = DEFAULT_WINDOW, min_margin: int = DEFAULT_MIN_MARGIN, device: int = 0,
-                     restatement: bool = False, max_span: Optional[int] = None, stats: Optional[dict] = None) -> Dict[str, np.ndarray]:
+                     restatement: bool = False, max_span: Optional[int] = None, stats: Optional[dict] = None,
+                     fragments: bool = False) -> Dict[str, np.ndarray]:
     """One chromosome: {slots, slot_offsets, first, links, set, flip, hp, ps}; the per-read arrays follow the reads of span after
-    span, within a span the BAMs one after the other."""
+    span, within a span the BAMs one after the other.  ``fragments`` (section 7i): the mates of a pair are joined across all
+    spans -- ``mate`` and ``fragment_links`` are in the result, the chain runs on the fragment links and both mates get one tag."""
     from .hotspots import MAX_LAUNCH_BASES
     step, n = int(max_span or MAX_LAUNCH_BASES), len(records)
     positions = [rec.pos for rec in records]
@@ -407,10 +526,18 @@ def chromosome_phase(handles: Sequence[BamFile], chromosome: str, length: int, r
     ph = None if restatement else Phaser(records, q_threshold, mapq_threshold, window, device)
     try:
         parts, links = [], np.zeros((n, window, 2), np.int32)
+        names, flags, sources, is_counted = [np.zeros(0, np.uint64)], [np.zeros(0, np.uint16)], [np.zeros(0, np.uint8)], [np.zeros(0, bool)]
         for lo in range(0, length, step):
             t0 = time.perf_counter()
             sets = [_from(h.fetch(chromosome, lo, min(lo + step, length)), lo) for h in handles]
             t1 = time.perf_counter()
+            if fragments:                               # what joins the mates, in the handle's read order
+                for i, rd in enumerate(sets):
+                    names.append(rd.name_hash)
+                    flags.append(rd.flags)
+                    sources.append(np.full(rd.n_reads, i, np.uint8))
+                    if restatement:
+                        is_counted.append(counted_mask(rd, mapq_threshold))
             if restatement:
                 slots, offsets, first = slots_of(sets, records, q_threshold, mapq_threshold)
                 links += links_of(slots, offsets, first, n, window)
@@ -428,15 +555,27 @@ def chromosome_phase(handles: Sequence[BamFile], chromosome: str, length: int, r
                 base += int(o[-1])
             out = dict(slots=np.concatenate([p[0] for p in parts] or [np.zeros(0, np.int8)]), slot_offsets=np.concatenate(offsets),
                        first=np.concatenate([p[2] for p in parts] or [np.zeros(0, np.int64)]), links=links)
-            out["set"], out["flip"] = chain(links, window, min_margin)
+            mate = None
+            if fragments:
+                mate, counts = join_mates(np.concatenate(names), np.concatenate(flags), np.concatenate(sources),
+                                          np.concatenate(is_counted))
+                out.update(mate=mate, fragment_links=links_of(out["slots"], out["slot_offsets"], out["first"], n, window, mate))
+                for k, v in counts.items():
+                    add(k, v)
+            out["set"], out["flip"] = chain(out["fragment_links"] if fragments else links, window, min_margin)
             add("chain_s", time.perf_counter() - t0)
-            out["hp"], out["ps"] = haplotags_of(out["slots"], out["slot_offsets"], out["first"], out["set"], out["flip"], positions)
+            out["hp"], out["ps"] = haplotags_of(out["slots"], out["slot_offsets"], out["first"], out["set"], out["flip"], positions,
+                                                mate)
         else:
+            if fragments:
+                ph.fragments(np.concatenate(names), np.concatenate(flags), np.concatenate(sources))
+                add("join_s", time.perf_counter() - t0)
+                t0 = time.perf_counter()
             out = ph.arrays()
-            out["set"], out["flip"] = chain_native(out["links"], window, min_margin)
+            out["set"], out["flip"] = chain_native(out["fragment_links" if fragments else "links"], window, min_margin)
             add("chain_s", time.perf_counter() - t0)
-            out["hp"], out["ps"] = ph.tag(out["set"], out["flip"])
-            for k, v in ph.stats().items():
+            out["hp"], out["ps"] = ph.tag(out["set"], out["flip"], fragments)
+            for k, v in dict(ph.stats(), **(ph.fragment_stats() if fragments else {})).items():
                 add(k, v)
         return out
     finally:
@@ -447,11 +586,12 @@ def chromosome_phase(handles: Sequence[BamFile], chromosome: str, length: int, r
 def write_phased_vcf(vcf_path: str, bams: Sequence[str], out_path: str, chromosomes: Optional[Sequence[str]] = None,
                      q_threshold: int = 10, mapq_threshold: int = 10, window: int = DEFAULT_WINDOW,
                      min_margin: int = DEFAULT_MIN_MARGIN, device: int = 0, restatement: bool = False, max_span: Optional[int] = None,
-                     stats: Optional[dict] = None, haplotags: Optional[dict] = None) -> str:
+                     stats: Optional[dict] = None, haplotags: Optional[dict] = None, fragments: bool = False) -> str:
     """``out_path``: the header of ``vcf_path`` with the PS declaration and its lines in its order, those of the records in a phase
     set of at least two rewritten by ``phased_line``.  Records of ``chromosomes`` (default: every chromosome of the file) are
     phased; chromosome lengths come from the BAM header.  ``restatement``: everything comes from the plain-Python rules instead of
-    the GPU (what the tests compare the GPU's file with).  ``haplotags``: filled with {chromosome: (hp, ps)}."""
+    the GPU (what the tests compare the GPU's file with).  ``haplotags``: filled with {chromosome: (hp, ps)}.  ``fragments``
+    (--phase_fragments, section 7i): the two mates of a read pair count as one fragment."""
     if not 1 <= len(bams) <= 2:
         raise ValueError("one BAM, or an Illumina and a PacBio BAM")
     if not 1 <= window <= MAX_WINDOW:
@@ -474,7 +614,7 @@ def write_phased_vcf(vcf_path: str, bams: Sequence[str], out_path: str, chromoso
                 raise ValueError(f"no sequence named {c!r} in the BAM header")
             records = [rec for _, rec in recs]
             got = chromosome_phase(handles, c, min(known[c] for known in lengths), records, q_threshold, mapq_threshold, window,
-                                   min_margin, device, restatement, max_span, stats)
+                                   min_margin, device, restatement, max_span, stats, fragments)
             t0 = time.perf_counter()
             set_pos = set_positions(got["set"], [rec.pos for rec in records])
             for (i, rec), flip, ps in zip(recs, got["flip"].tolist(), set_pos.tolist()):
@@ -508,6 +648,8 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--mapq_threshold", type=int, default=10, help="Mapping quality threshold")
     p.add_argument("--phase_window", type=int, default=DEFAULT_WINDOW, help="Records back that a record is linked to (1 to 32)")
     p.add_argument("--phase_min_margin", type=int, default=DEFAULT_MIN_MARGIN, help="Smallest |cis - trans| that joins a set")
+    p.add_argument("--phase_fragments", action="store_true", default=False,
+                   help="The two mates of a read pair act as one fragment: joined by name on the GPU, linked and tagged together")
     p.add_argument("--device", type=int, default=0, help="GPU index")
     return p
 
@@ -523,7 +665,7 @@ def main(argv=None) -> str:
     if len(bams) > 2:
         raise SystemExit("--bam takes one or two files")
     return write_phased_vcf(args.vcf, bams, args.output, args.chromosomes.split(",") if args.chromosomes else None, args.q_threshold,
-                            args.mapq_threshold, args.phase_window, args.phase_min_margin, args.device)
+                            args.mapq_threshold, args.phase_window, args.phase_min_margin, args.device, fragments=args.phase_fragments)
 
 
 if __name__ == "__main__":

@@ -779,9 +779,17 @@ void hello_refblocks_free(hello_refblocks* blocks);
  *          another chromosome are not linked) -> set [n_records] (the index of the record that opened the set of t) and flip.
  *   hello_phase_tag: with the chained set / flip of the handle's records, hp (1, 2, or 0) and ps (the POS of the read's phase set,
  *          or 0) of every read given to hello_phase_observe, in the order given (tag kernel over the slots kept on the device).
+ *   hello_phase_fragments: called once, after the last hello_phase_observe and before any tag call, with
+ *          name_hash / flags / source of EVERY read given so far, in the order given (n_reads must equal the handle's, else
+ *          HELLO_ERR_ARG).  The counted reads of all batches are grouped by (source, name_hash); a group of exactly two reads with
+ *          flag 0x1, one with flag & 0xC0 == 0x40 and one with == 0x80, is a pair, and mate[r] is the other read's index (-1 for
+ *          every other read).  The fragment links count every (pair or single read) once over its merged observations; the
+ *          per-read arrays 0 - 5 stay as they are.  Pair kernels (an open-addressing table, integer atomics) and fragment-link kernel.
+ *   hello_phase_tag_fragments: as hello_phase_tag, the two mates of a pair getting the hp / ps of their fragment (arrays 4 and 5).
  * Host memory in and out; phase.hip. */
 #define HELLO_PHASE_MAX_WINDOW 32
 #define HELLO_PHASE_STATS 9
+#define HELLO_PHASE_FRAGMENT_STATS 5
 enum {
     HELLO_PHASE_SLOTS = 0,         /* int8 [slots] */
     HELLO_PHASE_SLOT_OFFSETS = 1,  /* int64 [reads + 1]: an uncounted read has no slot */
@@ -789,6 +797,10 @@ enum {
     HELLO_PHASE_LINKS = 3,         /* int32 [n_records][window][2], summed over the batches */
     HELLO_PHASE_HP = 4,            /* uint8 [reads], after hello_phase_tag */
     HELLO_PHASE_PS = 5             /* int64 [reads], after hello_phase_tag */
+};
+enum {
+    HELLO_PHASE_MATE = 6,            /* int64 [reads], after hello_phase_fragments: the mate's index or -1 */
+    HELLO_PHASE_FRAGMENT_LINKS = 7   /* int32 [n_records][window][2], after hello_phase_fragments */
 };
 typedef struct hello_phase hello_phase;
 int hello_phase_observe(const uint8_t* bases, const uint8_t* quals, const int64_t* read_offsets, const uint32_t* cigars,
@@ -805,6 +817,12 @@ int hello_phase_array(const hello_phase* phase, int32_t which, const void** data
 /* stats[HELLO_PHASE_STATS]: records, reads given, reads counted, slots, observe / link / tag kernel ms (HIP events), plan ms,
  * total ms of the calls */
 int hello_phase_stats(const hello_phase* phase, double* stats);
+int hello_phase_fragments(hello_phase* phase, const uint64_t* name_hash, const uint16_t* flags, const uint8_t* source,
+                          int64_t n_reads);
+int hello_phase_tag_fragments(hello_phase* phase, const int32_t* set, const uint8_t* flip);
+/* stats[HELLO_PHASE_FRAGMENT_STATS]: pairs, groups of two or more reads that were not joined, pair / fragment-link / fragment-tag
+ * kernel ms (HIP events) */
+int hello_phase_fragment_stats(const hello_phase* phase, double* stats);
 void hello_phase_free(hello_phase* phase);
 
 /* Haplotags from a phased VCF (not in the reference; DESIGN.md section 7h states the rule, hello_amd/haplotag.py restates it in

@@ -6,6 +6,11 @@ read and visits every base, where the observe launch visits only the bases insid
     python tools/phase_bench.py [--length 1000000] [--coverage 30] [--read-length 150] [--repeats 3] [--profile FILE]
     python tools/phase_bench.py --pacbio [--pacbio-coverage 25] [--pacbio-read-length 3000]
     python tools/phase_bench.py --hybrid
+    python tools/phase_bench.py --paired [--insert 450] [--record-every 1000]
+
+--paired: the Illumina reads joined into pairs; the pass runs without and with ``fragments=True`` on the same BAM, interleaved,
+and the line holds both: the kernels' times (pair, fragment link and fragment tag beside observe, link and tag), the whole pass
+and the number of records that get a PS.
 
 Heterozygous records are planted in the VCF at one per --record-every bases (REF: the reference base; the reads are those of one
 donor, so most show the a allele: the walk and the slot count are what is timed, not the sets).  One warm-up run, then --repeats
@@ -27,6 +32,57 @@ from tools.hotspot_bench import synthesize  # noqa: E402
 from tools.refblocks_bench import emit  # noqa: E402
 
 
+def join_pairs(reads, insert, coverage, read_len):
+    """The reads (sorted by start) made into pairs whose starts lie about ``insert - read_len`` apart: every other stretch of k
+    reads joined with the next stretch, one name per pair, flags 0x43 / 0x83 beside the strand bit."""
+    k = max(1, round(coverage / read_len * (insert - read_len)))
+    for i in range(0, len(reads) - k):
+        if (i // k) % 2 == 0:
+            reads[i].name = reads[i + k].name = "p%d" % i
+            reads[i].flag |= 0x43
+            reads[i + k].flag |= 0x83
+    return reads
+
+
+def paired(args):
+    """--paired: the Illumina reads as pairs; the pass without and with --phase_fragments on the same BAM, interleaved."""
+    from hello_amd import phase
+    ref, reads = synthesize(args.length, args.coverage, args.read_length)
+    reads = join_pairs(reads, args.insert, args.coverage, args.read_length)
+    names = ("bam_decode_s", "plan_ms", "observe_ms", "link_ms", "tag_ms", "chain_s", "file_write_s", "pass_s")
+    extra = ("join_s", "pair_ms", "fragment_link_ms", "fragment_tag_ms")
+    times = {False: {k: [] for k in names}, True: {k: [] for k in names + extra}}
+    counts = {}
+    with tempfile.TemporaryDirectory() as d:
+        bam, vcf = os.path.join(d, "pairs.bam"), os.path.join(d, "results.output.vcf")
+        write_bam(bam, [("chr1", len(ref))], reads, index=True)
+        with open(vcf, "w") as fh:
+            fh.write("##fileformat=VCFv4.1\n#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\tSAMPLE1\n")
+            for p in range(args.record_every // 2, len(ref), args.record_every):
+                fh.write("chr1\t%d\t.\t%s\t%s\t30\t.\tHELLO\tGT\t0/1\n" % (p + 1, ref[p], "A" if ref[p] != "A" else "C"))
+        for i in range(args.repeats + 1):
+            for fragments in (False, True):
+                st: dict = {}
+                out = os.path.join(d, "out%d.phased.vcf" % fragments)
+                t0 = time.perf_counter()
+                phase.write_phased_vcf(vcf, [bam], out, stats=st, fragments=fragments)
+                wall = time.perf_counter() - t0
+                if i == 0:
+                    continue                                        # warm-up: library load, first launches
+                st.update(bam_decode_s=st["decode_s"], file_write_s=st["write_s"], pass_s=wall)
+                for k in times[fragments]:
+                    times[fragments][k].append(st[k])
+                with open(out, "rb") as fh:
+                    with_ps = sum(1 for line in fh if not line.startswith(b"#") and b"|" in line.split(b"\t")[9])
+                counts[fragments] = dict(records=int(st["records"]), slots=int(st["slots"]), records_with_ps=with_ps,
+                                         pairs=int(st.get("pairs", 0)), groups_refused=int(st.get("groups_refused", 0)))
+    out = {"phase": "illumina pairs", "length": args.length, "reads": len(reads), "insert": args.insert,
+           "record_every": args.record_every, "repeats": args.repeats}
+    for fragments, label in ((False, "per_read"), (True, "fragments")):
+        out[label] = dict(counts[fragments], **{k: spread(v) for k, v in times[fragments].items()})
+    emit(out, args)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--length", type=int, default=1_000_000)
@@ -38,8 +94,13 @@ def main():
     ap.add_argument("--pacbio-coverage", type=float, default=25)
     ap.add_argument("--pacbio-read-length", type=int, default=3000)
     ap.add_argument("--record-every", type=int, default=1000)
+    ap.add_argument("--paired", action="store_true", default=False,
+                    help="the Illumina reads as pairs: the pass without and with --phase_fragments (DESIGN.md section 7i)")
+    ap.add_argument("--insert", type=int, default=450, help="--paired: from the first mate's start to the second mate's end")
     ap.add_argument("--profile", help="append the JSON line to this file")
     args = ap.parse_args()
+    if args.paired:
+        return paired(args)
     from hello_amd import gvcf, phase
     from hello_amd.bam import BamFile
 
