@@ -32,6 +32,9 @@ _PROTOTYPES = (
 )
 
 
+MARKS: dict = {}   # os.path.abspath of a BAM -> its markdup.Marks; filled by markdup.applied alone, empty without --mark_duplicates
+
+
 def _lib():
     return bind(_PROTOTYPES)
 
@@ -111,7 +114,12 @@ class BamFile:
             n, used, blocks = C.c_int64(), C.c_int32(), C.c_int64()
             _check(self._lib.hello_bam_reads_info(r, C.byref(n), C.byref(used), C.byref(blocks)))
             out = {field: handle_array(self._lib.hello_bam_reads_array, r, which, dtype) for field, which, dtype in _ARRAYS}
-            return Reads(**out, used_index=bool(used.value), n_blocks=int(blocks.value))
+            reads = Reads(**out, used_index=bool(used.value), n_blocks=int(blocks.value))
+            if MARKS:                                   # markdup.applied: the duplicates of this BAM gain flag 0x400
+                marks = MARKS.get(os.path.abspath(self.path))
+                if marks is not None:
+                    marks.apply(chromosome, reads)
+            return reads
         finally:
             self._lib.hello_bam_reads_free(r)
 

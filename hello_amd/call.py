@@ -56,6 +56,10 @@ read the candidate stage fetches a haplotag from the phased VCF ``V`` (``a|b`` r
 tag, on the GPU (``hello_amd.haplotag``) -- the reference's workflow for its haplotagged PacBio model, without
 the outside tool that writes a tagged BAM.  ``--haplotag`` needs no phased VCF: pass 1 is this command with ``--phase`` in
 ``<workdir>/haplotag_pass1``, pass 2 is this command with ``--haplotag_vcf`` on pass 1's ``results.output.phased.vcf``.
+
+``--mark_duplicates`` (with ``--from_bam`` / ``--from_bams``, not in the reference, off by default) finds the PCR duplicates of the
+Illumina BAM on the GPU before the hotspot stage (``hello_amd.markdup``) and runs everything after it with flag
+0x400 set on them in what ``BamFile.fetch`` returns, so every stage drops them; ``<workdir>/duplicates.metrics.txt`` holds the counts.
 """
 from __future__ import annotations
 
@@ -306,6 +310,10 @@ def parser() -> argparse.ArgumentParser:
                     help="with --from_bam / --from_bams and --include_hp: two passes -- this command with --phase in "
                          "<workdir>/haplotag_pass1, then this command with --haplotag_vcf on the phased VCF of pass 1 (not in the "
                          "reference; one GPU)")
+    ap.add_argument("--mark_duplicates", action="store_true", default=False,
+                    help="with --from_bam / --from_bams: find the PCR duplicates of the Illumina BAM on the GPU first and let every "
+                         "stage drop them, as if the BAM carried flag 0x400 on them; writes <workdir>/duplicates.metrics.txt (not in "
+                         "the reference; one GPU; DESIGN.md 7j)")
     ap.add_argument("--device", type=int, default=0, help="GPU of a single-process run")
     ap.add_argument("--gpus", type=int, default=1,
                     help="processes / GPUs of this node: > 1 re-launches this command under torch.distributed.run "
@@ -591,6 +599,47 @@ def haplotag_passes(args) -> str:
     return main(second)
 
 
+def check_mark_duplicates(args) -> None:
+    """The refusals of --mark_duplicates, each naming the fix."""
+    if not getattr(args, "mark_duplicates", False):
+        return
+    if args.shards:
+        raise SystemExit("--mark_duplicates marks the reads the stages fetch from the BAM, and shard files hold reads that were fetched "
+                         "before: drop --shards and start from the BAM with --from_bam or --from_bams, or drop --mark_duplicates")
+    if not _bam_route(args):
+        raise SystemExit("--mark_duplicates finds the duplicates among the reads of the Illumina BAM, and this run has no BAM on its "
+                         "path: add --from_bam (one BAM) or --from_bams (--ibam and --pbam), or drop --mark_duplicates (python -m "
+                         "hello_amd.markdup saves the marks of a BAM on its own)")
+    if _several_processes(args):
+        raise SystemExit("--mark_duplicates hands its marks to the stages of its own process, on one GPU: run it with --gpus 1 as a "
+                         "plain command, or drop --mark_duplicates")
+    if not args.ibam:
+        raise SystemExit("--mark_duplicates keys a read pair by the 5' ends of both mates, which PacBio reads do not have, and the "
+                         "only BAM of this run is --pbam: give the Illumina BAM as --ibam, or drop --mark_duplicates")
+
+
+def with_duplicates_marked(args) -> str:
+    """--mark_duplicates: the marks of the route's Illumina BAM, once, then this command without the flag inside
+    ``markdup.applied`` -- every fetch of every stage (both passes of --haplotag too) sees flag 0x400 on the duplicates.  With
+    --from_bams the PacBio BAM is left as it is."""
+    from . import markdup
+    logger = logging.getLogger("hello_amd.call")
+    route = Route.from_args(args, need_ref=False)
+    os.makedirs(args.workdir, exist_ok=True)
+    stats: dict = {}
+    marks = markdup.find_duplicates(route.bams[0], route.chromosomes, device=route.device, stats=stats)
+    marks.write_metrics(os.path.join(args.workdir, "duplicates.metrics.txt"))
+    total = marks.total()
+    logger.info("--mark_duplicates: %d reads, %d pairs, %d duplicate reads (%d pairs, %d singles) in %.2f s (BAM decode %.2f s, "
+                "kernels %.1f ms)", total["reads"], total["pairs"], total["duplicate_reads"], total["duplicate_pairs"],
+                total["duplicate_singles"], stats.get("total_s", 0.0), stats.get("decode_s", 0.0),
+                sum(stats.get(k, 0.0) for k in ("ends_ms", "pair_ms", "key_ms", "mark_ms")))
+    rest = argparse.Namespace(**vars(args))
+    rest.mark_duplicates = False
+    with markdup.applied({route.bams[0]: marks}):
+        return main(rest)
+
+
 def run_resident(args) -> str:
     """--from_bam / --from_bams with --resident: hotspots and ``shard<N>.txt`` as ``shards_from_bam(s)`` write them, then ONE loop
     in this process: shard file -> candidate sites whose reads stay on the GPU (``candidates.resident_activity``) -> ``ShardScorer``
@@ -655,6 +704,9 @@ def main(args) -> str:
     check_gvcf(args)
     check_phase(args)
     check_haplotag(args)
+    check_mark_duplicates(args)
+    if getattr(args, "mark_duplicates", False):
+        return with_duplicates_marked(args)
     if getattr(args, "haplotag", False):
         return haplotag_passes(args)
     if getattr(args, "resident", False):

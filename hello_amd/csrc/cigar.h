@@ -1,5 +1,5 @@
 // What the host knows about a set of decoded BAM reads before a kernel may index with them: the CIGAR constants, the read filters
-// and the two validating walks the BAM-side stages share.  Plain C++17 -- no HIP, no kernel -- so the walks also build into a
+// and the validating walks of the BAM-side stages (two that they share, and the duplicate marker's).  Plain C++17 -- no HIP, no kernel -- so the walks also build into a
 // stand-alone host program (tests/abi/cigar_check.cpp).  Refusals are thrown as Fail; the entry points turn them into a status.
 #pragma once
 #include <algorithm>
@@ -153,6 +153,37 @@ inline bool counted_walk(const ReadsView& s, int64_t r, int mapq_threshold, int6
         raise(HELLO_ERR_ARG, "read %lld: its CIGAR consumes %lld bases, it has %lld", (long long)r, (long long)qlen,
               (long long)(s.read_off[r + 1] - s.read_off[r]));
     return true;
+}
+
+// The reads that take part in duplicate marking: mapped, primary, not a duplicate already; mapq, QC-fail and
+// the pairing flags do not matter.
+inline bool markdup_eligible(uint16_t flag) { return !(flag & (0x4 | 0x100 | 0x800 | 0x400)); }
+
+// The walk of the duplicate marker: every read's offsets and, for an eligible read, what the ends kernel relies on -- known
+// operations, a CIGAR that consumes exactly the read's bases and ends where ref_end says.  -> the eligible reads, in input order.
+inline std::vector<int64_t> markdup_walk(const ReadsView& s) {
+    std::vector<int64_t> list;
+    if (s.n > 0 && (s.read_off[0] != 0 || s.cigar_off[0] != 0)) raise(HELLO_ERR_ARG, "offsets do not start at 0");
+    for (int64_t r = 0; r < s.n; ++r) {
+        if (s.read_off[r + 1] < s.read_off[r] || s.cigar_off[r + 1] < s.cigar_off[r])
+            raise(HELLO_ERR_ARG, "read %lld: offsets decrease", (long long)r);
+        if (!markdup_eligible(s.flags[r])) continue;
+        int64_t qlen = 0, rlen = 0;
+        for (int64_t c = s.cigar_off[r]; c < s.cigar_off[r + 1]; ++c) {
+            const int op = s.cigars[c] & 15;
+            const int64_t len = s.cigars[c] >> 4;
+            if (op > 8) raise(HELLO_ERR_ARG, "read %lld: CIGAR operation %d", (long long)r, op);
+            if (is_query_op(op)) qlen += len;
+            if (is_ref_op(op)) rlen += len;
+        }
+        if (qlen != s.read_off[r + 1] - s.read_off[r])
+            raise(HELLO_ERR_ARG, "read %lld: CIGAR query length %lld, %lld bases", (long long)r, (long long)qlen,
+                  (long long)(s.read_off[r + 1] - s.read_off[r]));
+        if (s.ref_end[r] != s.ref_start[r] + std::max<int64_t>(rlen, 1))
+            raise(HELLO_ERR_ARG, "read %lld: ref_end does not match its CIGAR", (long long)r);
+        list.push_back(r);
+    }
+    return list;
 }
 
 }  // namespace

@@ -21,7 +21,8 @@
 // Fragments (hello_phase_fragments, hello_phase_tag_fragments): the two mates of a read pair act as one
 // fragment.  After the last observe the handle's slots are joined into one device array and three more launches run over the
 // counted reads of ALL batches, indexed c = 0..counted-1 in the order given:
-//   pair (two kernels): an open-addressing table of 2^k >= 2 counted slots in global memory.  Insert: a thread per counted read
+//   pair (two kernels; they live in phase_pair.h, which markdup.hip includes too): an open-addressing table of 2^k >= 2 counted
+//     slots in global memory.  Insert: a thread per counted read
 //     claims the slot of its (name_hash, source) with atomicCAS on an int32 owner (-1 empty, else the claiming read) or finds the
 //     slot whose owner has its key -- keys are compared in the input arrays, so no key value is reserved -- and counts itself
 //     into the slot: reads, first mates, second mates, the smallest index of each kind (atomicAdd / atomicMin, the result does
@@ -36,6 +37,7 @@
 #include <climits>
 #include <memory>
 
+#include "phase_pair.h"
 #include "phase_walk.h"
 #include "stage_host.h"
 
@@ -138,77 +140,6 @@ __global__ __launch_bounds__(kPhThreads) void phase_tag_kernel(PhTagArgs a) {
     }
     a.hp[k] = n1 > n2 ? 1 : n2 > n1 ? 2 : 0;
     a.ps[k] = pos;
-}
-
-// ---- fragments: pairing ------------------------------------------------------------------------------------------------------
-struct PhPairArgs {
-    const uint64_t* name;        // [counted]: name_hash, flags and source of the counted reads, gathered on the host
-    const uint16_t* flags;
-    const uint8_t* source;
-    int32_t* owner;              // [mask + 1]: -1 empty, else the counted read that claimed the slot
-    int32_t* count;              // reads of the slot's group
-    int32_t* n_first;            // those with flag 0x1 and flag & 0xC0 == 0x40
-    int32_t* n_second;           // ... == 0x80
-    int32_t* min_first;          // the smallest counted index of each kind
-    int32_t* min_second;
-    int32_t* mate;               // [counted]
-    int32_t* totals;             // pairs, groups_refused
-    int64_t n_counted;
-    uint32_t mask;
-};
-
-// The first slot probed for a key (phase.pair_table_slot restates it): every bit of the name reaches the slot.
-__host__ __device__ inline uint32_t pair_slot(uint64_t name, uint32_t source, uint32_t mask) {
-    uint64_t x = name ^ (name >> 29);
-    x *= 0xBF58476D1CE4E5B9ull;
-    x ^= x >> 32;
-    return ((uint32_t)x + source) & mask;
-}
-
-// The slot of c's group.  claim: an empty slot on the way becomes c's.  The table holds at least twice the counted reads, so a
-// probe ends at an empty slot or at its group's before it has come round; it wraps at the table's end.
-template <bool claim> __device__ inline uint32_t pair_probe(const PhPairArgs& a, int32_t c) {
-    const uint64_t name = a.name[c];
-    const uint32_t source = a.source[c];
-    uint32_t slot = pair_slot(name, source, a.mask);
-    for (uint32_t tried = 0; tried <= a.mask; ++tried) {
-        const int32_t o = claim ? atomicCAS(&a.owner[slot], -1, c) : a.owner[slot];
-        if (o < 0 || o == c) break;                                       // claimed just now (or, looking up, not there: never)
-        if (a.name[o] == name && a.source[o] == source) break;
-        slot = (slot + 1) & a.mask;
-    }
-    return slot;
-}
-
-__global__ __launch_bounds__(kPhThreads) void phase_pair_insert_kernel(PhPairArgs a) {
-    const int64_t i = (int64_t)blockIdx.x * kPhThreads + threadIdx.x;
-    if (i >= a.n_counted) return;
-    const int32_t c = (int32_t)i;
-    const uint32_t slot = pair_probe<true>(a, c);
-    atomicAdd(&a.count[slot], 1);
-    const int f = a.flags[c];
-    if ((f & 0x1) && (f & 0xC0) == 0x40) { atomicAdd(&a.n_first[slot], 1); atomicMin(&a.min_first[slot], c); }
-    if ((f & 0x1) && (f & 0xC0) == 0x80) { atomicAdd(&a.n_second[slot], 1); atomicMin(&a.min_second[slot], c); }
-}
-
-__global__ __launch_bounds__(kPhThreads) void phase_pair_lookup_kernel(PhPairArgs a) {
-    const int64_t i = (int64_t)blockIdx.x * kPhThreads + threadIdx.x;
-    bool joined = false, refused = false;                                               // of the group this thread owns
-    if (i < a.n_counted) {
-        const int32_t c = (int32_t)i;
-        const uint32_t slot = pair_probe<false>(a, c);
-        const int n = a.count[slot];
-        const bool pair = n == 2 && a.n_first[slot] == 1 && a.n_second[slot] == 1;
-        a.mate[c] = !pair ? -1 : a.min_first[slot] == c ? a.min_second[slot] : a.min_first[slot];
-        joined = a.owner[slot] == c && pair;                                            // a group is counted once, by its owner
-        refused = a.owner[slot] == c && !pair && n >= 2;
-    }
-    // one add per wave and counter instead of one per group: every lane reaches the ballots
-    const unsigned long long j = __ballot(joined), r = __ballot(refused);
-    if ((threadIdx.x & 63) == 0) {
-        if (j) atomicAdd(&a.totals[0], __popcll(j));
-        if (r) atomicAdd(&a.totals[1], __popcll(r));
-    }
 }
 
 // ---- fragments: links and tags -----------------------------------------------------------------------------------------------
@@ -344,12 +275,6 @@ struct hello_phase {
 
 namespace hello {
 namespace {
-
-unsigned blocks_for(int64_t items, int per_block) {
-    const int64_t n = (items + per_block - 1) / per_block;
-    if (n > INT32_MAX) raise(HELLO_ERR_ARG, "%lld items in one launch", (long long)items);
-    return (unsigned)n;
-}
 
 // The chained set / flip a tag call is given, validated -> per record the POS of its set's first record, 0 for a set of one.
 std::vector<int64_t> set_positions(const hello_phase* h, const int32_t* set, const uint8_t* flip) {
@@ -632,7 +557,7 @@ int hello_phase_fragments(hello_phase* h, const uint64_t* name_hash, const uint1
     for (const PhBatch& b : h->batches)
         for (int64_t r : b.reads) reads.push_back(b.read_base + r);
     const int64_t n = (int64_t)reads.size(), n_slots = (int64_t)h->slots.size();
-    if (n > (1 << 29)) return set_last_error(HELLO_ERR_ARG, "%lld counted reads in one chromosome", (long long)n);
+    if (n > kPairMaxReads) return set_last_error(HELLO_ERR_ARG, "%lld counted reads in one chromosome", (long long)n);
     std::vector<uint64_t> name((size_t)n);
     std::vector<uint16_t> fl((size_t)n);
     std::vector<uint8_t> src((size_t)n);
@@ -645,9 +570,6 @@ int hello_phase_fragments(hello_phase* h, const uint64_t* name_hash, const uint1
         first[c] = h->first[r];
         slot_off[c] = h->slot_offsets[r];                                  // an uncounted read has no slot: c's slots end where
     }                                                                       // those of c + 1 begin
-    uint32_t table = 2;
-    while ((int64_t)table < 2 * n) table <<= 1;
-
     std::vector<int32_t> mate((size_t)n, -1), link(h->links.size(), 0);
     int32_t totals[2] = {0, 0};
     float pair_ms = 0.0f, link_ms = 0.0f;
@@ -670,30 +592,10 @@ int hello_phase_fragments(hello_phase* h, const uint64_t* name_hash, const uint1
             at += b.n_slots;
         }
         if (at != n_slots) raise(HELLO_ERR_SHAPE, "the batches hold %lld slots, the handle %lld", (long long)at, (long long)n_slots);
-        PhPairArgs p{};
-        p.name = m.put(name.data(), name.size());
-        p.flags = m.put(fl.data(), fl.size());
-        p.source = m.put(src.data(), src.size());
-        p.owner = m.room<int32_t>(table);
-        HS_HIP(hipMemset(p.owner, 0xFF, (size_t)table * sizeof(int32_t)));
-        p.count = m.zeros<int32_t>(table);
-        p.n_first = m.zeros<int32_t>(table);
-        p.n_second = m.zeros<int32_t>(table);
-        p.min_first = m.room<int32_t>(table);
-        p.min_second = m.room<int32_t>(table);
-        HS_HIP(hipMemset(p.min_first, 0x7F, (size_t)table * sizeof(int32_t)));      // above every index
-        HS_HIP(hipMemset(p.min_second, 0x7F, (size_t)table * sizeof(int32_t)));
-        p.mate = h->d_frag_mate;
-        p.totals = m.zeros<int32_t>(2);
-        p.n_counted = n;
-        p.mask = table - 1;
+        pair_ms = pair_join(m, m.put(name.data(), name.size()), m.put(fl.data(), fl.size()), m.put(src.data(), src.size()), n,
+                            h->d_frag_mate, totals);
+        HS_HIP(hipMemcpy(mate.data(), h->d_frag_mate, mate.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
         KernelTimer timer;
-        timer.start();
-        hipLaunchKernelGGL(phase_pair_insert_kernel, dim3(blocks_for(n, kPhThreads)), dim3(kPhThreads), 0, 0, p);
-        hipLaunchKernelGGL(phase_pair_lookup_kernel, dim3(blocks_for(n, kPhThreads)), dim3(kPhThreads), 0, 0, p);
-        pair_ms = timer.stop();
-        HS_HIP(hipMemcpy(mate.data(), p.mate, mate.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-        HS_HIP(hipMemcpy(totals, p.totals, sizeof(totals), hipMemcpyDeviceToHost));
         if (n_slots > 0) {
             PhFragArgs a{};
             a.slots = h->d_frag_slots;

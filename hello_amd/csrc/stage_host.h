@@ -1,4 +1,4 @@
-// The HIP host layer under the BAM-side stages (hotspots.hip, candidates.hip, refblocks.hip, phase.hip, haplotag.hip): opening the device,
+// The HIP host layer under the BAM-side stages (hotspots.hip, candidates.hip, refblocks.hip, phase.hip, haplotag.hip, markdup.hip): opening the device,
 // owned device memory, the upload of a read set, timing a launch, and the tail of an entry point.  No kernel lives here.
 #pragma once
 #include <utility>

@@ -234,7 +234,7 @@ def pair_table_size(n_counted: int) -> int:
 
 
 def pair_table_slot(name_hash, source, size: int) -> np.ndarray:
-    """uint32: the first slot the pair kernels probe for (name_hash, source) in a table of ``size`` slots (phase.hip: pair_slot)."""
+    """uint32: the first slot the pair kernels probe for (name_hash, source) in a table of ``size`` slots (phase_pair.h: pair_slot)."""
     x = np.asarray(name_hash, np.uint64)
     x = x ^ (x >> np.uint64(29))
     x = x * np.uint64(0xBF58476D1CE4E5B9)

@@ -855,6 +855,48 @@ int hello_haplotag_reads(hello_haplotag* haplotag, const uint8_t* bases, const u
 int hello_haplotag_stats(const hello_haplotag* haplotag, double* stats);
 void hello_haplotag_free(hello_haplotag* haplotag);
 
+/* PCR duplicates among the reads of one chromosome of one BAM (not in the reference; DESIGN.md section 7j states the rules,
+ * hello_amd/markdup.py restates them in Python).  One handle per (BAM, chromosome).
+ *   hello_markdup_add: with *handle NULL it creates the handle; every call adds the reads of one span.  reads: the arrays of
+ *          hello_bam_fetch (`bases`, `mapq` and `source` are not read and may be NULL).  A read is eligible when
+ *          flag & (0x4 | 0x100 | 0x800 | 0x400) == 0.  Offsets that do not start at 0 or decrease, and an eligible read with an
+ *          unknown CIGAR operation, a CIGAR that does not consume its bases or a ref_end that its CIGAR does not give, are
+ *          refused (HELLO_ERR_ARG) before the device is opened and before any launch; so are more than 2^31 - 1 eligible reads
+ *          in one handle.  Ends kernel, a wave per eligible read: e = 2 end5 + strand (end5: ref_start minus the leading S / H
+ *          run of a forward read, ref_end - 1 plus the trailing S / H run of a reverse read) and score = the sum of the base
+ *          qualities >= 15, saturated at 2^30 - 1.  name_hash, flags, e and score of the eligible reads stay on the device.
+ *   hello_markdup_find: called once, after the last hello_markdup_add; a second call, and hello_markdup_add after it, are refused
+ *          (HELLO_ERR_ARG).  The eligible reads of all spans are joined into pairs by the mate join of hello_phase_fragments
+ *          (source 0 for all); a joined read is of kind 1 (pair), another read without flag 0x1 or with 0x8 of kind 2 (single),
+ *          every other eligible read of kind 3 (unresolved: never marked, shields nothing).  Key kernel (a second open-addressing
+ *          table, integer atomics): within one (lo, hi) of the mates' packed ends the pair with the largest summed score
+ *          survives, ties to the smaller of its smaller read index; within one e, every single is a duplicate where a joined
+ *          read has that e, else the single with the largest score survives, ties to the smaller index.  Mark kernel: kind and
+ *          duplicate of every read.  More than 2^29 eligible reads are refused (the tables are indexed with 32 bits).
+ *   hello_markdup_array: aligned with the reads given, in the order given; e and score after hello_markdup_add, the rest after
+ *          hello_markdup_find.  A read that is not eligible has e 0, score 0, mate -1, kind 0, duplicate 0.
+ * Host memory in and out; markdup.hip. */
+#define HELLO_MARKDUP_STATS 12
+enum {
+    HELLO_MARKDUP_E = 0,          /* int64 [reads] */
+    HELLO_MARKDUP_SCORE = 1,      /* int32 [reads] */
+    HELLO_MARKDUP_MATE = 2,       /* int64 [reads]: the mate's index or -1 */
+    HELLO_MARKDUP_KIND = 3,       /* uint8 [reads]: 0 not eligible, 1 pair, 2 single, 3 unresolved */
+    HELLO_MARKDUP_DUPLICATE = 4   /* uint8 [reads] */
+};
+typedef struct hello_markdup hello_markdup;
+int hello_markdup_add(const uint8_t* bases, const uint8_t* quals, const int64_t* read_offsets, const uint32_t* cigars,
+                      const int64_t* cigar_offsets, const int64_t* ref_starts, const int64_t* ref_ends, const uint8_t* mapq,
+                      const uint16_t* flags, const uint64_t* name_hash, const uint8_t* source, int64_t n_reads, int32_t device,
+                      hello_markdup** handle);
+int hello_markdup_find(hello_markdup* markdup);
+/* a pointer into `markdup` (valid until the next hello_markdup_* call on it) and its element count */
+int hello_markdup_array(const hello_markdup* markdup, int32_t which, const void** data, int64_t* count);
+/* stats[HELLO_MARKDUP_STATS]: reads given, eligible, pairs, singles, unresolved, groups of two or more reads that were not joined,
+ * duplicate pairs, duplicate singles, ends / pair / key / mark kernel ms (HIP events) */
+int hello_markdup_stats(const hello_markdup* markdup, double* stats);
+void hello_markdup_free(hello_markdup* markdup);
+
 #ifdef __cplusplus
 }
 #endif
