@@ -60,6 +60,11 @@ the outside tool that writes a tagged BAM.  ``--haplotag`` needs no phased VCF: 
 ``--mark_duplicates`` (with ``--from_bam`` / ``--from_bams``, not in the reference, off by default) finds the PCR duplicates of the
 Illumina BAM on the GPU before the hotspot stage (``hello_amd.markdup``) and runs everything after it with flag
 0x400 set on them in what ``BamFile.fetch`` returns, so every stage drops them; ``<workdir>/duplicates.metrics.txt`` holds the counts.
+
+``--qc`` (with ``--from_bam`` / ``--from_bams``, not in the reference, off by default) counts alignment, coverage and insert-size
+metrics of every BAM of the route on the GPU after ``results.output.vcf`` is complete (``hello_amd.qc``) and
+writes ``<workdir>/qc.illumina.*`` and / or ``qc.pacbio.*``: ``metrics.txt``, ``tables.npz``, ``windows.bedgraph`` (``--qc_window``)
+and, with ``--qc_regions BED``, ``targets.tsv``.  Under ``--mark_duplicates`` the marked reads count as duplicates and leave the depth.
 """
 from __future__ import annotations
 
@@ -314,6 +319,12 @@ def parser() -> argparse.ArgumentParser:
                     help="with --from_bam / --from_bams: find the PCR duplicates of the Illumina BAM on the GPU first and let every "
                          "stage drop them, as if the BAM carried flag 0x400 on them; writes <workdir>/duplicates.metrics.txt (not in "
                          "the reference; one GPU; DESIGN.md 7j)")
+    ap.add_argument("--qc", action="store_true", default=False,
+                    help="with --from_bam / --from_bams: count flag, mapping-quality, length, per-cycle quality and mismatch, depth "
+                         "and insert-size tables of every BAM of the route on the GPU and write <workdir>/qc.illumina.* / "
+                         "qc.pacbio.* (metrics.txt, tables.npz, windows.bedgraph; not in the reference; one GPU; DESIGN.md 7k)")
+    ap.add_argument("--qc_regions", help="--qc: a BED file of target intervals; depth on target and per target (targets.tsv)")
+    ap.add_argument("--qc_window", type=int, default=None, help="--qc: width of the depth windows of windows.bedgraph (default 1000)")
     ap.add_argument("--device", type=int, default=0, help="GPU of a single-process run")
     ap.add_argument("--gpus", type=int, default=1,
                     help="processes / GPUs of this node: > 1 re-launches this command under torch.distributed.run "
@@ -581,13 +592,14 @@ def _close_haplotagger(tagger) -> None:
 
 
 def haplotag_passes(args) -> str:
-    """--haplotag: pass 1 is this command without --haplotag, --gvcf, --annotate and --annotate_evidence and with --phase, in
+    """--haplotag: pass 1 is this command without --haplotag, --gvcf, --qc, --annotate and --annotate_evidence and with --phase, in
     ``<workdir>/haplotag_pass1``; pass 2 is this command with --haplotag_vcf on pass 1's phased VCF, in ``<workdir>``.  Both run in
     this process, each as the command would run alone (the hotspot stage runs twice).  --phase_fragments goes to pass 1, and to
     pass 2 only where --phase was given as well."""
     logger = logging.getLogger("hello_amd.call")
     first = argparse.Namespace(**vars(args))
-    first.haplotag = first.gvcf = first.annotate = first.annotate_evidence = False
+    first.haplotag = first.gvcf = first.annotate = first.annotate_evidence = first.qc = False
+    first.qc_regions = first.qc_window = None
     first.phase = True
     first.workdir = os.path.join(args.workdir, "haplotag_pass1")
     phased_path = main(first)[:-len(".vcf")] + ".phased.vcf"
@@ -640,6 +652,50 @@ def with_duplicates_marked(args) -> str:
         return main(rest)
 
 
+def check_qc(args) -> None:
+    """The refusals of --qc, --qc_regions and --qc_window, each naming the fix."""
+    if not getattr(args, "qc", False):
+        for flag in ("qc_regions", "qc_window"):
+            if getattr(args, flag, None) is not None:
+                raise SystemExit(f"--{flag} is an option of the metrics pass and there is none in this run: add --qc, or drop --{flag}")
+        return
+    if args.shards:
+        raise SystemExit("--qc measures the reads of the BAM(s), and shard files hold reads that were fetched and filtered before: "
+                         "drop --shards and start from the BAM with --from_bam or --from_bams, or drop --qc")
+    if not _bam_route(args):
+        raise SystemExit("--qc measures the reads of the BAM(s), and this run has no BAM on its path: add --from_bam (one BAM) or "
+                         "--from_bams (--ibam and --pbam), or drop --qc (python -m hello_amd.qc measures a BAM on its own)")
+    if _several_processes(args):
+        raise SystemExit("--qc runs its pass over the BAM(s) in one process on one GPU: run it with --gpus 1 as a plain command, or "
+                         "drop --qc and run python -m hello_amd.qc on the BAM(s)")
+    if getattr(args, "qc_window", None) is not None and args.qc_window < 1:
+        raise SystemExit("--qc_window is the width of a depth window: give 1 or more")
+
+
+def qc_pass(args, genome: Dict[str, str]) -> List[str]:
+    """--qc: the metrics of every BAM of the route, at the route's --mapq_threshold and chromosomes -> the files written,
+    ``<workdir>/qc.illumina.*`` and / or ``qc.pacbio.*``."""
+    if not getattr(args, "qc", False):
+        return []
+    from . import qc
+    route = Route.from_args(args, need_ref=False)
+    names = ("pacbio",) if route.pacbio else ("illumina", "pacbio")
+    targets = qc.read_bed(args.qc_regions) if getattr(args, "qc_regions", None) else None
+    window = qc.DEFAULT_WINDOW if getattr(args, "qc_window", None) is None else args.qc_window
+    written: List[str] = []
+    for bam, name in zip(route.bams, names):
+        stats: dict = {}
+        metrics = qc.measure(bam, genome, route.chromosomes or list(genome), targets, window, route.mapq_threshold,
+                             device=route.device, stats=stats)
+        written += metrics.write_all(os.path.join(args.workdir, "qc." + name))
+        total = metrics.total()
+        logging.getLogger("hello_amd.call").info(
+            "--qc %s: %d reads, %d measured, %d pairs in %.2f s (BAM decode %.2f s, kernels %.1f ms)", name, int(total["FLAGS"][0]),
+            int(total["STATS"][0]), int(total["STATS"][4]), stats.get("total_s", 0.0), stats.get("decode_s", 0.0),
+            sum(stats.get(k, 0.0) for k in ("reads_ms", "depth_ms", "pair_ms", "insert_ms")))
+    return written
+
+
 def run_resident(args) -> str:
     """--from_bam / --from_bams with --resident: hotspots and ``shard<N>.txt`` as ``shards_from_bam(s)`` write them, then ONE loop
     in this process: shard file -> candidate sites whose reads stay on the GPU (``candidates.resident_activity``) -> ``ShardScorer``
@@ -651,6 +707,7 @@ def run_resident(args) -> str:
     check_gvcf(args)
     check_phase(args)
     check_haplotag(args)
+    check_qc(args)
     route = Route.from_args(args)
     genome = read_fasta(route.ref, route.chromosomes)
     tagger = haplotagger_of(args, route)
@@ -696,6 +753,7 @@ def run_resident(args) -> str:
     logger.info("Completed runs in %.2f s. %d records in %s", time.perf_counter() - t0, n, result_path)
     gvcf_pass(args, result_path, genome)
     phase_pass(args, result_path)
+    qc_pass(args, genome)
     return result_path
 
 
@@ -705,6 +763,7 @@ def main(args) -> str:
     check_phase(args)
     check_haplotag(args)
     check_mark_duplicates(args)
+    check_qc(args)
     if getattr(args, "mark_duplicates", False):
         return with_duplicates_marked(args)
     if getattr(args, "haplotag", False):
@@ -810,6 +869,7 @@ def main(args) -> str:
         logger.info("Completed runs in %.2f s. %d records in %s", time.perf_counter() - t0, n, result_path)
         gvcf_pass(args, result_path, genomes)
         phase_pass(args, result_path)
+        qc_pass(args, genomes)
     if world > 1:
         import torch.distributed as dist
         dist.barrier()

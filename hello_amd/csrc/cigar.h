@@ -1,5 +1,5 @@
 // What the host knows about a set of decoded BAM reads before a kernel may index with them: the CIGAR constants, the read filters
-// and the validating walks of the BAM-side stages (two that they share, and the duplicate marker's).  Plain C++17 -- no HIP, no kernel -- so the walks also build into a
+// and the validating walks of the BAM-side stages (two that they share, the duplicate marker's and the quality metrics').  Plain C++17 -- no HIP, no kernel -- so the walks also build into a
 // stand-alone host program (tests/abi/cigar_check.cpp).  Refusals are thrown as Fail; the entry points turn them into a status.
 #pragma once
 #include <algorithm>
@@ -184,6 +184,51 @@ inline std::vector<int64_t> markdup_walk(const ReadsView& s) {
         list.push_back(r);
     }
     return list;
+}
+
+// The reads the quality metrics measure: mapped, primary, not a duplicate, not QC-fail; mapq and the pairing
+// flags do not matter.
+constexpr int kQcNotMeasured = 0x4 | 0x100 | 0x800 | 0x400 | 0x200;
+inline bool qc_measured(uint16_t flag) { return !(flag & kQcNotMeasured); }
+
+constexpr uint8_t kQcBelongs = 1, kQcMeasured = 2, kQcCounted = 4;
+constexpr int64_t kQcMaxReadBases = (int64_t(1) << 31) / 255;      // a read's qualities sum below 2^31
+
+// The walk of the quality metrics over the reads overlapping a span that starts at `lo`: every read's offsets and order and, for a
+// measured or counted read, what the kernels rely on -- a start on the reference, known operations, a CIGAR that consumes exactly
+// the read's bases and ends where ref_end says, and a quality sum that fits an int32.  -> per read kQcBelongs | kQcMeasured |
+// kQcCounted.
+inline std::vector<uint8_t> qc_walk(const ReadsView& s, int64_t lo, int mapq_threshold) {
+    std::vector<uint8_t> kind((size_t)s.n, 0);
+    if (s.n > 0 && (s.read_off[0] != 0 || s.cigar_off[0] != 0)) raise(HELLO_ERR_ARG, "offsets do not start at 0");
+    for (int64_t r = 0; r < s.n; ++r) {
+        if (s.read_off[r + 1] < s.read_off[r] || s.cigar_off[r + 1] < s.cigar_off[r])
+            raise(HELLO_ERR_ARG, "read %lld: offsets decrease", (long long)r);
+        if (r > 0 && s.ref_start[r] < s.ref_start[r - 1])
+            raise(HELLO_ERR_ARG, "read %lld: reads are not coordinate-sorted (the BAM must be)", (long long)r);
+        uint8_t k = s.ref_start[r] >= lo ? kQcBelongs : 0;
+        if (qc_measured(s.flags[r])) k |= kQcMeasured;
+        if (counted(s.flags[r], s.mapq[r], mapq_threshold)) k |= kQcCounted;
+        kind[(size_t)r] = k;
+        if (!(k & (kQcMeasured | kQcCounted))) continue;
+        if (s.ref_start[r] < 0) raise(HELLO_ERR_ARG, "read %lld: ref_start %lld", (long long)r, (long long)s.ref_start[r]);
+        int64_t qlen = 0, rlen = 0;
+        for (int64_t c = s.cigar_off[r]; c < s.cigar_off[r + 1]; ++c) {
+            const int op = s.cigars[c] & 15;
+            const int64_t len = s.cigars[c] >> 4;
+            if (op > 8) raise(HELLO_ERR_ARG, "read %lld: CIGAR operation %d", (long long)r, op);
+            if (is_query_op(op)) qlen += len;
+            if (is_ref_op(op)) rlen += len;
+        }
+        if (qlen != s.read_off[r + 1] - s.read_off[r])
+            raise(HELLO_ERR_ARG, "read %lld: CIGAR query length %lld, %lld bases", (long long)r, (long long)qlen,
+                  (long long)(s.read_off[r + 1] - s.read_off[r]));
+        if (s.ref_end[r] != s.ref_start[r] + std::max<int64_t>(rlen, 1))
+            raise(HELLO_ERR_ARG, "read %lld: ref_end does not match its CIGAR", (long long)r);
+        if (qlen > kQcMaxReadBases)
+            raise(HELLO_ERR_ARG, "read %lld: %lld bases, at most %lld", (long long)r, (long long)qlen, (long long)kQcMaxReadBases);
+    }
+    return kind;
 }
 
 }  // namespace

@@ -897,6 +897,62 @@ int hello_markdup_array(const hello_markdup* markdup, int32_t which, const void*
 int hello_markdup_stats(const hello_markdup* markdup, double* stats);
 void hello_markdup_free(hello_markdup* markdup);
 
+/* Alignment, coverage and insert-size metrics of one chromosome of one BAM (not in the reference; DESIGN.md section 7k states the
+ * rules, hello_amd/qc.py restates them in Python).  One handle per (BAM, chromosome); every table is int64.
+ *   hello_qc_add: with *handle NULL it creates the handle; every call adds the reads overlapping one span [lo, hi) of the
+ *          chromosome whose text is `reference` (all of it, reference_length bytes).  reads: the arrays of hello_bam_fetch
+ *          (`source` is not read and may be NULL), coordinate-sorted.  A read BELONGS to the span when lo <= ref_start; it is
+ *          MEASURED when flag & (0x4 | 0x100 | 0x800 | 0x400 | 0x200) == 0 and COUNTED by the gVCF's rule at mapq_threshold.
+ *          The per-read tables (FLAGS over the belonging reads; MAPQ, LENGTH, CYCLE, QUALITY over the belonging measured reads)
+ *          come from the reads kernel, the depth tables (every counted read given, over the positions of [lo, hi)) from the
+ *          depth kernel.  targets: sorted intervals [start, stop) with 0 <= start < stop that do not overlap (they may touch,
+ *          and may end behind the chromosome).  Refused (HELLO_ERR_ARG) before the device is opened and before any launch:
+ *          offsets that do not start at 0 or decrease; unsorted reads; a measured or counted read with a negative ref_start, an
+ *          unknown CIGAR operation, a CIGAR that does not consume exactly its bases or a ref_end its CIGAR does not give; a
+ *          belonging measured read of more than 2^31 / 255 bases; lo below the previous hi; hi <= lo or hi > reference_length;
+ *          window < 1; such targets; a reference length, targets, window, threshold or device other than the first call's.  A
+ *          refused call leaves the handle as it was.
+ *   hello_qc_finish: called once, after the last hello_qc_add; a second call, and hello_qc_add after it, are refused.  The
+ *          belonging measured reads of all spans are joined by the mate join of hello_phase_fragments (source 0 for all) and the
+ *          insert kernel fills INSERT.
+ *   hello_qc_array: INSERT after hello_qc_finish, the others after any hello_qc_add.
+ * Host memory in and out; qc.hip. */
+#define HELLO_QC_STATS 12
+#define HELLO_QC_FLAG_FIELDS 13      /* reads, unmapped, secondary, supplementary, duplicate, qc_fail, paired, proper_pair, read1,
+                                        read2, mate_unmapped, reverse, mapq0 */
+#define HELLO_QC_CYCLES 513          /* a base's index in sequencing order, the last bin holding "512 or more" */
+#define HELLO_QC_CYCLE_FIELDS 7      /* bases, quality_sum, aligned, mismatches, inserted, soft_clipped, deletions */
+#define HELLO_QC_LENGTHS 65536
+#define HELLO_QC_DEPTHS 1024
+#define HELLO_QC_INSERTS 4096        /* per orientation: FR, RF, TANDEM */
+enum {
+    HELLO_QC_FLAGS = 0,              /* [HELLO_QC_FLAG_FIELDS] */
+    HELLO_QC_MAPQ = 1,               /* [256] */
+    HELLO_QC_LENGTH = 2,             /* [HELLO_QC_LENGTHS] */
+    HELLO_QC_CYCLE = 3,              /* [2][HELLO_QC_CYCLES][HELLO_QC_CYCLE_FIELDS]: first mates and unpaired reads, then reads with 0x80 */
+    HELLO_QC_QUALITY = 4,            /* [256][2]: aligned bases of the reported quality, mismatches among them */
+    HELLO_QC_DEPTH_HIST = 5,         /* [HELLO_QC_DEPTHS] */
+    HELLO_QC_WINDOW_SUM = 6,         /* [ceil(reference_length / window)] */
+    HELLO_QC_TARGET_DEPTH_HIST = 7,  /* [HELLO_QC_DEPTHS] */
+    HELLO_QC_TARGET_SUM = 8,         /* [n_targets] */
+    HELLO_QC_TARGET_COVERED = 9,     /* [n_targets] */
+    HELLO_QC_INSERT = 10             /* [3][HELLO_QC_INSERTS] */
+};
+typedef struct hello_qc hello_qc;
+int hello_qc_add(const uint8_t* bases, const uint8_t* quals, const int64_t* read_offsets, const uint32_t* cigars,
+                 const int64_t* cigar_offsets, const int64_t* ref_starts, const int64_t* ref_ends, const uint8_t* mapq,
+                 const uint16_t* flags, const uint64_t* name_hash, const uint8_t* source, int64_t n_reads, const uint8_t* reference,
+                 int64_t reference_length, int64_t lo, int64_t hi, const int64_t* target_starts, const int64_t* target_stops,
+                 int64_t n_targets, int32_t mapq_threshold, int64_t window, int32_t device, hello_qc** handle);
+int hello_qc_finish(hello_qc* qc);
+/* a pointer into `qc` (valid until the next hello_qc_* call on it) and its element count */
+int hello_qc_array(const hello_qc* qc, int32_t which, const void** data, int64_t* count);
+/* stats[HELLO_QC_STATS]: reads given, belonging, belonging and measured, belonging and counted, measured reads with an aligned
+ * base behind the reference's end, positions whose reference byte is not ACGT, pairs, groups of two or more reads that were not
+ * joined, reads / depth / pair / insert kernel ms (HIP events) */
+int hello_qc_stats(const hello_qc* qc, double* stats);
+void hello_qc_free(hello_qc* qc);
+
 #ifdef __cplusplus
 }
 #endif
