@@ -20,11 +20,16 @@ _ARRAYS = (  # (field, hello_bam_* selector, dtype)
     ("flags", 8, np.uint16), ("name_hash", 9, np.uint64), ("strand", 10, np.uint8), ("hp", 11, np.uint8),
 )
 
+_MOD_ARRAYS = (  # after hello_bam_fetch_mods
+    ("deltas", 12, np.int32), ("probs", 13, np.uint8), ("offsets", 14, np.int64), ("mode", 15, np.uint8), ("state", 16, np.uint8),
+)
+
 _PROTOTYPES = (
     ("hello_bam_open", [C.c_char_p, i32, C.POINTER(vp)]),
     ("hello_bam_n_references", [vp]),
     ("hello_bam_reference", [vp, i32, C.POINTER(C.c_char_p), C.POINTER(i64)]),
     ("hello_bam_fetch", [vp, C.c_char_p, i64, i64, i32, C.POINTER(vp)]),
+    ("hello_bam_fetch_mods", [vp, C.c_char_p, i64, i64, i32, C.POINTER(vp)]),
     ("hello_bam_reads_info", [vp, C.POINTER(i64), C.POINTER(i32), C.POINTER(i64)]),
     ("hello_bam_reads_array", ARRAY_GETTER),
     ("hello_bam_reads_free", [vp], None),
@@ -88,6 +93,16 @@ class Reads:
         return Reads(**cat), source
 
 
+@dataclass
+class Mods:
+    """The 5mC calls of one region's records (MM / ML tags), read for read beside a ``Reads``."""
+    deltas: np.ndarray         # int32: per listed base the bases of its kind skipped before it, all reads concatenated
+    probs: np.ndarray          # uint8: its ML byte
+    offsets: np.ndarray        # int64 [R + 1]
+    mode: np.ndarray           # uint8: 0 implicit ('.' or absent), 1 unknown ('?')
+    state: np.ndarray          # uint8: 0 no modifications, 1 usable, 2 bad
+
+
 class BamFile:
     """An open BAM: ``references`` from its header, ``fetch(chromosome, start, stop)`` -> ``Reads``.  Not thread-safe."""
 
@@ -105,11 +120,18 @@ class BamFile:
 
     def fetch(self, chromosome: str, start: int = 0, stop: Optional[int] = None, use_index: Optional[bool] = None) -> Reads:
         """Records overlapping [start, stop).  use_index: None = the .bai when there is one, True = require it, False = scan."""
+        return self._fetch(self._lib.hello_bam_fetch, chromosome, start, stop, use_index)[0]
+
+    def fetch_with_mods(self, chromosome: str, start: int = 0, stop: Optional[int] = None,
+                        use_index: Optional[bool] = None) -> Tuple[Reads, Mods]:
+        """``fetch``, and the C+m calls of every record's MM / ML tags (never an error: a record's state says what was found)."""
+        return self._fetch(self._lib.hello_bam_fetch_mods, chromosome, start, stop, use_index, True)
+
+    def _fetch(self, entry, chromosome, start, stop, use_index, with_mods=False):
         if stop is None:
             stop = dict(self.references).get(chromosome, 0)
         r = C.c_void_p()
-        _check(self._lib.hello_bam_fetch(self._h, chromosome.encode(), int(start), int(stop),
-                                         -1 if use_index is None else int(bool(use_index)), C.byref(r)))
+        _check(entry(self._h, chromosome.encode(), int(start), int(stop), -1 if use_index is None else int(bool(use_index)), C.byref(r)))
         try:
             n, used, blocks = C.c_int64(), C.c_int32(), C.c_int64()
             _check(self._lib.hello_bam_reads_info(r, C.byref(n), C.byref(used), C.byref(blocks)))
@@ -119,7 +141,9 @@ class BamFile:
                 marks = MARKS.get(os.path.abspath(self.path))
                 if marks is not None:
                     marks.apply(chromosome, reads)
-            return reads
+            if not with_mods:
+                return reads, None
+            return reads, Mods(**{field: handle_array(self._lib.hello_bam_reads_array, r, which, dtype) for field, which, dtype in _MOD_ARRAYS})
         finally:
             self._lib.hello_bam_reads_free(r)
 

@@ -65,6 +65,11 @@ Illumina BAM on the GPU before the hotspot stage (``hello_amd.markdup``; DESIGN.
 metrics of every BAM of the route on the GPU after ``results.output.vcf`` is complete (``hello_amd.qc``) and
 writes ``<workdir>/qc.illumina.*`` and / or ``qc.pacbio.*``: ``metrics.txt``, ``tables.npz``, ``windows.bedgraph`` (``--qc_window``)
 and, with ``--qc_regions BED``, ``targets.tsv``.  Under ``--mark_duplicates`` the marked reads count as duplicates and leave the depth.
+
+``--methylation`` (with ``--from_bam --pbam`` / ``--from_bams``, not in the reference, off by default) counts the 5mC calls of the
+PacBio BAM's MM / ML tags per CpG site and haplotype on the GPU after ``results.output.vcf`` is complete
+(``hello_amd.methylation``) and writes ``<workdir>/methylation.combined.bed``, ``.hap1.bed``, ``.hap2.bed``
+and ``methylation.npz``.  A read's haplotype comes from ``--haplotag_vcf``, else from the phased VCF of ``--phase``, else from its HP tag.
 """
 from __future__ import annotations
 
@@ -325,6 +330,11 @@ def parser() -> argparse.ArgumentParser:
                          "qc.pacbio.* (metrics.txt, tables.npz, windows.bedgraph; not in the reference; one GPU; DESIGN.md 7k)")
     ap.add_argument("--qc_regions", help="--qc: a BED file of target intervals; depth on target and per target (targets.tsv)")
     ap.add_argument("--qc_window", type=int, default=None, help="--qc: width of the depth windows of windows.bedgraph (default 1000)")
+    ap.add_argument("--methylation", action="store_true", default=False,
+                    help="with --from_bam --pbam / --from_bams: count the 5mC calls of the PacBio BAM's MM / ML tags per CpG site and "
+                         "haplotype on the GPU and write <workdir>/methylation.{combined,hap1,hap2}.bed and methylation.npz; the "
+                         "haplotypes come from --haplotag_vcf, else --phase, else the HP tags (not in the reference; one GPU; "
+                         "DESIGN.md 7m)")
     ap.add_argument("--device", type=int, default=0, help="GPU of a single-process run")
     ap.add_argument("--gpus", type=int, default=1,
                     help="processes / GPUs of this node: > 1 re-launches this command under torch.distributed.run "
@@ -598,7 +608,7 @@ def haplotag_passes(args) -> str:
     pass 2 only where --phase was given as well."""
     logger = logging.getLogger("hello_amd.call")
     first = argparse.Namespace(**vars(args))
-    first.haplotag = first.gvcf = first.annotate = first.annotate_evidence = first.qc = False
+    first.haplotag = first.gvcf = first.annotate = first.annotate_evidence = first.qc = first.methylation = False
     first.qc_regions = first.qc_window = None
     first.phase = True
     first.workdir = os.path.join(args.workdir, "haplotag_pass1")
@@ -696,6 +706,53 @@ def qc_pass(args, genome: Dict[str, str]) -> List[str]:
     return written
 
 
+def check_methylation(args) -> None:
+    """The refusals of --methylation, each naming the fix."""
+    if not getattr(args, "methylation", False):
+        return
+    if args.shards:
+        raise SystemExit("--methylation reads the MM / ML tags of the PacBio BAM, and shard files hold reads that were fetched before "
+                         "without them: drop --shards and start from the BAM with --from_bam or --from_bams, or drop --methylation")
+    if not _bam_route(args):
+        raise SystemExit("--methylation reads the MM / ML tags of the PacBio BAM, and this run has no BAM on its path: add --from_bam "
+                         "(with --pbam) or --from_bams (--ibam and --pbam), or drop --methylation (python -m hello_amd.methylation "
+                         "counts a BAM on its own)")
+    if _several_processes(args):
+        raise SystemExit("--methylation runs its pass over the BAM in one process on one GPU: run it with --gpus 1 as a plain command, "
+                         "or drop --methylation and run python -m hello_amd.methylation on the BAM")
+    if not args.pbam:
+        raise SystemExit("--methylation counts the 5mC calls a PacBio instrument writes into MM / ML, and this route has no PacBio "
+                         "BAM: give it as --pbam, or drop --methylation")
+
+
+def methylation_pass(args, genome: Dict[str, str], result_path: str) -> List[str]:
+    """--methylation: the CpG methylation of the route's PacBio BAM at the route's --mapq_threshold and chromosomes -> the files
+    written, ``<workdir>/methylation.*.bed`` and ``methylation.npz``.  The reads' haplotypes: --haplotag_vcf, else the phased VCF
+    --phase wrote beside ``result_path``, else the BAM's HP tags."""
+    if not getattr(args, "methylation", False):
+        return []
+    from . import haplotag, methylation
+    route = Route.from_args(args, need_ref=False)
+    phased = getattr(args, "haplotag_vcf", None) or (result_path[:-len(".vcf")] + ".phased.vcf" if getattr(args, "phase", False) else None)
+    tagger = haplotag.Haplotagger(phased, route.chromosomes, route.q_threshold, route.mapq_threshold, route.device) if phased else None
+    stats: dict = {}
+    try:
+        found = methylation.measure(route.bams[-1], genome, route.chromosomes or list(genome), tagger, route.mapq_threshold,
+                                    device=route.device, stats=stats)
+    finally:
+        if tagger is not None:
+            tagger.close()
+    prefix = os.path.join(args.workdir, "methylation")
+    written = found.write_bed(prefix) + [found.save(prefix + ".npz")]
+    total = found.total()
+    logging.getLogger("hello_amd.call").info(
+        "--methylation: %d sites, %d reads counting (%d without calls, %d bad, %d hard-clipped), %d observations in %.2f s (BAM decode "
+        "%.2f s, kernels %.1f ms; haplotypes from %s)", total["n_sites"], total["counting"], total["reads_no_mods"],
+        total["reads_bad_mods"], total["reads_hard_clipped"], total["observations"], stats.get("total_s", 0.0),
+        stats.get("decode_s", 0.0), stats.get("sites_ms", 0.0) + stats.get("reads_ms", 0.0), phased or "the HP tags")
+    return written
+
+
 def run_resident(args) -> str:
     """--from_bam / --from_bams with --resident: hotspots and ``shard<N>.txt`` as ``shards_from_bam(s)`` write them, then ONE loop
     in this process: shard file -> candidate sites whose reads stay on the GPU (``candidates.resident_activity``) -> ``ShardScorer``
@@ -708,6 +765,7 @@ def run_resident(args) -> str:
     check_phase(args)
     check_haplotag(args)
     check_qc(args)
+    check_methylation(args)
     route = Route.from_args(args)
     genome = read_fasta(route.ref, route.chromosomes)
     tagger = haplotagger_of(args, route)
@@ -754,6 +812,7 @@ def run_resident(args) -> str:
     gvcf_pass(args, result_path, genome)
     phase_pass(args, result_path)
     qc_pass(args, genome)
+    methylation_pass(args, genome, result_path)
     return result_path
 
 
@@ -764,6 +823,7 @@ def main(args) -> str:
     check_haplotag(args)
     check_mark_duplicates(args)
     check_qc(args)
+    check_methylation(args)
     if getattr(args, "mark_duplicates", False):
         return with_duplicates_marked(args)
     if getattr(args, "haplotag", False):
@@ -870,6 +930,7 @@ def main(args) -> str:
         gvcf_pass(args, result_path, genomes)
         phase_pass(args, result_path)
         qc_pass(args, genomes)
+        methylation_pass(args, genomes, result_path)
     if world > 1:
         import torch.distributed as dist
         dist.barrier()

@@ -18,6 +18,7 @@
 #include <zlib.h>
 
 #include "../../include/hello_mi355x.h"
+#include "mods.h"
 
 namespace hello {
 int set_last_error(int code, const char* fmt, ...);      // engine.hip
@@ -41,6 +42,9 @@ struct hello_bam_reads {
     std::vector<uint8_t> mapq, strand, hp;
     std::vector<uint16_t> flag;
     std::vector<uint64_t> name_hash;
+    std::vector<int32_t> mod_deltas;    // hello_bam_fetch_mods alone fills these five
+    std::vector<uint8_t> mod_probs, mod_mode, mod_state;
+    std::vector<int64_t> mod_off{0};
     int32_t used_index = 0;
     int64_t blocks = 0;
 };
@@ -328,7 +332,7 @@ uint8_t find_hp_tag(const uint8_t* aux, const uint8_t* end) {
 }
 
 // append one record (the bytes after its block_size field) to the flat arrays
-void decode(hello_bam_reads* r, const uint8_t* b, int32_t block_size, const std::string& path) {
+void decode(hello_bam_reads* r, const uint8_t* b, int32_t block_size, const std::string& path, bool mods = false) {
     const int32_t pos = (int32_t)rd32(b + 4);
     const int l_name = b[8], mapq = b[9];
     const int n_cigar = rd16(b + 12), flag = rd16(b + 14);
@@ -370,6 +374,15 @@ void decode(hello_bam_reads* r, const uint8_t* b, int32_t block_size, const std:
     r->strand.push_back((flag & 16) ? 1 : 0);
     r->name_hash.push_back(fnv1a(name, l_name > 0 ? (size_t)l_name - 1 : 0));
     r->hp.push_back(find_hp_tag(b + need, b + block_size));
+    if (mods) {                                                      // MM / ML (mods.h): the 5mC calls of the record
+        hello::ModsOfRead m;
+        hello::find_mods(b + need, b + block_size, m);
+        r->mod_deltas.insert(r->mod_deltas.end(), m.deltas.begin(), m.deltas.end());
+        r->mod_probs.insert(r->mod_probs.end(), m.probs.begin(), m.probs.end());
+        r->mod_off.push_back((int64_t)r->mod_deltas.size());
+        r->mod_mode.push_back(m.mode);
+        r->mod_state.push_back(m.state);
+    }
 }
 
 }  // namespace
@@ -439,7 +452,8 @@ int hello_bam_reference(const hello_bam* bam, int32_t i, const char** name, int6
     return HELLO_OK;
 }
 
-int hello_bam_fetch(hello_bam* bam, const char* chromosome, int64_t start, int64_t stop, int32_t use_index, hello_bam_reads** out) try {
+static int fetch_records(hello_bam* bam, const char* chromosome, int64_t start, int64_t stop, int32_t use_index, bool mods,
+                         hello_bam_reads** out, const char* entry) try {
     if (!bam || !chromosome || !out) return set_last_error(HELLO_ERR_ARG, "NULL pointer");
     *out = nullptr;
     if (start < 0 || stop < start) return set_last_error(HELLO_ERR_ARG, "region [%lld, %lld) is not a region", (long long)start, (long long)stop);
@@ -476,7 +490,7 @@ int hello_bam_fetch(hello_bam* bam, const char* chromosome, int64_t start, int64
             }
             if ((flag & 4) || rlen == 0) rlen = 1;
             if (pos + rlen <= start) continue;
-            decode(r, b, block_size, bam->path);
+            decode(r, b, block_size, bam->path, mods);
         }
     }
     r->blocks = s.blocks;
@@ -485,7 +499,16 @@ int hello_bam_fetch(hello_bam* bam, const char* chromosome, int64_t start, int64
 } catch (const BamError& e) {
     return set_last_error(e.code, "%s", e.msg.c_str());
 } catch (...) {
-    return hello::exception_status("hello_bam_fetch");
+    return hello::exception_status(entry);
+}
+
+int hello_bam_fetch(hello_bam* bam, const char* chromosome, int64_t start, int64_t stop, int32_t use_index, hello_bam_reads** out) {
+    return fetch_records(bam, chromosome, start, stop, use_index, false, out, "hello_bam_fetch");
+}
+
+int hello_bam_fetch_mods(hello_bam* bam, const char* chromosome, int64_t start, int64_t stop, int32_t use_index,
+                         hello_bam_reads** out) {
+    return fetch_records(bam, chromosome, start, stop, use_index, true, out, "hello_bam_fetch_mods");
 }
 
 int hello_bam_reads_info(const hello_bam_reads* reads, int64_t* n_reads, int32_t* used_index, int64_t* n_blocks) {
@@ -511,6 +534,11 @@ int hello_bam_reads_array(const hello_bam_reads* r, int32_t which, const void** 
         case HELLO_BAM_NAME_HASH: *data = r->name_hash.data(); *count = (int64_t)r->name_hash.size(); break;
         case HELLO_BAM_STRAND: *data = r->strand.data(); *count = (int64_t)r->strand.size(); break;
         case HELLO_BAM_HP: *data = r->hp.data(); *count = (int64_t)r->hp.size(); break;
+        case HELLO_BAM_MOD_DELTAS: *data = r->mod_deltas.data(); *count = (int64_t)r->mod_deltas.size(); break;
+        case HELLO_BAM_MOD_PROBS: *data = r->mod_probs.data(); *count = (int64_t)r->mod_probs.size(); break;
+        case HELLO_BAM_MOD_OFFSETS: *data = r->mod_off.data(); *count = (int64_t)r->mod_off.size(); break;
+        case HELLO_BAM_MOD_MODE: *data = r->mod_mode.data(); *count = (int64_t)r->mod_mode.size(); break;
+        case HELLO_BAM_MOD_STATE: *data = r->mod_state.data(); *count = (int64_t)r->mod_state.size(); break;
         default: return set_last_error(HELLO_ERR_ARG, "no read array %d", which);
     }
     return HELLO_OK;

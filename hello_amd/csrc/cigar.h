@@ -231,5 +231,44 @@ inline std::vector<uint8_t> qc_walk(const ReadsView& s, int64_t lo, int mapq_thr
     return kind;
 }
 
+constexpr int BAM_CHARD_CLIP = 5;
+constexpr uint8_t kMethBelongs = 1, kMethCounted = 2, kMethHardClipped = 4;
+constexpr int64_t kMethMaxReads = (int64_t(1) << 31) / 255;        // counting reads of one handle: its 32-bit sums stay below 2^31
+
+// The walk of the methylation stage over the reads overlapping a span that starts at `lo`: every read's
+// offsets and order and, for a counted read, what the kernels rely on -- a start on the reference, known operations, a CIGAR that
+// consumes exactly the read's bases and ends where ref_end says.  -> per read kMethBelongs | kMethCounted | kMethHardClipped.
+inline std::vector<uint8_t> meth_walk(const ReadsView& s, int64_t lo, int mapq_threshold) {
+    std::vector<uint8_t> kind((size_t)s.n, 0);
+    if (s.n > 0 && (s.read_off[0] != 0 || s.cigar_off[0] != 0)) raise(HELLO_ERR_ARG, "offsets do not start at 0");
+    for (int64_t r = 0; r < s.n; ++r) {
+        if (s.read_off[r + 1] < s.read_off[r] || s.cigar_off[r + 1] < s.cigar_off[r])
+            raise(HELLO_ERR_ARG, "read %lld: offsets decrease", (long long)r);
+        if (r > 0 && s.ref_start[r] < s.ref_start[r - 1])
+            raise(HELLO_ERR_ARG, "read %lld: reads are not coordinate-sorted (the BAM must be)", (long long)r);
+        uint8_t k = s.ref_start[r] >= lo ? kMethBelongs : 0;
+        if (!counted(s.flags[r], s.mapq[r], mapq_threshold)) { kind[(size_t)r] = k; continue; }
+        k |= kMethCounted;
+        if (s.ref_start[r] < 0) raise(HELLO_ERR_ARG, "read %lld: ref_start %lld", (long long)r, (long long)s.ref_start[r]);
+        int64_t qlen = 0, rlen = 0;
+        for (int64_t c = s.cigar_off[r]; c < s.cigar_off[r + 1]; ++c) {
+            const int op = s.cigars[c] & 15;
+            const int64_t len = s.cigars[c] >> 4;
+            if (op > 8) raise(HELLO_ERR_ARG, "read %lld: CIGAR operation %d", (long long)r, op);
+            if (op == BAM_CHARD_CLIP) k |= kMethHardClipped;
+            if (is_query_op(op)) qlen += len;
+            if (is_ref_op(op)) rlen += len;
+        }
+        if (qlen != s.read_off[r + 1] - s.read_off[r])
+            raise(HELLO_ERR_ARG, "read %lld: CIGAR query length %lld, %lld bases", (long long)r, (long long)qlen,
+                  (long long)(s.read_off[r + 1] - s.read_off[r]));
+        if (s.ref_end[r] != s.ref_start[r] + std::max<int64_t>(rlen, 1))
+            raise(HELLO_ERR_ARG, "read %lld: ref_end does not match its CIGAR", (long long)r);
+        if (qlen > INT32_MAX) raise(HELLO_ERR_ARG, "read %lld: %lld bases, at most %d", (long long)r, (long long)qlen, INT32_MAX);
+        kind[(size_t)r] = k;
+    }
+    return kind;
+}
+
 }  // namespace
 }  // namespace hello

@@ -314,13 +314,22 @@ enum {
     HELLO_BAM_BASES = 0, HELLO_BAM_QUALS = 1, HELLO_BAM_READ_OFFSETS = 2, HELLO_BAM_CIGARS = 3, HELLO_BAM_CIGAR_OFFSETS = 4,
     HELLO_BAM_REF_STARTS = 5, HELLO_BAM_REF_ENDS = 6, HELLO_BAM_MAPQ = 7, HELLO_BAM_FLAGS = 8, HELLO_BAM_NAME_HASH = 9,
     HELLO_BAM_STRAND = 10,
-    HELLO_BAM_HP = 11          /* uint8: the HP integer tag (types c/C/s/S/i/I), 0 when absent or outside 0..255 */
+    HELLO_BAM_HP = 11,         /* uint8: the HP integer tag (types c/C/s/S/i/I), 0 when absent or outside 0..255 */
+    /* after hello_bam_fetch_mods alone (empty after hello_bam_fetch): the 5mC calls of the MM / ML tags, DESIGN.md section 7m */
+    HELLO_BAM_MOD_DELTAS = 12, /* int32: per listed base the bases of its kind skipped before it */
+    HELLO_BAM_MOD_PROBS = 13,  /* uint8: its ML byte */
+    HELLO_BAM_MOD_OFFSETS = 14, /* int64 [R + 1] into the two */
+    HELLO_BAM_MOD_MODE = 15,   /* uint8: 0 implicit ('.' or absent), 1 unknown ('?') */
+    HELLO_BAM_MOD_STATE = 16   /* uint8: 0 no modifications, 1 usable, 2 bad */
 };
 int hello_bam_open(const char* path, int32_t n_threads, hello_bam** out);
 int hello_bam_n_references(const hello_bam* bam);
 int hello_bam_reference(const hello_bam* bam, int32_t i, const char** name, int64_t* length);
 int hello_bam_fetch(hello_bam* bam, const char* chromosome, int64_t start, int64_t stop, int32_t use_index,
                     hello_bam_reads** out);
+/* hello_bam_fetch, and per record the C+m group of MM:Z with its bytes of ML:B:C (hello_amd/csrc/mods.h; never an error) */
+int hello_bam_fetch_mods(hello_bam* bam, const char* chromosome, int64_t start, int64_t stop, int32_t use_index,
+                         hello_bam_reads** out);
 int hello_bam_reads_info(const hello_bam_reads* reads, int64_t* n_reads, int32_t* used_index, int64_t* n_blocks);
 /* a pointer into `reads` (valid until hello_bam_reads_free) and its element count */
 int hello_bam_reads_array(const hello_bam_reads* reads, int32_t which, const void** data, int64_t* count);
@@ -952,6 +961,45 @@ int hello_qc_array(const hello_qc* qc, int32_t which, const void** data, int64_t
  * joined, reads / depth / pair / insert kernel ms (HIP events) */
 int hello_qc_stats(const hello_qc* qc, double* stats);
 void hello_qc_free(hello_qc* qc);
+
+/* CpG methylation per haplotype of one chromosome of one BAM, from the MM / ML calls of its reads (not in the reference; DESIGN.md
+ * section 7m states the rules, hello_amd/methylation.py restates them in Python).  One handle per (BAM, chromosome).
+ *   hello_meth_create: takes a copy of `reference` (all of the chromosome) and needs no device.  The first hello_meth_add that
+ *          passes its checks (or hello_meth_array) opens the device, uploads the copy, flags the CpG sites -- position p with
+ *          reference[p] & 0xDF == 'C', reference[p + 1] & 0xDF == 'G' -- as a bit vector with the sites before every 64-position
+ *          word, writes SITES and drops the copy.
+ *   hello_meth_add: the reads overlapping one span [lo, hi), coordinate-sorted: the arrays of hello_bam_fetch with `hp` (the
+ *          haplotype of every read: 1 and 2 have a class of their own) in the place of `source`, and those of hello_bam_fetch_mods
+ *          with their lengths.  A read BELONGS to the span when lo <= ref_start; a belonging read COUNTS when it is counted by the
+ *          gVCF's rule at the handle's mapq_threshold, its CIGAR has no H operation, its state is 1 and its last listed base
+ *          exists (found on the device).  Refused (HELLO_ERR_ARG) before any launch: offsets that do not start at 0 or decrease;
+ *          unsorted reads; a counted read with a negative ref_start, an unknown CIGAR operation, a CIGAR that does not consume
+ *          exactly its bases or a ref_end its CIGAR does not give; lo below the previous hi; hi <= lo or hi > reference_length;
+ *          modification offsets that do not start at 0, decrease or do not end at n_deltas; n_probs != n_deltas; a negative
+ *          delta; a state above 2 or a mode above 1; more than 2^31 / 255 counting reads in one handle (the device sums are
+ *          32-bit).  A refused call leaves the handle as it was.
+ *   hello_meth_array: SITES int64 [n_sites]; COUNTS int64 [n_sites][3][3] -- class (all, haplotype 1, haplotype 2) by counter
+ *          (modified: value >= 128, unmodified, sum of the values); STATUS uint8 per read of the last hello_meth_add.
+ * Host memory in and out; methylation.hip. */
+#define HELLO_METH_STATS 10
+enum {
+    HELLO_METH_SITES = 0,
+    HELLO_METH_COUNTS = 1,
+    HELLO_METH_STATUS = 2            /* 0 not belonging or not counted, 1 counting, 2 bad modifications, 3 none, 4 hard-clipped */
+};
+typedef struct hello_meth hello_meth;
+int hello_meth_create(const uint8_t* reference, int64_t reference_length, int32_t mapq_threshold, int32_t device, hello_meth** handle);
+int hello_meth_add(hello_meth* meth, const uint8_t* bases, const uint8_t* quals, const int64_t* read_offsets, const uint32_t* cigars,
+                   const int64_t* cigar_offsets, const int64_t* ref_starts, const int64_t* ref_ends, const uint8_t* mapq,
+                   const uint16_t* flags, const uint64_t* name_hash, const uint8_t* hp, int64_t n_reads, const int32_t* deltas,
+                   int64_t n_deltas, const uint8_t* probs, int64_t n_probs, const int64_t* mod_offsets, const uint8_t* mode,
+                   const uint8_t* state, int64_t lo, int64_t hi);
+/* a pointer into `meth` (valid until the next hello_meth_* call on it) and its element count */
+int hello_meth_array(hello_meth* meth, int32_t which, const void** data, int64_t* count);
+/* stats[HELLO_METH_STATS]: reads given, belonging, counting, belonging counted reads without modifications, with bad ones, with
+ * a hard clip, observations, sites, sites / reads kernel ms (HIP events) */
+int hello_meth_stats(const hello_meth* meth, double* stats);
+void hello_meth_free(hello_meth* meth);
 
 #ifdef __cplusplus
 }
