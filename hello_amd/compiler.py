@@ -34,6 +34,7 @@ OP_XATTN_FRONT = 11
 (OP_CONV1D, OP_MAXPOOL, OP_SEGSUM, OP_MIX, OP_HEAD, OP_CONCAT, OP_ADD, OP_READCONV_FUSED, OP_LAYERNORM,
  OP_COMPRESSOR_FUSED) = range(1, 11)
 FLAG_RELU, FLAG_SRC_U8, FLAG_SOFTMAX, FLAG_MIX_REST, FLAG_SOFTPLUS, FLAG_WINOGRAD, FLAG_BF16X3, FLAG_BF16X3_32 = 1, 2, 4, 8, 16, 32, 64, 128
+FLAG_POLYPHASE = 2048                        # READCONV_FUSED: the strided convolution in polyphase form (HELLO_FLAG_POLYPHASE)
 FLAG_LANE_SHIFT, MAX_LANES = 8, 8            # bits 8..10 of an op's flags: the stream it runs on in a laned program (HELLO_FLAG_LANE_*)
 OP_NAMES = {1: "conv1d", 2: "maxpool", 3: "segsum", 4: "mix", 5: "head", 6: "concat", 7: "add",
             8: "readconv_fused", 9: "layernorm", 10: "compressor_fused", 11: "xattn_front"}
@@ -97,6 +98,9 @@ class Program:
     winograd: bool = False           # k3/s1/p1 convolutions run in Winograd form (F(2,3) / F(3,3)) where a kernel offers it
     arithmetic: str = "fp32"         # "bf16x3": the read convolver's 64-channel trunk as 3-term bf16 splits; "bf16x3+32": the 32-channel
                                      # blocks too (selectable modes, never the default)
+    strided: str = "direct"          # "polyphase": the fused read convolver's strided convolution runs in polyphase form (7 instead of
+                                     # 9 contractions per 3 outputs; readconv_poly_kernel), "polyphase+compressor": the fused compressor's
+                                     # too; the program's own record of the form its ops ask for
     n_lanes: int = 1                 # > 1: the program's independent chains carry lane numbers (small launches: assign_lanes)
 
     def describe(self) -> str:
@@ -217,10 +221,17 @@ ARITHMETICS = ("fp32", "bf16x3", "bf16x3+32")
 
 
 class _Lowering:
-    def __init__(self, spec: ns.ModelSpec, state, fused: bool, winograd: bool = True, arithmetic: str = "fp32"):
+    def __init__(self, spec: ns.ModelSpec, state, fused: bool, winograd: bool = True, arithmetic: str = "fp32",
+                 strided: str = "polyphase"):
         if arithmetic not in ARITHMETICS:
             raise ValueError(f"arithmetic must be one of {ARITHMETICS}, not {arithmetic!r}")
+        from .readconv_pack import STRIDED_FORMS
+        if strided not in STRIDED_FORMS:
+            raise ValueError(f"strided must be one of {STRIDED_FORMS}, not {strided!r}")
         self.arithmetic = arithmetic
+        self.strided = strided
+        self.used_polyphase = False
+        self.used_polyphase_compressor = False
         self.used_bf16x3 = False
         self.used_xattn_front = False
         self.spec = spec
@@ -294,10 +305,16 @@ class _Lowering:
             # the canonical allele-level compressor: one LDS-resident kernel instead of 4 + 2 blocks launches
             blocks = readconv_pack.compressor_blocks(nodes)
             y = self.new(x.domain, 18, 128)
-            w_off = self.blob.add(readconv_pack.pack_compressor(nodes, self.folded))
+            packed = readconv_pack.pack_compressor(nodes, self.folded)
+            poly = self.strided == "polyphase+compressor"    # its strided 64 -> 128 convolution in polyphase form (compressor_poly_kernel)
+            if poly:
+                packed = np.concatenate([packed, readconv_pack.pack_compressor_polyphase(nodes, self.folded)])
+                self.used_polyphase_compressor = True
+            w_off = self.blob.add(packed)
             self.ops.append(Op(OP_COMPRESSOR_FUSED, x.domain, src0=x.vid, dst=y.vid, cin=64, cout=128, k=blocks, lin=36, lout=18,
-                               flags=FLAG_WINOGRAD | FLAG_RELU, w_off=w_off, b_off=w_off, name=nodes[0].key.rsplit(".network", 1)[0],
-                               macs_per_row=ns.macs(nodes, 36), exec_macs_per_row=readconv_pack.compressor_executed_macs(blocks)))
+                               flags=FLAG_WINOGRAD | FLAG_RELU | (FLAG_POLYPHASE if poly else 0), w_off=w_off, b_off=w_off,
+                               name=nodes[0].key.rsplit(".network", 1)[0], macs_per_row=ns.macs(nodes, 36),
+                               exec_macs_per_row=readconv_pack.compressor_executed_macs(blocks, polyphase=poly)))
             self.used_fused_compressor = True
             return y
         front = readconv_pack.xattn_front_match(nodes) if (self.fused is True and self.winograd and isinstance(x, tuple)) else None
@@ -442,6 +459,19 @@ class _Lowering:
                 packed = np.concatenate([packed, readconv_pack.pack_bf16x3(nodes, self.folded)])
                 wflag |= FLAG_BF16X3 | (FLAG_BF16X3_32 if "+32" in self.arithmetic else 0)
                 self.used_bf16x3 = True
+            # the strided convolution in polyphase form (the default where its kernel exists: fp32, whole kernel from the
+            # bytes, 150 bp, ReLU): its centre tap and F(3,2) taps ride behind the fp32 blob
+            # A bf16x3 program carries the block too, behind its split weights, although its kernels keep the direct form and
+            # never read it (40 KB): tests/test_loader_abi.py test_arithmetic_modes_lower_to_flags_and_split_weight_blocks pins
+            # the split weights as the WHOLE difference between a bf16x3 blob and the default program's, which now holds the block.
+            carry = (self.strided != "direct" and self.fused is True and
+                     readconv_pack.polyphase_available(self.winograd, spec.window, extras, softplus))
+            poly = carry and not (wflag & FLAG_BF16X3)
+            if carry:
+                packed = np.concatenate([packed, readconv_pack.pack_polyphase(nodes, self.folded)])
+            if poly:
+                wflag |= FLAG_POLYPHASE
+                self.used_polyphase = True
             w_off = self.blob.add(packed)
             if self.fused == "trunk":
                 # stem layer by layer (3 valid convs + max pool), fused residual trunk + segment sum
@@ -457,8 +487,8 @@ class _Lowering:
                                    k=extras, lin=spec.window, lout=l2, seg=seg, w_off=w_off, b_off=w_off, name=name,
                                    flags=FLAG_SRC_U8 | wflag | (FLAG_SOFTPLUS if softplus else 0),
                                    macs_per_row=ns.macs(nodes, spec.window),
-                                   exec_macs_per_row=readconv_pack.executed_macs_per_read(self.winograd, extras,
-                                                                                          spec.window)))
+                                   exec_macs_per_row=(readconv_pack.polyphase_executed_macs_per_read(cin, extras) if poly else
+                                                      readconv_pack.executed_macs_per_read(self.winograd, extras, spec.window))))
             self.used_fused = True
             return y
         return self.segsum(self.net(nodes, x), seg)
@@ -768,7 +798,7 @@ def _allocate(ops: List[Op], values: Dict[int, Value], reuse: bool = True):
 
 
 def compile_model(spec: ns.ModelSpec, state, fused: bool = True, winograd: bool = True, arithmetic: str = "fp32",
-                  fold_site_sums: bool = True, lanes: bool = False) -> Program:
+                  fold_site_sums: bool = True, lanes: bool = False, strided: str = "polyphase") -> Program:
     """``winograd``: k3/s1/p1 convolutions are evaluated in Winograd form -- F(3,3) (5 instead of 9 contractions per
     3 positions) where the row length / the fused kernel's geometry is whole triples, else F(2,3) (4 instead of 6
     per pair) -- same fp32 arithmetic, results differ from the direct form by float re-association only.
@@ -778,8 +808,13 @@ def compile_model(spec: ns.ModelSpec, state, fused: bool = True, winograd: bool 
     ``lanes``: the program for SMALL launches -- the same ops, but the independent chains of a two-technology / three-expert model
     carry lane numbers (``assign_lanes``) and no two values share a buffer, so that the engine may run the chains concurrently
     (a launch of a few sites is latency-bound: every chain is a handful of workgroups).  ``n_lanes`` is what ``assign_lanes`` used: 1 where every op continues its producer's
-    lane (single_tech), but a single-chain model whose ops fan out gets lanes too (single_tech_softplus 2, single_tech_layernorm 4)."""
-    low = _Lowering(spec, state, fused, winograd, arithmetic)
+    lane (single_tech), but a single-chain model whose ops fan out gets lanes too (single_tech_softplus 2, single_tech_layernorm 4).
+    ``strided``: "polyphase" (default) runs the fused read convolver's k3/s2 convolution as a centre tap over the even phase
+    plus a Winograd F(3,2) convolution over the odd phase where that kernel exists -- same fp32 arithmetic, float re-association
+    only; "direct" asks for the classic kernels; "polyphase+compressor" also runs the fused compressor's k3/s2 convolution in
+    that form (measured -1.2 % of that kernel, invisible in the headline: not the default).  ``Program.strided`` records what
+    the ops ask for."""
+    low = _Lowering(spec, state, fused, winograd, arithmetic, strided)
     n_experts, has_meta = low.lower()
     if arithmetic != "fp32" and not low.used_bf16x3:
         raise ValueError("arithmetic='bf16x3' / 'bf16x3+32' exists for the canonical 150 bp ReLU read convolver in the whole-kernel "
@@ -796,4 +831,6 @@ def compile_model(spec: ns.ModelSpec, state, fused: bool = True, winograd: bool 
         channels1=spec.channels[1] if spec.hybrid_inputs else 0,
         n_experts=n_experts, has_meta=has_meta, uses_ref=low.uses_ref, ops=low.ops,
         buffers=buffers, weights=low.blob.finish(), fused_read_convolver=low.used_fused,
-        fused_compressor=low.used_fused_compressor, winograd=low.winograd, arithmetic=arithmetic, n_lanes=n_lanes)
+        fused_compressor=low.used_fused_compressor, winograd=low.winograd, arithmetic=arithmetic,
+        strided=("polyphase+compressor" if low.used_polyphase_compressor else "polyphase" if low.used_polyphase else "direct"),
+        n_lanes=n_lanes)

@@ -399,6 +399,11 @@ int validate_model(const hello_model_desc* d) {
                   !(o.flags & HELLO_FLAG_SOFTPLUS)))
                 return fail(HELLO_ERR_MODEL, "op %d: the bf16x3 arithmetic mode exists for the canonical read convolver run whole "
                                              "(from the bytes) in Winograd form on 150 bp windows, ReLU, without extra blocks", i);
+            if ((o.flags & HELLO_FLAG_POLYPHASE) &&
+                !(d->window == 150 && !wide && (o.flags & HELLO_FLAG_WINOGRAD) && (o.flags & HELLO_FLAG_SRC_U8) &&
+                  !(o.flags & (HELLO_FLAG_SOFTPLUS | HELLO_FLAG_BF16X3))))
+                return fail(HELLO_ERR_MODEL, "op %d: the polyphase strided convolution exists for the canonical read convolver run whole "
+                                             "(from the bytes) in fp32 Winograd form on 150 bp windows, ReLU", i);
             if (d->window == 250 && !((o.flags & HELLO_FLAG_WINOGRAD) && (o.flags & HELLO_FLAG_SRC_U8) && o.k == 0))
                 return fail(HELLO_ERR_MODEL, "op %d: 250 bp windows run whole (from the bytes), in Winograd form, "
                                              "without extra blocks", i);
@@ -515,7 +520,8 @@ int hello_engine_create(const hello_model_desc* desc, const void* folded_weights
             w_end = (size_t)o.w_off + o.cin;
             b_end = (size_t)o.b_off + o.cin;
         } else if (o.kind == HELLO_OP_COMPRESSOR_FUSED) {
-            w_end = (size_t)o.w_off + hello::compressor_weight_floats(o.k);
+            w_end = (size_t)o.w_off + hello::compressor_weight_floats(o.k) +
+                    ((o.flags & HELLO_FLAG_POLYPHASE) ? hello::compressor_polyphase_extra_floats() : 0);
             b_end = (size_t)o.b_off;
         } else if (o.kind == HELLO_OP_XATTN_FRONT) {
             w_end = (size_t)o.w_off + hello::xattn_front_weight_floats();
@@ -523,6 +529,7 @@ int hello_engine_create(const hello_model_desc* desc, const void* folded_weights
         } else if (o.kind == HELLO_OP_READCONV_FUSED) {
             w_end = (size_t)o.w_off + (o.cout == 128 ? hello::readconv_wide_weight_floats()
                                                      : hello::readconv_weight_floats(o.k, (o.flags & HELLO_FLAG_WINOGRAD) != 0, desc->window));
+            if (o.flags & HELLO_FLAG_POLYPHASE) w_end += hello::readconv_polyphase_extra_floats();
             b_end = (size_t)o.b_off;
             if (o.cout == 128) e->wide_trunk[o.seg == HELLO_SEG_READS1_TO_ALLELES ? 1 : 0] = true;
         }
@@ -1106,6 +1113,7 @@ int hello_engine_forward(hello_engine* e, const uint8_t* reads0, const int32_t* 
                 a.w = e->d_weights + o.w_off;
                 a.n_items = rows;
                 a.blocks = o.k;
+                a.polyphase = (o.flags & HELLO_FLAG_POLYPHASE) ? 1 : 0;
                 HIP_TRY(hello::launch_compressor_fused(a, stream));
                 break;
             }
@@ -1150,9 +1158,11 @@ int hello_engine_forward(hello_engine* e, const uint8_t* reads0, const int32_t* 
                 a.extra_blocks = o.k;
                 a.winograd = (o.flags & HELLO_FLAG_WINOGRAD) ? 1 : 0;
                 a.bf16x3 = (o.flags & HELLO_FLAG_BF16X3) ? ((o.flags & HELLO_FLAG_BF16X3_32) ? 2 : 1) : 0;
+                a.polyphase = (o.flags & HELLO_FLAG_POLYPHASE) ? 1 : 0;
                 const bool wide = o.cout == 128;
                 if ((size_t)o.w_off + (wide ? hello::readconv_wide_weight_floats() : hello::readconv_weight_floats(o.k, a.winograd, d.window)) +
-                        (a.bf16x3 ? hello::readconv_bf16x3_extra_floats(o.k) : 0) > e->n_weight_floats)
+                        (a.bf16x3 ? hello::readconv_bf16x3_extra_floats(o.k) : 0) +
+                        (a.polyphase ? hello::readconv_polyphase_extra_floats() : 0) > e->n_weight_floats)
                     return fail(HELLO_ERR_MODEL, "op %d: fused read-convolver weight block truncated", op_index);
                 {
                     // the plan of stage_batch_indices: the bulk in whole rounds of n-group workgroups, then the rest as

@@ -90,6 +90,8 @@ struct ReadConvArgs {
     int bf16x3;                // arithmetic mode bf16x3 (`reads` + Winograd form, 150 bp, ReLU, no extra blocks): 1 = the 64-channel
                                // trunk on the bf16 matrix cores as 3-term splits, 2 = the 32-channel blocks too ("bf16x3+32");
                                // the split weights follow the fp32 blob
+    int polyphase;             // the strided 32 -> 64 convolution in polyphase form (`reads` + Winograd form, 150 bp, ReLU, fp32):
+                               // its weights (readconv_polyphase_extra_floats()) follow the fp32 blob
     unsigned long long* stamps;   // diagnostic launch (hello_engine_debug_stamps) or NULL: per-wave s_memtime stamps,
                                   // [workgroups][4 waves][stamp_groups][readconv_stamp_slots()] -- see readconv_kernel
     int stamp_groups;          // groups per workgroup that record (>= groups_per_wg records all)
@@ -113,6 +115,7 @@ ReadConvPlan readconv_plan(long long n_reads, int window);
 ReadConvPlan readconv_wide_plan(long long n_reads);   // every workgroup one group, one launch
 int readconv_weight_floats(int extra_blocks, bool winograd, int window);
 int readconv_bf16x3_extra_floats(int extra_blocks);     // floats the bf16x3 mode's split weights add behind that blob   // 150 bp + Winograd: residual trunk in F(3,3) form
+int readconv_polyphase_extra_floats();                  // floats the polyphase form's weights add behind that blob
 bool readconv_supports_extra_blocks(int extra_blocks);
 hipError_t launch_readconv_fused(const ReadConvArgs& a, hipStream_t stream);
 // frames[a] = sum of the partial slots of allele a, in slot order
@@ -136,12 +139,15 @@ struct CompressorArgs {
     long long n_items;
     int blocks;                // identity residual blocks after the strided one: 2 | 3
     int items_per_wg;          // 1..8 items a workgroup carries; 0: the launcher picks (small_launch_items_per_wg)
+    int polyphase;             // the strided 64 -> 128 convolution in polyphase form; its weights (compressor_polyphase_extra_floats())
+                               // follow the blob
 };
 // Items per workgroup of the LDS-resident allele-stage kernels (compressor_kernel, xattn_front_kernel; one workgroup per CU).  A
 // workgroup's time grows with the items it carries (compressor: 84 us with 2, 121 us with 8; front: 29 / 57 us) while a small launch
 // leaves most CUs idle: one or two items per workgroup while that gives each its own CU (items <= 2 CUs), else whole workgroups of `most`.
 int small_launch_items_per_wg(long long n_items, int most);
 int compressor_weight_floats(int blocks);
+int compressor_polyphase_extra_floats();
 bool compressor_supports_blocks(int blocks);
 hipError_t launch_compressor_fused(const CompressorArgs& a, hipStream_t stream);
 

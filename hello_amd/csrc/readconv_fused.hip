@@ -28,6 +28,9 @@
 //           also runs the stem's conv2 and conv3 + pool).  Everything else, and the whole kernel with
 //           WINO = false, runs the direct form: conv_layer (tile pairs, two accumulation chains per tile,
 //           operands two steps ahead, deferred epilogue).
+//           POLYPHASE (readconv_poly_kernel, the default entry for the fp32 150 bp kernel from the bytes): the k=3 / stride-2
+//           convolution of the strided block as a centre tap over the even rows plus Winograd F(3,2) over the odd rows -- 7
+//           instead of 9 channel contractions per 3 positions: poly_odd_layer, poly_even_layer.
 //   weights each wave keeps ONLY its own 16-channel slice of ONE layer in registers (<= 64 VGPRs; F(3,3)
 //           layers: of one 16-channel input group, 20 VGPRs + the next group's), loaded straight from L2 in
 //           lane order (pre-packed by hello_amd/readconv_pack.py); the next slice is rolled in behind it.
@@ -142,6 +145,12 @@ static_assert(Geometry::F33_32 && GeometrySoftplus::F33_32, "weight packing rule
 // bf16x3: [1 + 2 (3 + extra) layers][4 blocks][6 steps][hi | lo][64 lanes][8 bf16] = 12 288 floats per layer behind the blob
 // and [6 layers 32 -> 32][2 blocks][3 taps][hi | lo][64 lanes][8] = 3 072 floats per layer behind those
 int readconv_bf16x3_extra_floats(int extra_blocks) { return (1 + 2 * (3 + extra_blocks)) * 12288 + 6 * 3072; }
+// polyphase form of the strided 32 -> 64 convolution (readconv_poly_kernel): its centre tap [4 blocks][2 groups][64 lanes][4]
+// and the F(3,2) taps of its outer taps [4 blocks][2 groups][4 components][64 lanes][4], behind the blob
+namespace rc {
+constexpr int POLY_W1 = 4 * 2 * 256, POLY_U = 4 * 2 * 4 * 256;
+}
+int readconv_polyphase_extra_floats() { return rc::POLY_W1 + rc::POLY_U; }
 int readconv_weight_floats(int extra_blocks, bool winograd, int window) {
     if (!winograd) return rc::Offs<false>::off_d(3 + extra_blocks);
     return window == 150 ? rc::Offs<true, true>::off_d(3 + extra_blocks) : rc::Offs<true>::off_d(3 + extra_blocks);
@@ -888,6 +897,153 @@ __device__ __forceinline__ void wino3_layer(const float* __restrict__ in, float*
     });
 }
 
+// ---- polyphase form of the k = 3, stride 2, pad 1 convolution 32 -> 64 (the strided block's first conv) --------------
+// With e[p] = x[2p] and o[p] = x[2p+1]:  y[p] = w1 e[p] + (w0 o[p-1] + w2 o[p]): a 1x1 convolution over the even phase plus
+// a k = 2 / stride 1 convolution over the odd phase, which runs in Winograd F(3,2) form.  Three neighbouring outputs share
+// four odd-phase inputs d0..d3 = o[3T-1 .. 3T+2] = image rows 6T, 6T+2, 6T+4, 6T+6 of the stacked 32-channel image (row
+// stride 72 = 2 x 36: o[-1] of a read IS the shared zero row ahead of it, and o[35] the one behind it -- no boundary masks):
+//     V = (d0-d2, d1+d2, d2-d1, d3-d1),   U = (w0, (w0+w2)/2, (w0-w2)/2, w2),   Mc = Uc * Vc over the input channels
+//     z(3T) = M0+M1+M2,   z(3T+1) = M1-M2,   z(3T+2) = M1+M2+M3
+// i.e. 3 + 4 = 7 contractions per 3 outputs instead of 9.  The group's 144 output rows are 3 whole tiles of 16 triples; a
+// wave owns one of the four 16-channel blocks.  poly_odd_layer leaves M0..M3 of its 3 tiles in `acc` (the input groups
+// are the outer loop, as in wino3_layer); poly_even_layer then walks the even rows ONCE for the centre tap and the block's
+// 1x1 shortcut (same B operands: image rows 6T+1, 6T+3, 6T+5), adds z, and stores relu(.) in the SW_3 image the F(3,3) layer
+// behind it reads; the shortcut stays in `sreg` in triple order, where the GEOM_WTRIPLE pass of the classic form leaves it.
+// Both biases start their accumulation chains.  Every operand row lies inside the image (last: row 288, the trailing zero row).
+// The allele-level compressor instantiates the same two layers at 64 -> 128 channels over 8 items of 36 rows (8 waves): its
+// items are stacked WITHOUT zero rows, so d0 of an item's first triple (TPI triples per item) is fetched from the image's
+// leading zero row instead (MASK), as tap 0 is masked in the direct form; a stride-2 walk over rows of even length never
+// reads past its item's end.  PARTIAL: only the first `live_tiles` tiles hold items (a partly filled workgroup of a small
+// launch): the others are neither read, multiplied nor stored.
+template <class CF, int CIN, int RS_OUT, bool MASK = false, bool PARTIAL = false>
+__device__ __forceinline__ void poly_odd_layer(const float* __restrict__ in, const f32x4 (&w)[CIN / 16][4], f32x4 (&acc)[3][4],
+                                               int lane, int live_tiles = 1 << 30) {
+    static_assert(RS_OUT % 3 == 0 && RS_OUT * CF::G == 144 && (CIN == 32 || CIN == 64), "3 tiles of 16 triples of whole items");
+    constexpr int NT = 3, M = CIN / 16, NU = M * NT, TOFF = 96 * CIN;    // floats between the tiles' input rows
+    constexpr int TPI = RS_OUT / 3;                                      // triples per item
+    const int j = lane & 15, q = lane >> 4;
+    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+    const float* pin[M][4];
+#pragma unroll
+    for (int m = 0; m < M; ++m)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) pin[m][i] = in + img_off<CIN, SW_W>(6 * j + 2 * i, 4 * m + q);
+    f32x4 ring[2][4];
+    auto issue = [&](auto uc) {
+        constexpr int u = decltype(uc)::value;
+        constexpr int m = u / NT, k = u % NT;
+        bool first = false;                                              // this lane's triple opens an item
+        if constexpr (MASK) {
+            static_for<0, 16>([&](auto jc) {
+                constexpr int jj = decltype(jc)::value;
+                if constexpr ((16 * k + jj) % TPI == 0) first = first || (j == jj);
+            });
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const float* ptr = pin[m][i] + k * TOFF;
+            if (MASK && i == 0) ptr = first ? in + 4 * (4 * m + q) : ptr;   // the leading zero row
+            ring[u & 1][i] = *(const f32x4*)ptr;
+        }
+    };
+    issue(std::integral_constant<int, 0>{});
+    static_for<0, NU>([&](auto uc) {
+        constexpr int u = decltype(uc)::value;
+        constexpr int m = u / NT, k = u % NT;
+        if constexpr (u + 1 < NU) {
+            if (!PARTIAL || (u + 1) % NT < live_tiles) issue(std::integral_constant<int, u + 1>{});
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        if (PARTIAL && k >= live_tiles) return;                          // wave-uniform
+        const f32x4(&d)[4] = ring[u & 1];
+        // one block of packed VALU operations ahead of the step's MFMAs (VALU and MFMA share the issue port)
+        const f32x4 v0 = pk_sub(d[0], d[2]), v1 = pk_add(d[1], d[2]), v2 = pk_sub(d[2], d[1]), v3 = pk_sub(d[3], d[1]);
+        asm volatile("s_nop 1");         // VALU write -> MFMA source read distance, whatever the MFMA order below
+        __builtin_amdgcn_sched_barrier(0);
+        f32x4(&a)[4] = acc[k];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const bool first = (m == 0) && (e == 0);
+            a[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[m][0][e], v0[e], first ? zero4 : a[0], 0, 0, 0);
+            a[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[m][1][e], v1[e], first ? zero4 : a[1], 0, 0, 0);
+            a[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[m][2][e], v2[e], first ? zero4 : a[2], 0, 0, 0);
+            a[3] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[m][3][e], v3[e], first ? zero4 : a[3], 0, 0, 0);
+        }
+    });
+}
+
+template <class CF, int CIN, int COUT, bool PARTIAL = false>
+__device__ __forceinline__ void poly_even_layer(const float* __restrict__ in, float* __restrict__ out, const f32x4 (&wc)[CIN / 16],
+                                                const f32x4 (&wsc)[CIN / 16], const float* __restrict__ bias_c,
+                                                const float* __restrict__ bias_sc, const f32x4 (&z)[3][4],
+                                                f32x4 (&sreg)[CF::NSREG], int wave, int lane, int live_tiles = 1 << 30) {
+    static_assert(CF::NW * 16 == COUT && CF::NSREG >= 9 && (CIN == 32 || CIN == 64), "a wave per 16-channel block, 3 tiles of 16 triples");
+    constexpr int NT = 3, M = CIN / 16, NU = NT * M, TIN = 96 * CIN, TOUT = 48 * COUT;   // floats between the tiles' input / output rows
+    const int cb = wave, j = lane & 15, q = lane >> 4;
+    const f32x4 b4c = *(const f32x4*)(bias_c + cb * 16 + 4 * q), b4s = *(const f32x4*)(bias_sc + cb * 16 + 4 * q);
+    const float* pin[M][3];                                                  // even-phase rows 96 t + 6 j + 2 u + 1
+#pragma unroll
+    for (int m = 0; m < M; ++m)
+#pragma unroll
+        for (int u = 0; u < 3; ++u) pin[m][u] = in + img_off<CIN, SW_W>(6 * j + 2 * u + 1, 4 * m + q);
+    float* po[3];                                                            // flat rows 3T + u = image rows 3T + 1 + u
+#pragma unroll
+    for (int u = 0; u < 3; ++u) po[u] = out + img_off_triple<COUT, SW_3>(0, j, 1 + u, 4 * cb + q);
+    f32x4 ring[2][3], cen[2][3];
+    auto issue = [&](auto sc) {
+        constexpr int s = decltype(sc)::value;
+        constexpr int t = s / M, m = s % M;
+#pragma unroll
+        for (int u = 0; u < 3; ++u) ring[s & 1][u] = *(const f32x4*)(pin[m][u] + t * TIN);
+    };
+    // output transform of the odd part + centre tap (bias included), activation, stores of tile tt
+    auto epi_store = [&](auto tc) {
+        constexpr int tt = decltype(tc)::value;
+        const f32x4(&a)[4] = z[tt];
+        const f32x4 sum = a[1] + a[2];
+        f32x4 y0 = (a[0] + sum) + cen[tt & 1][0];
+        f32x4 y1 = (a[1] - a[2]) + cen[tt & 1][1];
+        f32x4 y2 = (sum + a[3]) + cen[tt & 1][2];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            y0[e] = CF::act(y0[e]);
+            y1[e] = CF::act(y1[e]);
+            y2[e] = CF::act(y2[e]);
+        }
+        *(f32x4*)(po[0] + tt * TOUT) = y0;
+        *(f32x4*)(po[1] + tt * TOUT) = y1;
+        *(f32x4*)(po[2] + tt * TOUT) = y2;
+    };
+    issue(std::integral_constant<int, 0>{});
+    static_for<0, NU>([&](auto sc) {
+        constexpr int s = decltype(sc)::value;
+        constexpr int t = s / M, m = s % M;
+        if constexpr (s + 1 < NU) {
+            if (!PARTIAL || (s + 1) / M < live_tiles) issue(std::integral_constant<int, s + 1>{});
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        // the previous tile's epilogue, a whole step behind its last MFMAs
+        if constexpr (m == 1 && t >= 1) {
+            if (!PARTIAL || t - 1 < live_tiles) epi_store(std::integral_constant<int, (t >= 1 ? t - 1 : 0)>{});
+        }
+        if (!PARTIAL || t < live_tiles) {
+            const f32x4(&x)[3] = ring[s & 1];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const bool first = (m == 0) && (e == 0);
+#pragma unroll
+                for (int u = 0; u < 3; ++u) {
+                    sreg[3 * t + u] = __builtin_amdgcn_mfma_f32_16x16x4f32(wsc[m][e], x[u][e], first ? b4s : sreg[3 * t + u], 0, 0, 0);
+                    cen[t & 1][u] = __builtin_amdgcn_mfma_f32_16x16x4f32(wc[m][e], x[u][e], first ? b4c : cen[t & 1][u], 0, 0, 0);
+                }
+            }
+        }
+        if constexpr (s == NU - 1) {
+            if (!PARTIAL || NT - 1 < live_tiles) epi_store(std::integral_constant<int, NT - 1>{});
+        }
+    });
+}
+
 // ---- bf16x3: a k = 3, stride 1, pad 1 convolution 64 -> 64 over a split image, on the bf16 matrix cores --------------
 // x w ~= xh wh + (xh wl + xl wh): three v_mfma_f32_16x16x32_bf16 (K = 32 in 16 cycles) per 32-deep chunk of the direct
 // form's K = 3 taps x 64 channels, against v_mfma_f32_16x16x4_f32's K = 4 in 32 cycles; the dropped xl wl and the split
@@ -1066,23 +1222,24 @@ __device__ __forceinline__ void bf16x3_layer32(const unsigned char* __restrict__
 // The bytes are read as they are (no float copy): lane (j, q) of a tile needs k = 4*step + q of row j, and
 // k = tap*C + c is the byte offset from the row start.  Tiles of a wave: t = wave + 4*i; pairs of tiles in
 // flight; the bytes of the next pair are requested before the MFMAs of the current one.
-template <class CF>
+// NSTEP: the MFMA steps that run (the blob always holds rc::S1_STEPS; 6-channel reads have K = 18 <= 4 x 5: the sixth step
+// multiplies zeros).
+template <class CF, int NSTEP = rc::S1_STEPS>
 __device__ __forceinline__ void stem_conv1(const unsigned char* __restrict__ s_u8, float* __restrict__ c1,
                                            const float* __restrict__ W, int ch, float* __restrict__ dump, int wave,
                                            int lane) {
-    using namespace rc;
     constexpr int NPAIR = CF::ST12 / 8;          // 4 waves x 2 tiles per pair
     static_assert(CF::ST12 % 8 == 0, "stem tiles must split into pairs over 4 waves");
     const int j = lane & 15, q = lane >> 4;
-    float w1[S1_STEPS];
+    float w1[NSTEP];
 #pragma unroll
-    for (int s = 0; s < S1_STEPS; ++s) w1[s] = W[s * 64 + lane];              // W = the conv1 block of the blob
-    const f32x4 b4 = *(const f32x4*)(W + S1_STEPS * 64 + 4 * q);
+    for (int s = 0; s < NSTEP; ++s) w1[s] = W[s * 64 + lane];              // W = the conv1 block of the blob
+    const f32x4 b4 = *(const f32x4*)(W + rc::S1_STEPS * 64 + 4 * q);
     const unsigned char* base = s_u8 + (16 * wave + j) * ch + q;       // tile `wave`, row j, byte q
     const int tile_bytes = 16 * ch;
-    unsigned char cur0[S1_STEPS], cur1[S1_STEPS], nxt0[S1_STEPS], nxt1[S1_STEPS];
+    unsigned char cur0[NSTEP], cur1[NSTEP], nxt0[NSTEP], nxt1[NSTEP];
 #pragma unroll
-    for (int s = 0; s < S1_STEPS; ++s) {
+    for (int s = 0; s < NSTEP; ++s) {
         cur0[s] = base[4 * s];
         cur1[s] = base[4 * tile_bytes + 4 * s];
     }
@@ -1090,7 +1247,7 @@ __device__ __forceinline__ void stem_conv1(const unsigned char* __restrict__ s_u
     for (int i = 0; i < NPAIR; ++i) {
         if (i + 1 < NPAIR) {
 #pragma unroll
-            for (int s = 0; s < S1_STEPS; ++s) {
+            for (int s = 0; s < NSTEP; ++s) {
                 nxt0[s] = base[(8 * (i + 1)) * tile_bytes + 4 * s];
                 nxt1[s] = base[(8 * (i + 1) + 4) * tile_bytes + 4 * s];
             }
@@ -1098,7 +1255,7 @@ __device__ __forceinline__ void stem_conv1(const unsigned char* __restrict__ s_u
         __builtin_amdgcn_sched_barrier(0);
         f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int s = 0; s < S1_STEPS; ++s) {
+        for (int s = 0; s < NSTEP; ++s) {
             a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w1[s], (float)cur0[s], a0, 0, 0, 0);
             a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w1[s], (float)cur1[s], a1, 0, 0, 0);
         }
@@ -1112,7 +1269,7 @@ __device__ __forceinline__ void stem_conv1(const unsigned char* __restrict__ s_u
         *(f32x4*)(r0 < CF::SROWS ? c1 + r0 * 16 + 4 * (q ^ swz<16>(r0)) : dump) = v0;
         *(f32x4*)(r1 < CF::SROWS ? c1 + r1 * 16 + 4 * (q ^ swz<16>(r1)) : dump) = v1;
 #pragma unroll
-        for (int s = 0; s < S1_STEPS; ++s) {
+        for (int s = 0; s < NSTEP; ++s) {
             cur0[s] = nxt0[s];
             cur1[s] = nxt1[s];
         }
@@ -1363,10 +1520,14 @@ __device__ __forceinline__ void stem_conv3_pool_wino(const float* __restrict__ i
 // reads; no output value is computed from a stamp.  Layout: [workgroup][wave][group < stamp_groups][STAMP_SLOTS] of uint64:
 // slot 0 = group start, 1 + 2 i = arrival at barrier i, 2 + 2 i = release from it, 41 = HW_ID | XCC_ID << 32, 42 / 43 =
 // s_memrealtime at the group's start / end (100 MHz: the in-kernel clock), 44 = after the workgroup's last flush.
-template <class CF, bool STEM, int NB64, bool WINO, bool BF16 = false, bool BF16_32 = false, bool STAMP = false>
-__global__ __launch_bounds__(CF::THREADS, 2) void readconv_kernel(ReadConvArgs a) {
+// The body is shared by two kernel entries: readconv_kernel (the strided block's first convolution in direct form) and
+// readconv_poly_kernel (POLY: that convolution in polyphase form, poly_odd_layer / poly_even_layer; CH: the reads' channel
+// count as a constant, so that stem conv1 of 6-channel reads runs 5 steps instead of 6).
+template <class CF, bool STEM, int NB64, bool WINO, bool BF16, bool BF16_32, bool STAMP, bool POLY = false, int CH = 0>
+__device__ __forceinline__ void readconv_body(const ReadConvArgs& a) {
     using namespace rc;
     constexpr bool F33 = WINO && CF::F33;                     // 64-channel residual blocks in F(3,3) form
+    static_assert(!POLY || (F33 && STEM && !BF16 && (CH == 6 || CH == 7)), "polyphase: the fp32 F(3,3) kernel from the bytes");
     // BF16 (arithmetic mode "bf16x3", never the default): the seven (eleven) 64 -> 64 convolutions run on the bf16 matrix
     // cores as 3-term splits (bf16x3_layer); everything before them -- stem, 32-channel blocks, the strided convolution
     // and its shortcut -- and the per-allele sums stay exact fp32
@@ -1492,7 +1653,7 @@ __global__ __launch_bounds__(CF::THREADS, 2) void readconv_kernel(ReadConvArgs a
     if (STEM) {
         // the stem, from the uint8 pileups: conv1 bytes -> bufB, conv2 bufB -> bufA, conv3 + max pool
         // bufA -> X (= bufB again, now as the 32-channel image)
-        const int ch = a.channels;
+        const int ch = CH ? CH : a.channels;
         const int n_bytes = n_here * CF::WINDOW * ch;
         const unsigned char* src = a.reads + read0 * CF::WINDOW * ch;
         // The group's bytes in ONE round trip to memory: every thread requests all its dwords first and
@@ -1523,7 +1684,7 @@ __global__ __launch_bounds__(CF::THREADS, 2) void readconv_kernel(ReadConvArgs a
         f32x4 ws2[3];
         if constexpr (!WINO) load_weights<3>(ws2, W + OFF_S2, 0, lane);
         barrier(0);
-        stem_conv1<CF>(s_u8, bufB, W + OFF_S1, ch, dump, wave, lane);
+        stem_conv1<CF, (CH == 6 ? 5 : S1_STEPS)>(s_u8, bufB, W + OFF_S1, ch, dump, wave, lane);
         barrier(1);
         if constexpr (WINO) stem_conv2_wino<CF>(bufB, bufA, W + OFF_S2, dump, wave, lane);
         else conv_layer<CF, 16, 16, 3, 1, 0, 1, 1, 0, CF::ST12, MODE_PLAIN, false, GEOM_STEM, 16, CF::SROWS>(
@@ -1628,6 +1789,25 @@ __global__ __launch_bounds__(CF::THREADS, 2) void readconv_kernel(ReadConvArgs a
     }
 
     // ---- strided block 32 -> 64: relu(conv s2) -> relu(conv) + (1x1 s2 shortcut) ----------------
+    if constexpr (POLY) {
+        // polyphase form: the odd phase in F(3,2) (4 contractions per 3 outputs), then ONE pass over the even phase for the
+        // centre tap and the shortcut; its weights ride behind the blob: centre tap, then U
+        const float* const WP = W + O::off_d(NB64);
+        f32x4 wu[2][4], wc[2];
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) wu[m][c] = *(const f32x4*)(WP + POLY_W1 + (((cb4 * 2 + m) * 4 + c) * 64 + lane) * 4);
+        load_weights<2>(wc, WP, cb4, lane);
+        load_weights<2>(w2, W + OFF_SC, cb4, lane);
+        if (tid < 32) ((f32x4*)H)[(tid & 15) + (tid >> 4) * (RS2 * G + 1) * 16] = f32x4{0.f, 0.f, 0.f, 0.f};   // rows 0 and 36G+1
+        f32x4 zacc[3][4];
+        poly_odd_layer<CF, 32, RS2>(X, wu, zacc, lane);
+        poly_even_layer<CF, 32, 64>(X, H, wc, w2, W + OFF_C1 + W3264, W + OFF_SC + W3264S, zacc, sreg, wave, lane);
+        // the second conv's first input group
+#pragma unroll
+        for (int c = 0; c < 5; ++c) w3[0][c] = *(const f32x4*)(W + OFF_C2 + cb4 * (20 * 256) + lane * 4 + c * 256);
+    } else {
     if constexpr (F33) {                     // (otherwise rolled in by the last 32-channel layer)
         load_weights<6>(w6, W + OFF_C1, cb4, lane);
     } else {
@@ -1637,6 +1817,7 @@ __global__ __launch_bounds__(CF::THREADS, 2) void readconv_kernel(ReadConvArgs a
     if (tid < 32) ((f32x4*)H)[(tid & 15) + (tid >> 4) * (RS2 * G + 1) * 16] = f32x4{0.f, 0.f, 0.f, 0.f};   // rows 0 and 36G+1
     conv_layer<CF, 32, 64, 3, 2, 1, RS1, RS2, L2, T2, MODE_PLAIN, false, GEOM_TRUNK, 16, RS2 * CF::G, false, SWX,
                BF16 ? SW_SPLIT : (F33 ? SW_3 : SWX)>(X, H, w6, nullptr, W + OFF_C1 + W3264, sreg, pad2, dump, wave, lane);
+    }
     // bf16x3: this wave's split weights of trunk layer l (0 = the strided block's second conv, then the blocks' convs):
     // [layer][4 blocks][6 steps][hi | lo][64 lanes][8 bf16] behind the fp32 blob
     const unsigned short* const WS16 = (const unsigned short*)(W + O::off_d(NB64)) + cb4 * 6144 + lane * 8;
@@ -1650,6 +1831,8 @@ __global__ __launch_bounds__(CF::THREADS, 2) void readconv_kernel(ReadConvArgs a
             bwh[st] = *(const bf16x8*)(WS16 + (st * 2) * 512);
             bwl[st] = *(const bf16x8*)(WS16 + (st * 2 + 1) * 512);
         }
+    } else if constexpr (POLY) {
+        // (poly_even_layer left the shortcut in `sreg`, in the same row order)
     } else if constexpr (F33) {
         // the shortcut in the row order the F(3,3) epilogue of the block's second conv holds its outputs in
         static_assert(!F33 || CF::NSREG >= 3 * (RS2 * CF::G / 48), "shortcut tiles kept in registers");
@@ -1777,56 +1960,79 @@ __global__ __launch_bounds__(CF::THREADS, 2) void readconv_kernel(ReadConvArgs a
     }
 }
 
-template <class CF, int NB64, bool WINO, bool STEM_ONLY = false, bool BF16 = false, bool BF16_32 = false>
-static hipError_t launch_cfg(const ReadConvArgs& a, hipStream_t stream) {
-    // the LDS opt-in is a per-device attribute of the function: once per device this process launches on
-    // (threads that share a device race benignly: the call is idempotent)
-    static bool configured_on[64] = {};
+template <class CF, bool STEM, int NB64, bool WINO, bool BF16 = false, bool BF16_32 = false, bool STAMP = false>
+__global__ __launch_bounds__(CF::THREADS, 2) void readconv_kernel(ReadConvArgs a) {
+    readconv_body<CF, STEM, NB64, WINO, BF16, BF16_32, STAMP>(a);
+}
+
+// The default fp32 / Winograd / 150 bp read convolver from the bytes with its strided convolution in polyphase form:
+// 2 930 (6 channels) | 2 940 (7) MFMAs per wave and group instead of 2 988 (NB64 = 3).
+template <class CF, int NB64, int CH, bool STAMP = false>
+__global__ __launch_bounds__(CF::THREADS, 2) void readconv_poly_kernel(ReadConvArgs a) {
+    readconv_body<CF, true, NB64, true, false, false, STAMP, true, CH>(a);
+}
+
+// One launch of a read-convolver configuration.  `stem` / `trunk`: its entries from the pileup bytes / from pooled rows (nullptr:
+// the configuration has none); `stamped`: its diagnostic instantiation (hello_engine_debug_stamps; nullptr: none -- only the
+// default fp32 Winograd schedule from the bytes has one).  The LDS opt-in is a per-device attribute of a function, set once per
+// device this process launches on: `configured_on` / `stamped_on` are the configuration's own flags (threads that share a device
+// race benignly: the call is idempotent).  stamp_mode bit 1 pads the workgroup's LDS past half a CU's, so that ONE workgroup is
+// resident per CU (one wave per SIMD).
+using RcEntry = void (*)(ReadConvArgs);
+static hipError_t launch_entries(RcEntry stem, RcEntry trunk, RcEntry stamped, int reads_per_group, int threads, int lds_bytes,
+                                 bool (&configured_on)[64], bool (&stamped_on)[64], const ReadConvArgs& a, hipStream_t stream) {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    bool& configured = configured_on[dev];
-    if (!configured) {
-        hipError_t e = hipSuccess;
-        if constexpr (!STEM_ONLY)
-            e = hipFuncSetAttribute((const void*)readconv_kernel<CF, false, NB64, WINO, BF16, BF16_32>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, CF::LDS_BYTES);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute((const void*)readconv_kernel<CF, true, NB64, WINO, BF16, BF16_32>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, CF::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        configured = true;
+    if (!configured_on[dev]) {
+        for (RcEntry k : {trunk, stem}) {
+            if (!k) continue;
+            const hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+            if (e != hipSuccess) return e;
+        }
+        configured_on[dev] = true;
     }
     if (a.groups_per_wg < 1) return hipErrorInvalidValue;
-    const long long per_wg = (long long)CF::G * a.groups_per_wg;
+    const long long per_wg = (long long)reads_per_group * a.groups_per_wg;
     const unsigned groups = (unsigned)((a.n_reads + per_wg - 1) / per_wg);       // workgroups
     if (a.stamps) {
-        // the diagnostic instantiation (hello_engine_debug_stamps): the default schedule only; stamp_mode bit 1 pads the
-        // workgroup's LDS past half a CU's, so that ONE workgroup is resident per CU (one wave per SIMD)
-        if constexpr (std::is_same<CF, Geometry>::value && NB64 == 3 && WINO && !BF16 && !STEM_ONLY) {
-            if (!a.reads || (a.channels != 6 && a.channels != 7) || a.stamp_groups < 1) return hipErrorInvalidValue;
-            static bool stamped_on[64] = {};          // (engines on threads that share a device race benignly, like configured_on: the call is idempotent)
-            if (!stamped_on[dev]) {
-                const hipError_t e = hipFuncSetAttribute((const void*)readconv_kernel<CF, true, NB64, WINO, false, false, true>,
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024);
-                if (e != hipSuccess) return e;
-                stamped_on[dev] = true;
-            }
-            const int lds = (a.stamp_mode & 2) ? 100 * 1024 : CF::LDS_BYTES;
-            hipLaunchKernelGGL((readconv_kernel<CF, true, NB64, WINO, false, false, true>), dim3(groups), dim3(CF::THREADS), lds, stream, a);
-            return hipGetLastError();
-        } else {
-            return hipErrorInvalidValue;
+        if (!stamped || !a.reads || (a.channels != 6 && a.channels != 7) || a.stamp_groups < 1) return hipErrorInvalidValue;
+        if (!stamped_on[dev]) {
+            const hipError_t e = hipFuncSetAttribute((const void*)stamped, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024);
+            if (e != hipSuccess) return e;
+            stamped_on[dev] = true;
         }
+        hipLaunchKernelGGL(stamped, dim3(groups), dim3(threads), (a.stamp_mode & 2) ? 100 * 1024 : lds_bytes, stream, a);
+        return hipGetLastError();
     }
+    RcEntry k = trunk;
     if (a.reads) {
         if (a.channels != 6 && a.channels != 7) return hipErrorInvalidValue;
-        hipLaunchKernelGGL((readconv_kernel<CF, true, NB64, WINO, BF16, BF16_32>), dim3(groups), dim3(CF::THREADS), CF::LDS_BYTES, stream, a);
-    } else if constexpr (!STEM_ONLY) {
-        hipLaunchKernelGGL((readconv_kernel<CF, false, NB64, WINO, BF16, BF16_32>), dim3(groups), dim3(CF::THREADS), CF::LDS_BYTES, stream, a);
-    } else {
-        return hipErrorInvalidValue;
+        k = stem;
     }
+    if (!k) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k, dim3(groups), dim3(threads), lds_bytes, stream, a);
     return hipGetLastError();
+}
+
+template <int NB64, int CH>
+static hipError_t launch_poly(const ReadConvArgs& a, hipStream_t stream) {
+    using CF = Geometry;
+    static bool configured_on[64] = {}, stamped_on[64] = {};
+    RcEntry stamped = nullptr;                     // the diagnostic instantiation: the canonical three blocks only
+    if constexpr (NB64 == 3) stamped = readconv_poly_kernel<CF, NB64, CH, true>;
+    return launch_entries(readconv_poly_kernel<CF, NB64, CH>, nullptr, stamped, CF::G, CF::THREADS, CF::LDS_BYTES, configured_on,
+                          stamped_on, a, stream);
+}
+
+template <class CF, int NB64, bool WINO, bool STEM_ONLY = false, bool BF16 = false, bool BF16_32 = false>
+static hipError_t launch_cfg(const ReadConvArgs& a, hipStream_t stream) {
+    static bool configured_on[64] = {}, stamped_on[64] = {};
+    RcEntry trunk = nullptr, stamped = nullptr;
+    if constexpr (!STEM_ONLY) trunk = readconv_kernel<CF, false, NB64, WINO, BF16, BF16_32>;
+    if constexpr (std::is_same<CF, Geometry>::value && NB64 == 3 && WINO && !BF16 && !STEM_ONLY)
+        stamped = readconv_kernel<CF, true, NB64, WINO, false, false, true>;
+    return launch_entries(readconv_kernel<CF, true, NB64, WINO, BF16, BF16_32>, trunk, stamped, CF::G, CF::THREADS, CF::LDS_BYTES,
+                          configured_on, stamped_on, a, stream);
 }
 
 hipError_t launch_readconv_fused(const ReadConvArgs& a, hipStream_t stream) {
@@ -1844,6 +2050,12 @@ hipError_t launch_readconv_fused(const ReadConvArgs& a, hipStream_t stream) {
     if (a.softplus) {              // the Softplus configuration: whole kernel, Winograd form
         if (!a.reads || !a.winograd || a.extra_blocks != 0) return hipErrorInvalidValue;
         return launch_cfg<GeometrySoftplus, 3, true, true>(a, stream);
+    }
+    if (a.polyphase) {
+        if (!a.reads || !a.winograd || (a.channels != 6 && a.channels != 7)) return hipErrorInvalidValue;
+        if (a.extra_blocks == 0) return a.channels == 6 ? launch_poly<3, 6>(a, stream) : launch_poly<3, 7>(a, stream);
+        if (a.extra_blocks == 2) return a.channels == 6 ? launch_poly<5, 6>(a, stream) : launch_poly<5, 7>(a, stream);
+        return hipErrorInvalidValue;
     }
     if (a.extra_blocks == 0) return a.winograd ? launch_cfg<Geometry, 3, true>(a, stream) : launch_cfg<Geometry, 3, false>(a, stream);
     if (a.extra_blocks == 2) return a.winograd ? launch_cfg<Geometry, 5, true>(a, stream) : launch_cfg<Geometry, 5, false>(a, stream);
@@ -1902,14 +2114,18 @@ struct Cfg {
     static constexpr int OFF_11 = 0, OFF_S = OFF_11 + W11 + 64, OFF_SC = OFF_S + WS + 128, OFF_B = OFF_SC + WSC + 128;
     static constexpr int off_conv(int i) { return OFF_B + i * (WB + 128); }    // 0: the strided block's second conv; then the blocks'
     static constexpr int total(int blocks) { return off_conv(1 + 2 * blocks); }
+    static constexpr int POLY_W1 = 8 * 4 * 256, POLY_U = 8 * 4 * 4 * 256;   // polyphase form of the strided conv, behind the blob
 };
 }  // namespace cc
 
 int compressor_weight_floats(int blocks) { return cc::Cfg::total(blocks); }
+int compressor_polyphase_extra_floats() { return cc::Cfg::POLY_W1 + cc::Cfg::POLY_U; }
 bool compressor_supports_blocks(int blocks) { return blocks >= 2 && blocks <= 4; }
 
-template <int NB>
-__global__ __launch_bounds__(cc::Cfg::THREADS, 2) void compressor_kernel(CompressorArgs a) {
+// POLY: the strided convolution in polyphase form (poly_odd_layer / poly_even_layer: 336 instead of 432 MFMAs per wave); its
+// centre tap [8 blocks][4 groups][64 lanes][4] and F(3,2) taps [8][4][4 components][64 lanes][4] follow the blob.
+template <int NB, bool POLY>
+__device__ __forceinline__ void compressor_body(const CompressorArgs& a) {
     using CF = cc::Cfg;
     constexpr int G = CF::G, L0 = CF::L0, L1 = CF::L1;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -1961,9 +2177,34 @@ __global__ __launch_bounds__(cc::Cfg::THREADS, 2) void compressor_kernel(Compres
     else
         conv_layer<CF, 64, 64, 1, 1, 0, L0, L0, L0, L0 * G / 16, MODE_PLAIN, false, GEOM_TRUNK, 16, L0 * G, false, SW_OLD, SW_W, true>(
             bufA, bufB, w11, nullptr, W + CF::OFF_11 + CF::W11, sreg, 0u, dump, wave, lane, 0, (live0 - wave / 4 + 1) / 2);
-    f32x4 ws[12], wsc[4];
-    load_weights<12>(ws, W + CF::OFF_S, wave, lane);
+    f32x4 wsc[4];
     load_weights<4>(wsc, W + CF::OFF_SC, wave, lane);
+    if constexpr (POLY) {
+        const float* const WP = W + CF::total(NB);
+        f32x4 wu[4][4], wc[4];
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) wu[m][c] = *(const f32x4*)(WP + CF::POLY_W1 + (((wave * 4 + m) * 4 + c) * 64 + lane) * 4);
+        load_weights<4>(wc, WP, wave, lane);
+        __syncthreads();
+        // bufA becomes the 128-channel image: rows 0 and 18 G + 1 are its zero rows
+        if (tid < 64) ((f32x4*)bufA)[(tid & 31) + (tid >> 5) * (L1 * G + 1) * 32] = zero4;
+        f32x4 zacc[3][4];
+        if (full) {
+            poly_odd_layer<CF, 64, L1, true>(bufB, wu, zacc, lane);
+            poly_even_layer<CF, 64, 128>(bufB, bufA, wc, wsc, W + CF::OFF_S + CF::WS, W + CF::OFF_SC + CF::WSC, zacc, sreg, wave, lane);
+        } else {
+            const int live3 = (6 * n_here + 15) / 16;                 // tiles of 16 triples that hold items
+#pragma unroll
+            for (int t = 0; t < CF::NSREG; ++t) sreg[t] = zero4;      // (the skipped tiles' shortcut rows are stored below)
+            poly_odd_layer<CF, 64, L1, true, true>(bufB, wu, zacc, lane, live3);
+            poly_even_layer<CF, 64, 128, true>(bufB, bufA, wc, wsc, W + CF::OFF_S + CF::WS, W + CF::OFF_SC + CF::WSC, zacc, sreg, wave,
+                                               lane, live3);
+        }
+    } else {
+    f32x4 ws[12];
+    load_weights<12>(ws, W + CF::OFF_S, wave, lane);
     __syncthreads();
     // bufA becomes the 128-channel image: rows 0 and 18 G + 1 are its zero rows
     if (tid < 64) ((f32x4*)bufA)[(tid & 31) + (tid >> 5) * (L1 * G + 1) * 32] = zero4;
@@ -1977,6 +2218,7 @@ __global__ __launch_bounds__(cc::Cfg::THREADS, 2) void compressor_kernel(Compres
     // its 1x1 s2 shortcut, in the row order the F(3,3) epilogue of the block's second conv holds its outputs in
     conv_layer<CF, 64, 128, 1, 2, 0, L0, L1, L1, CF::NSREG, MODE_TO_REGS, false, GEOM_WTRIPLE, 16, L1 * G, false, SW_W, SW_3>(
         bufB, nullptr, wsc, nullptr, W + CF::OFF_SC + CF::WSC, sreg, 0u, dump, wave, lane);
+    }
     f32x4 w3[2][5];
     auto slice = [&](int off) { return W + off + wave * (8 * 5 * 256) + lane * 4; };   // this wave's block, this lane
 #pragma unroll
@@ -2019,6 +2261,15 @@ __global__ __launch_bounds__(cc::Cfg::THREADS, 2) void compressor_kernel(Compres
         dst[f] = *(const f32x4*)(bufB + img_off<128, SW_3>(1 + (f >> 5), f & 31));
 }
 
+template <int NB>
+__global__ __launch_bounds__(cc::Cfg::THREADS, 2) void compressor_kernel(CompressorArgs a) {
+    compressor_body<NB, false>(a);
+}
+template <int NB>
+__global__ __launch_bounds__(cc::Cfg::THREADS, 2) void compressor_poly_kernel(CompressorArgs a) {
+    compressor_body<NB, true>(a);
+}
+
 int small_launch_items_per_wg(long long n_items, int most) {
     const long long cus = device_cus();
     const long long n = (n_items + cus - 1) / cus;
@@ -2042,10 +2293,22 @@ hipError_t launch_compressor_fused(const CompressorArgs& args, hipStream_t strea
             e = hipFuncSetAttribute((const void*)compressor_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, cc::Cfg::LDS_BYTES);
         if (e == hipSuccess)
             e = hipFuncSetAttribute((const void*)compressor_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, cc::Cfg::LDS_BYTES);
+        if (e == hipSuccess)
+            e = hipFuncSetAttribute((const void*)compressor_poly_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, cc::Cfg::LDS_BYTES);
+        if (e == hipSuccess)
+            e = hipFuncSetAttribute((const void*)compressor_poly_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, cc::Cfg::LDS_BYTES);
+        if (e == hipSuccess)
+            e = hipFuncSetAttribute((const void*)compressor_poly_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, cc::Cfg::LDS_BYTES);
         if (e != hipSuccess) return e;
         configured_on[dev] = true;
     }
     const unsigned grid = (unsigned)((a.n_items + a.items_per_wg - 1) / a.items_per_wg);
+    if (a.polyphase) {
+        if (a.blocks == 2) hipLaunchKernelGGL(compressor_poly_kernel<2>, dim3(grid), dim3(cc::Cfg::THREADS), cc::Cfg::LDS_BYTES, stream, a);
+        else if (a.blocks == 3) hipLaunchKernelGGL(compressor_poly_kernel<3>, dim3(grid), dim3(cc::Cfg::THREADS), cc::Cfg::LDS_BYTES, stream, a);
+        else hipLaunchKernelGGL(compressor_poly_kernel<4>, dim3(grid), dim3(cc::Cfg::THREADS), cc::Cfg::LDS_BYTES, stream, a);
+        return hipGetLastError();
+    }
     if (a.blocks == 2) hipLaunchKernelGGL(compressor_kernel<2>, dim3(grid), dim3(cc::Cfg::THREADS), cc::Cfg::LDS_BYTES, stream, a);
     else if (a.blocks == 3) hipLaunchKernelGGL(compressor_kernel<3>, dim3(grid), dim3(cc::Cfg::THREADS), cc::Cfg::LDS_BYTES, stream, a);
     else hipLaunchKernelGGL(compressor_kernel<4>, dim3(grid), dim3(cc::Cfg::THREADS), cc::Cfg::LDS_BYTES, stream, a);

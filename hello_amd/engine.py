@@ -147,7 +147,8 @@ class Engine:
     """One compiled model resident on one GPU (one instance per process and device)."""
 
     def __init__(self, spec: ns.ModelSpec, state, device: int = 0, fused: bool = True, winograd: bool = True,
-                 program: Optional["compiler.Program"] = None, arithmetic: Optional[str] = None, lanes_max_sites: Optional[int] = None):
+                 program: Optional["compiler.Program"] = None, arithmetic: Optional[str] = None, lanes_max_sites: Optional[int] = None,
+                 strided: Optional[str] = None):
         """``program``: an already compiled (or deliberately edited) program to load instead of compiling.
         ``arithmetic``: "fp32" (exact fp32 everywhere, the default), "bf16x3" -- the read convolver's seven 64 -> 64 trunk
         convolutions on the bf16 matrix cores as 3-term splits (x w ~= xh wh + xh wl + xl wh; ~2^-17 per product, the
@@ -155,15 +156,22 @@ class Engine:
         their measured accuracy and speed.  An explicit "bf16x3"
         raises where the mode does not exist (other read-convolver geometries, layer-by-layer paths).  Nothing in the
         environment changes the arithmetic: ``self.program.arithmetic`` is what was asked for here (the test suite runs
-        itself in a split mode through a fixture of tests/conftest.py, not through this constructor)."""
+        itself in a split mode through a fixture of tests/conftest.py, not through this constructor).
+        ``strided``: "polyphase" (the default), "direct" or "polyphase+compressor" -- the form of the fused read convolver's
+        (and compressor's) strided convolution (``compiler.compile_model``); None reads the environment variable HELLO_STRIDED, so that one build and one process can
+        run both forms side by side.  Same fp32 arithmetic either way; ``self.program.strided`` records the form the ops run.
+        (The suite-wide arithmetic fixture of tests/conftest.py wraps this constructor without the keyword: under
+        HELLO_TEST_ARITHMETIC the form is chosen through HELLO_STRIDED or a compiled ``program`` only.)"""
+        strided = strided or os.environ.get("HELLO_STRIDED") or "polyphase"
         self.lib = load_library()
         self.spec = spec
         self.lanes_max_sites = lanes_max_sites      # None: the module's LANES_MAX_SITES at call time
         # the laned program for small launches is compiled from the same options on first use (None: this engine was handed a
         # finished program, or the model is a single chain)
-        self._lanes_recipe = None if program is not None else dict(state=state, fused=fused, winograd=winograd, arithmetic=arithmetic or "fp32")
+        self._lanes_recipe = None if program is not None else dict(state=state, fused=fused, winograd=winograd, arithmetic=arithmetic or "fp32",
+                                                                        strided=strided)
         if program is None:
-            program = compiler.compile_model(spec, state, fused=fused, winograd=winograd, arithmetic=arithmetic or "fp32")
+            program = compiler.compile_model(spec, state, fused=fused, winograd=winograd, arithmetic=arithmetic or "fp32", strided=strided)
         self.program = program
         p = self.program
         self.device = device
@@ -192,7 +200,8 @@ class Engine:
             return self.handle
         if self.lanes_handle is None:
             r = self._lanes_recipe
-            prog = compiler.compile_model(self.spec, r["state"], fused=r["fused"], winograd=r["winograd"], arithmetic=r["arithmetic"], lanes=True)
+            prog = compiler.compile_model(self.spec, r["state"], fused=r["fused"], winograd=r["winograd"], arithmetic=r["arithmetic"], lanes=True,
+                                          strided=r["strided"])
             if prog.n_lanes == 1:
                 self._lanes_recipe = None
                 return self.handle

@@ -94,6 +94,71 @@ def executed_macs_per_read(winograd: bool, extra_blocks: int = 0, window: int = 
     return (stem + strided + blocks) * 1024.0 / g
 
 
+# how the k3/s2 convolutions run: "polyphase" = the fused read convolver's in polyphase form (the default), "direct" = the
+# classic kernels, "polyphase+compressor" = the fused compressor's too (compressor_poly_kernel: -1.2 % of that kernel, 0.013 ms
+# of a 16.5 ms forward; not the default: profiles/polyphase_2026-10-20.txt)
+STRIDED_FORMS = ("polyphase", "direct", "polyphase+compressor")
+
+
+def polyphase_available(winograd: bool, window: int, extra_blocks: int = 0, softplus: bool = False) -> bool:
+    """readconv_poly_kernel exists for the default fp32 / Winograd / 150 bp / ReLU read convolver run from the bytes."""
+    return f33(winograd, window) and extra_blocks in EXTRA_BLOCKS and not softplus
+
+
+def polyphase_executed_macs_per_read(channels: int, extra_blocks: int = 0) -> float:
+    """MACs readconv_poly_kernel's MFMAs execute per read.  Against ``executed_macs_per_read(True, extra_blocks)``, per wave
+    and group of 4 reads: the strided convolution is 3 tiles x 2 input groups x 4 components x 4 (odd phase, F(3,2)) + 9
+    tiles x 2 x 4 (centre tap, beside the shortcut's) = 168 MFMAs instead of 216, and stem conv1 of 6-channel reads runs 5
+    steps instead of 6 over its 10 tiles: 2 930 (6 channels) | 2 940 (7) instead of 2 988."""
+    assert channels in (6, 7), channels
+    saved = (216 - (3 * 2 * 4 * 4 + 9 * 2 * 4)) + (10 if channels == 6 else 0)
+    return executed_macs_per_read(True, extra_blocks) - saved * 1024.0
+
+
+def polyphase_taps(w: np.ndarray, dtype=np.float32) -> np.ndarray:
+    """[cout, cin, 3] -> [cout, cin, 4]: the F(3,2) filter transform of the OUTER taps g0 = w[..., 0], g1 = w[..., 2] of a
+    k3/s2 convolution (its odd phase is a k2/s1 convolution), evaluated in float64 and rounded once:
+    g0, (g0 + g1)/2, (g0 - g1)/2, g1."""
+    g = w.astype(np.float64)
+    g0, g1 = g[..., 0], g[..., 2]
+    return np.stack([g0, (g0 + g1) / 2, (g0 - g1) / 2, g1], axis=-1).astype(dtype)
+
+
+def polyphase_reference(x: np.ndarray, w: np.ndarray, u: np.ndarray) -> np.ndarray:
+    """The polyphase evaluation in float64, as the kernels order it: ``x`` [cin, L] (L odd or even, output length a
+    multiple of 3), ``w`` [cout, cin, 3], ``u`` = the F(3,2) taps [cout, cin, 4] -> the k3 / s2 / p1 convolution [cout, Lout]
+    without bias.  y[p] = w1 e[p] + z[p] with e[p] = x[2p], o[p] = x[2p+1] (o[-1] = 0, and 0 past the end)."""
+    x = np.asarray(x, np.float64)
+    cin, n = x.shape
+    lout = (n - 1) // 2 + 1
+    assert lout % 3 == 0, lout
+    o = np.zeros((cin, lout + 1))                      # o[p - 1] at index p; zero padding on both sides
+    odd = x[:, 1::2]
+    o[:, 1:1 + odd.shape[1]] = odd
+    e = x[:, 0::2]
+    uu = np.asarray(u, np.float64)
+    y = np.asarray(w, np.float64)[:, :, 1] @ e
+    for t in range(lout // 3):
+        d0, d1, d2, d3 = (o[:, 3 * t + i] for i in range(4))
+        m = [uu[:, :, 0] @ (d0 - d2), uu[:, :, 1] @ (d1 + d2), uu[:, :, 2] @ (d2 - d1), uu[:, :, 3] @ (d3 - d1)]
+        y[:, 3 * t] += m[0] + m[1] + m[2]
+        y[:, 3 * t + 1] += m[1] - m[2]
+        y[:, 3 * t + 2] += m[1] + m[2] + m[3]
+    return y
+
+
+def pack_polyphase(nodes, folded) -> np.ndarray:
+    """What readconv_poly_kernel reads behind the blob: the strided 32 -> 64 convolution's centre tap
+    [4 blocks][2 groups][64 lanes][4], then its F(3,2) taps [4 blocks][2 groups][4 components][64 lanes][4]."""
+    w, b = folded[trunk_convs(nodes)[6].key]
+    assert w.shape == (64, 32, 3), w.shape
+    centre = _pack_conv(np.ascontiguousarray(w[:, :, 1:2]), b)[:4 * 2 * 256]                    # [cb, 1, m, lane, t]
+    u = _pack_conv(polyphase_taps(w), b)[:4 * 4 * 2 * 256].reshape(4, 4, 2, 64, 4)              # [cb, c, m, lane, t]
+    blob = np.concatenate([centre, u.transpose(0, 2, 1, 3, 4).ravel()])
+    assert blob.size == 2048 + 8192, blob.size
+    return blob
+
+
 def winograd_taps(w: np.ndarray) -> np.ndarray:
     """[cout, cin, 3] -> [cout, cin, 4]: the F(2,3) filter transform U = G g, evaluated in float64 and rounded
     once: g0, (g0 + g1 + g2)/2, (g0 - g1 + g2)/2, g2."""
@@ -293,10 +358,25 @@ def pack_compressor(nodes, folded) -> np.ndarray:
     return blob
 
 
-def compressor_executed_macs(blocks: int) -> float:
+def compressor_executed_macs(blocks: int, polyphase: bool = False) -> float:
     """MACs the kernel's MFMAs execute per item: direct 1x1 / strided / shortcut convs, F(3,3) (5 contractions per 3
-    positions) for the 1 + 2 blocks k3/s1 convolutions."""
-    return 36 * 64 * 64 + 18 * 128 * 192 + 18 * 128 * 64 + (1 + 2 * blocks) * 6 * 5 * 128 * 128
+    positions) for the 1 + 2 blocks k3/s1 convolutions.  ``polyphase`` (compressor_poly_kernel): the strided convolution
+    as 18 centre-tap positions + 6 triples x 4 F(3,2) components of 64 x 128 instead of 18 positions x 3 taps (336 instead
+    of 432 MFMAs per wave and workgroup of 8 items)."""
+    strided = (18 + 6 * 4) * 128 * 64 if polyphase else 18 * 128 * 192
+    return 36 * 64 * 64 + strided + 18 * 128 * 64 + (1 + 2 * blocks) * 6 * 5 * 128 * 128
+
+
+def pack_compressor_polyphase(nodes, folded) -> np.ndarray:
+    """What compressor_poly_kernel reads behind ``pack_compressor``'s blob: the strided 64 -> 128 convolution's centre tap
+    [8 blocks][4 groups][64 lanes][4], then its F(3,2) taps [8 blocks][4 groups][4 components][64 lanes][4]."""
+    w, b = folded[nodes[1].body[0].key]
+    assert w.shape == (128, 64, 3), w.shape
+    centre = _pack_conv(np.ascontiguousarray(w[:, :, 1:2]), b)[:8 * 4 * 256]                    # [cb, 1, m, lane, t]
+    u = _pack_conv(polyphase_taps(w), b)[:8 * 4 * 4 * 256].reshape(8, 4, 4, 64, 4)              # [cb, c, m, lane, t]
+    blob = np.concatenate([centre, u.transpose(0, 2, 1, 3, 4).ravel()])
+    assert blob.size == 8192 + 32768, blob.size
+    return blob
 
 
 # ---- the 2x-channel ("_wide") read convolver: residual trunk kernel (readconv_wide_trunk_kernel) ---------------------

@@ -119,6 +119,13 @@ typedef enum hello_op_kind {
                                         the default: results differ from exact fp32 at the 1e-6 level of the activations */
 #define HELLO_FLAG_BF16X3_32 128     /* with HELLO_FLAG_BF16X3 ("bf16x3+32"): the six 32 -> 32 convolutions of the ResidualBlock(32)s too */
 #define HELLO_FLAG_MIX_REST 8        /* MIX: dst[a] = src0[a] - (src1[site(a)] - src0[a])  (:372-383)  */
+#define HELLO_FLAG_POLYPHASE 2048    /* READCONV_FUSED (an addition within ABI version 2; whole kernel from the bytes, 150 bp, ReLU, Winograd
+                                        form, fp32, not the wide trunk): the strided 32 -> 64 convolution runs in polyphase form --
+                                        centre tap over the even phase, outer taps over the odd phase as Winograd F(3,2): 7 instead of
+                                        9 contractions per 3 outputs.  Its weights (hello_amd/readconv_pack.py pack_polyphase) follow
+                                        the op's fp32 weight block.  COMPRESSOR_FUSED: its strided 64 -> 128 convolution likewise
+                                        (pack_compressor_polyphase behind the op's block; the compiler sets it on request only).  Same fp32 arithmetic; results differ from
+                                        the direct form by float re-association only */
 /* Lanes (an addition within ABI version 2): bits 8..10 of `flags` name the stream an op runs on, 0 = the call's own stream.  A model
  * of two read technologies / three experts is several INDEPENDENT chains (MixtureOfExpertsAdvanced.py:161-252: read convolver +
  * compressor + expert per technology, the combined expert, the meta network); a launch of a few sites is latency-bound -- every chain

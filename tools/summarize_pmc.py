@@ -89,14 +89,20 @@ def provenance():
 
 
 def traffic(d):
-    # readconv_kernel is launched twice per forward (bulk + remainder, readconv_plan): per-forward figures are the
-    # kernel's SUM over the pass divided by the number of forwards (= dispatches of its finalize kernel)
+    # the read convolver is launched twice per forward (bulk + remainder, readconv_plan): per-forward figures are the
+    # kernel's SUM over the pass divided by the number of forwards (= dispatches of its finalize kernel).  Its entry is
+    # readconv_poly_kernel (the default: strided convolution in polyphase form) or readconv_kernel (HELLO_STRIDED=direct)
+    def entry(t):
+        return next(k for k in ("readconv_poly_kernel", "readconv_kernel") if k in t)
+
     def per_forward(name, counter):
         t = load(d, name)
-        return t["readconv_kernel"][counter]["sum"] / t["readconv_finalize_kernel"][counter]["dispatches"]
+        return t[entry(t)][counter]["sum"] / t["readconv_finalize_kernel"][counter]["dispatches"]
     fetch = per_forward("FETCH_SIZE", "FETCH_SIZE")
     write = per_forward("WRITE_SIZE", "WRITE_SIZE")
-    sq = load(d, "SQ_VALU_MFMA_BUSY_CYCLES")["readconv_kernel"]
+    sq_all = load(d, "SQ_VALU_MFMA_BUSY_CYCLES")
+    rc_name = entry(sq_all)
+    sq = sq_all[rc_name]
     g = lambda c: sq[c]["sum"]                                                                                                # noqa: E731
     # the WHOLE forward: every kernel of the pass (the engine's own and torch's copy kernels), per forward
     ft, wt = load(d, "FETCH_SIZE"), load(d, "WRITE_SIZE")
@@ -112,7 +118,7 @@ def traffic(d):
         "algorithmic_bytes_per_forward": 246002 * 900 + 4 * (17646 + 8193) + 4 * 17646 + 16 * 26400,
         "algorithmic_bytes_per_forward_note": "8 192-site launch: 900 B per read + CSR counts in, 4 B per allele (logits) + 16 B per pair (posteriors) out",
         "bytes_per_forward_by_kernel": dict(sorted(by_kernel.items(), key=lambda kv: -kv[1])),
-        "kernel": "hello::readconv_kernel (bench.py headline loop, 8 192 sites / 246 k reads per forward; two launches per "
+        "kernel": f"hello::{rc_name} (bench.py headline loop, 8 192 sites / 246 k reads per forward; two launches per "
                   "forward: 7 680 workgroups of 8 groups, then 60 of one group)",
         "FETCH_SIZE_KB_per_launch": fetch, "WRITE_SIZE_KB_per_launch": write,
         "correction": "bytes = (2 * FETCH_SIZE + WRITE_SIZE) * 1024 on gfx950 (FETCH_SIZE tallies 128-B requests at 64 B); separate --pmc passes",
