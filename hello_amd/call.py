@@ -70,6 +70,12 @@ and, with ``--qc_regions BED``, ``targets.tsv``.  Under ``--mark_duplicates`` th
 PacBio BAM's MM / ML tags per CpG site and haplotype on the GPU after ``results.output.vcf`` is complete
 (``hello_amd.methylation``) and writes ``<workdir>/methylation.combined.bed``, ``.hap1.bed``, ``.hap2.bed``
 and ``methylation.npz``.  A read's haplotype comes from ``--haplotag_vcf``, else from the phased VCF of ``--phase``, else from its HP tag.
+
+``--contamination --contamination_sites V`` (with ``--from_bam`` / ``--from_bams``, not in the reference, off by default) counts the
+bases of every BAM of the route at the sites of ``V`` on the GPU after ``results.output.vcf`` is complete
+(``hello_amd.contamination``), estimates each BAM's contamination and, with two BAMs, whether they hold one
+person, and writes ``<workdir>/contamination.illumina.*`` and / or ``contamination.pacbio.*`` (``txt``, ``pileup.tsv``, ``npz``) and
+``contamination.identity.txt``.  Under ``--mark_duplicates`` the marked reads leave the pileup.
 """
 from __future__ import annotations
 
@@ -335,6 +341,12 @@ def parser() -> argparse.ArgumentParser:
                          "haplotype on the GPU and write <workdir>/methylation.{combined,hap1,hap2}.bed and methylation.npz; the "
                          "haplotypes come from --haplotag_vcf, else --phase, else the HP tags (not in the reference; one GPU; "
                          "DESIGN.md 7m)")
+    ap.add_argument("--contamination", action="store_true", default=False,
+                    help="with --from_bam / --from_bams and --contamination_sites: count the bases of every BAM of the route at the "
+                         "sites on the GPU, estimate its contamination and, with two BAMs, whether they hold one person; writes "
+                         "<workdir>/contamination.illumina.* / contamination.pacbio.* (txt, pileup.tsv, npz) and "
+                         "contamination.identity.txt (not in the reference; one GPU; DESIGN.md 7n)")
+    ap.add_argument("--contamination_sites", help="--contamination: a VCF (plain or .gz) of biallelic SNVs with INFO AF, common ones")
     ap.add_argument("--device", type=int, default=0, help="GPU of a single-process run")
     ap.add_argument("--gpus", type=int, default=1,
                     help="processes / GPUs of this node: > 1 re-launches this command under torch.distributed.run "
@@ -609,7 +621,8 @@ def haplotag_passes(args) -> str:
     logger = logging.getLogger("hello_amd.call")
     first = argparse.Namespace(**vars(args))
     first.haplotag = first.gvcf = first.annotate = first.annotate_evidence = first.qc = first.methylation = False
-    first.qc_regions = first.qc_window = None
+    first.contamination = False
+    first.qc_regions = first.qc_window = first.contamination_sites = None
     first.phase = True
     first.workdir = os.path.join(args.workdir, "haplotag_pass1")
     phased_path = main(first)[:-len(".vcf")] + ".phased.vcf"
@@ -753,6 +766,58 @@ def methylation_pass(args, genome: Dict[str, str], result_path: str) -> List[str
     return written
 
 
+def check_contamination(args) -> None:
+    """The refusals of --contamination and --contamination_sites, each naming the fix."""
+    if not getattr(args, "contamination", False):
+        if getattr(args, "contamination_sites", None) is not None:
+            raise SystemExit("--contamination_sites is an option of the contamination pass and there is none in this run: add "
+                             "--contamination, or drop --contamination_sites")
+        return
+    if getattr(args, "contamination_sites", None) is None:
+        raise SystemExit("--contamination counts the reads at known sites and was given none: add --contamination_sites with a VCF "
+                         "of common biallelic SNVs that carry INFO AF, or drop --contamination")
+    if args.shards:
+        raise SystemExit("--contamination counts the reads of the BAM(s), and shard files hold reads that were fetched and filtered "
+                         "before: drop --shards and start from the BAM with --from_bam or --from_bams, or drop --contamination")
+    if not _bam_route(args):
+        raise SystemExit("--contamination counts the reads of the BAM(s), and this run has no BAM on its path: add --from_bam (one "
+                         "BAM) or --from_bams (--ibam and --pbam), or drop --contamination (python -m hello_amd.contamination "
+                         "measures BAMs on their own)")
+    if _several_processes(args):
+        raise SystemExit("--contamination runs its pass over the BAM(s) in one process on one GPU: run it with --gpus 1 as a plain "
+                         "command, or drop --contamination and run python -m hello_amd.contamination on the BAM(s)")
+
+
+def contamination_pass(args, genome: Dict[str, str]) -> List[str]:
+    """--contamination: the pileup at --contamination_sites of every BAM of the route, at the route's thresholds and chromosomes,
+    and the estimates on it -> the files written, ``<workdir>/contamination.illumina.*`` and / or ``contamination.pacbio.*`` and,
+    with two BAMs, ``contamination.identity.txt``."""
+    if not getattr(args, "contamination", False):
+        return []
+    from . import contamination as cn
+    route = Route.from_args(args, need_ref=False)
+    names = ("pacbio",) if route.pacbio else ("illumina", "pacbio")
+    chromosomes = route.chromosomes or list(genome)
+    sites = cn.read_sites(args.contamination_sites, genome, chromosomes)
+    written: List[str] = []
+    found = []
+    for bam, name in zip(route.bams, names):
+        stats: dict = {}
+        got = cn.measure(bam, genome, chromosomes, sites, route.q_threshold, route.mapq_threshold, route.device, stats)
+        found.append(got)
+        written += got.write_all(os.path.join(args.workdir, "contamination." + name))
+        total, est = got.total(), got.estimate()
+        logging.getLogger("hello_amd.call").info(
+            "--contamination %s: %d sites (%d records skipped), %d reads counting, %d observations, error rate %.4f, contamination "
+            "%.3f [%.3f, %.3f] in %.2f s (BAM decode %.2f s, kernels %.1f ms)", name, total["n_sites"], sum(got.skipped.values()),
+            total["counting"], total["observations"], est["error_rate"], est["k"] / 1000, est["k_lo"] / 1000, est["k_hi"] / 1000,
+            stats.get("total_s", 0.0), stats.get("decode_s", 0.0), stats.get("sites_ms", 0.0) + stats.get("reads_ms", 0.0))
+    if len(found) == 2:
+        written.append(cn.write_identity(os.path.join(args.workdir, "contamination.identity.txt"), *found))
+        logging.getLogger("hello_amd.call").info("--contamination identity: LOD %.3f over %d sites: %s", *cn.identity_of(*found))
+    return written
+
+
 def run_resident(args) -> str:
     """--from_bam / --from_bams with --resident: hotspots and ``shard<N>.txt`` as ``shards_from_bam(s)`` write them, then ONE loop
     in this process: shard file -> candidate sites whose reads stay on the GPU (``candidates.resident_activity``) -> ``ShardScorer``
@@ -766,6 +831,7 @@ def run_resident(args) -> str:
     check_haplotag(args)
     check_qc(args)
     check_methylation(args)
+    check_contamination(args)
     route = Route.from_args(args)
     genome = read_fasta(route.ref, route.chromosomes)
     tagger = haplotagger_of(args, route)
@@ -813,6 +879,7 @@ def run_resident(args) -> str:
     phase_pass(args, result_path)
     qc_pass(args, genome)
     methylation_pass(args, genome, result_path)
+    contamination_pass(args, genome)
     return result_path
 
 
@@ -824,6 +891,7 @@ def main(args) -> str:
     check_mark_duplicates(args)
     check_qc(args)
     check_methylation(args)
+    check_contamination(args)
     if getattr(args, "mark_duplicates", False):
         return with_duplicates_marked(args)
     if getattr(args, "haplotag", False):
@@ -931,6 +999,7 @@ def main(args) -> str:
         phase_pass(args, result_path)
         qc_pass(args, genomes)
         methylation_pass(args, genomes, result_path)
+        contamination_pass(args, genomes)
     if world > 1:
         import torch.distributed as dist
         dist.barrier()

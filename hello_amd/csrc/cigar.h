@@ -270,5 +270,16 @@ inline std::vector<uint8_t> meth_walk(const ReadsView& s, int64_t lo, int mapq_t
     return kind;
 }
 
+constexpr uint8_t kPileBelongs = kMethBelongs, kPileCounted = kMethCounted;
+constexpr int64_t kPileMaxReads = INT32_MAX;                       // counting reads of one handle: a read adds at most 1 to a counter
+
+// The walk of the pileup at sites: what meth_walk checks and refuses, in its words -- the kernels rely on
+// the same things.  A hard clip consumes nothing and is no cause to leave a read out.  -> per read kPileBelongs | kPileCounted.
+inline std::vector<uint8_t> pileup_walk(const ReadsView& s, int64_t lo, int mapq_threshold) {
+    std::vector<uint8_t> kind = meth_walk(s, lo, mapq_threshold);
+    for (uint8_t& k : kind) k &= kPileBelongs | kPileCounted;
+    return kind;
+}
+
 }  // namespace
 }  // namespace hello

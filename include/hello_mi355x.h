@@ -1008,6 +1008,58 @@ int hello_meth_array(hello_meth* meth, int32_t which, const void** data, int64_t
 int hello_meth_stats(const hello_meth* meth, double* stats);
 void hello_meth_free(hello_meth* meth);
 
+/* Base counts per strand at a given list of positions of one chromosome of one BAM -- a pileup at sites -- and on top of it the
+ * contamination of the BAM and the identity of two BAMs (not in the reference; DESIGN.md section 7n states the rules,
+ * hello_amd/contamination.py restates them in Python).  One handle per (BAM, chromosome).
+ *   hello_pileup_create: takes a copy of `pos` (0-based, strictly ascending, inside [0, chromosome_length)) and needs no device.
+ *          The first hello_pileup_add that passes its checks (or hello_pileup_array of COUNTS) opens the device and builds the
+ *          bit vector of the sites with the sites before every 64-position word.  Refused: NULL, a negative count, a length
+ *          outside [0, 2^31 - 1], a position that is not above the one before it or lies outside the chromosome.
+ *   hello_pileup_option: HELLO_PILEUP_FORM 0 (the default) runs the reads kernel in two phases -- a lane per read ORs the words
+ *          under the read, a wave walks every read that covers a site -- and 1 walks every counting read with a wave.  Both give
+ *          the same bytes.  HELLO_PILEUP_SHARE: the counting reads of a workgroup of that kernel, 1 to 1 024, or 0 (the default):
+ *          every hello_pileup_add sizes it for about 4 096 workgroups.
+ *   hello_pileup_add: the reads overlapping one span [lo, hi), coordinate-sorted: the arrays of hello_bam_fetch.  A read BELONGS
+ *          to the span when lo <= ref_start; a belonging read COUNTS when it is counted by the gVCF's rule at the handle's
+ *          mapq_threshold.  A counting read observes a site under an M / = / X operation (bins A C G T, OTHER, or LOWQ below
+ *          q_threshold, the byte folded with & 0xDF) and under a D operation (bin DEL).  Spans ascend and do not overlap.
+ *          Refused, before the device is looked for: what hello_meth_add refuses of the reads and the span, in its words, and
+ *          more than 2^31 - 1 counting reads in one handle (the device counters are 32-bit).  A refused call leaves the handle
+ *          as it was.
+ *   hello_pileup_array: COUNTS int64 [n_sites][2][7] -- strand (flag 0x10) by bin; STATUS uint8 per read of the last add.
+ *   hello_contam_estimate / hello_contam_identity: host only, no device.  `r`, `a`, `o`: per site the counts of REF, of ALT and
+ *          of the two other bases; `af` the ALT allele's frequency, inside (0, 1).  Refused: NULL, a negative n or count, such
+ *          an af.
+ * Host memory in and out; pileup.hip, contam.h. */
+#define HELLO_PILEUP_STATS 8
+#define HELLO_PILEUP_BINS 7          /* A, C, G, T, OTHER, DEL, LOWQ */
+#define HELLO_CONTAM_GRID 501        /* alpha_k = k / 1000 */
+#define HELLO_CONTAM_OUT 505
+enum {
+    HELLO_PILEUP_COUNTS = 0,
+    HELLO_PILEUP_STATUS = 1          /* 0 not belonging or not counted, 1 counting, 2 counting with an observation */
+};
+enum { HELLO_PILEUP_FORM = 0, HELLO_PILEUP_SHARE = 1 };
+typedef struct hello_pileup hello_pileup;
+int hello_pileup_create(const int64_t* pos, int64_t n_sites, int64_t chromosome_length, int32_t q_threshold, int32_t mapq_threshold,
+                        int32_t device, hello_pileup** handle);
+int hello_pileup_option(hello_pileup* pileup, int32_t which, int32_t value);
+int hello_pileup_add(hello_pileup* pileup, const uint8_t* bases, const uint8_t* quals, const int64_t* read_offsets,
+                     const uint32_t* cigars, const int64_t* cigar_offsets, const int64_t* ref_starts, const int64_t* ref_ends,
+                     const uint8_t* mapq, const uint16_t* flags, const uint64_t* name_hash, const uint8_t* hp, int64_t n_reads,
+                     int64_t lo, int64_t hi);
+/* a pointer into `pileup` (valid until the next hello_pileup_* call on it) and its element count */
+int hello_pileup_array(hello_pileup* pileup, int32_t which, const void** data, int64_t* count);
+/* stats[HELLO_PILEUP_STATS]: reads given, belonging, counting, counting reads with an observation, observations, sites, sites /
+ * reads kernel ms (HIP events) */
+int hello_pileup_stats(const hello_pileup* pileup, double* stats);
+void hello_pileup_free(hello_pileup* pileup);
+/* out[HELLO_CONTAM_OUT]: the error rate, k of the greatest likelihood, k_lo, k_hi, LL[HELLO_CONTAM_GRID] */
+int hello_contam_estimate(const int64_t* r, const int64_t* a, const int64_t* o, const double* af, int64_t n, double* out);
+/* out[2]: LOD, the number of sites used */
+int hello_contam_identity(const int64_t* r1, const int64_t* a1, const int64_t* o1, const int64_t* r2, const int64_t* a2,
+                          const int64_t* o2, const double* af, int64_t n, double* out);
+
 #ifdef __cplusplus
 }
 #endif
