@@ -17,19 +17,17 @@ from __future__ import annotations
 import argparse
 import ctypes as C
 import gzip
-import io
 import logging
 import os
 import sys
-import time
-import zipfile
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from ._abi import ARRAY_GETTER, READS, STATS_GETTER, bind, check, handle_array, handle_stats, i32, i64, vp
-from .bam import BamFile, Reads
+from ._abi import ARRAY_GETTER, READS, STATS_GETTER, bind, check, i32, i64, vp
+from .bam import Reads
 from .gvcf import _bytes_of, counted
+from .spans import Handle, measure_spans, save_tables
 
 BINS = ("A", "C", "G", "T", "OTHER", "DEL", "LOWQ")         # the bins of COUNTS [n_sites, 2 strands, 7]
 A, C_, G, T, OTHER, DEL, LOWQ = range(7)
@@ -332,15 +330,17 @@ def identity_native(r1, a1, o1, r2, a2, o2, af) -> Tuple[float, int]:
     return float(out[0]), int(out[1])
 
 
-class Pileup:
+class Pileup(Handle):
     """One (BAM, chromosome)'s ``hello_pileup`` handle: ``add`` takes the reads overlapping a span, ``arrays`` gives COUNTS and the
     STATUS of the last ``add``.  ``form``: TWO_PHASE (the default) or PLAIN; ``share``: the counting reads of a workgroup of the
     reads kernel, 1 to MAX_SHARE, or 0 (the default: every ``add`` sizes it) -- the same bytes whatever they are."""
+    NAME, STAT_NAMES, TIMES = "pileup", STAT_NAMES, STAT_NAMES[len(COUNT_NAMES):]
+    ARRAYS = (("COUNTS", 0, np.int64, (-1, 2, 7)), ("STATUS", 1, np.uint8, None))
 
     def __init__(self, pos, length: int, q_threshold: int = 10, mapq_threshold: int = 10, device: int = 0, form: int = TWO_PHASE,
                  share: int = 0):
         pos = _i64(pos)
-        self._lib, self._h = _lib(), C.c_void_p()
+        super().__init__(_lib())
         check(self._lib.hello_pileup_create(pos.ctypes.data, int(pos.shape[0]), int(length), int(q_threshold), int(mapq_threshold),
                                             int(device), C.byref(self._h)))
         try:
@@ -354,24 +354,6 @@ class Pileup:
 
     def add(self, reads: Reads, lo: int, hi: int) -> None:
         check(self._lib.hello_pileup_add(self._h, *reads.pointers(reads.hp), int(reads.n_reads), int(lo), int(hi)))
-
-    def arrays(self) -> Dict[str, np.ndarray]:
-        get = lambda which, dtype: handle_array(self._lib.hello_pileup_array, self._h, which, dtype)      # noqa: E731
-        return dict(COUNTS=get(0, np.int64).reshape(-1, 2, 7), STATUS=get(1, np.uint8))
-
-    def stats(self) -> Dict[str, float]:
-        return handle_stats(self._lib.hello_pileup_stats, self._h, STAT_NAMES)
-
-    def close(self) -> None:
-        if self._h:
-            self._lib.hello_pileup_free(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
 
 def counted_on_gpu(spans: Sequence[Tuple[Reads, int, int]], pos, length: int, q_threshold: int = 10, mapq_threshold: int = 10,
@@ -446,12 +428,7 @@ class Contamination:
         for i, c in enumerate(names):
             for name, a in self.tables[c].items():
                 out["%s_%d" % (name, i)] = a
-        with zipfile.ZipFile(path, "w", zipfile.ZIP_STORED) as z:           # np.savez's layout with a fixed time stamp: the same
-            for name, a in out.items():                                     # tables give the same bytes
-                data = io.BytesIO()
-                np.lib.format.write_array(data, np.asanyarray(a), allow_pickle=False)
-                z.writestr(zipfile.ZipInfo(name + ".npy", date_time=(1980, 1, 1, 0, 0, 0)), data.getvalue())
-        return path
+        return save_tables(path, out)
 
     @classmethod
     def load(cls, path: str, native: bool = True) -> "Contamination":
@@ -497,54 +474,12 @@ def measure(bam: str, fasta, chromosomes: Optional[Sequence[str]], sites: Sites,
     {chromosome: sequence}; ``restatement``: from the plain-Python rules instead of the GPU and the library.  ``stats``: the library's
     kernel times and the seconds of decoding (``decode_s``), of the library's calls (``device_s``) and of the whole pass
     (``total_s``) are added."""
-    from .hotspots import MAX_LAUNCH_BASES
-    if isinstance(fasta, str):
-        from .call import read_fasta
-        genome = read_fasta(fasta, chromosomes)
-    else:
-        genome = fasta
-    step = int(max_span or MAX_LAUNCH_BASES)
-    add = (lambda k, v: stats.__setitem__(k, stats.get(k, 0.0) + v)) if stats is not None else (lambda k, v: None)
     out = Contamination(sites, native=not restatement)
-    t_all = time.perf_counter()
-    with BamFile(bam) as handle:
-        known = dict(handle.references)
-        for c in (chromosomes or list(genome)):
-            if c not in genome or c not in known:
-                raise ValueError(f"no sequence named {c!r} in the " + ("BAM header" if c in genome else "reference"))
-            length = len(genome[c])
-            if length != known[c]:
-                raise ValueError(f"{c}: {length} bases in the reference, {known[c]} in the BAM header")
-            site = sites.per_chromosome[c]
-            spans = []
-            t0 = time.perf_counter()
-            pileup = None if restatement else Pileup(site["POS"], length, q_threshold, mapq_threshold, device, form, share)
-            add("device_s", time.perf_counter() - t0)
-            try:
-                for lo in range(0, length, step):
-                    hi = min(lo + step, length)
-                    t0 = time.perf_counter()
-                    rd = handle.fetch(c, lo, hi)
-                    t1 = time.perf_counter()
-                    if restatement:
-                        spans.append((rd, lo, hi))
-                    else:
-                        pileup.add(rd, lo, hi)
-                    add("decode_s", t1 - t0)
-                    add("device_s", time.perf_counter() - t1)
-                t0 = time.perf_counter()
-                if restatement:
-                    tables, counts = restated(spans, site["POS"], length, q_threshold, mapq_threshold)
-                else:
-                    tables, counts = pileup.arrays(), pileup.stats()
-                    for k in STAT_NAMES[len(COUNT_NAMES):]:
-                        add(k, counts[k])
-                add("device_s", time.perf_counter() - t0)
-            finally:
-                if pileup is not None:
-                    pileup.close()
-            out.set(c, site, tables["COUNTS"], counts)
-    add("total_s", time.perf_counter() - t_all)
+    at = sites.per_chromosome
+    measure_spans(bam, fasta, chromosomes, max_span, stats, restatement,
+                  open_handle=lambda c, ref: Pileup(at[c]["POS"], ref.shape[0], q_threshold, mapq_threshold, device, form, share),
+                  restated=lambda c, ref, spans: restated(spans, at[c]["POS"], ref.shape[0], q_threshold, mapq_threshold),
+                  done=lambda c, ref, tables, counts: out.set(c, at[c], tables["COUNTS"], counts))
     return out
 
 

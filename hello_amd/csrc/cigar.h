@@ -1,5 +1,6 @@
 // What the host knows about a set of decoded BAM reads before a kernel may index with them: the CIGAR constants, the read filters
-// and the validating walks of the BAM-side stages (two that they share, the duplicate marker's and the quality metrics').  Plain C++17 -- no HIP, no kernel -- so the walks also build into a
+// and the validating walks of the BAM-side stages (strict_walk, counted_walk, and exact_walk under the duplicate marker's, the
+// quality metrics', the methylation's and the pileup's).  Plain C++17 -- no HIP, no kernel -- so the walks also build into a
 // stand-alone host program (tests/abi/cigar_check.cpp).  Refusals are thrown as Fail; the entry points turn them into a status.
 #pragma once
 #include <algorithm>
@@ -28,7 +29,8 @@ struct Fail {
     throw Fail{code, buf};
 }
 
-constexpr int BAM_CMATCH = 0, BAM_CINS = 1, BAM_CDEL = 2, BAM_CREF_SKIP = 3, BAM_CSOFT_CLIP = 4, BAM_CEQUAL = 7, BAM_CDIFF = 8;
+constexpr int BAM_CMATCH = 0, BAM_CINS = 1, BAM_CDEL = 2, BAM_CREF_SKIP = 3, BAM_CSOFT_CLIP = 4, BAM_CHARD_CLIP = 5, BAM_CPAD = 6,
+              BAM_CEQUAL = 7, BAM_CDIFF = 8;
 
 inline bool is_query_op(int op) { return op == 0 || op == 1 || op == 4 || op == 7 || op == 8; }
 inline bool is_ref_op(int op) { return op == 0 || op == 2 || op == 3 || op == 7 || op == 8; }
@@ -155,32 +157,62 @@ inline bool counted_walk(const ReadsView& s, int64_t r, int mapq_threshold, int6
     return true;
 }
 
+// Where a read set begins and how read r follows read r - 1: the offsets start at 0 and do not decrease, and (`sorted`) the reads
+// are in coordinate order.
+inline void check_read_order(const ReadsView& s, int64_t r, bool sorted) {
+    if (r == 0 && (s.read_off[0] != 0 || s.cigar_off[0] != 0)) raise(HELLO_ERR_ARG, "offsets do not start at 0");
+    if (s.read_off[r + 1] < s.read_off[r] || s.cigar_off[r + 1] < s.cigar_off[r])
+        raise(HELLO_ERR_ARG, "read %lld: offsets decrease", (long long)r);
+    if (sorted && r > 0 && s.ref_start[r] < s.ref_start[r - 1])
+        raise(HELLO_ERR_ARG, "read %lld: reads are not coordinate-sorted (the BAM must be)", (long long)r);
+}
+
+// What a kernel that walks read r's CIGAR over its bases relies on: known operations, a CIGAR that consumes exactly the read's
+// bases and ends where ref_end says.  -> the query and reference length and whether an operation is a hard clip.
+struct ExactWalk {
+    int64_t qlen = 0, rlen = 0;
+    bool hard_clipped = false;
+};
+inline ExactWalk exact_walk(const ReadsView& s, int64_t r) {
+    ExactWalk w;
+    for (int64_t c = s.cigar_off[r]; c < s.cigar_off[r + 1]; ++c) {
+        const int op = s.cigars[c] & 15;
+        const int64_t len = s.cigars[c] >> 4;
+        if (op > 8) raise(HELLO_ERR_ARG, "read %lld: CIGAR operation %d", (long long)r, op);
+        if (op == BAM_CHARD_CLIP) w.hard_clipped = true;
+        if (is_query_op(op)) w.qlen += len;
+        if (is_ref_op(op)) w.rlen += len;
+    }
+    if (w.qlen != s.read_off[r + 1] - s.read_off[r])
+        raise(HELLO_ERR_ARG, "read %lld: CIGAR query length %lld, %lld bases", (long long)r, (long long)w.qlen,
+              (long long)(s.read_off[r + 1] - s.read_off[r]));
+    if (s.ref_end[r] != s.ref_start[r] + std::max<int64_t>(w.rlen, 1))
+        raise(HELLO_ERR_ARG, "read %lld: ref_end does not match its CIGAR", (long long)r);
+    return w;
+}
+
+// exact_walk for a read of a span-wise stage, which also needs the read to start on the reference and to have at most
+// `max_bases` bases.
+inline ExactWalk exact_walk_on_reference(const ReadsView& s, int64_t r, int64_t max_bases) {
+    if (s.ref_start[r] < 0) raise(HELLO_ERR_ARG, "read %lld: ref_start %lld", (long long)r, (long long)s.ref_start[r]);
+    const ExactWalk w = exact_walk(s, r);
+    if (w.qlen > max_bases)
+        raise(HELLO_ERR_ARG, "read %lld: %lld bases, at most %lld", (long long)r, (long long)w.qlen, (long long)max_bases);
+    return w;
+}
+
 // The reads that take part in duplicate marking: mapped, primary, not a duplicate already; mapq, QC-fail and
 // the pairing flags do not matter.
 inline bool markdup_eligible(uint16_t flag) { return !(flag & (0x4 | 0x100 | 0x800 | 0x400)); }
 
-// The walk of the duplicate marker: every read's offsets and, for an eligible read, what the ends kernel relies on -- known
-// operations, a CIGAR that consumes exactly the read's bases and ends where ref_end says.  -> the eligible reads, in input order.
+// The walk of the duplicate marker: every read's offsets and, for an eligible read, what the ends kernel relies on (exact_walk).
+// -> the eligible reads, in input order.
 inline std::vector<int64_t> markdup_walk(const ReadsView& s) {
     std::vector<int64_t> list;
-    if (s.n > 0 && (s.read_off[0] != 0 || s.cigar_off[0] != 0)) raise(HELLO_ERR_ARG, "offsets do not start at 0");
     for (int64_t r = 0; r < s.n; ++r) {
-        if (s.read_off[r + 1] < s.read_off[r] || s.cigar_off[r + 1] < s.cigar_off[r])
-            raise(HELLO_ERR_ARG, "read %lld: offsets decrease", (long long)r);
+        check_read_order(s, r, false);
         if (!markdup_eligible(s.flags[r])) continue;
-        int64_t qlen = 0, rlen = 0;
-        for (int64_t c = s.cigar_off[r]; c < s.cigar_off[r + 1]; ++c) {
-            const int op = s.cigars[c] & 15;
-            const int64_t len = s.cigars[c] >> 4;
-            if (op > 8) raise(HELLO_ERR_ARG, "read %lld: CIGAR operation %d", (long long)r, op);
-            if (is_query_op(op)) qlen += len;
-            if (is_ref_op(op)) rlen += len;
-        }
-        if (qlen != s.read_off[r + 1] - s.read_off[r])
-            raise(HELLO_ERR_ARG, "read %lld: CIGAR query length %lld, %lld bases", (long long)r, (long long)qlen,
-                  (long long)(s.read_off[r + 1] - s.read_off[r]));
-        if (s.ref_end[r] != s.ref_start[r] + std::max<int64_t>(rlen, 1))
-            raise(HELLO_ERR_ARG, "read %lld: ref_end does not match its CIGAR", (long long)r);
+        exact_walk(s, r);
         list.push_back(r);
     }
     return list;
@@ -195,76 +227,34 @@ constexpr uint8_t kQcBelongs = 1, kQcMeasured = 2, kQcCounted = 4;
 constexpr int64_t kQcMaxReadBases = (int64_t(1) << 31) / 255;      // a read's qualities sum below 2^31
 
 // The walk of the quality metrics over the reads overlapping a span that starts at `lo`: every read's offsets and order and, for a
-// measured or counted read, what the kernels rely on -- a start on the reference, known operations, a CIGAR that consumes exactly
-// the read's bases and ends where ref_end says, and a quality sum that fits an int32.  -> per read kQcBelongs | kQcMeasured |
-// kQcCounted.
+// measured or counted read, what the kernels rely on (exact_walk_on_reference; the bound keeps a quality sum inside an int32).
+// -> per read kQcBelongs | kQcMeasured | kQcCounted.
 inline std::vector<uint8_t> qc_walk(const ReadsView& s, int64_t lo, int mapq_threshold) {
     std::vector<uint8_t> kind((size_t)s.n, 0);
-    if (s.n > 0 && (s.read_off[0] != 0 || s.cigar_off[0] != 0)) raise(HELLO_ERR_ARG, "offsets do not start at 0");
     for (int64_t r = 0; r < s.n; ++r) {
-        if (s.read_off[r + 1] < s.read_off[r] || s.cigar_off[r + 1] < s.cigar_off[r])
-            raise(HELLO_ERR_ARG, "read %lld: offsets decrease", (long long)r);
-        if (r > 0 && s.ref_start[r] < s.ref_start[r - 1])
-            raise(HELLO_ERR_ARG, "read %lld: reads are not coordinate-sorted (the BAM must be)", (long long)r);
+        check_read_order(s, r, true);
         uint8_t k = s.ref_start[r] >= lo ? kQcBelongs : 0;
         if (qc_measured(s.flags[r])) k |= kQcMeasured;
         if (counted(s.flags[r], s.mapq[r], mapq_threshold)) k |= kQcCounted;
         kind[(size_t)r] = k;
-        if (!(k & (kQcMeasured | kQcCounted))) continue;
-        if (s.ref_start[r] < 0) raise(HELLO_ERR_ARG, "read %lld: ref_start %lld", (long long)r, (long long)s.ref_start[r]);
-        int64_t qlen = 0, rlen = 0;
-        for (int64_t c = s.cigar_off[r]; c < s.cigar_off[r + 1]; ++c) {
-            const int op = s.cigars[c] & 15;
-            const int64_t len = s.cigars[c] >> 4;
-            if (op > 8) raise(HELLO_ERR_ARG, "read %lld: CIGAR operation %d", (long long)r, op);
-            if (is_query_op(op)) qlen += len;
-            if (is_ref_op(op)) rlen += len;
-        }
-        if (qlen != s.read_off[r + 1] - s.read_off[r])
-            raise(HELLO_ERR_ARG, "read %lld: CIGAR query length %lld, %lld bases", (long long)r, (long long)qlen,
-                  (long long)(s.read_off[r + 1] - s.read_off[r]));
-        if (s.ref_end[r] != s.ref_start[r] + std::max<int64_t>(rlen, 1))
-            raise(HELLO_ERR_ARG, "read %lld: ref_end does not match its CIGAR", (long long)r);
-        if (qlen > kQcMaxReadBases)
-            raise(HELLO_ERR_ARG, "read %lld: %lld bases, at most %lld", (long long)r, (long long)qlen, (long long)kQcMaxReadBases);
+        if (k & (kQcMeasured | kQcCounted)) exact_walk_on_reference(s, r, kQcMaxReadBases);
     }
     return kind;
 }
 
-constexpr int BAM_CHARD_CLIP = 5;
 constexpr uint8_t kMethBelongs = 1, kMethCounted = 2, kMethHardClipped = 4;
 constexpr int64_t kMethMaxReads = (int64_t(1) << 31) / 255;        // counting reads of one handle: its 32-bit sums stay below 2^31
 
 // The walk of the methylation stage over the reads overlapping a span that starts at `lo`: every read's
-// offsets and order and, for a counted read, what the kernels rely on -- a start on the reference, known operations, a CIGAR that
-// consumes exactly the read's bases and ends where ref_end says.  -> per read kMethBelongs | kMethCounted | kMethHardClipped.
+// offsets and order and, for a counted read, what the kernels rely on (exact_walk_on_reference).  -> per read kMethBelongs |
+// kMethCounted | kMethHardClipped.
 inline std::vector<uint8_t> meth_walk(const ReadsView& s, int64_t lo, int mapq_threshold) {
     std::vector<uint8_t> kind((size_t)s.n, 0);
-    if (s.n > 0 && (s.read_off[0] != 0 || s.cigar_off[0] != 0)) raise(HELLO_ERR_ARG, "offsets do not start at 0");
     for (int64_t r = 0; r < s.n; ++r) {
-        if (s.read_off[r + 1] < s.read_off[r] || s.cigar_off[r + 1] < s.cigar_off[r])
-            raise(HELLO_ERR_ARG, "read %lld: offsets decrease", (long long)r);
-        if (r > 0 && s.ref_start[r] < s.ref_start[r - 1])
-            raise(HELLO_ERR_ARG, "read %lld: reads are not coordinate-sorted (the BAM must be)", (long long)r);
+        check_read_order(s, r, true);
         uint8_t k = s.ref_start[r] >= lo ? kMethBelongs : 0;
-        if (!counted(s.flags[r], s.mapq[r], mapq_threshold)) { kind[(size_t)r] = k; continue; }
-        k |= kMethCounted;
-        if (s.ref_start[r] < 0) raise(HELLO_ERR_ARG, "read %lld: ref_start %lld", (long long)r, (long long)s.ref_start[r]);
-        int64_t qlen = 0, rlen = 0;
-        for (int64_t c = s.cigar_off[r]; c < s.cigar_off[r + 1]; ++c) {
-            const int op = s.cigars[c] & 15;
-            const int64_t len = s.cigars[c] >> 4;
-            if (op > 8) raise(HELLO_ERR_ARG, "read %lld: CIGAR operation %d", (long long)r, op);
-            if (op == BAM_CHARD_CLIP) k |= kMethHardClipped;
-            if (is_query_op(op)) qlen += len;
-            if (is_ref_op(op)) rlen += len;
-        }
-        if (qlen != s.read_off[r + 1] - s.read_off[r])
-            raise(HELLO_ERR_ARG, "read %lld: CIGAR query length %lld, %lld bases", (long long)r, (long long)qlen,
-                  (long long)(s.read_off[r + 1] - s.read_off[r]));
-        if (s.ref_end[r] != s.ref_start[r] + std::max<int64_t>(rlen, 1))
-            raise(HELLO_ERR_ARG, "read %lld: ref_end does not match its CIGAR", (long long)r);
-        if (qlen > INT32_MAX) raise(HELLO_ERR_ARG, "read %lld: %lld bases, at most %d", (long long)r, (long long)qlen, INT32_MAX);
+        if (counted(s.flags[r], s.mapq[r], mapq_threshold))
+            k |= kMethCounted | (exact_walk_on_reference(s, r, INT32_MAX).hard_clipped ? kMethHardClipped : 0);
         kind[(size_t)r] = k;
     }
     return kind;

@@ -5,29 +5,28 @@
 // Host: the classes of the reads and the validation of every counted read (cigar.h: meth_walk) and of the modification arrays
 // (mods.h: mods_walk) -- the kernels index with both -- and the scratch slices of the reads whose targets do not fit in LDS.
 // Device, once per handle, three kernels over the reference:
-//   flag: a wave per 64 positions; the ballot of "C here, G next" is the word of the site bit vector, its popcount the word's count.
-//   scan: one workgroup walks the word counts 1 024 at a time with a carry -> the sites before every word.  The rank of a site
-//     at p is before[p >> 6] + popcount(bits[p >> 6] & below(p)).
+//   flag: a wave per 64 positions; the ballot of "C here, G next" is the word of the site bit vector (site_bits.h).
+//   scan: site_bits.h's, over the words' popcounts -> the sites before every word, which give a site its rank.
 //   compact: a wave per word writes the positions of its set bits to SITES at their ranks.
 // and per hello_meth_add one kernel, a workgroup per kMethChunkReads candidate reads, a wave per read:
 //   step 1: the candidate bytes of the read ('C', or 'G' for a reverse read) are summed with ballots; the deltas are prefix-summed
 //     64 at a time with a carry into the targets t_k = k + delta_0 + .. + delta_k (LDS, or the read's scratch slice); the read is
 //     refused into its status byte when t_last is no candidate.
-//   step 2: the CIGAR operation by operation (wave-uniform loop) with the lanes on an operation's bases, as refblocks_kernel walks
-//     it.  Over every query-consuming operation the wave keeps the running count of candidates; a candidate lane inside M / = / X
+//   step 2: the CIGAR operation by operation (wave-uniform loop) with the lanes on an operation's bases (read_walk.h: the decoder).
+//     Over every query-consuming operation the wave keeps the running count of candidates; a candidate lane inside M / = / X
 //     looks up the site bit at its position, binary-searches its ordinal in the targets and adds to the site's nine counters.
 // Every output is an integer sum, so no result depends on the order of the atomic adds: two runs give the same bytes.
 #include <memory>
 
 #include "mods.h"
-#include "stage_host.h"
+#include "read_walk.h"
+#include "site_bits.h"
 
 namespace hello {
 namespace {
 
 constexpr int kMethThreads = 256;
 constexpr int kMethWaves = kMethThreads / 64;
-constexpr int kMethScanThreads = 1024;
 constexpr int kMethShare = 1024;             // targets of a wave's read in LDS; a read that lists more has a scratch slice
 constexpr int kMethChunkReads = 4;           // reads per workgroup: a wave each, so that 2 000 long reads fill the chip
 constexpr int kMethCounters = 9;             // [class][counter]
@@ -36,7 +35,6 @@ struct MethSitesArgs {
     const uint8_t* ref;
     int64_t length, n_words;
     unsigned long long* bits;    // [n_words]
-    int* count;                  // [n_words]
     int* before;                 // [n_words + 1]
     int64_t* sites;              // [n_sites]
 };
@@ -48,36 +46,7 @@ __global__ __launch_bounds__(kMethThreads) void meth_flag_kernel(MethSitesArgs a
     const int64_t p = w * 64 + lane;
     const bool site = p + 1 < a.length && (a.ref[p] & 0xDF) == 'C' && (a.ref[p + 1] & 0xDF) == 'G';
     const unsigned long long b = __ballot(site);
-    if (lane == 0) {
-        a.bits[w] = b;
-        a.count[w] = __popcll(b);
-    }
-}
-
-__global__ __launch_bounds__(kMethScanThreads) void meth_scan_kernel(MethSitesArgs a) {
-    __shared__ int wave_sum[kMethScanThreads / 64];
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    int carry = 0;                                                        // below 2^30: a site takes two positions
-    for (int64_t base = 0; base < a.n_words; base += kMethScanThreads) {
-        const int64_t i = base + tid;
-        const int v = i < a.n_words ? a.count[i] : 0;
-        int s = v;
-        for (int d = 1; d < 64; d <<= 1) {
-            const int t = __shfl_up(s, d, 64);
-            if (lane >= d) s += t;
-        }
-        if (lane == 63) wave_sum[wave] = s;
-        __syncthreads();
-        int pre = 0, total = 0;
-        for (int k = 0; k < kMethScanThreads / 64; ++k) {
-            if (k < wave) pre += wave_sum[k];
-            total += wave_sum[k];
-        }
-        if (i < a.n_words) a.before[i] = carry + pre + s - v;
-        carry += total;
-        __syncthreads();
-    }
-    if (tid == 0) a.before[a.n_words] = carry;
+    if (lane == 0) a.bits[w] = b;
 }
 
 __global__ __launch_bounds__(kMethThreads) void meth_compact_kernel(MethSitesArgs a) {
@@ -105,9 +74,7 @@ struct MethReadsArgs {
     int32_t* scratch;
     uint8_t* refused;            // [n_list]: 1 when the last listed base is no candidate of the read
     int64_t n_list;
-    const unsigned long long* bits;
-    const int* before;
-    int64_t length, n_words;
+    SiteBits sb;                 // the CpG sites
     unsigned* counts;            // [n_sites][3][3]
     unsigned long long* observations;
 };
@@ -163,22 +130,21 @@ __global__ __launch_bounds__(kMethThreads) void meth_reads_kernel(MethReadsArgs 
         int64_t rf = a.ref_start[r];
         int rd = 0, running = 0, n_obs = 0;
         for (int64_t ci = 0; ci < n_ops; ++ci) {
-            const unsigned c = a.cigars[c0 + ci];
-            const int op = c & 15u, n = (int)(c >> 4);
-            const bool m = op == BAM_CMATCH || op == BAM_CEQUAL || op == BAM_CDIFF;
-            if (m || op == BAM_CINS || op == BAM_CSOFT_CLIP) {
+            const CigarOp o = decode_op(a.cigars[c0 + ci]);
+            const int n = o.n;
+            if (o.on_read()) {
                 for (int j0 = 0; j0 < n; j0 += 64) {
                     const int j = j0 + lane;
                     const bool is_candidate = j < n && bases[rd + j] == candidate;       // rd + n <= len: meth_walk
                     const unsigned long long all = __ballot(is_candidate);
                     bool observed = false;
-                    if (m && is_candidate) {
+                    if (o.m && is_candidate) {
                         const int from_left = running + __popcll(all & below);
                         const int ordinal = reverse ? total - 1 - from_left : from_left;
                         const int64_t pos = rf + j, p = reverse ? pos - 1 : pos;
-                        if (pos < a.length && p >= 0) {
-                            const unsigned long long w = a.bits[p >> 6];
-                            if ((w >> (p & 63)) & 1ull) {
+                        if (pos < a.sb.length && p >= 0) {
+                            const unsigned long long w = a.sb.word(p);
+                            if (SiteBits::has(w, p)) {
                                 int x = 0, y = n_targets;                     // the first target at or above the ordinal
                                 while (x < y) {
                                     const int mid = (x + y) >> 1;
@@ -188,7 +154,7 @@ __global__ __launch_bounds__(kMethThreads) void meth_reads_kernel(MethReadsArgs 
                                 if (is_listed || !unknown) {
                                     observed = true;
                                     const int v = is_listed ? a.probs[m0 + x] : 0;
-                                    const int rank = a.before[p >> 6] + __popcll(w & ((1ull << (p & 63)) - 1ull));
+                                    const int rank = a.sb.rank(w, p);
                                     const int counter = v >= 128 ? 0 : 1;
                                     for (int which = 0; which <= cls; which += cls ? cls : 1) {
                                         unsigned* e = a.counts + (int64_t)rank * kMethCounters + which * 3;
@@ -200,11 +166,11 @@ __global__ __launch_bounds__(kMethThreads) void meth_reads_kernel(MethReadsArgs 
                         }
                     }
                     n_obs += __popcll(__ballot(observed));
-                    running += __popcll(all);
+                    running += __popcll(all);                             // over every operation that consumes the read
                 }
                 rd += n;
-                if (m) rf += n;
-            } else if (op == BAM_CDEL || op == BAM_CREF_SKIP) {
+                if (o.m) rf += n;
+            } else if (o.op == BAM_CDEL || o.op == BAM_CREF_SKIP) {
                 rf += n;
             }
         }
@@ -215,19 +181,14 @@ __global__ __launch_bounds__(kMethThreads) void meth_reads_kernel(MethReadsArgs 
 }  // namespace
 }  // namespace hello
 
-struct hello_meth {
-    int device = 0;
+struct hello_meth : hello::SpanHandle<HELLO_METH_STATS> {
     int32_t mapq_threshold = 0;
-    int64_t reference_length = 0, n_words = 0, n_sites = 0, last_hi = 0, counting_given = 0;
-    hello::DevMem mem;                           // bits, before and counts live as long as the handle
-    const unsigned long long* bits = nullptr;
-    const int* before = nullptr;
-    unsigned* counts = nullptr;
-    std::vector<int64_t> sites, host_counts;
-    std::vector<uint8_t> status;
-    bool counts_fetched = false, built = false;
+    hello::DevMem mem;                           // bits and before live as long as the handle
+    hello::SiteBits sb{};
+    hello::CountTable counts;                    // [n_sites][3][3]
+    std::vector<int64_t> sites;
+    bool built = false;
     std::vector<uint8_t> reference;              // until the device side is built
-    double stats[HELLO_METH_STATS] = {0};
 };
 
 extern "C" {
@@ -241,36 +202,29 @@ static void meth_build_sites(hello_meth* h) {
     MethSitesArgs a{};
     DevMem keep, m;                              // m: what only the site kernels need
     a.ref = m.put(h->reference.data(), h->reference.size());
-    a.length = h->reference_length;
-    a.n_words = h->n_words;
-    a.bits = keep.room<unsigned long long>((size_t)h->n_words);
-    a.count = m.room<int>((size_t)h->n_words);
-    a.before = keep.room<int>((size_t)h->n_words + 1);
-    const unsigned blocks = (unsigned)((h->n_words + kMethWaves - 1) / kMethWaves);
+    a.length = h->length;
+    a.n_words = (h->length + 63) / 64;
+    a.bits = keep.room<unsigned long long>((size_t)a.n_words);
+    a.before = keep.room<int>((size_t)a.n_words + 1);
+    const unsigned blocks = (unsigned)((a.n_words + kMethWaves - 1) / kMethWaves);
     KernelTimer timer;
+    float ms = 0.0f;
     timer.start();
     if (blocks) hipLaunchKernelGGL(meth_flag_kernel, dim3(blocks), dim3(kMethThreads), 0, 0, a);
-    hipLaunchKernelGGL(meth_scan_kernel, dim3(1), dim3(kMethScanThreads), 0, 0, a);
-    float ms = timer.stop();
-    int n_sites = 0;
-    HS_HIP(hipMemcpy(&n_sites, a.before + h->n_words, sizeof(int), hipMemcpyDeviceToHost));
+    const int n_sites = build_scan(timer, a.bits, a.before, a.n_words, ms);
     a.sites = m.room<int64_t>((size_t)n_sites);
     timer.start();
     if (blocks) hipLaunchKernelGGL(meth_compact_kernel, dim3(blocks), dim3(kMethThreads), 0, 0, a);
     ms += timer.stop();
     std::vector<int64_t> sites((size_t)n_sites);
     if (n_sites) HS_HIP(hipMemcpy(sites.data(), a.sites, (size_t)n_sites * sizeof(int64_t), hipMemcpyDeviceToHost));
-    unsigned* counts = keep.zeros<unsigned>((size_t)n_sites * kMethCounters);
-    std::vector<int64_t> host_counts((size_t)n_sites * kMethCounters, 0);
+    CountTable counts;
+    counts.build((size_t)n_sites * kMethCounters);
     // ---- nothing can fail from here on
     h->mem.ptrs.swap(keep.ptrs);
-    h->bits = a.bits;
-    h->before = a.before;
-    h->counts = counts;
-    h->n_sites = n_sites;
+    h->sb = SiteBits{a.bits, a.before, a.length, a.n_words};
+    h->counts.swap(counts);
     h->sites.swap(sites);
-    h->host_counts.swap(host_counts);
-    h->counts_fetched = true;
     std::vector<uint8_t>().swap(h->reference);
     h->stats[7] = (double)n_sites;
     h->stats[8] = ms;
@@ -287,8 +241,7 @@ int hello_meth_create(const uint8_t* reference, int64_t reference_length, int32_
     std::unique_ptr<hello_meth> h(new hello_meth());
     h->device = device;
     h->mapq_threshold = mapq_threshold;
-    h->reference_length = reference_length;
-    h->n_words = (reference_length + 63) / 64;
+    h->length = reference_length;
     h->reference.assign(reference, reference + reference_length);
     *handle = h.release();
     return HELLO_OK;
@@ -305,12 +258,7 @@ int hello_meth_add(hello_meth* h, const uint8_t* bases, const uint8_t* quals, co
         !mapq || !flags || !hp || !mode || !state)) || (n_deltas > 0 && (!deltas || !probs)))
         return set_last_error(HELLO_ERR_ARG, "NULL pointer");
     if (n_reads < 0) return set_last_error(HELLO_ERR_ARG, "negative count");
-    if (lo < 0 || hi <= lo || hi > h->reference_length)
-        return set_last_error(HELLO_ERR_ARG, "span [%lld, %lld) of a reference of %lld bases", (long long)lo, (long long)hi,
-                              (long long)h->reference_length);
-    if (lo < h->last_hi)
-        return set_last_error(HELLO_ERR_ARG, "span [%lld, %lld) begins below %lld, where the previous one ended", (long long)lo,
-                              (long long)hi, (long long)h->last_hi);
+    h->check_span(lo, hi);
 
     // ---- the reads and their modifications: validated, then the kernel's list and the scratch slices
     const ReadsView in{bases, quals, read_offsets, cigars, cigar_offsets, ref_starts, ref_ends, mapq, flags, name_hash, n_reads};
@@ -335,8 +283,7 @@ int hello_meth_add(hello_meth* h, const uint8_t* bases, const uint8_t* quals, co
         if (n_t > kMethShare) n_scratch += n_t;
     }
     const int64_t n_list = (int64_t)list.size();
-    if (h->counting_given + n_list > kMethMaxReads)
-        return set_last_error(HELLO_ERR_ARG, "more than %lld counting reads in one handle: its sums are 32-bit", (long long)kMethMaxReads);
+    h->take_counting(n_list, kMethMaxReads, "sums");
     const int64_t n_blocks = (n_list + kMethChunkReads - 1) / kMethChunkReads;
 
     meth_build_sites(h);
@@ -360,15 +307,14 @@ int hello_meth_add(hello_meth* h, const uint8_t* bases, const uint8_t* quals, co
         a.scratch = m.room<int32_t>((size_t)n_scratch);
         a.refused = m.zeros<uint8_t>((size_t)n_list);
         a.n_list = n_list;
-        a.bits = h->bits; a.before = h->before;
-        a.length = h->reference_length; a.n_words = h->n_words;
-        a.counts = h->counts;
+        a.sb = h->sb;
+        a.counts = h->counts.device;
         a.observations = m.zeros<unsigned long long>(1);
         KernelTimer timer;
         timer.start();
         hipLaunchKernelGGL(meth_reads_kernel, dim3((unsigned)n_blocks), dim3(kMethThreads), 0, 0, a);
         reads_ms = timer.stop();
-        h->counts_fetched = false;
+        h->counts.fetched = false;
         HS_HIP(hipMemcpy(refused.data(), a.refused, (size_t)n_list, hipMemcpyDeviceToHost));
         HS_HIP(hipMemcpy(&observations, a.observations, sizeof(observations), hipMemcpyDeviceToHost));
     }
@@ -399,15 +345,7 @@ int hello_meth_array(hello_meth* h, int32_t which, const void** data, int64_t* c
     if (which == HELLO_METH_SITES || which == HELLO_METH_COUNTS) meth_build_sites(h);
     switch (which) {
         case HELLO_METH_SITES: *data = h->sites.data(); *count = (int64_t)h->sites.size(); break;
-        case HELLO_METH_COUNTS:
-            if (!h->counts_fetched) {
-                HS_HIP(hipSetDevice(h->device));
-                std::vector<unsigned> got(h->host_counts.size());
-                if (!got.empty()) HS_HIP(hipMemcpy(got.data(), h->counts, got.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
-                std::copy(got.begin(), got.end(), h->host_counts.begin());
-                h->counts_fetched = true;
-            }
-            *data = h->host_counts.data(); *count = (int64_t)h->host_counts.size(); break;
+        case HELLO_METH_COUNTS: *data = h->counts.fetch(h->device).data(); *count = (int64_t)h->counts.host.size(); break;
         case HELLO_METH_STATUS: *data = h->status.data(); *count = (int64_t)h->status.size(); break;
         default: return set_last_error(HELLO_ERR_ARG, "array selector %d", which);
     }
@@ -416,8 +354,7 @@ int hello_meth_array(hello_meth* h, int32_t which, const void** data, int64_t* c
 
 int hello_meth_stats(const hello_meth* h, double* stats) {
     if (!h || !stats) return hello::set_last_error(HELLO_ERR_ARG, "NULL pointer");
-    std::copy(h->stats, h->stats + HELLO_METH_STATS, stats);
-    return HELLO_OK;
+    return h->copy_stats(stats);
 }
 
 void hello_meth_free(hello_meth* h) { delete h; }

@@ -5,28 +5,28 @@
 // Host: the classes of the reads and the validation of every counted read (cigar.h: pileup_walk) -- the kernels index with it.
 // Device, once per handle, two kernels over the uploaded positions:
 //   set:  a lane per site ORs its bit into the 64-position word of the site bit vector.
-//   scan: one workgroup walks the words' popcounts 1 024 at a time with a carry -> the sites before every word.  The positions
-//     ascend, so the rank of the site at p, before[p >> 6] + popcount(bits[p >> 6] & below(p)), is its index in the list.
+//   scan: site_bits.h's, over the words' popcounts -> the sites before every word.  The positions ascend, so the rank of the
+//     site at p (SiteBits::rank) is its index in the list.
 // and per hello_pileup_add one kernel, a workgroup per `share` counting reads (at most kPileShare; sized for kPileGroups workgroups):
 //   phase 1, a lane per read: the words of the bit vector under [ref_start, ref_end) are ORed, two to four for a short read; the
 //     reads that cover a site are compacted into LDS with ballots and popcounts.  A site list is sparse and most short reads cover
 //     none, so most reads end here without their CIGAR being read.
 //   phase 2, a wave per surviving read: the CIGAR operation by operation (wave-uniform loop) with the lanes on an operation's
-//     bases, as refblocks_kernel walks it.  A lane in M / = / X / D tests its position's bit and on a hit adds 1 to
+//     bases (read_walk.h: the decoder).  A lane in M / = / X / D tests its position's bit and on a hit adds 1 to
 //     COUNTS[rank][strand][bin] in global memory.
 //   The plain form (HELLO_PILEUP_FORM 1) skips phase 1: every counting read is walked.  Section 7n has both measured.
 // Every output is an integer sum, so no result depends on the order of the atomic adds: two runs give the same bytes.
 #include <memory>
 
 #include "contam.h"
-#include "stage_host.h"
+#include "read_walk.h"
+#include "site_bits.h"
 
 namespace hello {
 namespace {
 
 constexpr int kPileThreads = 256;
 constexpr int kPileWaves = kPileThreads / 64;
-constexpr int kPileScanThreads = 1024;
 constexpr int kPileShare = 1024;             // the most counting reads of a workgroup: rounds of phase 1, then its four waves share phase 2
 constexpr int kPileGroups = 4096;            // the share of a launch is sized for about so many workgroups: 2 000 long reads get a
                                              // wave each, 200 000 short ones 49 to a workgroup, a chromosome's 50 M the whole 1 024
@@ -47,33 +47,6 @@ __global__ __launch_bounds__(kPileThreads) void pile_set_kernel(PileSitesArgs a)
     atomicOr(a.bits + (p >> 6), 1ull << (p & 63));
 }
 
-// methylation.hip's scan, over the popcounts of the words.
-__global__ __launch_bounds__(kPileScanThreads) void pile_scan_kernel(PileSitesArgs a) {
-    __shared__ int wave_sum[kPileScanThreads / 64];
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    int carry = 0;                                                        // at most n_sites, below 2^31
-    for (int64_t base = 0; base < a.n_words; base += kPileScanThreads) {
-        const int64_t i = base + tid;
-        const int v = i < a.n_words ? __popcll(a.bits[i]) : 0;
-        int s = v;
-        for (int d = 1; d < 64; d <<= 1) {
-            const int t = __shfl_up(s, d, 64);
-            if (lane >= d) s += t;
-        }
-        if (lane == 63) wave_sum[wave] = s;
-        __syncthreads();
-        int pre = 0, total = 0;
-        for (int k = 0; k < kPileScanThreads / 64; ++k) {
-            if (k < wave) pre += wave_sum[k];
-            total += wave_sum[k];
-        }
-        if (i < a.n_words) a.before[i] = carry + pre + s - v;
-        carry += total;
-        __syncthreads();
-    }
-    if (tid == 0) a.before[a.n_words] = carry;
-}
-
 struct PileReadsArgs {
     const uint8_t* bases;
     const uint8_t* quals;
@@ -86,27 +59,11 @@ struct PileReadsArgs {
     const int64_t* list;         // [n_list]: the belonging counted reads, in input order
     uint8_t* seen;               // [n_list], zeroed: 1 when the read made an observation
     int64_t n_list;
-    const unsigned long long* bits;
-    const int* before;
-    int64_t length, n_words;
+    SiteBits sb;                 // the sites given
     int q_threshold, share;      // share: the counting reads of a workgroup, 1 .. kPileShare
     unsigned* counts;            // [n_sites][2][7]
     unsigned long long* group_obs;   // [workgroups]: the observations of each
 };
-
-// Whether a word of the bit vector under [s, e) has a bit inside it; e <= length, so every word exists.
-__device__ inline bool pile_covers(const unsigned long long* bits, int64_t s, int64_t e) {
-    if (s >= e) return false;
-    const int64_t w0 = s >> 6, w1 = (e - 1) >> 6;
-    unsigned long long any = 0;
-    for (int64_t w = w0; w <= w1; ++w) {
-        unsigned long long b = bits[w];
-        if (w == w0) b &= ~0ull << (s & 63);
-        if (w == w1 && ((e & 63) != 0)) b &= (1ull << (e & 63)) - 1ull;
-        any |= b;
-    }
-    return any != 0;
-}
 
 // Integer adds of 1 straight to the global table: a read meets few sites, so there is nothing for a workgroup to combine.
 template <bool kTwoPhase>
@@ -127,8 +84,8 @@ __global__ __launch_bounds__(kPileThreads) void pile_reads_kernel(PileReadsArgs 
             bool hit = false;
             if (i < n_mine) {
                 const int64_t r = a.list[k_lo + i];
-                const int64_t e = a.ref_end[r] < a.length ? a.ref_end[r] : a.length;
-                hit = pile_covers(a.bits, a.ref_start[r], e);
+                const int64_t e = a.ref_end[r] < a.sb.length ? a.ref_end[r] : a.sb.length;
+                hit = a.sb.any_in(a.ref_start[r], e);
             }
             const unsigned long long b = __ballot(hit);
             if (lane == 0) wave_count[wave] = __popcll(b);
@@ -155,24 +112,23 @@ __global__ __launch_bounds__(kPileThreads) void pile_reads_kernel(PileReadsArgs 
         int64_t rf = a.ref_start[r], rd = 0;
         int n_obs = 0;
         for (int64_t ci = 0; ci < n_ops; ++ci) {
-            const unsigned c = a.cigars[c0 + ci];
-            const int op = c & 15u, n = (int)(c >> 4);
-            const bool m = op == BAM_CMATCH || op == BAM_CEQUAL || op == BAM_CDIFF;
-            if (m || op == BAM_CDEL) {
+            const CigarOp o = decode_op(a.cigars[c0 + ci]);
+            const int n = o.n;
+            if (o.m || o.op == BAM_CDEL) {
                 for (int j0 = 0; j0 < n; j0 += 64) {
                     const int j = j0 + lane;
                     const int64_t p = rf + j;                                 // rf >= 0: pileup_walk
                     bool observed = false;
-                    if (j < n && p < a.length) {
-                        const unsigned long long w = a.bits[p >> 6];
-                        if ((w >> (p & 63)) & 1ull) {
+                    if (j < n && p < a.sb.length) {
+                        const unsigned long long w = a.sb.word(p);
+                        if (SiteBits::has(w, p)) {
                             int bin = kBinDel;
-                            if (m) {                                          // rd + n <= the read's bases: pileup_walk
+                            if (o.m) {                                        // rd + n <= the read's bases: pileup_walk
                                 const int b = a.bases[q0 + rd + j] & 0xDF;
                                 bin = a.quals[q0 + rd + j] < a.q_threshold ? kBinLowq
                                       : b == 'A' ? 0 : b == 'C' ? 1 : b == 'G' ? 2 : b == 'T' ? 3 : kBinOther;
                             }
-                            const int64_t rank = a.before[p >> 6] + __popcll(w & ((1ull << (p & 63)) - 1ull));
+                            const int64_t rank = a.sb.rank(w, p);
                             atomicAdd(a.counts + (rank * 2 + strand) * kPileBins + bin, 1u);
                             observed = true;
                         }
@@ -180,10 +136,10 @@ __global__ __launch_bounds__(kPileThreads) void pile_reads_kernel(PileReadsArgs 
                     n_obs += __popcll(__ballot(observed));
                 }
                 rf += n;
-                if (m) rd += n;
-            } else if (op == BAM_CINS || op == BAM_CSOFT_CLIP) {
+                if (o.m) rd += n;
+            } else if (o.op == BAM_CINS || o.op == BAM_CSOFT_CLIP) {
                 rd += n;
-            } else if (op == BAM_CREF_SKIP) {
+            } else if (o.op == BAM_CREF_SKIP) {
                 rf += n;
             }
         }
@@ -203,18 +159,15 @@ __global__ __launch_bounds__(kPileThreads) void pile_reads_kernel(PileReadsArgs 
 }  // namespace
 }  // namespace hello
 
-struct hello_pileup {
-    int device = 0, form = 0, share = 0;         // share 0: sized by the launch
+struct hello_pileup : hello::SpanHandle<HELLO_PILEUP_STATS> {
+    int form = 0, share = 0;                     // share 0: sized by the launch
     int32_t q_threshold = 0, mapq_threshold = 0;
-    int64_t length = 0, n_words = 0, n_sites = 0, last_hi = 0, counting_given = 0;
-    hello::DevMem mem;                           // bits, before and counts live as long as the handle
-    const unsigned long long* bits = nullptr;
-    const int* before = nullptr;
-    unsigned* counts = nullptr;
-    std::vector<int64_t> pos, host_counts;
-    std::vector<uint8_t> status;
-    bool counts_fetched = true, built = false;
-    double stats[HELLO_PILEUP_STATS] = {0};
+    int64_t n_sites = 0;
+    hello::DevMem mem;                           // bits and before live as long as the handle
+    hello::SiteBits sb{};
+    hello::CountTable counts;                    // [n_sites][2][7]
+    std::vector<int64_t> pos;                    // until the device side is built
+    bool built = false;
 };
 
 extern "C" {
@@ -228,21 +181,21 @@ static void pile_build_sites(hello_pileup* h) {
     DevMem keep, m;
     a.pos = m.put(h->pos.data(), h->pos.size());
     a.n_sites = h->n_sites;
-    a.n_words = h->n_words;
-    a.bits = keep.zeros<unsigned long long>((size_t)h->n_words);
-    a.before = keep.room<int>((size_t)h->n_words + 1);
-    unsigned* counts = keep.zeros<unsigned>((size_t)h->n_sites * 2 * kPileBins);
+    a.n_words = (h->length + 63) / 64;
+    a.bits = keep.zeros<unsigned long long>((size_t)a.n_words);
+    a.before = keep.room<int>((size_t)a.n_words + 1);
+    CountTable counts;
+    counts.build((size_t)h->n_sites * 2 * kPileBins);
     const unsigned blocks = (unsigned)((h->n_sites + kPileThreads - 1) / kPileThreads);
     KernelTimer timer;
+    float ms = 0.0f;
     timer.start();
     if (blocks) hipLaunchKernelGGL(pile_set_kernel, dim3(blocks), dim3(kPileThreads), 0, 0, a);
-    hipLaunchKernelGGL(pile_scan_kernel, dim3(1), dim3(kPileScanThreads), 0, 0, a);
-    const float ms = timer.stop();
+    build_scan(timer, a.bits, a.before, a.n_words, ms);                // -> n_sites: the positions ascend strictly
     // ---- nothing can fail from here on
     h->mem.ptrs.swap(keep.ptrs);
-    h->bits = a.bits;
-    h->before = a.before;
-    h->counts = counts;
+    h->sb = SiteBits{a.bits, a.before, h->length, a.n_words};
+    h->counts.swap(counts);
     std::vector<int64_t>().swap(h->pos);
     h->stats[6] = ms;
     h->built = true;
@@ -269,10 +222,8 @@ int hello_pileup_create(const int64_t* pos, int64_t n_sites, int64_t chromosome_
     h->q_threshold = q_threshold;
     h->mapq_threshold = mapq_threshold;
     h->length = chromosome_length;
-    h->n_words = (chromosome_length + 63) / 64;
     h->n_sites = n_sites;
     h->pos.assign(pos, pos + n_sites);
-    h->host_counts.assign((size_t)n_sites * 2 * kPileBins, 0);
     h->stats[5] = (double)n_sites;
     *handle = h.release();
     return HELLO_OK;
@@ -299,12 +250,7 @@ int hello_pileup_add(hello_pileup* h, const uint8_t* bases, const uint8_t* quals
     if (!h || !read_offsets || !cigar_offsets || (n_reads > 0 && (!bases || !quals || !cigars || !ref_starts || !ref_ends || !mapq || !flags)))
         return set_last_error(HELLO_ERR_ARG, "NULL pointer");
     if (n_reads < 0) return set_last_error(HELLO_ERR_ARG, "negative count");
-    if (lo < 0 || hi <= lo || hi > h->length)
-        return set_last_error(HELLO_ERR_ARG, "span [%lld, %lld) of a reference of %lld bases", (long long)lo, (long long)hi,
-                              (long long)h->length);
-    if (lo < h->last_hi)
-        return set_last_error(HELLO_ERR_ARG, "span [%lld, %lld) begins below %lld, where the previous one ended", (long long)lo,
-                              (long long)hi, (long long)h->last_hi);
+    h->check_span(lo, hi);
 
     // ---- the reads: validated, then the kernel's list
     const ReadsView in{bases, quals, read_offsets, cigars, cigar_offsets, ref_starts, ref_ends, mapq, flags, name_hash, n_reads};
@@ -317,8 +263,7 @@ int hello_pileup_add(hello_pileup* h, const uint8_t* bases, const uint8_t* quals
         if (kind[(size_t)r] & kPileCounted) list.push_back(r);
     }
     const int64_t n_list = (int64_t)list.size();
-    if (h->counting_given + n_list > kPileMaxReads)
-        return set_last_error(HELLO_ERR_ARG, "more than %lld counting reads in one handle: its counters are 32-bit", (long long)kPileMaxReads);
+    h->take_counting(n_list, kPileMaxReads, "counters");
     const int64_t share = h->share ? h->share : std::min<int64_t>(kPileShare, std::max<int64_t>(kPileWaves, (n_list + kPileGroups - 1) / kPileGroups));
     const int64_t n_blocks = (n_list + share - 1) / share;
 
@@ -338,18 +283,17 @@ int hello_pileup_add(hello_pileup* h, const uint8_t* bases, const uint8_t* quals
         a.list = m.put(list.data(), list.size());
         a.seen = m.zeros<uint8_t>((size_t)n_list);
         a.n_list = n_list;
-        a.bits = h->bits; a.before = h->before;
-        a.length = h->length; a.n_words = h->n_words;
+        a.sb = h->sb;
         a.q_threshold = h->q_threshold;
         a.share = (int)share;
-        a.counts = h->counts;
+        a.counts = h->counts.device;
         a.group_obs = m.room<unsigned long long>((size_t)n_blocks);
         KernelTimer timer;
         timer.start();
         if (h->form == 0) hipLaunchKernelGGL(pile_reads_kernel<true>, dim3((unsigned)n_blocks), dim3(kPileThreads), 0, 0, a);
         else hipLaunchKernelGGL(pile_reads_kernel<false>, dim3((unsigned)n_blocks), dim3(kPileThreads), 0, 0, a);
         reads_ms = timer.stop();
-        h->counts_fetched = false;
+        h->counts.fetched = false;
         HS_HIP(hipMemcpy(seen.data(), a.seen, (size_t)n_list, hipMemcpyDeviceToHost));
         HS_HIP(hipMemcpy(group_obs.data(), a.group_obs, (size_t)n_blocks * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     }
@@ -381,14 +325,7 @@ int hello_pileup_array(hello_pileup* h, int32_t which, const void** data, int64_
     switch (which) {
         case HELLO_PILEUP_COUNTS:
             pile_build_sites(h);
-            if (!h->counts_fetched) {
-                HS_HIP(hipSetDevice(h->device));
-                std::vector<unsigned> got(h->host_counts.size());
-                if (!got.empty()) HS_HIP(hipMemcpy(got.data(), h->counts, got.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
-                std::copy(got.begin(), got.end(), h->host_counts.begin());
-                h->counts_fetched = true;
-            }
-            *data = h->host_counts.data(); *count = (int64_t)h->host_counts.size(); break;
+            *data = h->counts.fetch(h->device).data(); *count = (int64_t)h->counts.host.size(); break;
         case HELLO_PILEUP_STATUS: *data = h->status.data(); *count = (int64_t)h->status.size(); break;
         default: return set_last_error(HELLO_ERR_ARG, "array selector %d", which);
     }
@@ -397,8 +334,7 @@ int hello_pileup_array(hello_pileup* h, int32_t which, const void** data, int64_
 
 int hello_pileup_stats(const hello_pileup* h, double* stats) {
     if (!h || !stats) return hello::set_last_error(HELLO_ERR_ARG, "NULL pointer");
-    std::copy(h->stats, h->stats + HELLO_PILEUP_STATS, stats);
-    return HELLO_OK;
+    return h->copy_stats(stats);
 }
 
 void hello_pileup_free(hello_pileup* h) { delete h; }

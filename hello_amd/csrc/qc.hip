@@ -20,6 +20,7 @@
 #include <memory>
 
 #include "phase_pair.h"
+#include "read_walk.h"
 #include "stage_host.h"
 
 namespace hello {
@@ -113,10 +114,10 @@ __global__ __launch_bounds__(kQcThreads) void qc_reads_kernel(QcReadsArgs a) {
         int rd = 0;
         bool past = false;
         for (int64_t ci = 0; ci < n_ops; ++ci) {
-            const unsigned c = a.cigars[c0 + ci];
-            const int op = c & 15u, n = (int)(c >> 4);
-            const bool m = op == BAM_CMATCH || op == BAM_CEQUAL || op == BAM_CDIFF;
-            if (m || op == BAM_CINS || op == BAM_CSOFT_CLIP) {
+            const CigarOp o = decode_op(a.cigars[c0 + ci]);
+            const int op = o.op, n = o.n;
+            const bool m = o.m;
+            if (o.on_read()) {
                 const int field = m ? F_ALIGNED : op == BAM_CINS ? F_INSERTED : F_SOFT;
                 for (int j0 = 0; j0 < n; j0 += 64) {
                     const int j = j0 + lane;
@@ -358,12 +359,7 @@ int hello_qc_add(const uint8_t* bases, const uint8_t* quals, const int64_t* read
     hello_qc* h = *handle;
     if (h && h->finished) return set_last_error(HELLO_ERR_ARG, "reads cannot be added after hello_qc_finish");
     if (h && device != h->device) return set_last_error(HELLO_ERR_ARG, "a further call names another device than the first");
-    if (lo < 0 || hi <= lo || hi > reference_length)
-        return set_last_error(HELLO_ERR_ARG, "span [%lld, %lld) of a reference of %lld bases", (long long)lo, (long long)hi,
-                              (long long)reference_length);
-    if (h && lo < h->last_hi)
-        return set_last_error(HELLO_ERR_ARG, "span [%lld, %lld) begins below %lld, where the previous one ended", (long long)lo,
-                              (long long)hi, (long long)h->last_hi);
+    check_span(lo, hi, reference_length, h ? h->last_hi : 0);
     if (window < 1) return set_last_error(HELLO_ERR_ARG, "window %lld: at least 1", (long long)window);
     for (int64_t i = 0; i < n_targets; ++i)
         if (target_starts[i] < 0 || target_starts[i] >= target_stops[i] || (i > 0 && target_starts[i] < target_stops[i - 1]))

@@ -31,7 +31,6 @@ constexpr int kRbTile = 1024;
 constexpr int kRbThreads = 256;
 constexpr int kRbPer = kRbTile / kRbThreads;
 constexpr int kRbExcluded = -2;            // key of a position that belongs to no block
-constexpr int BAM_CPAD = 6;
 
 struct RbRun {
     int64_t start, end;

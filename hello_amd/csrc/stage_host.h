@@ -1,5 +1,6 @@
 // The HIP host layer under the BAM-side stages (hotspots.hip, candidates.hip, refblocks.hip, phase.hip, haplotag.hip, markdup.hip): opening the device,
-// owned device memory, the upload of a read set, timing a launch, and the tail of an entry point.  No kernel lives here.
+// owned device memory, the upload of a read set, timing a launch, the tail of an entry point, and what a handle that takes a
+// chromosome span after span keeps (SpanHandle, CountTable).  No kernel lives here.
 #pragma once
 #include <utility>
 
@@ -105,7 +106,62 @@ struct KernelTimer {               // HIP events around a launch on the default 
     KernelTimer& operator=(const KernelTimer&) = delete;
 };
 
-struct PairHash {                                                  // (name hash, strand): a read pair's two mates stay distinct
+// What a handle that takes a chromosome's reads span after span keeps (hello_meth, hello_pileup; hello_qc shares check_span).
+inline void check_span(int64_t lo, int64_t hi, int64_t length, int64_t last_hi) {
+    if (lo < 0 || hi <= lo || hi > length)
+        raise(HELLO_ERR_ARG, "span [%lld, %lld) of a reference of %lld bases", (long long)lo, (long long)hi, (long long)length);
+    if (lo < last_hi)
+        raise(HELLO_ERR_ARG, "span [%lld, %lld) begins below %lld, where the previous one ended", (long long)lo, (long long)hi,
+              (long long)last_hi);
+}
+
+template <int kStats> struct SpanHandle {
+    int device = 0;
+    int64_t length = 0, last_hi = 0, counting_given = 0;
+    std::vector<uint8_t> status;                 // of the last add, per read
+    double stats[kStats] = {0};
+    void check_span(int64_t lo, int64_t hi) const { hello::check_span(lo, hi, length, last_hi); }
+    // n more counting reads: refused past `cap`, which keeps the handle's 32-bit `what` from overflowing.  The add that has passed
+    // all its checks commits them to counting_given itself.
+    void take_counting(int64_t n, int64_t cap, const char* what) const {
+        if (counting_given + n > cap)
+            raise(HELLO_ERR_ARG, "more than %lld counting reads in one handle: its %s are 32-bit", (long long)cap, what);
+    }
+    int copy_stats(double* out) const {
+        std::copy(stats, stats + kStats, out);
+        return HELLO_OK;
+    }
+};
+
+// A table of 32-bit counters the kernels add to, and its 64-bit copy on the host, fetched when asked for after a launch.
+struct CountTable {
+    DevMem mem;
+    unsigned* device = nullptr;
+    std::vector<int64_t> host;
+    bool fetched = true;
+    void build(size_t n) {                                         // zeros on both sides
+        device = mem.zeros<unsigned>(n);
+        host.assign(n, 0);
+    }
+    void swap(CountTable& o) {
+        mem.ptrs.swap(o.mem.ptrs);
+        std::swap(device, o.device);
+        host.swap(o.host);
+        std::swap(fetched, o.fetched);
+    }
+    const std::vector<int64_t>& fetch(int on_device) {
+        if (!fetched) {
+            HS_HIP(hipSetDevice(on_device));
+            std::vector<unsigned> got(host.size());
+            if (!got.empty()) HS_HIP(hipMemcpy(got.data(), device, got.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
+            std::copy(got.begin(), got.end(), host.begin());
+            fetched = true;
+        }
+        return host;
+    }
+};
+
+struct PairHash {                                                // (name hash, strand): a read pair's two mates stay distinct
     size_t operator()(const std::pair<uint64_t, int>& k) const { return (size_t)(k.first * 0x9E3779B97F4A7C15ull) ^ (size_t)k.second; }
 };
 

@@ -289,9 +289,9 @@ def chromosome_blocks(handles: Sequence[BamFile], chromosome: str, reference, ex
                       mapq_threshold: int, gq_binsize: int, device: int = 0, restatement: bool = False,
                       max_span: Optional[int] = None, stats: Optional[dict] = None) -> Blocks:
     """The blocks of one whole chromosome: one call per span of at most ``max_span`` positions, joined at the span boundaries."""
-    from .hotspots import MAX_LAUNCH_BASES
+    from .spans import adder, span_step
     ref = _bytes_of(reference)
-    length, step = int(ref.shape[0]), int(max_span or MAX_LAUNCH_BASES)
+    length, step, add = int(ref.shape[0]), span_step(max_span), adder(stats)
     parts = []
     for lo in range(0, length, step):
         hi = min(lo + step, length)
@@ -304,17 +304,15 @@ def chromosome_blocks(handles: Sequence[BamFile], chromosome: str, reference, ex
             blocks, st = blocks_of(n_ref, n_total, inside, gq_binsize, lo), {}
         else:
             blocks, st, _ = find_blocks(sets, ref, lo, hi, inside, q_threshold, mapq_threshold, gq_binsize, device=device)
-        if stats is not None:
-            stats["decode_s"] = stats.get("decode_s", 0.0) + (t1 - t0)
-            stats["find_s"] = stats.get("find_s", 0.0) + (time.perf_counter() - t1)
-            stats["calls"] = stats.get("calls", 0) + 1
-            for k, v in st.items():
-                stats[k] = stats.get(k, 0.0) + v
+        add("decode_s", t1 - t0)
+        add("find_s", time.perf_counter() - t1)
+        add("calls", 1)
+        for k, v in st.items():
+            add(k, v)
         parts.append(blocks)
     t0 = time.perf_counter()
     joined = join_blocks(parts)
-    if stats is not None:
-        stats["join_s"] = stats.get("join_s", 0.0) + (time.perf_counter() - t0)
+    add("join_s", time.perf_counter() - t0)
     return joined
 
 

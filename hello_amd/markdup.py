@@ -25,9 +25,10 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import bam as _bam
-from ._abi import ARRAY_GETTER, READS, STATS_GETTER, bind, check, handle_array, handle_stats, i32, i64, vp
+from ._abi import ARRAY_GETTER, READS, STATS_GETTER, bind, check, i32, i64, vp
 from .bam import BamFile, Reads
 from .phase import _from, join_mates
+from .spans import Handle, adder, span_step
 
 NOT_ELIGIBLE = 0x4 | 0x100 | 0x800 | 0x400          # unmapped, secondary, supplementary, a duplicate already
 DUPLICATE = 0x400
@@ -168,13 +169,16 @@ def _lib():
     return bind(_PROTOTYPES)
 
 
-class Deduper:
+class Deduper(Handle):
     """One (BAM, chromosome)'s ``hello_markdup`` handle: ``add`` takes the reads of a span, ``find`` (once, after the last ``add``)
     joins the mates and marks, ``arrays`` gives e, score, mate, kind and duplicate of every read given, in the order given."""
+    NAME, STAT_NAMES = "markdup", STAT_NAMES
+    ARRAYS = (("e", E, np.int64, None), ("score", SCORE, np.int32, None), ("mate", MATE, np.int64, None),
+              ("kind", KIND, np.uint8, None), ("duplicate", DUP, np.uint8, None))
 
     def __init__(self, device: int = 0):
+        super().__init__(_lib())
         self._device = int(device)
-        self._lib, self._h = _lib(), C.c_void_p()
         self._found = False
 
     def add(self, reads: Reads) -> None:
@@ -184,28 +188,8 @@ class Deduper:
         check(self._lib.hello_markdup_find(self._h))
         self._found = True
 
-    def _array(self, which: int, dtype) -> np.ndarray:
-        return handle_array(self._lib.hello_markdup_array, self._h, which, dtype)
-
-    def arrays(self) -> Dict[str, np.ndarray]:
-        out = dict(e=self._array(E, np.int64), score=self._array(SCORE, np.int32))
-        if self._found:
-            out.update(mate=self._array(MATE, np.int64), kind=self._array(KIND, np.uint8), duplicate=self._array(DUP, np.uint8))
-        return out
-
-    def stats(self) -> Dict[str, float]:
-        return handle_stats(self._lib.hello_markdup_stats, self._h, STAT_NAMES)
-
-    def close(self) -> None:
-        if self._h:
-            self._lib.hello_markdup_free(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
+    def _has(self, name: str) -> bool:
+        return name in ("e", "score") or self._found
 
 
 def find_arrays(reads: Reads, device: int = 0) -> Tuple[Dict[str, np.ndarray], Dict[str, float]]:
@@ -309,9 +293,7 @@ def find_duplicates(bam: str, chromosomes: Optional[Sequence[str]] = None, max_s
     """The duplicates of one BAM, chromosome after chromosome (default: every sequence of its header).  ``restatement``: from the
     plain-Python rules instead of the GPU.  ``stats``: the library's statistics and the seconds of decoding (``decode_s``), of the
     kernels' calls (``device_s``), of the host's gather of the identities (``gather_s``) and of the whole pass (``total_s``) are added."""
-    from .hotspots import MAX_LAUNCH_BASES
-    step = int(max_span or MAX_LAUNCH_BASES)
-    add = (lambda k, v: stats.__setitem__(k, stats.get(k, 0.0) + v)) if stats is not None else (lambda k, v: None)
+    step, add = span_step(max_span), adder(stats)
     marks = Marks()
     t_all = time.perf_counter()
     with BamFile(bam) as handle:

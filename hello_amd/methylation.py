@@ -15,18 +15,16 @@ from __future__ import annotations
 
 import argparse
 import ctypes as C
-import io
 import logging
 import sys
-import time
-import zipfile
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from ._abi import ARRAY_GETTER, READS, STATS_GETTER, bind, check, handle_array, handle_stats, i32, i64, vp
-from .bam import BamFile, Mods, Reads
+from ._abi import ARRAY_GETTER, READS, STATS_GETTER, bind, check, i32, i64, vp
+from .bam import Mods, Reads
 from .gvcf import _bytes_of, counted
+from .spans import Handle, measure_spans, save_tables
 
 NONE, USABLE, BAD = 0, 1, 2                                # a read's modification state
 MODIFIED, UNMODIFIED, ML_SUM = range(3)                    # the counters of COUNTS [n_sites, 3, 3]; the classes: all, hap 1, hap 2
@@ -236,37 +234,21 @@ def _lib():
     return bind(_PROTOTYPES)
 
 
-class Counter:
+class Counter(Handle):
     """One (BAM, chromosome)'s ``hello_meth`` handle: creating it flags the CpG sites of ``reference`` on the device, ``add`` takes
     the reads overlapping a span with their modifications, ``arrays`` gives SITES, COUNTS and the STATUS of the last ``add``."""
+    NAME, STAT_NAMES, TIMES = "meth", STAT_NAMES, STAT_NAMES[len(COUNT_NAMES):]
+    ARRAYS = (("SITES", 0, np.int64, None), ("COUNTS", 1, np.int64, (-1, 3, 3)), ("STATUS", 2, np.uint8, None))
 
     def __init__(self, reference, mapq_threshold: int = 10, device: int = 0):
         ref = np.ascontiguousarray(_bytes_of(reference))
-        self._lib, self._h = _lib(), C.c_void_p()
+        super().__init__(_lib())
         check(self._lib.hello_meth_create(ref.ctypes.data, int(ref.shape[0]), int(mapq_threshold), int(device), C.byref(self._h)))
 
     def add(self, reads: Reads, mods: Mods, lo: int, hi: int) -> None:
         check(self._lib.hello_meth_add(self._h, *reads.pointers(reads.hp), int(reads.n_reads), mods.deltas.ctypes.data,
                                        int(mods.deltas.shape[0]), mods.probs.ctypes.data, int(mods.probs.shape[0]),
                                        mods.offsets.ctypes.data, mods.mode.ctypes.data, mods.state.ctypes.data, int(lo), int(hi)))
-
-    def arrays(self) -> Dict[str, np.ndarray]:
-        get = lambda which, dtype: handle_array(self._lib.hello_meth_array, self._h, which, dtype)      # noqa: E731
-        return dict(SITES=get(0, np.int64), COUNTS=get(1, np.int64).reshape(-1, 3, 3), STATUS=get(2, np.uint8))
-
-    def stats(self) -> Dict[str, float]:
-        return handle_stats(self._lib.hello_meth_stats, self._h, STAT_NAMES)
-
-    def close(self) -> None:
-        if self._h:
-            self._lib.hello_meth_free(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
 
 def counted_on_gpu(spans: Sequence[Tuple[Reads, Mods, int, int]], reference, mapq_threshold: int = 10,
@@ -308,12 +290,7 @@ class Methylation:
         for i, c in enumerate(names):
             for name, a in self.tables[c].items():
                 out["%s_%d" % (name, i)] = a
-        with zipfile.ZipFile(path, "w", zipfile.ZIP_STORED) as z:           # np.savez's layout with a fixed time stamp: the same
-            for name, a in out.items():                                     # tables give the same bytes
-                data = io.BytesIO()
-                np.lib.format.write_array(data, np.asanyarray(a), allow_pickle=False)
-                z.writestr(zipfile.ZipInfo(name + ".npy", date_time=(1980, 1, 1, 0, 0, 0)), data.getvalue())
-        return path
+        return save_tables(path, out)
 
     @classmethod
     def load(cls, path: str) -> "Methylation":
@@ -345,55 +322,12 @@ def measure(bam: str, fasta, chromosomes: Optional[Sequence[str]] = None, haplot
     {chromosome: sequence}; ``haplotagger``: its ``retag(chromosome, reads)`` replaces the BAM's own HP; ``restatement``: from the
     plain-Python rules instead of the GPU.  ``stats``: the library's kernel times and the seconds of decoding (``decode_s``), of
     the library's calls (``device_s``) and of the whole pass (``total_s``) are added."""
-    from .hotspots import MAX_LAUNCH_BASES
-    if isinstance(fasta, str):
-        from .call import read_fasta
-        genome = read_fasta(fasta, chromosomes)
-    else:
-        genome = fasta
-    step = int(max_span or MAX_LAUNCH_BASES)
-    add = (lambda k, v: stats.__setitem__(k, stats.get(k, 0.0) + v)) if stats is not None else (lambda k, v: None)
     out = Methylation()
-    t_all = time.perf_counter()
-    with BamFile(bam) as handle:
-        known = dict(handle.references)
-        for c in (chromosomes or list(genome)):
-            if c not in genome or c not in known:
-                raise ValueError(f"no sequence named {c!r} in the " + ("BAM header" if c in genome else "reference"))
-            ref = np.ascontiguousarray(_bytes_of(genome[c]))
-            if ref.shape[0] != known[c]:
-                raise ValueError(f"{c}: {ref.shape[0]} bases in the reference, {known[c]} in the BAM header")
-            spans = []
-            t0 = time.perf_counter()
-            counter = None if restatement else Counter(ref, mapq_threshold, device)
-            add("device_s", time.perf_counter() - t0)
-            try:
-                for lo in range(0, ref.shape[0], step):
-                    hi = min(lo + step, ref.shape[0])
-                    t0 = time.perf_counter()
-                    rd, mods = handle.fetch_with_mods(c, lo, hi)
-                    t1 = time.perf_counter()
-                    if haplotagger is not None:
-                        rd = haplotagger.retag(c, rd)
-                    if restatement:
-                        spans.append((rd, mods, lo, hi))
-                    else:
-                        counter.add(rd, mods, lo, hi)
-                    add("decode_s", t1 - t0)
-                    add("device_s", time.perf_counter() - t1)
-                t0 = time.perf_counter()
-                if restatement:
-                    tables, counts = restated(spans, ref, mapq_threshold)
-                else:
-                    tables, counts = counter.arrays(), counter.stats()
-                    for k in STAT_NAMES[len(COUNT_NAMES):]:
-                        add(k, counts[k])
-                add("device_s", time.perf_counter() - t0)
-            finally:
-                if counter is not None:
-                    counter.close()
-            out.set(c, tables, counts)
-    add("total_s", time.perf_counter() - t_all)
+    measure_spans(bam, fasta, chromosomes, max_span, stats, restatement,
+                  open_handle=lambda c, ref: Counter(ref, mapq_threshold, device),
+                  restated=lambda c, ref, spans: restated(spans, ref, mapq_threshold),
+                  done=lambda c, ref, tables, counts: out.set(c, tables, counts),
+                  with_mods=True, retag=haplotagger.retag if haplotagger is not None else None)
     return out
 
 

@@ -27,9 +27,10 @@ from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
-from ._abi import ARRAY_GETTER, READS, STATS_GETTER, bind, check, handle_array, handle_stats, i32, i64, vp
+from ._abi import ARRAY_GETTER, READS, STATS_GETTER, bind, check, handle_stats, i32, i64, vp
 from .bam import BamFile, Reads
 from .gvcf import counted
+from .spans import Handle, adder, span_step
 
 NONE = -1
 MAX_WINDOW = 32                             # HELLO_PHASE_MAX_WINDOW
@@ -364,11 +365,12 @@ def _lib():
     return bind(_PROTOTYPES)
 
 
-class Phaser:
+class Phaser(Handle):
     """One chromosome's ``hello_phase`` handle: ``observe`` adds a batch of read sets, ``arrays`` gives the slots and the links so
     far, ``tag`` the haplotype of every read given, in the order given.  ``fragments`` (once, after the last ``observe``) joins
     the mates of all batches; ``arrays`` then holds ``mate`` and ``fragment_links`` too, and ``tag(..., fragments=True)`` tags both
     mates of a pair alike."""
+    NAME, STAT_NAMES = "phase", STAT_NAMES
 
     def __init__(self, records: Sequence[Record], q_threshold: int = 10, mapq_threshold: int = 10, window: int = DEFAULT_WINDOW,
                  device: int = 0):
@@ -379,7 +381,10 @@ class Phaser:
         self._alleles = np.frombuffer(b"".join(text), np.uint8)
         self._offsets = np.concatenate([[0], np.cumsum([len(x) for x in text])]).astype(np.int64)
         self._tail = (int(q_threshold), int(mapq_threshold), int(window), int(device))
-        self._lib, self._h = _lib(), C.c_void_p()
+        super().__init__(_lib())
+        shape = (self.n_records, self.window, 2)
+        self.ARRAYS = (("slots", SLOTS, np.int8, None), ("slot_offsets", SLOT_OFFSETS, np.int64, None), ("first", FIRST, np.int64, None),
+                       ("links", LINKS, np.int32, shape), ("mate", MATE, np.int64, None), ("fragment_links", FRAGMENT_LINKS, np.int32, shape))
         self._joined = False
 
     def fragments(self, name_hash, flags, source) -> np.ndarray:
@@ -404,16 +409,8 @@ class Phaser:
         check(self._lib.hello_phase_observe(*r.pointers(source), int(r.n_reads), ptr(self._starts), ptr(self._ends),
                                             ptr(self._alleles), ptr(self._offsets), self.n_records, *self._tail, C.byref(self._h)))
 
-    def _array(self, which: int, dtype) -> np.ndarray:
-        return handle_array(self._lib.hello_phase_array, self._h, which, dtype)
-
-    def arrays(self) -> Dict[str, np.ndarray]:
-        shape = (self.n_records, self.window, 2)
-        out = dict(slots=self._array(SLOTS, np.int8), slot_offsets=self._array(SLOT_OFFSETS, np.int64),
-                   first=self._array(FIRST, np.int64), links=self._array(LINKS, np.int32).reshape(shape))
-        if self._joined:
-            out.update(mate=self._array(MATE, np.int64), fragment_links=self._array(FRAGMENT_LINKS, np.int32).reshape(shape))
-        return out
+    def _has(self, name: str) -> bool:
+        return name not in ("mate", "fragment_links") or self._joined
 
     def tag(self, sets, flip, fragments: bool = False) -> Tuple[np.ndarray, np.ndarray]:
         sets, flip = np.ascontiguousarray(sets, np.int32), np.ascontiguousarray(flip, np.uint8)
@@ -423,19 +420,6 @@ class Phaser:
         check(tag(self._h, sets.ctypes.data, flip.ctypes.data))
         return self._array(HP, np.uint8), self._array(PS, np.int64)
 
-    def stats(self) -> Dict[str, float]:
-        return handle_stats(self._lib.hello_phase_stats, self._h, STAT_NAMES)
-
-    def close(self) -> None:
-        if self._h:
-            self._lib.hello_phase_free(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
 
 def find_observations(reads: Sequence[Reads], records: Sequence[Record], q_threshold: int = 10, mapq_threshold: int = 10,
@@ -518,11 +502,10 @@ def chromosome_phase(handles: Sequence[BamFile], chromosome: str, length: int, r
     """One chromosome: {slots, slot_offsets, first, links, set, flip, hp, ps}; the per-read arrays follow the reads of span after
     span, within a span the BAMs one after the other.  ``fragments`` (section 7i): the mates of a pair are joined across all
     spans -- ``mate`` and ``fragment_links`` are in the result, the chain runs on the fragment links and both mates get one tag."""
-    from .hotspots import MAX_LAUNCH_BASES
-    step, n = int(max_span or MAX_LAUNCH_BASES), len(records)
+    step, n = span_step(max_span), len(records)
     positions = [rec.pos for rec in records]
     _check_sorted(records)
-    add = (lambda k, v: stats.__setitem__(k, stats.get(k, 0.0) + v)) if stats is not None else (lambda k, v: None)
+    add = adder(stats)
     ph = None if restatement else Phaser(records, q_threshold, mapq_threshold, window, device)
     try:
         parts, links = [], np.zeros((n, window, 2), np.int32)

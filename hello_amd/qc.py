@@ -15,20 +15,18 @@ from __future__ import annotations
 
 import argparse
 import ctypes as C
-import io
 import logging
 import math
 import sys
-import time
-import zipfile
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from ._abi import ARRAY_GETTER, READS, STATS_GETTER, bind, check, handle_array, handle_stats, i32, i64, vp
-from .bam import BamFile, Reads
+from ._abi import ARRAY_GETTER, READS, STATS_GETTER, bind, check, i32, i64, vp
+from .bam import Reads
 from .gvcf import _bytes_of, counted
 from .phase import join_mates
+from .spans import Handle, measure_spans, save_tables
 
 NOT_MEASURED = 0x4 | 0x100 | 0x800 | 0x400 | 0x200      # unmapped, secondary, supplementary, duplicate, QC-fail
 FLAG_NAMES = ("reads", "unmapped", "secondary", "supplementary", "duplicate", "qc_fail", "paired", "proper_pair", "read1", "read2",
@@ -244,16 +242,18 @@ def _lib():
     return bind(_PROTOTYPES)
 
 
-class Meter:
+class Meter(Handle):
     """One (BAM, chromosome)'s ``hello_qc`` handle: ``add`` takes the reads overlapping a span, ``finish`` (once, after the last
     ``add``) joins the mates and fills INSERT, ``arrays`` gives the tables by name."""
+    NAME, STAT_NAMES, TIMES = "qc", STAT_NAMES, STAT_NAMES[len(COUNT_NAMES):]
+    ARRAYS = tuple((name, which, np.int64, SHAPES.get(name)) for which, name in enumerate(TABLE_NAMES))
 
     def __init__(self, reference, targets: Targets = (), window: int = DEFAULT_WINDOW, mapq_threshold: int = 10, device: int = 0):
         self._ref = np.ascontiguousarray(_bytes_of(reference))
         t = np.asarray(list(targets), np.int64).reshape(-1, 2)               # the library refuses what check_targets would
         self._starts, self._stops = np.ascontiguousarray(t[:, 0]), np.ascontiguousarray(t[:, 1])
         self._window, self._threshold, self._device = int(window), int(mapq_threshold), int(device)
-        self._lib, self._h = _lib(), C.c_void_p()
+        super().__init__(_lib())
         self._finished = False
 
     def add(self, reads: Reads, lo: int, hi: int) -> None:
@@ -265,27 +265,12 @@ class Meter:
         check(self._lib.hello_qc_finish(self._h))
         self._finished = True
 
-    def arrays(self) -> Dict[str, np.ndarray]:
-        out = {}
-        for which, name in enumerate(TABLE_NAMES):
-            if name != "INSERT" or self._finished:
-                a = handle_array(self._lib.hello_qc_array, self._h, which, np.int64)
-                out[name] = a.reshape(SHAPES[name]) if name in SHAPES else a
-        return out
+    def _has(self, name: str) -> bool:
+        return name != "INSERT" or self._finished
 
-    def stats(self) -> Dict[str, float]:
-        return handle_stats(self._lib.hello_qc_stats, self._h, STAT_NAMES)
-
-    def close(self) -> None:
-        if self._h:
-            self._lib.hello_qc_free(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
+    def results(self):
+        self.finish()
+        return super().results()
 
 
 def metered(spans: Sequence[Tuple[Reads, int, int]], reference, targets: Targets = (), window: int = DEFAULT_WINDOW,
@@ -294,8 +279,7 @@ def metered(spans: Sequence[Tuple[Reads, int, int]], reference, targets: Targets
     with Meter(reference, targets, window, mapq_threshold, device) as meter:
         for reads, lo, hi in spans:
             meter.add(reads, lo, hi)
-        meter.finish()
-        return meter.arrays(), meter.stats()
+        return meter.results()
 
 
 # ------------------------------------------------------------------------------------------------
@@ -392,12 +376,7 @@ class Metrics:
             out["targets_%d" % i] = self.targets[c]
             for name, a in self.tables[c].items():
                 out["%s_%d" % (name, i)] = a
-        with zipfile.ZipFile(path, "w", zipfile.ZIP_STORED) as z:           # np.savez's layout with a fixed time stamp: the same
-            for name, a in out.items():                                     # tables give the same bytes
-                data = io.BytesIO()
-                np.lib.format.write_array(data, np.asanyarray(a), allow_pickle=False)
-                z.writestr(zipfile.ZipInfo(name + ".npy", date_time=(1980, 1, 1, 0, 0, 0)), data.getvalue())
-        return path
+        return save_tables(path, out)
 
     @classmethod
     def load(cls, path: str) -> "Metrics":
@@ -477,55 +456,14 @@ def measure(bam: str, fasta, chromosomes: Optional[Sequence[str]] = None, target
     {chromosome: sequence}; ``targets``: {chromosome: intervals} as ``read_bed`` gives them; ``restatement``: from the plain-Python
     rules instead of the GPU.  ``stats``: the library's kernel times and the seconds of decoding (``decode_s``), of the library's
     calls (``device_s``) and of the whole pass (``total_s``) are added."""
-    from .hotspots import MAX_LAUNCH_BASES
     if window < 1:
         raise ValueError("window: at least 1")
-    if isinstance(fasta, str):
-        from .call import read_fasta
-        genome = read_fasta(fasta, chromosomes)
-    else:
-        genome = fasta
-    step = int(max_span or MAX_LAUNCH_BASES)
-    add = (lambda k, v: stats.__setitem__(k, stats.get(k, 0.0) + v)) if stats is not None else (lambda k, v: None)
     metrics = Metrics(window, targets is not None)
-    t_all = time.perf_counter()
-    with BamFile(bam) as handle:
-        known = dict(handle.references)
-        for c in (chromosomes or list(genome)):
-            if c not in genome or c not in known:
-                raise ValueError(f"no sequence named {c!r} in the " + ("BAM header" if c in genome else "reference"))
-            ref = np.ascontiguousarray(_bytes_of(genome[c]))
-            if ref.shape[0] != known[c]:
-                raise ValueError(f"{c}: {ref.shape[0]} bases in the reference, {known[c]} in the BAM header")
-            mine = check_targets((targets or {}).get(c, ()))
-            spans = []
-            meter = None if restatement else Meter(ref, mine, window, mapq_threshold, device)
-            try:
-                for lo in range(0, ref.shape[0], step):
-                    hi = min(lo + step, ref.shape[0])
-                    t0 = time.perf_counter()
-                    rd = handle.fetch(c, lo, hi)
-                    t1 = time.perf_counter()
-                    if restatement:
-                        spans.append((rd, lo, hi))
-                    else:
-                        meter.add(rd, lo, hi)
-                    add("decode_s", t1 - t0)
-                    add("device_s", time.perf_counter() - t1)
-                t0 = time.perf_counter()
-                if restatement or ref.shape[0] == 0:
-                    tables, counts = restated(spans, ref, mine, window, mapq_threshold)
-                else:
-                    meter.finish()
-                    tables, counts = meter.arrays(), meter.stats()
-                    for k in STAT_NAMES[len(COUNT_NAMES):]:
-                        add(k, counts[k])
-                add("device_s", time.perf_counter() - t0)
-            finally:
-                if meter is not None:
-                    meter.close()
-            metrics.set(c, ref.shape[0], tables, counts, mine)
-    add("total_s", time.perf_counter() - t_all)
+    mine = lambda c: check_targets((targets or {}).get(c, ()))      # noqa: E731
+    measure_spans(bam, fasta, chromosomes, max_span, stats, restatement,       # a chromosome without positions has no add: restated
+                  open_handle=lambda c, ref: Meter(ref, mine(c), window, mapq_threshold, device) if ref.shape[0] else None,
+                  restated=lambda c, ref, spans: restated(spans, ref, mine(c), window, mapq_threshold),
+                  done=lambda c, ref, tables, counts: metrics.set(c, ref.shape[0], tables, counts, mine(c)))
     return metrics
 
 

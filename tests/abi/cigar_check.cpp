@@ -1,4 +1,4 @@
-// The two host read walks of hello_amd/csrc/cigar.h over hand-made read sets, as a stand-alone host program: built by
+// The strict, counted and exact host read walks of hello_amd/csrc/cigar.h over hand-made read sets, as a stand-alone host program: built by
 // tests/test_stage_host.py with -fsanitize=address,undefined and run directly.  Exits non-zero on the first mismatch.
 #include <cstdio>
 #include <cstdlib>
@@ -86,7 +86,24 @@ Counted counted_all(const Set& s, int mapq_threshold) {
     return c;
 }
 
-const std::string kArg = std::to_string(HELLO_ERR_ARG) + " ", kShape = std::to_string(HELLO_ERR_SHAPE) + " ";
+// exact_walk of read r (on the reference with `max_bases` when it is given): (the refusal or "", what it returns)
+std::pair<std::string, ExactWalk> exact(const Set& s, int64_t r, int64_t max_bases = -1) {
+    try {
+        return {"", max_bases < 0 ? exact_walk(s.view(), r) : exact_walk_on_reference(s.view(), r, max_bases)};
+    } catch (const Fail& f) {
+        return {std::to_string(f.code) + " " + f.msg, ExactWalk{}};
+    }
+}
+std::string order(const Set& s, int64_t r, bool sorted) {
+    try {
+        check_read_order(s.view(), r, sorted);
+    } catch (const Fail& f) {
+        return std::to_string(f.code) + " " + f.msg;
+    }
+    return "";
+}
+
+const std::string kArg =std::to_string(HELLO_ERR_ARG) + " ", kShape = std::to_string(HELLO_ERR_SHAPE) + " ";
 
 }  // namespace
 
@@ -184,6 +201,54 @@ int main() {
         ReadLayout out;
         EXPECT(strict(s, kStrictRegions, out) == "" && (out.plant_off == std::vector<int64_t>{0}) && out.plant.empty());
         EXPECT(counted_all(s, 10).refusal == "" && counted_all(s, 10).reads.empty());
+    }
+    {   // exact walk: the lengths of the worked read, and a hard clip seen but consuming nothing
+        Set s;
+        s.add(10, {{3, 'M'}, {2, 'I'}, {4, 'M'}, {1, 'D'}, {5, 'M'}});
+        s.add(11, {{2, 'H'}, {1, 'S'}, {3, '='}, {2, 'N'}, {1, 'P'}, {2, 'X'}, {3, 'H'}});
+        const ExactWalk a = exact(s, 0).second, b = exact(s, 1).second;
+        EXPECT(exact(s, 0).first == "" && a.qlen == 14 && a.rlen == 13 && !a.hard_clipped);
+        EXPECT(exact(s, 1).first == "" && b.qlen == 6 && b.rlen == 7 && b.hard_clipped);
+    }
+    {   // exact walk: an empty CIGAR belongs to a read without bases that ends one past its start
+        Set s;
+        s.add(4, {});
+        const auto e = exact(s, 0);
+        EXPECT(e.first == "" && e.second.qlen == 0 && e.second.rlen == 0 && !e.second.hard_clipped);
+        Set with_bases;
+        with_bases.add(4, {}, 0, 60, 3);
+        EXPECT(exact(with_bases, 0).first == kArg + "read 0: CIGAR query length 0, 3 bases");
+    }
+    {   // exact walk: each refusal once, with HELLO_ERR_ARG; the unknown operation comes before the lengths
+        Set s;
+        s.add(0, {{3, 'M'}, {2, '9'}}, 0, 60, 7);
+        s.add(1, {{5, 'M'}}, 0, 60, 4);
+        s.add(2, {{5, 'M'}}, 0, 60, 6);
+        s.add(3, {{4, 'M'}}, 0, 60, -1, 1);
+        s.add(4, {{4, 'M'}}, 0, 60, -1, -1);
+        EXPECT(exact(s, 0).first == kArg + "read 0: CIGAR operation 9");
+        EXPECT(exact(s, 1).first == kArg + "read 1: CIGAR query length 5, 4 bases");
+        EXPECT(exact(s, 2).first == kArg + "read 2: CIGAR query length 5, 6 bases");
+        EXPECT(exact(s, 3).first == kArg + "read 3: ref_end does not match its CIGAR");
+        EXPECT(exact(s, 4).first == kArg + "read 4: ref_end does not match its CIGAR");
+    }
+    {   // exact walk on the reference: a start below 0 and the bound on the bases
+        Set s;
+        s.add(-1, {{4, 'M'}});
+        s.add(3, {{4, 'M'}});
+        EXPECT(exact(s, 0, 100).first == kArg + "read 0: ref_start -1");
+        EXPECT(exact(s, 1, 4).first == "" && exact(s, 1, 3).first == kArg + "read 1: 4 bases, at most 3");
+    }
+    {   // the order of a read set
+        Set s;
+        s.add(9, {{4, 'M'}});
+        s.add(8, {{4, 'M'}});
+        EXPECT(order(s, 0, true) == "" && order(s, 1, false) == "");
+        EXPECT(order(s, 1, true) == kArg + "read 1: reads are not coordinate-sorted (the BAM must be)");
+        s.read_off[2] = 3;
+        EXPECT(order(s, 1, false) == kArg + "read 1: offsets decrease");
+        s.read_off[0] = 1;
+        EXPECT(order(s, 0, false) == kArg + "offsets do not start at 0");
     }
     if (failures) {
         std::fprintf(stderr, "%d mismatches\n", failures);

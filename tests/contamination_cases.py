@@ -162,6 +162,31 @@ def survivor_launch(k: int, tail: int = 100) -> List[tuple]:
     return hits + misses + rest
 
 
+# ---- the scan's carry: a chromosome of three rounds of the site scan ------------------------------------------------------------
+CARRY_LENGTH = 2 * 65536 + 48                      # 2 049 words: two full rounds of 1 024 words and a third of one word
+CARRY_SPAN = 50000
+CARRY_NAMED = (0, 65535, 65536, 131071, 131072, CARRY_LENGTH - 1)      # the last and first bit of a round, and both ends
+
+
+def carry(seed: int = 23):
+    """-> (reference, sites, rows sorted by position): the named sites and 40 at seeded positions, a read of 20 to 150 bases over
+    every site on alternating strands, and one read across each of the two round edges."""
+    rng = np.random.default_rng(seed)
+    reference = "".join(rng.choice(list("ACGT"), size=CARRY_LENGTH))
+    sites = np.array(sorted(set(CARRY_NAMED) | set(int(p) for p in rng.integers(1, CARRY_LENGTH - 1, size=40))), np.int64)
+    rows: List[tuple] = []
+
+    def add(flag, pos, n):
+        rows.append((len(rows) + 1, flag, pos, [(M, n)], reference[pos:pos + n], q(n), 60))
+    for k, p in enumerate(int(p) for p in sites):
+        n = int(rng.integers(20, 151))
+        add(REV if k % 2 else 0, max(0, min(p - int(rng.integers(0, n)), CARRY_LENGTH - n)), n)
+    add(0, 65536 - 50, 100)
+    add(REV, 131072 - 40, 70)
+    rows.sort(key=lambda r: r[2])
+    return reference, sites, rows
+
+
 # ---- the driver's BAMs: people with genotypes at known sites ---------------------------------------------------------------------
 DRIVER_LENGTH = 20000
 

@@ -247,3 +247,39 @@ def stress(seed: int = 13):
     late.ml = [77]
     rows.sort(key=lambda r: r.pos)
     return reference, rows
+
+
+# ---- the scan's carry: a chromosome of three rounds of the site scan ------------------------------------------------------------
+CARRY_LENGTH = 2 * 65536 + 48                      # 2 049 words: two full rounds of 1 024 words and a third of one word
+CARRY_SPAN = 50000
+# A CpG takes two positions, so of the last bit of a round and the first bit of the next only one can be a site: the first edge has
+# its site on the last bit (65 535) and the next at 65 537, the second on bit 62 (131 070) and on the first bit (131 072).
+CARRY_NAMED = (0, 65535, 65537, 131070, 131072, CARRY_LENGTH - 2)
+
+
+def carry(seed: int = 29):
+    """-> (reference, sites, rows sorted by position): a text without G but for the CG planted at the named sites and at 40 seeded
+    positions, a read of 20 to 150 bases over every site on alternating strands that lists its CpGs, and one read across each of
+    the two round edges."""
+    rng = np.random.default_rng(seed)
+    reference = "".join(rng.choice(list("ACT"), size=CARRY_LENGTH))
+    sites = set(CARRY_NAMED)
+    for p in (int(p) for p in rng.integers(3, CARRY_LENGTH - 4, size=40)):
+        if all(abs(p - s) > 2 for s in sites):
+            sites.add(p)
+    for p in sites:
+        reference = _plant(reference, p, "CG")
+    rows: List[Row] = []
+
+    def add(flag, pos, n):
+        stored, reverse = reference[pos:pos + n], bool(flag & REV)
+        wanted = cpgs_of(stored, reverse)
+        rows.append(Row(flag, pos, [(M, n)], stored, mm_of(stored, reverse, wanted, ("", ".", "?")[len(rows) % 3]),
+                        [int(x) for x in rng.integers(0, 256, size=len(wanted))], len(rows) % 4))
+    for k, p in enumerate(sorted(sites)):
+        n = int(rng.integers(20, 151))
+        add(REV if k % 2 else 0, max(0, min(p - int(rng.integers(0, n - 1)), CARRY_LENGTH - n)), n)      # over p and p + 1
+    add(0, 65536 - 50, 100)
+    add(REV, 131072 - 40, 70)
+    rows.sort(key=lambda r: r.pos)
+    return reference, np.array(sorted(sites), np.int64), rows

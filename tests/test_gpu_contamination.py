@@ -117,6 +117,31 @@ def test_edge_stress_on_one_chromosome():
         assert np.array_equal(p.arrays()["STATUS"], cn.tables_of(reads, sites, cc.LENGTH, 0, cc.LENGTH)["status"])
 
 
+def test_the_site_scan_carries_from_one_round_of_1024_words_into_the_next():
+    """A chromosome of 2 049 words: the scan of csrc/site_bits.h makes two full rounds and a third of one word, with sites on the
+    last bit of a round and on the first bit of the next."""
+    _, sites, rows = cc.carry()
+    L = cc.CARRY_LENGTH
+    assert L == 2 * 65536 + 48 and (L + 63) // 64 == 2 * 1024 + 1 and cc.CARRY_NAMED == (0, 65535, 65536, 131071, 131072, L - 1)
+    assert set(cc.CARRY_NAMED) <= set(sites.tolist()) and sites.shape[0] > 40
+    assert all(20 <= len(r[4]) <= 150 for r in rows) and {r[1] & cc.REV for r in rows} == {0, cc.REV}
+    assert any(r[2] < 65536 < r[2] + len(r[4]) for r in rows) and any(r[2] < 131072 < r[2] + len(r[4]) for r in rows)
+    reads = cc.read_set(rows)
+    cut = [(cc.read_set(cc.overlapping(rows, lo, min(lo + cc.CARRY_SPAN, L))), lo, min(lo + cc.CARRY_SPAN, L))
+           for lo in range(0, L, cc.CARRY_SPAN)]
+    want, counts = cn.restated([(reads, 0, L)], sites, L)
+    for p in cc.CARRY_NAMED:                                              # the restatement alone counts on every named site
+        assert want["COUNTS"][int(np.searchsorted(sites, p))].sum() >= 1, p
+    runs = []
+    for spans in ([(reads, 0, L)], cut, [(reads, 0, L)], cut):
+        for form in FORMS:
+            got, stats = cn.counted_on_gpu(spans, sites, L, form=form)
+            same_counts(got["COUNTS"], want["COUNTS"])
+            assert {k: int(stats[k]) for k in cn.METRIC_STATS} == {k: counts[k] for k in cn.METRIC_STATS}
+            runs.append(got["COUNTS"].tobytes())
+    assert len(set(runs)) == 1
+
+
 @pytest.mark.parametrize("survivors", cc.SURVIVORS)
 def test_phase_1_compacts_exactly_so_many_reads_of_a_workgroups_share(survivors):
     _, sites, _ = cc.stress()

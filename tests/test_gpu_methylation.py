@@ -119,6 +119,31 @@ def test_edge_stress_on_one_chromosome(tmp_path_factory):
     assert st["sites_ms"] > 0 and st["reads_ms"] > 0
 
 
+def test_the_site_scan_carries_from_one_round_of_1024_words_into_the_next():
+    """A chromosome of 2 049 words: the scan of csrc/site_bits.h makes two full rounds and a third of one word.  A CpG takes two
+    positions, so of the two positions at a round edge one is a site (mc.CARRY_NAMED)."""
+    reference, sites, rows = mc.carry()
+    L = mc.CARRY_LENGTH
+    assert L == 2 * 65536 + 48 and (L + 63) // 64 == 2 * 1024 + 1 and np.array_equal(me.sites_of(reference), sites)
+    assert set(mc.CARRY_NAMED) <= set(sites.tolist()) and sites[0] == 0 and sites[-1] == L - 2 and sites.shape[0] > 40
+    assert [p >> 6 for p in mc.CARRY_NAMED] == [0, 1023, 1024, 2047, 2048, 2048] and 65535 % 64 == 63 and 131072 % 64 == 0
+    assert all(20 <= len(r.bases) <= 150 for r in rows) and {r.flag & mc.REV for r in rows} == {0, mc.REV}
+    assert any(r.pos < 65536 < r.end for r in rows) and any(r.pos < 131072 < r.end for r in rows)        # a read across each edge
+    reads, mods = mc.read_set(rows)
+    cut = [mc.read_set(mc.overlapping(rows, lo, min(lo + mc.CARRY_SPAN, L))) + (lo, min(lo + mc.CARRY_SPAN, L))
+           for lo in range(0, L, mc.CARRY_SPAN)]
+    want, counts = me.restated([(reads, mods, 0, L)], reference)
+    for p in mc.CARRY_NAMED:                                              # the restatement alone counts on every named site
+        assert want["COUNTS"][int(np.searchsorted(sites, p)), 0, :2].sum() >= 1, p
+    runs = []
+    for spans in ([(reads, mods, 0, L)], cut, [(reads, mods, 0, L)], cut):
+        got, stats = me.counted_on_gpu(spans, reference)
+        assert np.array_equal(got["SITES"], want["SITES"]) and np.array_equal(got["COUNTS"], want["COUNTS"])
+        assert {k: int(stats[k]) for k in me.METRIC_STATS} == {k: counts[k] for k in me.METRIC_STATS}
+        runs.append(got["SITES"].tobytes() + got["COUNTS"].tobytes())
+    assert len(set(runs)) == 1
+
+
 # ---- (4) the driver -------------------------------------------------------------------------------------------------------------
 FILES = ("methylation.combined.bed", "methylation.hap1.bed", "methylation.hap2.bed", "methylation.npz")
 _driver: dict = {}
