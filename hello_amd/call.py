@@ -76,6 +76,14 @@ bases of every BAM of the route at the sites of ``V`` on the GPU after ``results
 (``hello_amd.contamination``), estimates each BAM's contamination and, with two BAMs, whether they hold one
 person, and writes ``<workdir>/contamination.illumina.*`` and / or ``contamination.pacbio.*`` (``txt``, ``pileup.tsv``, ``npz``) and
 ``contamination.identity.txt``.  Under ``--mark_duplicates`` the marked reads leave the pileup.
+
+``--sv`` (with ``--from_bam`` / ``--from_bams``, not in the reference, off by default) finds the deletions and insertions of at least
+``--sv_min_size`` bases that the reads of every BAM of the route carry as one ``D`` or ``I`` operation, on the GPU after
+``results.output.vcf`` is complete (``hello_amd.sv``): left-aligned, clustered (``--sv_cluster_gap``,
+``--sv_len_ratio``, ``--sv_min_support``) and genotyped against the reads that span them (``--sv_flank``).  It writes
+``<workdir>/sv.illumina.*`` and / or ``sv.pacbio.*`` (``vcf`` with symbolic ``<DEL>`` / ``<INS>`` alleles, ``npz``).  A read's haplotype
+comes from ``--haplotag_vcf``, else from the phased VCF of ``--phase``, else from its HP tag; under ``--mark_duplicates`` the marked
+reads leave the pass.  Split alignments, clipped ends and discordant pairs are not looked at.
 """
 from __future__ import annotations
 
@@ -266,6 +274,7 @@ def features_dir_name(ibam: Optional[str], pbam: Optional[str]) -> str:
 
 
 def parser() -> argparse.ArgumentParser:
+    from . import sv
     ap = argparse.ArgumentParser(description="HELLO variant scoring on MI355X, with call.py's command line")
     ap.add_argument("--ibam", help="Illumina BAM file (names the features directory; read by --from_bam / --from_bams)")
     ap.add_argument("--pbam", help="PacBio BAM file (names the features directory; read by --from_bam / --from_bams)")
@@ -347,6 +356,12 @@ def parser() -> argparse.ArgumentParser:
                          "<workdir>/contamination.illumina.* / contamination.pacbio.* (txt, pileup.tsv, npz) and "
                          "contamination.identity.txt (not in the reference; one GPU; DESIGN.md 7n)")
     ap.add_argument("--contamination_sites", help="--contamination: a VCF (plain or .gz) of biallelic SNVs with INFO AF, common ones")
+    ap.add_argument("--sv", action="store_true", default=False,
+                    help="with --from_bam / --from_bams: find the deletions and insertions of at least --sv_min_size bases that the "
+                         "reads of every BAM of the route carry as one D or I operation, on the GPU, and write <workdir>/sv.illumina.* "
+                         "/ sv.pacbio.* (vcf, npz); the haplotypes come from --haplotag_vcf, else --phase, else the HP tags (not in "
+                         "the reference; one GPU; DESIGN.md 7p)")
+    sv.add_options(ap, given_or_none=True)
     ap.add_argument("--device", type=int, default=0, help="GPU of a single-process run")
     ap.add_argument("--gpus", type=int, default=1,
                     help="processes / GPUs of this node: > 1 re-launches this command under torch.distributed.run "
@@ -621,8 +636,10 @@ def haplotag_passes(args) -> str:
     logger = logging.getLogger("hello_amd.call")
     first = argparse.Namespace(**vars(args))
     first.haplotag = first.gvcf = first.annotate = first.annotate_evidence = first.qc = first.methylation = False
-    first.contamination = False
+    first.contamination = first.sv = False
     first.qc_regions = first.qc_window = first.contamination_sites = None
+    for flag in SV_OPTIONS:
+        setattr(first, flag, None)
     first.phase = True
     first.workdir = os.path.join(args.workdir, "haplotag_pass1")
     phased_path = main(first)[:-len(".vcf")] + ".phased.vcf"
@@ -818,6 +835,68 @@ def contamination_pass(args, genome: Dict[str, str]) -> List[str]:
     return written
 
 
+SV_OPTIONS = ("sv_min_size", "sv_min_support", "sv_flank", "sv_cluster_gap", "sv_len_ratio")
+
+
+def _sv_values(args) -> Tuple[int, int, int, int, float]:
+    """(min_size, min_support, flank, cluster_gap, len_ratio): the --sv_* options given, else the defaults of ``hello_amd.sv``."""
+    from . import sv
+    defaults = (sv.MIN_SIZE, sv.MIN_SUPPORT, sv.FLANK, sv.CLUSTER_GAP, sv.LEN_RATIO)
+    return tuple(d if getattr(args, flag, None) is None else getattr(args, flag) for flag, d in zip(SV_OPTIONS, defaults))
+
+
+def check_sv(args) -> None:
+    """The refusals of --sv and the --sv_* options, each naming the fix."""
+    if not getattr(args, "sv", False):
+        for flag in SV_OPTIONS:
+            if getattr(args, flag, None) is not None:
+                raise SystemExit(f"--{flag} is an option of the pass over large deletions and insertions and there is none in this "
+                                 f"run: add --sv, or drop --{flag}")
+        return
+    if args.shards:
+        raise SystemExit("--sv reads the CIGARs of the reads of the BAM(s), and shard files hold reads that were fetched and filtered "
+                         "before: drop --shards and start from the BAM with --from_bam or --from_bams, or drop --sv")
+    if not _bam_route(args):
+        raise SystemExit("--sv reads the CIGARs of the reads of the BAM(s), and this run has no BAM on its path: add --from_bam (one "
+                         "BAM) or --from_bams (--ibam and --pbam), or drop --sv (python -m hello_amd.sv searches BAMs on their own)")
+    if _several_processes(args):
+        raise SystemExit("--sv runs its pass over the BAM(s) in one process on one GPU: run it with --gpus 1 as a plain command, or "
+                         "drop --sv and run python -m hello_amd.sv on the BAM(s)")
+    from . import sv
+    sv.check_options(*_sv_values(args))
+
+
+def sv_pass(args, genome: Dict[str, str], result_path: str) -> List[str]:
+    """--sv: the large deletions and insertions of every BAM of the route at the route's --mapq_threshold and chromosomes -> the
+    files written, ``<workdir>/sv.illumina.*`` and / or ``sv.pacbio.*``.  The reads' haplotypes: --haplotag_vcf, else the phased VCF
+    --phase wrote beside ``result_path``, else the BAMs' HP tags."""
+    if not getattr(args, "sv", False):
+        return []
+    from . import haplotag, sv
+    route = Route.from_args(args, need_ref=False)
+    names = ("pacbio",) if route.pacbio else ("illumina", "pacbio")
+    min_size, min_support, flank, cluster_gap, len_ratio = _sv_values(args)
+    phased = getattr(args, "haplotag_vcf", None) or (result_path[:-len(".vcf")] + ".phased.vcf" if getattr(args, "phase", False) else None)
+    tagger = haplotag.Haplotagger(phased, route.chromosomes, route.q_threshold, route.mapq_threshold, route.device) if phased else None
+    written: List[str] = []
+    try:
+        for bam, name in zip(route.bams, names):
+            stats: dict = {}
+            found = sv.measure(bam, genome, route.chromosomes or list(genome), tagger, min_size, flank, route.mapq_threshold, cluster_gap,
+                               sv.percent_of(len_ratio), min_support, device=route.device, stats=stats)
+            written += found.write_all(os.path.join(args.workdir, "sv." + name))
+            total = found.total()
+            logging.getLogger("hello_amd.call").info(
+                "--sv %s: %d reads counting, %d walked, %d signatures, %d events in %.2f s (BAM decode %.2f s, kernels %.1f ms; "
+                "haplotypes from %s)", name, total["counting"], total["walked"], total["signatures"], total["candidates"],
+                stats.get("total_s", 0.0), stats.get("decode_s", 0.0),
+                sum(stats.get(k, 0.0) for k in ("cover_ms", "reads_ms", "finish_ms")), phased or "the HP tags")
+    finally:
+        if tagger is not None:
+            tagger.close()
+    return written
+
+
 def run_resident(args) -> str:
     """--from_bam / --from_bams with --resident: hotspots and ``shard<N>.txt`` as ``shards_from_bam(s)`` write them, then ONE loop
     in this process: shard file -> candidate sites whose reads stay on the GPU (``candidates.resident_activity``) -> ``ShardScorer``
@@ -832,6 +911,7 @@ def run_resident(args) -> str:
     check_qc(args)
     check_methylation(args)
     check_contamination(args)
+    check_sv(args)
     route = Route.from_args(args)
     genome = read_fasta(route.ref, route.chromosomes)
     tagger = haplotagger_of(args, route)
@@ -880,6 +960,7 @@ def run_resident(args) -> str:
     qc_pass(args, genome)
     methylation_pass(args, genome, result_path)
     contamination_pass(args, genome)
+    sv_pass(args, genome, result_path)
     return result_path
 
 
@@ -892,6 +973,7 @@ def main(args) -> str:
     check_qc(args)
     check_methylation(args)
     check_contamination(args)
+    check_sv(args)
     if getattr(args, "mark_duplicates", False):
         return with_duplicates_marked(args)
     if getattr(args, "haplotag", False):
@@ -1000,6 +1082,7 @@ def main(args) -> str:
         qc_pass(args, genomes)
         methylation_pass(args, genomes, result_path)
         contamination_pass(args, genomes)
+        sv_pass(args, genomes, result_path)
     if world > 1:
         import torch.distributed as dist
         dist.barrier()

@@ -1,6 +1,6 @@
 // What the host knows about a set of decoded BAM reads before a kernel may index with them: the CIGAR constants, the read filters
 // and the validating walks of the BAM-side stages (strict_walk, counted_walk, and exact_walk under the duplicate marker's, the
-// quality metrics', the methylation's and the pileup's).  Plain C++17 -- no HIP, no kernel -- so the walks also build into a
+// quality metrics', the methylation's, the pileup's and the large events').  Plain C++17 -- no HIP, no kernel -- so the walks also build into a
 // stand-alone host program (tests/abi/cigar_check.cpp).  Refusals are thrown as Fail; the entry points turn them into a status.
 #pragma once
 #include <algorithm>
@@ -269,6 +269,30 @@ inline std::vector<uint8_t> pileup_walk(const ReadsView& s, int64_t lo, int mapq
     std::vector<uint8_t> kind = meth_walk(s, lo, mapq_threshold);
     for (uint8_t& k : kind) k &= kPileBelongs | kPileCounted;
     return kind;
+}
+
+// The walk of the large deletions and insertions: pileup_walk's classes and refusals, unchanged, and on top
+// of them the walk list -- the counting, belonging reads with an I or D operation of at least `min_size` bases, in input order --
+// and the count of those operations, which no count of signatures exceeds: the kernel's output buffer is sized with it.
+struct SvWalk {
+    std::vector<uint8_t> kind;       // per read kPileBelongs | kPileCounted
+    std::vector<int64_t> walk;
+    int64_t n_ops = 0;
+};
+inline SvWalk sv_walk(const ReadsView& s, int64_t lo, int mapq_threshold, int64_t min_size) {
+    SvWalk w;
+    w.kind = pileup_walk(s, lo, mapq_threshold);
+    for (int64_t r = 0; r < s.n; ++r) {
+        if (w.kind[(size_t)r] != (kPileBelongs | kPileCounted)) continue;
+        int64_t n = 0;
+        for (int64_t c = s.cigar_off[r]; c < s.cigar_off[r + 1]; ++c) {
+            const int op = s.cigars[c] & 15;
+            if ((op == BAM_CINS || op == BAM_CDEL) && (int64_t)(s.cigars[c] >> 4) >= min_size) ++n;
+        }
+        if (n) w.walk.push_back(r);
+        w.n_ops += n;
+    }
+    return w;
 }
 
 }  // namespace

@@ -1,0 +1,501 @@
+// Large deletions and insertions from the reads' own CIGARs (include/hello_mi355x.h: hello_sv_*): the chromosome's text and, span
+// after span, its reads -> signatures (one per I or D operation of at least min_size bases, left-aligned against the reference),
+// clusters of them and a genotype per cluster.  Not in the reference; DESIGN.md section 7p states the rules and hello_amd/sv.py
+// restates them in Python, integer for integer.
+//
+// Host: the classes of the reads, the validation of every counted read and the walk list (cigar.h: sv_walk) -- the kernels index
+// with it -- and at finish the clusters and genotypes (sv.h).
+// Device, per hello_sv_add two kernels:
+//   cover: a lane per counting, belonging read adds +1 and -1 to the difference array of the spanning depth.
+//   reads: a wave per read of the walk list, the workgroup's waves sharing its reads.  The lanes sit on 64 operations per step
+//     (read_walk.h: the decoder); two inclusive scans by shuffles turn the operations' advances into the reference and the query
+//     cursor of every lane, their totals carrying into the next step.  A ballot marks the signatures; for each, in a wave-uniform
+//     loop, the whole wave tests cond(j) of the move to the left 64 at a time, and the first failing lane ends it.  Lane 0 takes a
+//     slot of the output with one returning atomicAdd: there are as many slots as sv_walk counted operations.
+// and at hello_sv_finish two more:
+//   tile: a workgroup per 1 024 positions sums the difference array into a 64-bit sum; the host scans the sums.
+//   span: a wave per candidate adds its tile's prefix to the lanes' sum of diff[tile start .. pos].
+// The cover is an integer sum and the signatures are sorted by the host before anyone sees them: two runs give the same bytes.
+#include <memory>
+
+#include "read_walk.h"
+#include "stage_host.h"
+#include "sv.h"
+
+namespace hello {
+namespace {
+
+constexpr int kSvThreads = 256;
+constexpr int kSvWaves = kSvThreads / 64;
+constexpr int kSvShare = 1024;               // the most walked reads of a workgroup
+constexpr int kSvGroups = 4096;              // the share of a launch is sized for about so many workgroups (pileup.hip)
+constexpr int kSvTile = 1024;
+constexpr int64_t kSvMaxReads = INT32_MAX;   // counting reads of one handle: the difference array is 32-bit
+
+struct SvCoverArgs {
+    const int64_t* ref_start;
+    const int64_t* ref_end;
+    const int64_t* list;         // [n_list]: the belonging counted reads, in input order
+    int64_t n_list, length;
+    int flank;
+    int* diff;                   // [length + 1]
+};
+
+// e = ref_end: it is s + rlen but for a read without a reference operation (s + 1), which is shorter than 2 flank either way.
+__global__ __launch_bounds__(kSvThreads) void sv_cover_kernel(SvCoverArgs a) {
+    const int64_t k = (int64_t)blockIdx.x * kSvThreads + threadIdx.x;
+    if (k >= a.n_list) return;
+    const int64_t r = a.list[k];
+    const int64_t s = a.ref_start[r], e = a.ref_end[r];                   // 0 <= s < e: sv_walk
+    const int64_t from = s + a.flank;
+    if (e - s < 2 * (int64_t)a.flank || from >= a.length) return;
+    const int64_t last = e - a.flank < a.length - 1 ? e - a.flank : a.length - 1;     // from <= last <= length - 1
+    atomicAdd(a.diff + from, 1);
+    atomicAdd(a.diff + last + 1, -1);
+}
+
+struct SvReadsArgs {
+    const uint8_t* bases;
+    const int64_t* read_off;
+    const uint32_t* cigars;
+    const int64_t* cigar_off;
+    const int64_t* ref_start;
+    const int64_t* ref_end;
+    const uint16_t* flags;
+    const uint8_t* hp;
+    const int64_t* list;         // [n_list]: the walk list
+    const int64_t* ordinal;      // [n_list]: the read's index among the handle's counting reads
+    uint8_t* seen;               // [n_list], zeroed: 1 when the read gave a signature
+    int64_t n_list;
+    const uint8_t* ref;          // [length]
+    int64_t length;
+    int min_size, flank, share;
+    SvSig* out;                  // [capacity]
+    unsigned long long* cursor;  // zeroed: the slots taken
+    unsigned long long capacity;
+};
+
+__device__ __forceinline__ long long sv_scan(long long v, int lane) {
+    for (int d = 1; d < 64; d <<= 1) {
+        const long long up = __shfl_up(v, d, 64);
+        if (lane >= d) v += up;
+    }
+    return v;
+}
+
+__global__ __launch_bounds__(kSvThreads) void sv_reads_kernel(SvReadsArgs a) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t k_lo = (int64_t)blockIdx.x * a.share;
+    const int64_t k_hi = k_lo + a.share < a.n_list ? k_lo + a.share : a.n_list;
+    for (int64_t k = k_lo + wave; k < k_hi; k += kSvWaves) {
+        const int64_t r = a.list[k];
+        const int64_t s = a.ref_start[r], e = a.ref_end[r];               // a walked read has a D or an aligned base: e = s + rlen
+        const uint8_t* bases = a.bases + a.read_off[r];
+        const int64_t c0 = a.cigar_off[r], n_ops = a.cigar_off[r + 1] - c0;
+        long long rf = s, rd = 0;
+        bool any = false;
+        for (int64_t i0 = 0; i0 < n_ops; i0 += 64) {
+            const int64_t i = i0 + lane;
+            const CigarOp o = i < n_ops ? decode_op(a.cigars[c0 + i]) : CigarOp{BAM_CPAD, 0, false};
+            const long long on_ref = o.m || o.op == BAM_CDEL || o.op == BAM_CREF_SKIP ? o.n : 0;
+            const long long on_read = o.on_read() ? o.n : 0;
+            const long long ref_sum = sv_scan(on_ref, lane), read_sum = sv_scan(on_read, lane);
+            const long long p = rf + ref_sum - on_ref, q = rd + read_sum - on_read;     // where the lane's operation begins
+            rf += __shfl(ref_sum, 63, 64);
+            rd += __shfl(read_sum, 63, 64);
+            const bool event = (o.op == BAM_CINS || o.op == BAM_CDEL) && o.n >= a.min_size;
+            const long long pe = o.op == BAM_CDEL ? p + o.n : p;
+            const bool is_signature = event && p - s >= a.flank && e - pe >= a.flank && pe <= a.length;
+            unsigned long long todo = __ballot(is_signature);
+            any = any || todo != 0ull;
+            while (todo) {                                                // wave-uniform
+                const int src = __ffsll((long long)todo) - 1;
+                todo &= todo - 1ull;
+                const long long sp = __shfl(p, src, 64), sq = __shfl(q, src, 64);
+                const int n = __shfl(o.n, src, 64);
+                const bool ins = __shfl(o.op, src, 64) == BAM_CINS;
+                // the move to the left: j < sp - s keeps every index at or above s >= 0; sp <= pe <= length keeps it below length
+                const long long bound = sp - s;
+                long long shift = 0;
+                for (long long j0 = 0;; j0 += 64) {
+                    const long long j = j0 + lane;
+                    bool holds = false;
+                    if (j < bound) {
+                        const int left = a.ref[sp - 1 - j] & 0xDF;
+                        const int right = ins && j < n ? bases[sq + n - 1 - j] : a.ref[sp - 1 - j + n];   // sq + n <= the read's bases
+                        holds = left == (right & 0xDF);
+                    }
+                    const unsigned long long all = __ballot(holds);
+                    if (all != ~0ull) {                                   // the lane at j = bound fails at the latest
+                        shift = j0 + (__ffsll((long long)~all) - 1);
+                        break;
+                    }
+                }
+                if (lane == 0) {
+                    const unsigned long long slot = atomicAdd(a.cursor, 1ull);
+                    if (slot < a.capacity) {                              // always: sv_walk counted the operations
+                        SvSig g;
+                        g.pos = sp - shift;
+                        g.ordinal = a.ordinal[k];
+                        g.op_index = i0 + src;
+                        g.len = n;
+                        g.shift = (int32_t)shift;                         // shift <= pos < 2^31
+                        g.type = ins ? kSvIns : kSvDel;
+                        g.strand = (a.flags[r] & 0x10) ? 1 : 0;
+                        g.hp = a.hp[r];
+                        g.pad = 0;
+                        a.out[slot] = g;
+                    }
+                }
+            }
+        }
+        if (lane == 0 && any) a.seen[k] = 1;
+    }
+}
+
+struct SvSpanArgs {
+    const int* diff;             // [length + 1]
+    int64_t n_diff, n_tiles;
+    long long* tile_sum;         // [n_tiles]; for the span kernel the sums before every tile
+    const int64_t* pos;          // [n_candidates], each inside [0, length]
+    int64_t n_candidates;
+    long long* depth;            // [n_candidates]
+};
+
+__global__ __launch_bounds__(kSvThreads) void sv_tile_kernel(SvSpanArgs a) {
+    __shared__ long long part[kSvWaves];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int64_t t0 = (int64_t)blockIdx.x * kSvTile;
+    long long sum = 0;
+    for (int j = tid; j < kSvTile; j += kSvThreads)
+        if (t0 + j < a.n_diff) sum += a.diff[t0 + j];
+    for (int d = 32; d > 0; d >>= 1) sum += __shfl_down(sum, d, 64);
+    if (lane == 0) part[wave] = sum;
+    __syncthreads();
+    if (tid == 0) {
+        long long total = 0;
+        for (int w = 0; w < kSvWaves; ++w) total += part[w];
+        a.tile_sum[blockIdx.x] = total;
+    }
+}
+
+__global__ __launch_bounds__(kSvThreads) void sv_span_kernel(SvSpanArgs a) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t c = (int64_t)blockIdx.x * kSvWaves + wave;
+    if (c >= a.n_candidates) return;                                      // the whole wave
+    const int64_t pos = a.pos[c], tile = pos / kSvTile, t0 = tile * kSvTile;      // pos < n_diff
+    long long sum = 0;
+    for (int64_t j = t0 + lane; j <= pos; j += 64) sum += a.diff[j];
+    for (int d = 32; d > 0; d >>= 1) sum += __shfl_down(sum, d, 64);
+    if (lane == 0) a.depth[c] = a.tile_sum[tile] + sum;
+}
+
+constexpr int kSvSigColumns = 8, kSvCandColumns = 20;
+
+}  // namespace
+}  // namespace hello
+
+struct hello_sv : hello::SpanHandle<HELLO_SV_STATS> {
+    int32_t min_size = 0, flank = 0, mapq_threshold = 0;
+    hello::DevMem mem;                           // the reference text and the difference array live as long as the handle
+    const uint8_t* ref = nullptr;
+    int* diff = nullptr;
+    bool built = false, finished = false, sorted = true;
+    std::vector<uint8_t> reference;              // until the device side is built
+    std::vector<hello::SvSig> sigs;
+    std::vector<int64_t> sig_cols[hello::kSvSigColumns], cand_cols[hello::kSvCandColumns];
+};
+
+extern "C" {
+
+// The device side of a handle, built when the first hello_sv_add has passed its checks.
+static void sv_build(hello_sv* h) {
+    using namespace hello;
+    if (h->built) return;
+    open_device(h->device);
+    DevMem keep;
+    const uint8_t* ref = keep.put(h->reference.data(), h->reference.size());
+    int* diff = keep.zeros<int>((size_t)h->length + 1);
+    // ---- nothing can fail from here on
+    h->mem.ptrs.swap(keep.ptrs);
+    h->ref = ref;
+    h->diff = diff;
+    std::vector<uint8_t>().swap(h->reference);
+    h->built = true;
+}
+
+// The SIGNATURES columns of the handle, in sv_sort's order.
+static void sv_signature_columns(hello_sv* h) {
+    using namespace hello;
+    if (h->sorted) return;
+    sv_sort(h->sigs);
+    for (auto& c : h->sig_cols) c.resize(h->sigs.size());
+    for (size_t i = 0; i < h->sigs.size(); ++i) {
+        const SvSig& g = h->sigs[i];
+        const int64_t row[kSvSigColumns] = {g.type, g.pos, g.len, g.shift, g.ordinal, g.op_index, g.strand, g.hp};
+        for (int c = 0; c < kSvSigColumns; ++c) h->sig_cols[c][i] = row[c];
+    }
+    h->sorted = true;
+}
+
+int hello_sv_create(const uint8_t* reference, int64_t reference_length, int32_t min_size, int32_t flank, int32_t mapq_threshold,
+                    int32_t device, hello_sv** handle) try {
+    using namespace hello;
+    if (!reference || !handle) return set_last_error(HELLO_ERR_ARG, "NULL pointer");
+    *handle = nullptr;
+    if (reference_length < 0 || reference_length > INT32_MAX)
+        return set_last_error(HELLO_ERR_ARG, "reference of %lld bases: 0 to %d", (long long)reference_length, INT32_MAX);
+    if (min_size < 1) return set_last_error(HELLO_ERR_ARG, "min_size %d: at least 1", min_size);
+    if (flank < 1) return set_last_error(HELLO_ERR_ARG, "flank %d: at least 1", flank);
+    std::unique_ptr<hello_sv> h(new hello_sv());
+    h->device = device;
+    h->min_size = min_size;
+    h->flank = flank;
+    h->mapq_threshold = mapq_threshold;
+    h->length = reference_length;
+    h->reference.assign(reference, reference + reference_length);
+    *handle = h.release();
+    return HELLO_OK;
+} HS_ENTRY_END("hello_sv_create")
+
+int hello_sv_add(hello_sv* h, const uint8_t* bases, const uint8_t* quals, const int64_t* read_offsets, const uint32_t* cigars,
+                 const int64_t* cigar_offsets, const int64_t* ref_starts, const int64_t* ref_ends, const uint8_t* mapq,
+                 const uint16_t* flags, const uint64_t* name_hash, const uint8_t* hp, int64_t n_reads, int64_t lo, int64_t hi) try {
+    using namespace hello;
+    if (!h || !read_offsets || !cigar_offsets || (n_reads > 0 && (!bases || !cigars || !ref_starts || !ref_ends || !mapq || !flags || !hp)))
+        return set_last_error(HELLO_ERR_ARG, "NULL pointer");
+    if (n_reads < 0) return set_last_error(HELLO_ERR_ARG, "negative count");
+    if (h->finished) return set_last_error(HELLO_ERR_ARG, "hello_sv_add after hello_sv_finish: the handle takes no more reads");
+    h->check_span(lo, hi);
+
+    // ---- the reads: validated, then the kernels' lists
+    const ReadsView in{bases, quals, read_offsets, cigars, cigar_offsets, ref_starts, ref_ends, mapq, flags, name_hash, n_reads};
+    const SvWalk walk = sv_walk(in, lo, h->mapq_threshold, h->min_size);
+    std::vector<int64_t> list, ordinal;
+    std::vector<uint8_t> status((size_t)n_reads, 0);
+    int64_t n_belonging = 0;
+    size_t next = 0;
+    for (int64_t r = 0; r < n_reads; ++r) {
+        if (!(walk.kind[(size_t)r] & kPileBelongs)) continue;
+        ++n_belonging;
+        if (!(walk.kind[(size_t)r] & kPileCounted)) continue;
+        if (next < walk.walk.size() && walk.walk[next] == r) {
+            ordinal.push_back(h->counting_given + (int64_t)list.size());
+            ++next;
+        }
+        status[(size_t)r] = 1;
+        list.push_back(r);
+    }
+    const int64_t n_list = (int64_t)list.size(), n_walk = (int64_t)walk.walk.size();
+    h->take_counting(n_list, kSvMaxReads, "cover sums");
+    const int64_t share = std::min<int64_t>(kSvShare, std::max<int64_t>(kSvWaves, (n_walk + kSvGroups - 1) / kSvGroups));
+    const int64_t n_blocks = (n_walk + share - 1) / share;
+
+    sv_build(h);
+    HS_HIP(hipSetDevice(h->device));
+    std::vector<uint8_t> seen((size_t)n_walk, 0);
+    std::vector<SvSig> found;
+    float cover_ms = 0.0f, reads_ms = 0.0f;
+    if (n_list > 0) {
+        DevMem m;
+        const int64_t* d_start = m.put(ref_starts, (size_t)n_reads);
+        const int64_t* d_end = m.put(ref_ends, (size_t)n_reads);
+        SvReadsArgs a{};
+        SvSig* got = nullptr;
+        if (n_walk > 0) {                            // every upload before the first kernel: a failure leaves the cover as it was
+            const size_t nb = (size_t)read_offsets[n_reads], nc = (size_t)cigar_offsets[n_reads];
+            a.bases = m.put(bases, nb);
+            a.read_off = m.put(read_offsets, (size_t)n_reads + 1);
+            a.cigars = m.put(cigars, nc);
+            a.cigar_off = m.put(cigar_offsets, (size_t)n_reads + 1);
+            a.ref_start = d_start;
+            a.ref_end = d_end;
+            a.flags = m.put(flags, (size_t)n_reads);
+            a.hp = m.put(hp, (size_t)n_reads);
+            a.list = m.put(walk.walk.data(), walk.walk.size());
+            a.ordinal = m.put(ordinal.data(), ordinal.size());
+            a.seen = m.zeros<uint8_t>((size_t)n_walk);
+            a.n_list = n_walk;
+            a.ref = h->ref;
+            a.length = h->length;
+            a.min_size = h->min_size;
+            a.flank = h->flank;
+            a.share = (int)share;
+            a.out = got = m.room<SvSig>((size_t)walk.n_ops);
+            a.cursor = m.zeros<unsigned long long>(1);
+            a.capacity = (unsigned long long)walk.n_ops;
+        }
+        KernelTimer timer;
+        if (n_walk > 0) {                            // the reads first: a refusal here has not touched the cover
+            timer.start();
+            hipLaunchKernelGGL(sv_reads_kernel, dim3((unsigned)n_blocks), dim3(kSvThreads), 0, 0, a);
+            reads_ms = timer.stop();
+            unsigned long long taken = 0;
+            HS_HIP(hipMemcpy(&taken, a.cursor, sizeof(taken), hipMemcpyDeviceToHost));
+            if (taken > a.capacity) raise(HELLO_ERR_HIP, "%llu signatures for %llu counted operations", taken, a.capacity);
+            found.resize((size_t)taken);
+            if (taken) HS_HIP(hipMemcpy(found.data(), got, (size_t)taken * sizeof(SvSig), hipMemcpyDeviceToHost));
+            HS_HIP(hipMemcpy(seen.data(), a.seen, (size_t)n_walk, hipMemcpyDeviceToHost));
+        }
+        h->sigs.reserve(h->sigs.size() + found.size());
+        SvCoverArgs c{d_start, d_end, m.put(list.data(), list.size()), n_list, h->length, h->flank, h->diff};
+        timer.start();
+        hipLaunchKernelGGL(sv_cover_kernel, dim3((unsigned)((n_list + kSvThreads - 1) / kSvThreads)), dim3(kSvThreads), 0, 0, c);
+        cover_ms = timer.stop();
+    }
+
+    // ---- nothing can fail from here on
+    int64_t n_seen = 0;
+    for (int64_t k = 0; k < n_walk; ++k) {
+        status[(size_t)walk.walk[(size_t)k]] = seen[(size_t)k] ? 3 : 2;
+        n_seen += seen[(size_t)k] ? 1 : 0;
+    }
+    if (!found.empty()) {
+        h->sigs.insert(h->sigs.end(), found.begin(), found.end());
+        h->sorted = false;
+    }
+    h->status = std::move(status);
+    h->counting_given += n_list;
+    h->last_hi = hi;
+    h->stats[0] += (double)n_reads;
+    h->stats[1] += (double)n_belonging;
+    h->stats[2] += (double)n_list;
+    h->stats[3] += (double)n_walk;
+    h->stats[4] += (double)n_seen;
+    h->stats[5] += (double)found.size();
+    h->stats[7] += cover_ms;
+    h->stats[8] += reads_ms;
+    return HELLO_OK;
+} HS_ENTRY_END("hello_sv_add")
+
+static int sv_check_clustering(int64_t cluster_gap, int32_t len_ratio_percent, int32_t min_support) {
+    using namespace hello;
+    if (cluster_gap < 0) return set_last_error(HELLO_ERR_ARG, "cluster_gap %lld: 0 or more", (long long)cluster_gap);
+    if (len_ratio_percent < 1 || len_ratio_percent > 100)
+        return set_last_error(HELLO_ERR_ARG, "len_ratio_percent %d: 1 to 100", len_ratio_percent);
+    if (min_support < 1) return set_last_error(HELLO_ERR_ARG, "min_support %d: at least 1", min_support);
+    return HELLO_OK;
+}
+
+int hello_sv_cluster(const int64_t* signatures, int64_t n, int64_t cluster_gap, int32_t len_ratio_percent, int32_t min_support,
+                     int64_t* out, int64_t* n_out) try {
+    using namespace hello;
+    if (!n_out || (n > 0 && (!signatures || !out))) return set_last_error(HELLO_ERR_ARG, "NULL pointer");
+    if (n < 0) return set_last_error(HELLO_ERR_ARG, "negative count");
+    if (int rc = sv_check_clustering(cluster_gap, len_ratio_percent, min_support)) return rc;
+    std::vector<SvSig> sigs((size_t)n);
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t* g = signatures + i * kSvSigColumns;
+        if ((g[0] != kSvDel && g[0] != kSvIns) || g[2] < 1 || g[2] > INT32_MAX || g[6] < 0 || g[6] > 1 || g[7] < 0 || g[7] > 255)
+            return set_last_error(HELLO_ERR_ARG, "signature %lld: type %lld, len %lld, strand %lld, hp %lld", (long long)i,
+                                  (long long)g[0], (long long)g[2], (long long)g[6], (long long)g[7]);
+        sigs[(size_t)i] = SvSig{g[1], g[4], g[5], (int32_t)g[2], (int32_t)g[3], (uint8_t)g[0], (uint8_t)g[6], (uint8_t)g[7], 0};
+    }
+    sv_sort(sigs);
+    const std::vector<SvCandidate> found = sv_cluster(sigs, cluster_gap, len_ratio_percent, min_support);
+    for (size_t i = 0; i < found.size(); ++i) {
+        const SvCandidate& c = found[i];
+        const int64_t row[HELLO_SV_CLUSTER_COLUMNS] = {c.type, c.pos, c.len, c.dv, c.dv_fwd, c.dv_rev, c.hp[0], c.hp[1], c.hp[2],
+                                                       c.pos_min, c.pos_max, c.len_min, c.len_max};
+        std::copy(row, row + HELLO_SV_CLUSTER_COLUMNS, out + i * HELLO_SV_CLUSTER_COLUMNS);
+    }
+    *n_out = (int64_t)found.size();
+    return HELLO_OK;
+} HS_ENTRY_END("hello_sv_cluster")
+
+int hello_sv_finish(hello_sv* h, int64_t cluster_gap, int32_t len_ratio_percent, int32_t min_support) try {
+    using namespace hello;
+    if (!h) return set_last_error(HELLO_ERR_ARG, "NULL pointer");
+    if (h->finished) return set_last_error(HELLO_ERR_ARG, "hello_sv_finish twice: the handle is finished");
+    if (int rc = sv_check_clustering(cluster_gap, len_ratio_percent, min_support)) return rc;
+    sv_signature_columns(h);
+    const std::vector<SvCandidate> found = sv_cluster(h->sigs, cluster_gap, len_ratio_percent, min_support);
+    const size_t n = found.size();
+    std::vector<long long> depth(n, 0);
+    float ms = 0.0f;
+    if (n > 0) {                                     // a candidate has signatures, so an add has built the device side
+        HS_HIP(hipSetDevice(h->device));
+        DevMem m;
+        std::vector<int64_t> pos(n);
+        for (size_t i = 0; i < n; ++i) pos[i] = found[i].pos;
+        SvSpanArgs a{};
+        a.diff = h->diff;
+        a.n_diff = h->length + 1;
+        a.n_tiles = (a.n_diff + kSvTile - 1) / kSvTile;
+        a.tile_sum = m.room<long long>((size_t)a.n_tiles);
+        a.pos = m.put(pos.data(), n);
+        a.n_candidates = (int64_t)n;
+        a.depth = m.room<long long>(n);
+        KernelTimer timer;
+        timer.start();
+        hipLaunchKernelGGL(sv_tile_kernel, dim3((unsigned)a.n_tiles), dim3(kSvThreads), 0, 0, a);
+        ms = timer.stop();
+        std::vector<long long> sums((size_t)a.n_tiles), before((size_t)a.n_tiles);
+        HS_HIP(hipMemcpy(sums.data(), a.tile_sum, sums.size() * sizeof(long long), hipMemcpyDeviceToHost));
+        long long running = 0;
+        for (size_t t = 0; t < sums.size(); ++t) {
+            before[t] = running;
+            running += sums[t];
+        }
+        HS_HIP(hipMemcpy(a.tile_sum, before.data(), before.size() * sizeof(long long), hipMemcpyHostToDevice));
+        timer.start();
+        hipLaunchKernelGGL(sv_span_kernel, dim3((unsigned)((n + kSvWaves - 1) / kSvWaves)), dim3(kSvThreads), 0, 0, a);
+        ms += timer.stop();
+        HS_HIP(hipMemcpy(depth.data(), a.depth, n * sizeof(long long), hipMemcpyDeviceToHost));
+    }
+    std::vector<int64_t> cols[kSvCandColumns];
+    for (auto& c : cols) c.resize(n);
+    for (size_t i = 0; i < n; ++i) {
+        const SvCandidate& c = found[i];
+        int64_t g[kSvGenotypeColumns];
+        const int64_t dp = (int64_t)depth[i], dr = sv_depth_ref(dp, c.dv);
+        sv_genotype(c.dv, dr, g);
+        const int64_t row[kSvCandColumns] = {c.type, c.pos, c.len, c.dv, c.dv_fwd, c.dv_rev, c.hp[0], c.hp[1], c.hp[2], c.pos_min,
+                                             c.pos_max, c.len_min, c.len_max, dp, dr, g[0], g[1], g[2], g[3], g[4]};
+        for (int k = 0; k < kSvCandColumns; ++k) cols[k][i] = row[k];
+    }
+    // ---- nothing can fail from here on
+    for (int k = 0; k < kSvCandColumns; ++k) h->cand_cols[k].swap(cols[k]);
+    h->finished = true;
+    h->stats[6] = (double)n;
+    h->stats[9] += ms;
+    return HELLO_OK;
+} HS_ENTRY_END("hello_sv_finish")
+
+int hello_sv_array(hello_sv* h, int32_t which, const void** data, int64_t* count) try {
+    using namespace hello;
+    if (!h || !data || !count) return set_last_error(HELLO_ERR_ARG, "NULL pointer");
+    if (which >= HELLO_SV_SIGNATURES_TYPE && which <= HELLO_SV_SIGNATURES_HP) {
+        sv_signature_columns(h);
+        const std::vector<int64_t>& c = h->sig_cols[which - HELLO_SV_SIGNATURES_TYPE];
+        *data = c.data(); *count = (int64_t)c.size();
+    } else if (which >= HELLO_SV_CANDIDATES_TYPE && which <= HELLO_SV_CANDIDATES_PL2) {
+        if (!h->finished) return set_last_error(HELLO_ERR_ARG, "array selector %d before hello_sv_finish", which);
+        const std::vector<int64_t>& c = h->cand_cols[which - HELLO_SV_CANDIDATES_TYPE];
+        *data = c.data(); *count = (int64_t)c.size();
+    } else if (which == HELLO_SV_STATUS) {
+        *data = h->status.data(); *count = (int64_t)h->status.size();
+    } else {
+        return set_last_error(HELLO_ERR_ARG, "array selector %d", which);
+    }
+    return HELLO_OK;
+} HS_ENTRY_END("hello_sv_array")
+
+int hello_sv_stats(const hello_sv* h, double* stats) {
+    if (!h || !stats) return hello::set_last_error(HELLO_ERR_ARG, "NULL pointer");
+    return h->copy_stats(stats);
+}
+
+void hello_sv_free(hello_sv* h) { delete h; }
+
+int hello_sv_genotype(const int64_t* dv, const int64_t* dr, int64_t n, int64_t* out) try {
+    using namespace hello;
+    if (!out || (n > 0 && (!dv || !dr))) return set_last_error(HELLO_ERR_ARG, "NULL pointer");
+    if (n < 0) return set_last_error(HELLO_ERR_ARG, "negative count");
+    for (int64_t i = 0; i < n; ++i)
+        if (dv[i] < 0 || dr[i] < 0) return set_last_error(HELLO_ERR_ARG, "candidate %lld: count %lld", (long long)i, (long long)std::min(dv[i], dr[i]));
+    for (int64_t i = 0; i < n; ++i) sv_genotype(dv[i], dr[i], out + i * kSvGenotypeColumns);
+    return HELLO_OK;
+} HS_ENTRY_END("hello_sv_genotype")
+
+}  // extern "C"

@@ -1060,6 +1060,81 @@ int hello_contam_estimate(const int64_t* r, const int64_t* a, const int64_t* o, 
 int hello_contam_identity(const int64_t* r1, const int64_t* a1, const int64_t* o1, const int64_t* r2, const int64_t* a2,
                           const int64_t* o2, const double* af, int64_t n, double* out);
 
+/* Large deletions and insertions of one chromosome of one BAM from the reads' own CIGARs: every I or D operation of at least
+ * min_size bases inside one alignment record, left-aligned against the reference, clustered and genotyped (not in the reference;
+ * DESIGN.md section 7p states the rules, hello_amd/sv.py restates them in Python).  Split alignments, clipped ends and discordant
+ * pairs are not looked at.  One handle per (BAM, chromosome).
+ *   hello_sv_create: takes a copy of `reference` and needs no device.  The first hello_sv_add that passes its checks opens the
+ *          device, uploads the text and zeroes the cover's difference array (int32 [length + 1]); both live as long as the handle.
+ *          Refused: NULL, a length outside [0, 2^31 - 1], min_size < 1, flank < 1.
+ *   hello_sv_add: the reads overlapping one span [lo, hi), coordinate-sorted: the arrays of hello_bam_fetch with `hp`.  A read
+ *          belongs and counts by hello_pileup_add's rules.  Every counting, belonging read adds to the cover; those with an I or D
+ *          of at least min_size bases are walked by a wave each, and each such operation that keeps `flank` reference bases of the
+ *          read on both sides and ends inside the chromosome becomes a signature.  Refused, before the device is looked for: what
+ *          hello_pileup_add refuses of the reads and the span, in its words, more than 2^31 - 1 counting reads in one handle, and
+ *          a call after hello_sv_finish.  A refused call leaves the handle as it was.
+ *   hello_sv_finish: clusters the signatures on the host (cluster_gap >= 0 positions, len_ratio_percent 1 to 100, min_support >= 1
+ *          distinct reads), reads the spanning depth of every candidate off the difference array on the device and genotypes it.
+ *          Refused a second time.
+ *   hello_sv_array: int64 each.  The SIGNATURES columns, sorted by (type, pos, len, ordinal, operation index); the CANDIDATES
+ *          columns, after hello_sv_finish, sorted by (pos, type, len); STATUS uint8 per read of the last add.
+ *   hello_sv_genotype: host only, no device.  `dv`, `dr`: per candidate the reads with the event and the spanning reads without;
+ *          out int64 [n][HELLO_SV_GENOTYPE_COLUMNS]: GT (0, 1, 2 for 0/0, 0/1, 1/1), GQ, PL of the three.  Refused: NULL, a
+ *          negative n or count.
+ * Host memory in and out; sv.hip, sv.h. */
+#define HELLO_SV_STATS 10
+#define HELLO_SV_GENOTYPE_COLUMNS 5
+enum {
+    HELLO_SV_SIGNATURES_TYPE = 0,        /* 0 DEL, 1 INS */
+    HELLO_SV_SIGNATURES_POS = 1,         /* 0-based, after the move to the left */
+    HELLO_SV_SIGNATURES_LEN = 2,
+    HELLO_SV_SIGNATURES_SHIFT = 3,
+    HELLO_SV_SIGNATURES_ORDINAL = 4,     /* the read's index among the handle's counting reads */
+    HELLO_SV_SIGNATURES_OP = 5,          /* the operation's index in the read's CIGAR */
+    HELLO_SV_SIGNATURES_STRAND = 6,      /* flag 0x10 */
+    HELLO_SV_SIGNATURES_HP = 7,
+    HELLO_SV_CANDIDATES_TYPE = 8,
+    HELLO_SV_CANDIDATES_POS = 9,
+    HELLO_SV_CANDIDATES_LEN = 10,
+    HELLO_SV_CANDIDATES_DV = 11,
+    HELLO_SV_CANDIDATES_DV_FWD = 12,
+    HELLO_SV_CANDIDATES_DV_REV = 13,
+    HELLO_SV_CANDIDATES_HP0 = 14,
+    HELLO_SV_CANDIDATES_HP1 = 15,
+    HELLO_SV_CANDIDATES_HP2 = 16,
+    HELLO_SV_CANDIDATES_POS_MIN = 17,
+    HELLO_SV_CANDIDATES_POS_MAX = 18,
+    HELLO_SV_CANDIDATES_LEN_MIN = 19,
+    HELLO_SV_CANDIDATES_LEN_MAX = 20,
+    HELLO_SV_CANDIDATES_DP = 21,
+    HELLO_SV_CANDIDATES_DR = 22,
+    HELLO_SV_CANDIDATES_GT = 23,
+    HELLO_SV_CANDIDATES_GQ = 24,
+    HELLO_SV_CANDIDATES_PL0 = 25,
+    HELLO_SV_CANDIDATES_PL1 = 26,
+    HELLO_SV_CANDIDATES_PL2 = 27,
+    HELLO_SV_STATUS = 28                 /* 0 not belonging or not counted, 1 counting, 2 walked, 3 walked with a signature */
+};
+typedef struct hello_sv hello_sv;
+int hello_sv_create(const uint8_t* reference, int64_t reference_length, int32_t min_size, int32_t flank, int32_t mapq_threshold,
+                    int32_t device, hello_sv** handle);
+int hello_sv_add(hello_sv* sv, const uint8_t* bases, const uint8_t* quals, const int64_t* read_offsets, const uint32_t* cigars,
+                 const int64_t* cigar_offsets, const int64_t* ref_starts, const int64_t* ref_ends, const uint8_t* mapq,
+                 const uint16_t* flags, const uint64_t* name_hash, const uint8_t* hp, int64_t n_reads, int64_t lo, int64_t hi);
+int hello_sv_finish(hello_sv* sv, int64_t cluster_gap, int32_t len_ratio_percent, int32_t min_support);
+/* a pointer into `sv` (valid until the next hello_sv_* call on it) and its element count */
+int hello_sv_array(hello_sv* sv, int32_t which, const void** data, int64_t* count);
+/* stats[HELLO_SV_STATS]: reads given, belonging, counting, walked, walked reads with a signature, signatures, candidates, cover /
+ * reads / finish kernel ms (HIP events) */
+int hello_sv_stats(const hello_sv* sv, double* stats);
+void hello_sv_free(hello_sv* sv);
+int hello_sv_genotype(const int64_t* dv, const int64_t* dr, int64_t n, int64_t* out);
+/* The clustering of hello_sv_finish alone, host only: signatures int64 [n][8] in the SIGNATURES columns' order, any row order ->
+ * out int64 [*n_out][HELLO_SV_CLUSTER_COLUMNS], the CANDIDATES columns TYPE .. LEN_MAX; `out` has room for n rows. */
+#define HELLO_SV_CLUSTER_COLUMNS 13
+int hello_sv_cluster(const int64_t* signatures, int64_t n, int64_t cluster_gap, int32_t len_ratio_percent, int32_t min_support,
+                     int64_t* out, int64_t* n_out);
+
 #ifdef __cplusplus
 }
 #endif

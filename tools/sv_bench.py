@@ -1,0 +1,123 @@
+"""Benchmark of the large deletions and insertions (hello_sv_*) on two synthetic loads: about 200 k reads of
+150 bases, and about 20 k reads of 15 kb with several hundred CIGAR operations each.  Per load: the cover, reads and finish kernels'
+ms (HIP events, ``hello_sv_stats``), the wall ms of ``hello_sv_add`` and of ``hello_sv_finish``, and the host's own validating walk
+of the same reads -- the wall ms of a ``hello_sv_add`` on a handle made for a device that does not exist, which runs the span check,
+``sv_walk`` and the kernels' lists and is refused where it opens the device.
+
+    python tools/sv_bench.py [--load short|long|both] [--warmup 2] [--repeats 7] [--profile FILE]
+
+--warmup untimed runs, then --repeats timed ones; prints one JSON line per load with the minimum, the median and the maximum of each
+time and, with --profile, appends it to FILE."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from hello_amd import sv  # noqa: E402
+from hello_amd.bam import Reads  # noqa: E402
+
+M, I, D = 0, 1, 2
+
+
+def spread(values):
+    v = np.asarray(values, float)
+    return {"min": round(float(v.min()), 4), "median": round(float(np.median(v)), 4), "max": round(float(v.max()), 4)}
+
+
+def synthesize(load: str, seed: int = 1):
+    """-> (reference uint8, Reads, the mean operations per read)."""
+    rng = np.random.default_rng(seed)
+    if load == "short":                                  # 30x over 1 Mb; one read in fifty has a deletion of 60 bases: 45M 60D 105M
+        length, n_reads, read_len = 1_000_000, 200_000, 150
+        starts = np.sort(rng.integers(0, length - 300, size=n_reads))
+        with_event = rng.random(n_reads) < 0.02
+        plain, event, before, grid = [(M, 150)], [(M, 45), (D, 60), (M, 105)], 45, 2000
+    else:                                                # 30x over 10 Mb; 250 times 29M 1I 29M 1D, and in one read of four a 300D
+        length, n_reads, read_len = 10_000_000, 20_000, 15_000
+        starts = np.sort(rng.integers(0, length - 16_000, size=n_reads))
+        with_event = rng.random(n_reads) < 0.25
+        unit = [(M, 29), (I, 1), (M, 29), (D, 1)]
+        plain, event, before, grid = unit * 250 + [(M, 250)], unit * 125 + [(D, 300)] + unit * 125 + [(M, 250)], 125 * 59, 50_000
+    # the events lie on a grid, so that clusters form
+    starts[with_event] = np.maximum((starts[with_event] + before) // grid * grid, grid) - before
+    order = np.argsort(starts, kind="stable")
+    starts, with_event = starts[order], with_event[order]
+    reference = rng.choice(np.frombuffer(b"ACGT", np.uint8), size=length)
+    packed = [np.array([n << 4 | op for op, n in ops], np.uint32) for ops in (plain, event)]
+    which = with_event.astype(np.int64)
+    cigars = np.concatenate([packed[k] for k in which])
+    cigar_offsets = np.concatenate([[0], np.cumsum(np.array([len(plain), len(event)])[which])]).astype(np.int64)
+    on_ref = np.array([sum(n for op, n in ops if op != I) for ops in (plain, event)], np.int64)[which]
+    on_read = np.array([sum(n for op, n in ops if op != D) for ops in (plain, event)], np.int64)[which]
+    assert int(on_read.min()) == int(on_read.max()) == read_len
+    n_bases = int(on_read.sum())
+    reads = Reads(bases=rng.choice(np.frombuffer(b"ACGT", np.uint8), size=n_bases), quals=np.full(n_bases, 30, np.uint8),
+                  read_offsets=np.concatenate([[0], np.cumsum(on_read)]).astype(np.int64), cigars=cigars, cigar_offsets=cigar_offsets,
+                  ref_starts=starts.astype(np.int64), ref_ends=(starts + on_ref).astype(np.int64), mapq=np.full(n_reads, 60, np.uint8),
+                  flags=(rng.integers(0, 2, size=n_reads) * 0x10).astype(np.uint16), name_hash=np.arange(n_reads, dtype=np.uint64),
+                  strand=np.zeros(n_reads, np.uint8), hp=rng.integers(0, 3, size=n_reads).astype(np.uint8))
+    return reference, reads, float(np.diff(cigar_offsets).mean())
+
+
+def host_walk_ms(reference, reads) -> float:
+    """The wall ms of an add that is refused where it opens the device: the span check, sv_walk and the kernels' lists."""
+    with sv.Caller(reference, device=1 << 20) as caller:
+        t0 = time.perf_counter()
+        try:
+            caller.add(reads, 0, reference.shape[0])
+        except RuntimeError as refused:
+            if "device" not in str(refused):
+                raise
+        else:
+            raise RuntimeError("the add on a device that does not exist was not refused")
+        return (time.perf_counter() - t0) * 1e3
+
+
+def run(load: str, warmup: int, repeats: int) -> dict:
+    reference, reads, ops = synthesize(load)
+    times = {k: [] for k in ("cover_ms", "reads_ms", "finish_ms", "add_wall_ms", "finish_wall_ms", "host_walk_ms")}
+    counts = {}
+    for n in range(warmup + repeats):
+        with sv.Caller(reference) as caller:
+            t0 = time.perf_counter()
+            caller.add(reads, 0, reference.shape[0])
+            t1 = time.perf_counter()
+            caller.finish()
+            t2 = time.perf_counter()
+            stats = caller.stats()
+        walk = host_walk_ms(reference, reads)
+        if n < warmup:
+            continue
+        for k in ("cover_ms", "reads_ms", "finish_ms"):
+            times[k].append(stats[k])
+        times["add_wall_ms"].append((t1 - t0) * 1e3)
+        times["finish_wall_ms"].append((t2 - t1) * 1e3)
+        times["host_walk_ms"].append(walk)
+        counts = {k: int(stats[k]) for k in sv.COUNT_NAMES}
+    return dict(load=load, reads=reads.n_reads, bases=int(reads.bases.shape[0]), operations_per_read=round(ops, 1),
+                reference_bases=int(reference.shape[0]), warmup=warmup, repeats=repeats, **counts, **{k: spread(v) for k, v in times.items()})
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("--load", choices=["short", "long", "both"], default="both")
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--profile", help="append every JSON line to this file")
+    args = ap.parse_args()
+    for load in (("short", "long") if args.load == "both" else (args.load,)):
+        line = json.dumps(run(load, args.warmup, args.repeats))
+        print(line, flush=True)
+        if args.profile:
+            with open(args.profile, "a") as fh:
+                fh.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
