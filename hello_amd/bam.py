@@ -24,12 +24,15 @@ _MOD_ARRAYS = (  # after hello_bam_fetch_mods
     ("deltas", 12, np.int32), ("probs", 13, np.uint8), ("offsets", 14, np.int64), ("mode", 15, np.uint8), ("state", 16, np.uint8),
 )
 
+_SA_ARRAYS = (("bytes", 17, np.uint8), ("offsets", 18, np.int64))  # after hello_bam_fetch_sa
+
 _PROTOTYPES = (
     ("hello_bam_open", [C.c_char_p, i32, C.POINTER(vp)]),
     ("hello_bam_n_references", [vp]),
     ("hello_bam_reference", [vp, i32, C.POINTER(C.c_char_p), C.POINTER(i64)]),
     ("hello_bam_fetch", [vp, C.c_char_p, i64, i64, i32, C.POINTER(vp)]),
     ("hello_bam_fetch_mods", [vp, C.c_char_p, i64, i64, i32, C.POINTER(vp)]),
+    ("hello_bam_fetch_sa", [vp, C.c_char_p, i64, i64, i32, C.POINTER(vp)]),
     ("hello_bam_reads_info", [vp, C.POINTER(i64), C.POINTER(i32), C.POINTER(i64)]),
     ("hello_bam_reads_array", ARRAY_GETTER),
     ("hello_bam_reads_free", [vp], None),
@@ -103,6 +106,13 @@ class Mods:
     state: np.ndarray          # uint8: 0 no modifications, 1 usable, 2 bad
 
 
+@dataclass
+class Splits:
+    """The SA tags of one region's records, read for read beside a ``Reads``."""
+    bytes: np.ndarray          # uint8: the text of every record's SA:Z tag without its NUL, all records concatenated
+    offsets: np.ndarray        # int64 [R + 1]; a record without SA, or with SA of another type, has an empty range
+
+
 class BamFile:
     """An open BAM: ``references`` from its header, ``fetch(chromosome, start, stop)`` -> ``Reads``.  Not thread-safe."""
 
@@ -127,6 +137,11 @@ class BamFile:
         """``fetch``, and the C+m calls of every record's MM / ML tags (never an error: a record's state says what was found)."""
         return self._fetch(self._lib.hello_bam_fetch_mods, chromosome, start, stop, use_index, True)
 
+    def fetch_with_sa(self, chromosome: str, start: int = 0, stop: Optional[int] = None,
+                      use_index: Optional[bool] = None) -> Tuple[Reads, Splits]:
+        """``fetch``, and the text of every record's SA tag (never an error: a record without one has an empty range)."""
+        return self._fetch(self._lib.hello_bam_fetch_sa, chromosome, start, stop, use_index, _SA_ARRAYS)
+
     def _fetch(self, entry, chromosome, start, stop, use_index, with_mods=False):
         if stop is None:
             stop = dict(self.references).get(chromosome, 0)
@@ -143,6 +158,8 @@ class BamFile:
                     marks.apply(chromosome, reads)
             if not with_mods:
                 return reads, None
+            if with_mods is _SA_ARRAYS:
+                return reads, Splits(**{field: handle_array(self._lib.hello_bam_reads_array, r, which, dtype) for field, which, dtype in _SA_ARRAYS})
             return reads, Mods(**{field: handle_array(self._lib.hello_bam_reads_array, r, which, dtype) for field, which, dtype in _MOD_ARRAYS})
         finally:
             self._lib.hello_bam_reads_free(r)

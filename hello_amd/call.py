@@ -81,7 +81,9 @@ person, and writes ``<workdir>/contamination.illumina.*`` and / or ``contaminati
 ``--sv_min_size`` bases that the reads of every BAM of the route carry as one ``D`` or ``I`` operation, on the GPU after
 ``results.output.vcf`` is complete (``hello_amd.sv``): left-aligned, clustered (``--sv_cluster_gap``,
 ``--sv_len_ratio``, ``--sv_min_support``) and genotyped against the reads that span them (``--sv_flank``).  It writes
-``<workdir>/sv.illumina.*`` and / or ``sv.pacbio.*`` (``vcf`` with symbolic ``<DEL>`` / ``<INS>`` alleles, ``npz``).  A read's haplotype
+``<workdir>/sv.illumina.*`` and / or ``sv.pacbio.*`` (``vcf`` with symbolic ``<DEL>`` / ``<INS>`` alleles, ``npz``).  With
+``--sv_split`` the SA tags of the reads are read too and the junctions of split alignments join the same clusters (``<DUP>`` and
+``<INV>`` alleles, the ``SR`` field).  A read's haplotype
 comes from ``--haplotag_vcf``, else from the phased VCF of ``--phase``, else from its HP tag; under ``--mark_duplicates`` the marked
 reads leave the pass.  Split alignments, clipped ends and discordant pairs are not looked at.
 """
@@ -362,6 +364,10 @@ def parser() -> argparse.ArgumentParser:
                          "/ sv.pacbio.* (vcf, npz); the haplotypes come from --haplotag_vcf, else --phase, else the HP tags (not in "
                          "the reference; one GPU; DESIGN.md 7p)")
     sv.add_options(ap, given_or_none=True)
+    ap.add_argument("--sv_split", action="store_true", default=False,
+                    help="with --sv: also read the SA tags of the reads and call deletions, insertions, duplications and inversions "
+                         "from split alignments; sv.*.vcf gains <DUP> and <INV> alleles and the SR field (not in the reference; "
+                         "DESIGN.md section 7q)")
     ap.add_argument("--device", type=int, default=0, help="GPU of a single-process run")
     ap.add_argument("--gpus", type=int, default=1,
                     help="processes / GPUs of this node: > 1 re-launches this command under torch.distributed.run "
@@ -636,7 +642,7 @@ def haplotag_passes(args) -> str:
     logger = logging.getLogger("hello_amd.call")
     first = argparse.Namespace(**vars(args))
     first.haplotag = first.gvcf = first.annotate = first.annotate_evidence = first.qc = first.methylation = False
-    first.contamination = first.sv = False
+    first.contamination = first.sv = first.sv_split = False
     first.qc_regions = first.qc_window = first.contamination_sites = None
     for flag in SV_OPTIONS:
         setattr(first, flag, None)
@@ -848,6 +854,9 @@ def _sv_values(args) -> Tuple[int, int, int, int, float]:
 def check_sv(args) -> None:
     """The refusals of --sv and the --sv_* options, each naming the fix."""
     if not getattr(args, "sv", False):
+        if getattr(args, "sv_split", False):
+            raise SystemExit("--sv_split adds the split alignments to the pass over large deletions and insertions and there is none in "
+                             "this run: add --sv, or drop --sv_split")
         for flag in SV_OPTIONS:
             if getattr(args, flag, None) is not None:
                 raise SystemExit(f"--{flag} is an option of the pass over large deletions and insertions and there is none in this "
@@ -883,14 +892,19 @@ def sv_pass(args, genome: Dict[str, str], result_path: str) -> List[str]:
         for bam, name in zip(route.bams, names):
             stats: dict = {}
             found = sv.measure(bam, genome, route.chromosomes or list(genome), tagger, min_size, flank, route.mapq_threshold, cluster_gap,
-                               sv.percent_of(len_ratio), min_support, device=route.device, stats=stats)
+                               sv.percent_of(len_ratio), min_support, device=route.device, stats=stats,
+                               split=bool(getattr(args, "sv_split", False)))
             written += found.write_all(os.path.join(args.workdir, "sv." + name))
             total = found.total()
             logging.getLogger("hello_amd.call").info(
                 "--sv %s: %d reads counting, %d walked, %d signatures, %d events in %.2f s (BAM decode %.2f s, kernels %.1f ms; "
                 "haplotypes from %s)", name, total["counting"], total["walked"], total["signatures"], total["candidates"],
                 stats.get("total_s", 0.0), stats.get("decode_s", 0.0),
-                sum(stats.get(k, 0.0) for k in ("cover_ms", "reads_ms", "finish_ms")), phased or "the HP tags")
+                sum(stats.get(k, 0.0) for k in sv.TIME_NAMES), phased or "the HP tags")
+            if found.split:
+                logging.getLogger("hello_amd.call").info(
+                    "--sv_split %s: %d reads with an SA tag (%d malformed, %d with more than 7 entries), %d junctions, %d rows", name,
+                    total["split_reads"], total["bad_sa"], total["too_many"], total["junctions"], total["split_signatures"])
     finally:
         if tagger is not None:
             tagger.close()

@@ -45,6 +45,9 @@ struct hello_bam_reads {
     std::vector<int32_t> mod_deltas;    // hello_bam_fetch_mods alone fills these five
     std::vector<uint8_t> mod_probs, mod_mode, mod_state;
     std::vector<int64_t> mod_off{0};
+    std::vector<uint8_t> sa_bytes;      // hello_bam_fetch_sa alone fills these two
+    std::vector<int64_t> sa_off;
+    bool with_sa = false;               // made by hello_bam_fetch_sa: the two SA selectors exist for it alone
     int32_t used_index = 0;
     int64_t blocks = 0;
 };
@@ -331,8 +334,46 @@ uint8_t find_hp_tag(const uint8_t* aux, const uint8_t* end) {
     return 0;
 }
 
+// The text of the first SA field among a record's auxiliary fields [aux, end), without its NUL: [*text, *text + n).  n = 0 where
+// there is none, where it is not of type Z, or where the fields before it cannot be walked (as for HP).
+size_t find_sa_tag(const uint8_t* aux, const uint8_t* end, const uint8_t** text) {
+    auto scalar = [](uint8_t t) -> int {
+        switch (t) {
+            case 'A': case 'c': case 'C': return 1;
+            case 's': case 'S': return 2;
+            case 'i': case 'I': case 'f': return 4;
+            default: return 0;
+        }
+    };
+    while (end - aux >= 3) {
+        const bool is_sa = aux[0] == 'S' && aux[1] == 'A';
+        const uint8_t type = aux[2];
+        aux += 3;
+        if (type == 'Z' || type == 'H') {
+            const uint8_t* z = (const uint8_t*)memchr(aux, 0, (size_t)(end - aux));
+            if (!z) break;
+            if (is_sa) { *text = aux; return type == 'Z' ? (size_t)(z - aux) : 0; }
+            aux = z + 1;
+        } else if (type == 'B') {
+            if (end - aux < 5) break;
+            const int w = scalar(aux[0]);
+            const uint32_t n = rd32(aux + 1);
+            if (is_sa || !w || (uint64_t)n * w > (uint64_t)(end - aux - 5)) break;
+            aux += 5 + (size_t)n * w;
+        } else {
+            const int w = scalar(type);
+            if (is_sa || !w || end - aux < w) break;
+            aux += w;
+        }
+    }
+    return 0;
+}
+
+enum FetchKind { kFetchPlain = 0, kFetchMods = 1, kFetchSa = 2 };
+
 // append one record (the bytes after its block_size field) to the flat arrays
-void decode(hello_bam_reads* r, const uint8_t* b, int32_t block_size, const std::string& path, bool mods = false) {
+void decode(hello_bam_reads* r, const uint8_t* b, int32_t block_size, const std::string& path, FetchKind kind = kFetchPlain) {
+    const bool mods = kind == kFetchMods;
     const int32_t pos = (int32_t)rd32(b + 4);
     const int l_name = b[8], mapq = b[9];
     const int n_cigar = rd16(b + 12), flag = rd16(b + 14);
@@ -382,6 +423,12 @@ void decode(hello_bam_reads* r, const uint8_t* b, int32_t block_size, const std:
         r->mod_off.push_back((int64_t)r->mod_deltas.size());
         r->mod_mode.push_back(m.mode);
         r->mod_state.push_back(m.state);
+    }
+    if (kind == kFetchSa) {
+        const uint8_t* text = nullptr;
+        const size_t n = find_sa_tag(b + need, b + block_size, &text);
+        if (n) r->sa_bytes.insert(r->sa_bytes.end(), text, text + n);
+        r->sa_off.push_back((int64_t)r->sa_bytes.size());
     }
 }
 
@@ -452,7 +499,7 @@ int hello_bam_reference(const hello_bam* bam, int32_t i, const char** name, int6
     return HELLO_OK;
 }
 
-static int fetch_records(hello_bam* bam, const char* chromosome, int64_t start, int64_t stop, int32_t use_index, bool mods,
+static int fetch_records(hello_bam* bam, const char* chromosome, int64_t start, int64_t stop, int32_t use_index, FetchKind kind,
                          hello_bam_reads** out, const char* entry) try {
     if (!bam || !chromosome || !out) return set_last_error(HELLO_ERR_ARG, "NULL pointer");
     *out = nullptr;
@@ -463,6 +510,10 @@ static int fetch_records(hello_bam* bam, const char* chromosome, int64_t start, 
     if (tid < 0) return set_last_error(HELLO_ERR_ARG, "%s: no reference named '%s' in its header", bam->path.c_str(), chromosome);
     auto* r = new hello_bam_reads();
     std::unique_ptr<hello_bam_reads> own(r);
+    if (kind == kFetchSa) {
+        r->with_sa = true;
+        r->sa_off.push_back(0);
+    }
     Stream s(bam->fh, bam->threads, bam->path);
     bool empty = false;
     uint64_t voff = use_index == 0 ? UINT64_MAX : index_offset(bam->path, tid, start, &empty);
@@ -490,7 +541,7 @@ static int fetch_records(hello_bam* bam, const char* chromosome, int64_t start, 
             }
             if ((flag & 4) || rlen == 0) rlen = 1;
             if (pos + rlen <= start) continue;
-            decode(r, b, block_size, bam->path, mods);
+            decode(r, b, block_size, bam->path, kind);
         }
     }
     r->blocks = s.blocks;
@@ -503,12 +554,16 @@ static int fetch_records(hello_bam* bam, const char* chromosome, int64_t start, 
 }
 
 int hello_bam_fetch(hello_bam* bam, const char* chromosome, int64_t start, int64_t stop, int32_t use_index, hello_bam_reads** out) {
-    return fetch_records(bam, chromosome, start, stop, use_index, false, out, "hello_bam_fetch");
+    return fetch_records(bam, chromosome, start, stop, use_index, kFetchPlain, out, "hello_bam_fetch");
 }
 
 int hello_bam_fetch_mods(hello_bam* bam, const char* chromosome, int64_t start, int64_t stop, int32_t use_index,
                          hello_bam_reads** out) {
-    return fetch_records(bam, chromosome, start, stop, use_index, true, out, "hello_bam_fetch_mods");
+    return fetch_records(bam, chromosome, start, stop, use_index, kFetchMods, out, "hello_bam_fetch_mods");
+}
+
+int hello_bam_fetch_sa(hello_bam* bam, const char* chromosome, int64_t start, int64_t stop, int32_t use_index, hello_bam_reads** out) {
+    return fetch_records(bam, chromosome, start, stop, use_index, kFetchSa, out, "hello_bam_fetch_sa");
 }
 
 int hello_bam_reads_info(const hello_bam_reads* reads, int64_t* n_reads, int32_t* used_index, int64_t* n_blocks) {
@@ -539,6 +594,12 @@ int hello_bam_reads_array(const hello_bam_reads* r, int32_t which, const void** 
         case HELLO_BAM_MOD_OFFSETS: *data = r->mod_off.data(); *count = (int64_t)r->mod_off.size(); break;
         case HELLO_BAM_MOD_MODE: *data = r->mod_mode.data(); *count = (int64_t)r->mod_mode.size(); break;
         case HELLO_BAM_MOD_STATE: *data = r->mod_state.data(); *count = (int64_t)r->mod_state.size(); break;
+        case HELLO_BAM_SA_BYTES:
+        case HELLO_BAM_SA_OFFSETS:
+            if (!r->with_sa) return set_last_error(HELLO_ERR_ARG, "no read array %d: hello_bam_fetch_sa alone fills it", which);
+            if (which == HELLO_BAM_SA_BYTES) { *data = r->sa_bytes.data(); *count = (int64_t)r->sa_bytes.size(); }
+            else { *data = r->sa_off.data(); *count = (int64_t)r->sa_off.size(); }
+            break;
         default: return set_last_error(HELLO_ERR_ARG, "no read array %d", which);
     }
     return HELLO_OK;

@@ -12,6 +12,7 @@ namespace hello {
 namespace {
 
 constexpr int kSvDel = 0, kSvIns = 1;
+constexpr int kSvClustered = 5;      // the types below it are clustered: DEL, INS and the three of the split alignments (sv_split.h)
 
 struct SvSig {                       // one I or D operation of a read, left-aligned: what sv_reads_kernel writes
     int64_t pos, ordinal, op_index;
@@ -29,16 +30,17 @@ inline void sv_sort(std::vector<SvSig>& sigs) {
 constexpr int kSvCandidateColumns = 13;
 struct SvCandidate {
     int64_t type, pos, len, dv, dv_fwd, dv_rev, hp[3], pos_min, pos_max, len_min, len_max;
+    int64_t sr;                      // the distinct reads with a row of a split alignment (operation index below 0): section 7q
 };
 
 // One group of signatures, ordered by (len, pos, ordinal, operation index) -> a candidate when its distinct reads number at least
 // min_support.  A read's strand and hp are the same in all its signatures, so the first of each ordinal stands for the read.
 inline void sv_group(const SvSig* g, size_t m, int64_t min_support, std::vector<SvCandidate>& out) {
     std::vector<int64_t> pos(m);
-    std::vector<std::tuple<int64_t, int, int>> reads(m);
+    std::vector<std::tuple<int64_t, int, int, int>> reads(m);    // a read's split rows sort before its others
     for (size_t i = 0; i < m; ++i) {
         pos[i] = g[i].pos;
-        reads[i] = std::make_tuple(g[i].ordinal, (int)g[i].strand, g[i].hp == 1 || g[i].hp == 2 ? (int)g[i].hp : 0);
+        reads[i] = std::make_tuple(g[i].ordinal, g[i].op_index < 0 ? 0 : 1, (int)g[i].strand, g[i].hp == 1 || g[i].hp == 2 ? (int)g[i].hp : 0);
     }
     std::sort(reads.begin(), reads.end());
     std::sort(pos.begin(), pos.end());
@@ -46,8 +48,9 @@ inline void sv_group(const SvSig* g, size_t m, int64_t min_support, std::vector<
     for (size_t i = 0; i < m; ++i) {
         if (i > 0 && std::get<0>(reads[i]) == std::get<0>(reads[i - 1])) continue;
         ++c.dv;
-        ++(std::get<1>(reads[i]) ? c.dv_rev : c.dv_fwd);
-        ++c.hp[std::get<2>(reads[i])];
+        c.sr += std::get<1>(reads[i]) == 0;
+        ++(std::get<2>(reads[i]) ? c.dv_rev : c.dv_fwd);
+        ++c.hp[std::get<3>(reads[i])];
     }
     if (c.dv < min_support) return;
     c.type = g[0].type;
@@ -66,7 +69,7 @@ inline std::vector<SvCandidate> sv_cluster(const std::vector<SvSig>& sigs, int64
     std::vector<SvCandidate> out;
     std::vector<SvSig> run;
     size_t i = 0;
-    while (i < sigs.size()) {
+    while (i < sigs.size() && sigs[i].type < kSvClustered) {
         size_t j = i + 1;
         while (j < sigs.size() && sigs[j].type == sigs[i].type && sigs[j].pos - sigs[j - 1].pos <= cluster_gap) ++j;
         run.assign(sigs.begin() + (ptrdiff_t)i, sigs.begin() + (ptrdiff_t)j);
@@ -91,7 +94,8 @@ inline std::vector<SvCandidate> sv_cluster(const std::vector<SvSig>& sigs, int64
 constexpr int kSvGenotypeColumns = 5;       // GT (0, 1, 2 for 0/0, 0/1, 1/1), GQ, PL of 0/0, 0/1, 1/1
 constexpr double kSvEpsilon = 0.05;
 
-inline int64_t sv_depth_ref(int64_t dp, int64_t dv) { return std::max<int64_t>(0, dp - dv); }
+// A supporter with a split row ends at the breakpoint and is not among the spanning reads (section 7q); with sr = 0 this is 7p's.
+inline int64_t sv_depth_ref(int64_t dp, int64_t dv, int64_t sr = 0) { return std::max<int64_t>(0, dp - (dv - sr)); }
 
 // DV reads that show the event and DR that span it without -> out[kSvGenotypeColumns].
 inline void sv_genotype(int64_t dv, int64_t dr, int64_t* out) {

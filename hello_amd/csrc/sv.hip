@@ -12,6 +12,11 @@
 //     cursor of every lane, their totals carrying into the next step.  A ballot marks the signatures; for each, in a wave-uniform
 //     loop, the whole wave tests cond(j) of the move to the left 64 at a time, and the first failing lane ends it.  Lane 0 takes a
 //     slot of the output with one returning atomicAdd: there are as many slots as sv_walk counted operations.
+//   split (hello_sv_add_split alone): a wave per counting read with an SA tag.  A ballot of ';' hands the
+//     tag's entries to lanes 1 .. 7, which parse them (sv_split.h: parse_sa_entry); the wave sums the primary's CIGAR into lane 0's
+//     segment; shuffles rank the segments along the read, a lane per pair of neighbours classifies the junction (sv_junction), and
+//     each DEL moves to the left with the loop the reads kernel uses (sv_wave_left_shift).  Lane 0 takes the rows' slots with one
+//     returning atomicAdd: the host counted at most 7 per read.  Status and junction counts go to per-read arrays.
 // and at hello_sv_finish two more:
 //   tile: a workgroup per 1 024 positions sums the difference array into a 64-bit sum; the host scans the sums.
 //   span: a wave per candidate adds its tile's prefix to the lanes' sum of diff[tile start .. pos].
@@ -21,6 +26,7 @@
 #include "read_walk.h"
 #include "stage_host.h"
 #include "sv.h"
+#include "sv_split.h"
 
 namespace hello {
 namespace {
@@ -83,6 +89,25 @@ __device__ __forceinline__ long long sv_scan(long long v, int lane) {
     return v;
 }
 
+// The move to the left of an event of n bases at reference position sp (an insertion's bases begin at bases[sq]), by the whole wave:
+// the greatest k with cond(j) for all j < k, over j < bound only.  cond(j) is tested 64 at a time and the first failing lane ends
+// it.  The caller's bounds: sp - bound >= 0 keeps every index at or above 0, and sp + n <= length (a deletion) or sp <= length
+// (an insertion, with sq + n inside the read's bases) keeps it below length.
+__device__ __forceinline__ long long sv_wave_left_shift(const uint8_t* ref, const uint8_t* bases, long long sp, long long sq, long long n,
+                                                        bool ins, long long bound, int lane) {
+    for (long long j0 = 0;; j0 += 64) {
+        const long long j = j0 + lane;
+        bool holds = false;
+        if (j < bound) {
+            const int left = ref[sp - 1 - j] & 0xDF;
+            const int right = ins && j < n ? bases[sq + n - 1 - j] : ref[sp - 1 - j + n];
+            holds = left == (right & 0xDF);
+        }
+        const unsigned long long all = __ballot(holds);
+        if (all != ~0ull) return j0 + (__ffsll((long long)~all) - 1);     // the lane at j = bound fails at the latest
+    }
+}
+
 __global__ __launch_bounds__(kSvThreads) void sv_reads_kernel(SvReadsArgs a) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int64_t k_lo = (int64_t)blockIdx.x * a.share;
@@ -115,22 +140,7 @@ __global__ __launch_bounds__(kSvThreads) void sv_reads_kernel(SvReadsArgs a) {
                 const int n = __shfl(o.n, src, 64);
                 const bool ins = __shfl(o.op, src, 64) == BAM_CINS;
                 // the move to the left: j < sp - s keeps every index at or above s >= 0; sp <= pe <= length keeps it below length
-                const long long bound = sp - s;
-                long long shift = 0;
-                for (long long j0 = 0;; j0 += 64) {
-                    const long long j = j0 + lane;
-                    bool holds = false;
-                    if (j < bound) {
-                        const int left = a.ref[sp - 1 - j] & 0xDF;
-                        const int right = ins && j < n ? bases[sq + n - 1 - j] : a.ref[sp - 1 - j + n];   // sq + n <= the read's bases
-                        holds = left == (right & 0xDF);
-                    }
-                    const unsigned long long all = __ballot(holds);
-                    if (all != ~0ull) {                                   // the lane at j = bound fails at the latest
-                        shift = j0 + (__ffsll((long long)~all) - 1);
-                        break;
-                    }
-                }
+                const long long shift = sv_wave_left_shift(a.ref, bases, sp, sq, n, ins, sp - s, lane);
                 if (lane == 0) {
                     const unsigned long long slot = atomicAdd(a.cursor, 1ull);
                     if (slot < a.capacity) {                              // always: sv_walk counted the operations
@@ -150,6 +160,210 @@ __global__ __launch_bounds__(kSvThreads) void sv_reads_kernel(SvReadsArgs a) {
             }
         }
         if (lane == 0 && any) a.seen[k] = 1;
+    }
+}
+
+struct SvSplitArgs {
+    const uint32_t* cigars;
+    const int64_t* cigar_off;
+    const int64_t* ref_start;
+    const uint8_t* mapq;
+    const uint16_t* flags;
+    const uint8_t* hp;
+    const uint8_t* sa;           // the SA texts of the reads
+    const int64_t* sa_off;       // [n_reads + 1]: validated by the host, monotone and inside `sa`
+    const int64_t* list;         // [n_list]: the split list, the counting, belonging reads with a tag
+    const int64_t* ordinal;      // [n_list]
+    int64_t n_list;
+    const uint64_t* contigs;     // [n_contigs]: FNV-1a of the names, all different
+    int n_contigs, own;
+    const uint8_t* ref;          // [length]
+    int64_t length;
+    int min_size, flank, mapq_threshold, share;
+    uint8_t* status;             // [n_list]: kSplitParsed .. kSplitTooMany
+    uint32_t* counts;            // [n_list]: junctions | dropped << 8 | small << 16 | unplaced << 24, each at most 7
+    SvSig* out;                  // [capacity]
+    unsigned long long* cursor;  // zeroed: the slots taken
+    unsigned long long capacity;
+};
+
+__device__ __forceinline__ long long sv_wave_sum(long long v) {
+    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+
+// The segment lane `src` holds (every lane may name another one).
+__device__ __forceinline__ SvSegment sv_shfl_segment(const SvSegment& g, int src) {
+    SvSegment o;
+    o.s = __shfl((long long)g.s, src, 64);
+    o.e = __shfl((long long)g.e, src, 64);
+    o.a = __shfl((long long)g.a, src, 64);
+    o.m = __shfl((long long)g.m, src, 64);
+    o.b = __shfl((long long)g.b, src, 64);
+    o.qs = __shfl((long long)g.qs, src, 64);
+    o.qe = __shfl((long long)g.qe, src, 64);
+    o.hash = 0;
+    o.tid = __shfl(g.tid, src, 64);
+    o.mapq = __shfl(g.mapq, src, 64);
+    o.strand = __shfl(g.strand, src, 64);
+    o.ok = 1;
+    return o;
+}
+
+// A wave per read of the split list.  Lane 0 holds the primary's segment, lanes 1 .. n the entries of the
+// tag in their order.  Every byte index lies inside the tag's own [t0, t1); every reference index is sv_wave_left_shift's, whose
+// bounds sv_junction guarantees: an own segment lies inside [0, length], a DEL's pos - bound is its left segment's start and its
+// pos + len the other breakpoint.
+__global__ __launch_bounds__(kSvThreads) void sv_split_kernel(SvSplitArgs a) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t k_lo = (int64_t)blockIdx.x * a.share;
+    const int64_t k_hi = k_lo + a.share < a.n_list ? k_lo + a.share : a.n_list;
+    for (int64_t k = k_lo + wave; k < k_hi; k += kSvWaves) {
+        const int64_t r = a.list[k];
+        const int64_t t0 = a.sa_off[r], t1 = a.sa_off[r + 1];             // t0 < t1: the host lists reads with a tag
+        // ---- the entries' extents: a ballot of ';' per 64 bytes, the count carrying across the steps
+        int n_semi = 0;
+        long long my_begin = t0, my_end = t0, next_begin = t0, last_semi = -1;
+        for (int64_t i0 = t0; i0 < t1; i0 += 64) {
+            const int64_t i = i0 + lane;
+            unsigned long long mask = __ballot(i < t1 && a.sa[i] == ';');
+            while (mask && n_semi < kMaxSegments - 1) {                   // wave-uniform
+                const long long at = i0 + (__ffsll((long long)mask) - 1);
+                mask &= mask - 1ull;
+                if (lane == n_semi + 1) { my_begin = next_begin; my_end = at; }
+                next_begin = at + 1;
+                last_semi = at;
+                ++n_semi;
+            }
+            if (mask) {                                                   // an eighth entry: only counted
+                n_semi += __popcll(mask);
+                last_semi = i0 + 63 - __clzll((long long)mask);
+            }
+        }
+        if (n_semi > kMaxSegments - 1 || n_semi == 0 || last_semi != t1 - 1) {
+            if (lane == 0) {
+                a.status[k] = n_semi > kMaxSegments - 1 ? kSplitTooMany : kSplitBadSa;
+                a.counts[k] = 0u;
+            }
+            continue;
+        }
+        const int n_seg = n_semi + 1;
+        // ---- the segments: lanes 1 .. n parse an entry each; the wave sums the primary's CIGAR and lane 0 takes its clips
+        SvSegment g{};
+        g.ok = 1;
+        g.tid = -1;
+        if (lane >= 1 && lane < n_seg) g = parse_sa_entry(a.sa, my_begin, my_end);
+        const int64_t c0 = a.cigar_off[r], n_ops = a.cigar_off[r + 1] - c0;
+        long long pm = 0, pr = 0, clipped = 0;
+        for (int64_t i = lane; i < n_ops; i += 64) {
+            const uint32_t c = a.cigars[c0 + i];
+            const int op = c & 15;
+            const long long n = c >> 4;
+            if (op == BAM_CMATCH || op == BAM_CEQUAL || op == BAM_CDIFF) { pm += n; pr += n; }
+            else if (op == BAM_CINS) pm += n;
+            else if (op == BAM_CDEL || op == BAM_CREF_SKIP) pr += n;
+            else if (op == BAM_CSOFT_CLIP || op == BAM_CHARD_CLIP) clipped += n;
+        }
+        pm = sv_wave_sum(pm);
+        pr = sv_wave_sum(pr);
+        clipped = sv_wave_sum(clipped);
+        if (lane == 0) {
+            int64_t i = 0, j = n_ops;
+            long long lead = 0, trail = 0;
+            for (; i < n_ops; ++i) {
+                const uint32_t c = a.cigars[c0 + i];
+                if ((c & 15) != BAM_CSOFT_CLIP && (c & 15) != BAM_CHARD_CLIP) break;
+                lead += c >> 4;
+            }
+            for (; j > i; --j) {
+                const uint32_t c = a.cigars[c0 + j - 1];
+                if ((c & 15) != BAM_CSOFT_CLIP && (c & 15) != BAM_CHARD_CLIP) break;
+                trail += c >> 4;
+            }
+            g.s = a.ref_start[r];
+            g.e = g.s + pr;
+            g.a = lead;
+            g.m = pm;
+            g.b = trail;
+            g.tid = a.own;
+            g.mapq = a.mapq[r];
+            g.strand = (a.flags[r] & 0x10) ? 1 : 0;
+            sv_orient(g);
+            g.ok = pm >= 1 && pr >= 1 && lead + trail == clipped && g.e <= a.length;
+        }
+        const long long L = __shfl((long long)(g.a + g.m + g.b), 0, 64);
+        if (lane >= 1 && lane < n_seg && g.a + g.m + g.b != L) g.ok = 0;
+        for (int e = 1; e < n_seg; ++e) {                                 // the contig of every entry: the lanes on the table
+            const unsigned long long h = __shfl((unsigned long long)g.hash, e, 64);
+            int tid = -1;
+            for (int c1 = 0; c1 < a.n_contigs && tid < 0; c1 += 64) {
+                const int c = c1 + lane;
+                const unsigned long long hit = __ballot(c < a.n_contigs && a.contigs[c] == h);
+                if (hit) tid = c1 + (__ffsll((long long)hit) - 1);
+            }
+            if (lane == e) g.tid = tid;
+        }
+        if (lane >= 1 && lane < n_seg && g.tid == a.own && g.e > a.length) g.ok = 0;
+        if (__ballot(lane < n_seg && !g.ok)) {
+            if (lane == 0) {
+                a.status[k] = kSplitBadSa;
+                a.counts[k] = 0u;
+            }
+            continue;
+        }
+        // ---- the ranks by (qs, qe, lane): at most 8 segments, all against all
+        int rank = 0;
+        for (int j = 0; j < n_seg; ++j) {
+            const long long qs = __shfl((long long)g.qs, j, 64), qe = __shfl((long long)g.qe, j, 64);
+            const bool before = qs != g.qs ? qs < g.qs : qe != g.qe ? qe < g.qe : j < lane;
+            rank += j != lane && before;
+        }
+        int holder = 0;                                                   // lane k: the lane whose segment has rank k
+        for (int j = 0; j < n_seg; ++j)
+            if (__shfl(rank, j, 64) == lane) holder = j;
+        const int next = __shfl_down(holder, 1, 64);
+        const bool mine = lane < n_seg - 1;                               // a lane per pair of neighbours
+        const SvSegment A = sv_shfl_segment(g, mine ? holder : 0), B = sv_shfl_segment(g, mine ? next : 0);
+        SvJunction j{};
+        if (mine) j = sv_junction(A, B, a.own, a.length, a.min_size, a.flank, a.mapq_threshold);
+        // ---- the move to the left of every deletion without bases between its segments
+        long long moved = 0;
+        unsigned long long todo = __ballot(mine && j.outcome == kJunctionRow && j.bound > 0);
+        while (todo) {                                                    // wave-uniform
+            const int src = __ffsll((long long)todo) - 1;
+            todo &= todo - 1ull;
+            const long long sp = __shfl((long long)j.pos, src, 64), n = __shfl((long long)j.len, src, 64);
+            const long long bound = __shfl((long long)j.bound, src, 64);
+            const long long shift = sv_wave_left_shift(a.ref, nullptr, sp, 0, n, false, bound, lane);
+            if (lane == src) moved = shift;
+        }
+        // ---- the rows: lane 0 takes the slots of all of them at once
+        const bool is_row = mine && j.outcome == kJunctionRow;
+        const unsigned long long rows = __ballot(is_row);
+        unsigned long long base = 0;
+        if (lane == 0 && rows) base = atomicAdd(a.cursor, (unsigned long long)__popcll(rows));
+        base = __shfl(base, 0, 64);
+        const unsigned long long slot = base + (unsigned long long)__popcll(rows & ((1ull << lane) - 1ull));
+        if (is_row && slot < a.capacity) {                                // always: the host counted the ';' of the tags
+            SvSig o;
+            o.pos = j.pos - moved;
+            o.ordinal = a.ordinal[k];
+            o.op_index = -(int64_t)(lane + 1);
+            o.len = (int32_t)j.len;
+            o.shift = j.type == kSvBnd ? (int32_t)j.shift : (int32_t)moved;
+            o.type = (uint8_t)j.type;
+            o.strand = (a.flags[r] & 0x10) ? 1 : 0;
+            o.hp = a.hp[r];
+            o.pad = 0;
+            a.out[slot] = o;
+        }
+        const unsigned n_dropped = (unsigned)__popcll(__ballot(mine && j.outcome == kJunctionDropped));
+        const unsigned n_small = (unsigned)__popcll(__ballot(mine && j.outcome == kJunctionSmall));
+        const unsigned n_unplaced = (unsigned)__popcll(__ballot(mine && j.outcome == kJunctionUnplaced));
+        if (lane == 0) {
+            a.status[k] = rows ? kSplitRow : kSplitParsed;
+            a.counts[k] = (unsigned)(n_seg - 1) | n_dropped << 8 | n_small << 16 | n_unplaced << 24;
+        }
     }
 }
 
@@ -203,7 +417,10 @@ struct hello_sv : hello::SpanHandle<HELLO_SV_STATS> {
     bool built = false, finished = false, sorted = true;
     std::vector<uint8_t> reference;              // until the device side is built
     std::vector<hello::SvSig> sigs;
-    std::vector<int64_t> sig_cols[hello::kSvSigColumns], cand_cols[hello::kSvCandColumns];
+    std::vector<int64_t> sig_cols[hello::kSvSigColumns], cand_cols[hello::kSvCandColumns], cand_sr;
+    std::vector<uint64_t> contigs;               // hello_sv_contigs: FNV-1a of the names; empty until then
+    int32_t own = -1;
+    std::vector<uint8_t> split_status;           // of the last add, per read
 };
 
 extern "C" {
@@ -258,21 +475,34 @@ int hello_sv_create(const uint8_t* reference, int64_t reference_length, int32_t 
     return HELLO_OK;
 } HS_ENTRY_END("hello_sv_create")
 
-int hello_sv_add(hello_sv* h, const uint8_t* bases, const uint8_t* quals, const int64_t* read_offsets, const uint32_t* cigars,
-                 const int64_t* cigar_offsets, const int64_t* ref_starts, const int64_t* ref_ends, const uint8_t* mapq,
-                 const uint16_t* flags, const uint64_t* name_hash, const uint8_t* hp, int64_t n_reads, int64_t lo, int64_t hi) try {
+// hello_sv_add (sa_offsets == nullptr) and hello_sv_add_split: refusals are thrown.
+static void sv_add(hello_sv* h, const uint8_t* bases, const uint8_t* quals, const int64_t* read_offsets, const uint32_t* cigars,
+                   const int64_t* cigar_offsets, const int64_t* ref_starts, const int64_t* ref_ends, const uint8_t* mapq,
+                   const uint16_t* flags, const uint64_t* name_hash, const uint8_t* hp, const uint8_t* sa_bytes,
+                   const int64_t* sa_offsets, int64_t n_sa_bytes, int64_t n_reads, int64_t lo, int64_t hi) {
     using namespace hello;
+    const char* entry = sa_offsets ? "hello_sv_add_split" : "hello_sv_add";
     if (!h || !read_offsets || !cigar_offsets || (n_reads > 0 && (!bases || !cigars || !ref_starts || !ref_ends || !mapq || !flags || !hp)))
-        return set_last_error(HELLO_ERR_ARG, "NULL pointer");
-    if (n_reads < 0) return set_last_error(HELLO_ERR_ARG, "negative count");
-    if (h->finished) return set_last_error(HELLO_ERR_ARG, "hello_sv_add after hello_sv_finish: the handle takes no more reads");
+        raise(HELLO_ERR_ARG, "NULL pointer");
+    if (n_reads < 0) raise(HELLO_ERR_ARG, "negative count");
+    if (h->finished) raise(HELLO_ERR_ARG, "%s after hello_sv_finish: the handle takes no more reads", entry);
+    if (sa_offsets) {
+        if (h->contigs.empty()) raise(HELLO_ERR_ARG, "hello_sv_add_split before hello_sv_contigs: the handle knows no contig names");
+        if (n_sa_bytes < 0 || (n_sa_bytes > 0 && !sa_bytes)) raise(HELLO_ERR_ARG, "%lld SA bytes", (long long)n_sa_bytes);
+        if (sa_offsets[0] < 0) raise(HELLO_ERR_ARG, "SA offsets begin at %lld", (long long)sa_offsets[0]);
+        for (int64_t r = 0; r < n_reads; ++r)
+            if (sa_offsets[r + 1] < sa_offsets[r]) raise(HELLO_ERR_ARG, "read %lld: SA offsets decrease", (long long)r);
+        if (sa_offsets[n_reads] > n_sa_bytes)
+            raise(HELLO_ERR_ARG, "SA offsets end at %lld, %lld SA bytes", (long long)sa_offsets[n_reads], (long long)n_sa_bytes);
+    }
     h->check_span(lo, hi);
 
     // ---- the reads: validated, then the kernels' lists
     const ReadsView in{bases, quals, read_offsets, cigars, cigar_offsets, ref_starts, ref_ends, mapq, flags, name_hash, n_reads};
     const SvWalk walk = sv_walk(in, lo, h->mapq_threshold, h->min_size);
-    std::vector<int64_t> list, ordinal;
-    std::vector<uint8_t> status((size_t)n_reads, 0);
+    std::vector<int64_t> list, ordinal, split_list, split_ordinal;
+    std::vector<uint8_t> status((size_t)n_reads, 0), split_status((size_t)n_reads, kSplitNone);
+    int64_t split_capacity = 0;                      // min(7, the ';' of the tag) per read of the split list: no more rows
     int64_t n_belonging = 0;
     size_t next = 0;
     for (int64_t r = 0; r < n_reads; ++r) {
@@ -283,10 +513,16 @@ int hello_sv_add(hello_sv* h, const uint8_t* bases, const uint8_t* quals, const 
             ordinal.push_back(h->counting_given + (int64_t)list.size());
             ++next;
         }
+        if (sa_offsets && sa_offsets[r + 1] > sa_offsets[r]) {
+            split_list.push_back(r);
+            split_ordinal.push_back(h->counting_given + (int64_t)list.size());
+            const int64_t n_semi = std::count(sa_bytes + sa_offsets[r], sa_bytes + sa_offsets[r + 1], (uint8_t)';');
+            split_capacity += std::min<int64_t>(kMaxSegments - 1, n_semi);
+        }
         status[(size_t)r] = 1;
         list.push_back(r);
     }
-    const int64_t n_list = (int64_t)list.size(), n_walk = (int64_t)walk.walk.size();
+    const int64_t n_list = (int64_t)list.size(), n_walk = (int64_t)walk.walk.size(), n_split = (int64_t)split_list.size();
     h->take_counting(n_list, kSvMaxReads, "cover sums");
     const int64_t share = std::min<int64_t>(kSvShare, std::max<int64_t>(kSvWaves, (n_walk + kSvGroups - 1) / kSvGroups));
     const int64_t n_blocks = (n_walk + share - 1) / share;
@@ -294,8 +530,10 @@ int hello_sv_add(hello_sv* h, const uint8_t* bases, const uint8_t* quals, const 
     sv_build(h);
     HS_HIP(hipSetDevice(h->device));
     std::vector<uint8_t> seen((size_t)n_walk, 0);
-    std::vector<SvSig> found;
-    float cover_ms = 0.0f, reads_ms = 0.0f;
+    std::vector<SvSig> found, joined;
+    std::vector<uint8_t> split_state((size_t)n_split, 0);
+    std::vector<uint32_t> split_counts((size_t)n_split, 0);
+    float cover_ms = 0.0f, reads_ms = 0.0f, split_ms = 0.0f;
     if (n_list > 0) {
         DevMem m;
         const int64_t* d_start = m.put(ref_starts, (size_t)n_reads);
@@ -337,7 +575,47 @@ int hello_sv_add(hello_sv* h, const uint8_t* bases, const uint8_t* quals, const 
             if (taken) HS_HIP(hipMemcpy(found.data(), got, (size_t)taken * sizeof(SvSig), hipMemcpyDeviceToHost));
             HS_HIP(hipMemcpy(seen.data(), a.seen, (size_t)n_walk, hipMemcpyDeviceToHost));
         }
-        h->sigs.reserve(h->sigs.size() + found.size());
+        if (n_split > 0) {                           // the split alignments: nothing of the handle is touched either
+            SvSplitArgs p{};
+            p.cigars = a.cigars ? a.cigars : m.put(cigars, (size_t)cigar_offsets[n_reads]);
+            p.cigar_off = a.cigar_off ? a.cigar_off : m.put(cigar_offsets, (size_t)n_reads + 1);
+            p.ref_start = d_start;
+            p.mapq = m.put(mapq, (size_t)n_reads);
+            p.flags = a.flags ? a.flags : m.put(flags, (size_t)n_reads);
+            p.hp = a.hp ? a.hp : m.put(hp, (size_t)n_reads);
+            p.sa = m.put(sa_bytes, (size_t)sa_offsets[n_reads]);
+            p.sa_off = m.put(sa_offsets, (size_t)n_reads + 1);
+            p.list = m.put(split_list.data(), split_list.size());
+            p.ordinal = m.put(split_ordinal.data(), split_ordinal.size());
+            p.n_list = n_split;
+            p.contigs = m.put(h->contigs.data(), h->contigs.size());
+            p.n_contigs = (int)h->contigs.size();
+            p.own = h->own;
+            p.ref = h->ref;
+            p.length = h->length;
+            p.min_size = h->min_size;
+            p.flank = h->flank;
+            p.mapq_threshold = h->mapq_threshold;
+            const int64_t part = std::min<int64_t>(kSvShare, std::max<int64_t>(kSvWaves, (n_split + kSvGroups - 1) / kSvGroups));
+            p.share = (int)part;
+            p.status = m.zeros<uint8_t>((size_t)n_split);
+            p.counts = m.zeros<uint32_t>((size_t)n_split);
+            SvSig* rows = m.room<SvSig>((size_t)split_capacity);
+            p.out = rows;
+            p.cursor = m.zeros<unsigned long long>(1);
+            p.capacity = (unsigned long long)split_capacity;
+            timer.start();
+            hipLaunchKernelGGL(sv_split_kernel, dim3((unsigned)((n_split + part - 1) / part)), dim3(kSvThreads), 0, 0, p);
+            split_ms = timer.stop();
+            unsigned long long taken = 0;
+            HS_HIP(hipMemcpy(&taken, p.cursor, sizeof(taken), hipMemcpyDeviceToHost));
+            if (taken > p.capacity) raise(HELLO_ERR_HIP, "%llu rows for %llu entries of the SA tags", taken, p.capacity);
+            joined.resize((size_t)taken);
+            if (taken) HS_HIP(hipMemcpy(joined.data(), rows, (size_t)taken * sizeof(SvSig), hipMemcpyDeviceToHost));
+            HS_HIP(hipMemcpy(split_state.data(), p.status, (size_t)n_split, hipMemcpyDeviceToHost));
+            HS_HIP(hipMemcpy(split_counts.data(), p.counts, (size_t)n_split * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        }
+        h->sigs.reserve(h->sigs.size() + found.size() + joined.size());
         SvCoverArgs c{d_start, d_end, m.put(list.data(), list.size()), n_list, h->length, h->flank, h->diff};
         timer.start();
         hipLaunchKernelGGL(sv_cover_kernel, dim3((unsigned)((n_list + kSvThreads - 1) / kSvThreads)), dim3(kSvThreads), 0, 0, c);
@@ -350,10 +628,25 @@ int hello_sv_add(hello_sv* h, const uint8_t* bases, const uint8_t* quals, const 
         status[(size_t)walk.walk[(size_t)k]] = seen[(size_t)k] ? 3 : 2;
         n_seen += seen[(size_t)k] ? 1 : 0;
     }
-    if (!found.empty()) {
+    if (!found.empty() || !joined.empty()) {
         h->sigs.insert(h->sigs.end(), found.begin(), found.end());
+        h->sigs.insert(h->sigs.end(), joined.begin(), joined.end());
         h->sorted = false;
     }
+    for (int64_t k = 0; k < n_split; ++k) {
+        const uint32_t c = split_counts[(size_t)k];
+        split_status[(size_t)split_list[(size_t)k]] = split_state[(size_t)k];
+        h->stats[11] += split_state[(size_t)k] == kSplitBadSa;
+        h->stats[12] += split_state[(size_t)k] == kSplitTooMany;
+        h->stats[13] += (double)(c & 255u);
+        h->stats[14] += (double)(c >> 8 & 255u);
+        h->stats[15] += (double)(c >> 16 & 255u);
+        h->stats[16] += (double)(c >> 24);
+    }
+    h->stats[10] += (double)n_split;
+    h->stats[17] += (double)joined.size();
+    h->stats[18] += split_ms;
+    h->split_status = std::move(split_status);
     h->status = std::move(status);
     h->counting_given += n_list;
     h->last_hi = hi;
@@ -365,8 +658,49 @@ int hello_sv_add(hello_sv* h, const uint8_t* bases, const uint8_t* quals, const 
     h->stats[5] += (double)found.size();
     h->stats[7] += cover_ms;
     h->stats[8] += reads_ms;
+}
+
+int hello_sv_add(hello_sv* h, const uint8_t* bases, const uint8_t* quals, const int64_t* read_offsets, const uint32_t* cigars,
+                 const int64_t* cigar_offsets, const int64_t* ref_starts, const int64_t* ref_ends, const uint8_t* mapq,
+                 const uint16_t* flags, const uint64_t* name_hash, const uint8_t* hp, int64_t n_reads, int64_t lo, int64_t hi) try {
+    sv_add(h, bases, quals, read_offsets, cigars, cigar_offsets, ref_starts, ref_ends, mapq, flags, name_hash, hp, nullptr, nullptr, 0,
+           n_reads, lo, hi);
     return HELLO_OK;
 } HS_ENTRY_END("hello_sv_add")
+
+int hello_sv_add_split(hello_sv* h, const uint8_t* bases, const uint8_t* quals, const int64_t* read_offsets, const uint32_t* cigars,
+                       const int64_t* cigar_offsets, const int64_t* ref_starts, const int64_t* ref_ends, const uint8_t* mapq,
+                       const uint16_t* flags, const uint64_t* name_hash, const uint8_t* hp, const uint8_t* sa_bytes,
+                       const int64_t* sa_offsets, int64_t n_sa_bytes, int64_t n_reads, int64_t lo, int64_t hi) try {
+    if (!sa_offsets) return hello::set_last_error(HELLO_ERR_ARG, "NULL pointer");
+    sv_add(h, bases, quals, read_offsets, cigars, cigar_offsets, ref_starts, ref_ends, mapq, flags, name_hash, hp, sa_bytes, sa_offsets,
+           n_sa_bytes, n_reads, lo, hi);
+    return HELLO_OK;
+} HS_ENTRY_END("hello_sv_add_split")
+
+int hello_sv_contigs(hello_sv* h, const char* const* names, int64_t n, int64_t own) try {
+    using namespace hello;
+    if (!h || !names) return set_last_error(HELLO_ERR_ARG, "NULL pointer");
+    if (n < 1 || n > INT32_MAX) return set_last_error(HELLO_ERR_ARG, "%lld contigs: at least 1", (long long)n);
+    if (own < 0 || own >= n) return set_last_error(HELLO_ERR_ARG, "own contig %lld of %lld", (long long)own, (long long)n);
+    if (!h->contigs.empty()) return set_last_error(HELLO_ERR_ARG, "hello_sv_contigs twice: the handle has its contig names");
+    std::vector<std::pair<uint64_t, std::string>> seen;
+    std::vector<uint64_t> hashes;
+    for (int64_t i = 0; i < n; ++i) {
+        if (!names[i]) return set_last_error(HELLO_ERR_ARG, "NULL pointer");
+        seen.emplace_back(sv_name_hash(names[i]), names[i]);
+        hashes.push_back(seen.back().first);
+    }
+    std::sort(seen.begin(), seen.end());
+    for (size_t i = 1; i < seen.size(); ++i) {
+        if (seen[i].first != seen[i - 1].first) continue;
+        if (seen[i].second == seen[i - 1].second) return set_last_error(HELLO_ERR_ARG, "contig '%s' twice", seen[i].second.c_str());
+        return set_last_error(HELLO_ERR_ARG, "contigs '%s' and '%s' have one FNV-1a hash", seen[i - 1].second.c_str(), seen[i].second.c_str());
+    }
+    h->contigs.swap(hashes);
+    h->own = (int32_t)own;
+    return HELLO_OK;
+} HS_ENTRY_END("hello_sv_contigs")
 
 static int sv_check_clustering(int64_t cluster_gap, int32_t len_ratio_percent, int32_t min_support) {
     using namespace hello;
@@ -377,8 +711,9 @@ static int sv_check_clustering(int64_t cluster_gap, int32_t len_ratio_percent, i
     return HELLO_OK;
 }
 
-int hello_sv_cluster(const int64_t* signatures, int64_t n, int64_t cluster_gap, int32_t len_ratio_percent, int32_t min_support,
-                     int64_t* out, int64_t* n_out) try {
+// hello_sv_cluster (types below 2, 13 columns) and hello_sv_cluster_split (types below kSvClustered, SR as the 14th).
+static int sv_cluster_rows(const int64_t* signatures, int64_t n, int64_t cluster_gap, int32_t len_ratio_percent, int32_t min_support,
+                           int64_t* out, int64_t* n_out, int n_types, int columns) {
     using namespace hello;
     if (!n_out || (n > 0 && (!signatures || !out))) return set_last_error(HELLO_ERR_ARG, "NULL pointer");
     if (n < 0) return set_last_error(HELLO_ERR_ARG, "negative count");
@@ -386,7 +721,7 @@ int hello_sv_cluster(const int64_t* signatures, int64_t n, int64_t cluster_gap, 
     std::vector<SvSig> sigs((size_t)n);
     for (int64_t i = 0; i < n; ++i) {
         const int64_t* g = signatures + i * kSvSigColumns;
-        if ((g[0] != kSvDel && g[0] != kSvIns) || g[2] < 1 || g[2] > INT32_MAX || g[6] < 0 || g[6] > 1 || g[7] < 0 || g[7] > 255)
+        if (g[0] < 0 || g[0] >= n_types || g[2] < 1 || g[2] > INT32_MAX || g[6] < 0 || g[6] > 1 || g[7] < 0 || g[7] > 255)
             return set_last_error(HELLO_ERR_ARG, "signature %lld: type %lld, len %lld, strand %lld, hp %lld", (long long)i,
                                   (long long)g[0], (long long)g[2], (long long)g[6], (long long)g[7]);
         sigs[(size_t)i] = SvSig{g[1], g[4], g[5], (int32_t)g[2], (int32_t)g[3], (uint8_t)g[0], (uint8_t)g[6], (uint8_t)g[7], 0};
@@ -395,13 +730,24 @@ int hello_sv_cluster(const int64_t* signatures, int64_t n, int64_t cluster_gap, 
     const std::vector<SvCandidate> found = sv_cluster(sigs, cluster_gap, len_ratio_percent, min_support);
     for (size_t i = 0; i < found.size(); ++i) {
         const SvCandidate& c = found[i];
-        const int64_t row[HELLO_SV_CLUSTER_COLUMNS] = {c.type, c.pos, c.len, c.dv, c.dv_fwd, c.dv_rev, c.hp[0], c.hp[1], c.hp[2],
-                                                       c.pos_min, c.pos_max, c.len_min, c.len_max};
-        std::copy(row, row + HELLO_SV_CLUSTER_COLUMNS, out + i * HELLO_SV_CLUSTER_COLUMNS);
+        const int64_t row[HELLO_SV_CLUSTER_SPLIT_COLUMNS] = {c.type, c.pos, c.len, c.dv, c.dv_fwd, c.dv_rev, c.hp[0], c.hp[1], c.hp[2],
+                                                             c.pos_min, c.pos_max, c.len_min, c.len_max, c.sr};
+        std::copy(row, row + columns, out + i * columns);
     }
     *n_out = (int64_t)found.size();
     return HELLO_OK;
+}
+
+int hello_sv_cluster(const int64_t* signatures, int64_t n, int64_t cluster_gap, int32_t len_ratio_percent, int32_t min_support,
+                     int64_t* out, int64_t* n_out) try {
+    return sv_cluster_rows(signatures, n, cluster_gap, len_ratio_percent, min_support, out, n_out, 2, HELLO_SV_CLUSTER_COLUMNS);
 } HS_ENTRY_END("hello_sv_cluster")
+
+int hello_sv_cluster_split(const int64_t* signatures, int64_t n, int64_t cluster_gap, int32_t len_ratio_percent, int32_t min_support,
+                           int64_t* out, int64_t* n_out) try {
+    return sv_cluster_rows(signatures, n, cluster_gap, len_ratio_percent, min_support, out, n_out, hello::kSvClustered,
+                           HELLO_SV_CLUSTER_SPLIT_COLUMNS);
+} HS_ENTRY_END("hello_sv_cluster_split")
 
 int hello_sv_finish(hello_sv* h, int64_t cluster_gap, int32_t len_ratio_percent, int32_t min_support) try {
     using namespace hello;
@@ -443,19 +789,21 @@ int hello_sv_finish(hello_sv* h, int64_t cluster_gap, int32_t len_ratio_percent,
         ms += timer.stop();
         HS_HIP(hipMemcpy(depth.data(), a.depth, n * sizeof(long long), hipMemcpyDeviceToHost));
     }
-    std::vector<int64_t> cols[kSvCandColumns];
+    std::vector<int64_t> cols[kSvCandColumns], sr(n);
     for (auto& c : cols) c.resize(n);
     for (size_t i = 0; i < n; ++i) {
         const SvCandidate& c = found[i];
         int64_t g[kSvGenotypeColumns];
-        const int64_t dp = (int64_t)depth[i], dr = sv_depth_ref(dp, c.dv);
+        const int64_t dp = (int64_t)depth[i], dr = sv_depth_ref(dp, c.dv, c.sr);
         sv_genotype(c.dv, dr, g);
         const int64_t row[kSvCandColumns] = {c.type, c.pos, c.len, c.dv, c.dv_fwd, c.dv_rev, c.hp[0], c.hp[1], c.hp[2], c.pos_min,
                                              c.pos_max, c.len_min, c.len_max, dp, dr, g[0], g[1], g[2], g[3], g[4]};
         for (int k = 0; k < kSvCandColumns; ++k) cols[k][i] = row[k];
+        sr[i] = c.sr;
     }
     // ---- nothing can fail from here on
     for (int k = 0; k < kSvCandColumns; ++k) h->cand_cols[k].swap(cols[k]);
+    h->cand_sr.swap(sr);
     h->finished = true;
     h->stats[6] = (double)n;
     h->stats[9] += ms;
@@ -473,6 +821,11 @@ int hello_sv_array(hello_sv* h, int32_t which, const void** data, int64_t* count
         if (!h->finished) return set_last_error(HELLO_ERR_ARG, "array selector %d before hello_sv_finish", which);
         const std::vector<int64_t>& c = h->cand_cols[which - HELLO_SV_CANDIDATES_TYPE];
         *data = c.data(); *count = (int64_t)c.size();
+    } else if (which == HELLO_SV_CANDIDATES_SR) {
+        if (!h->finished) return set_last_error(HELLO_ERR_ARG, "array selector %d before hello_sv_finish", which);
+        *data = h->cand_sr.data(); *count = (int64_t)h->cand_sr.size();
+    } else if (which == HELLO_SV_SPLIT_STATUS) {
+        *data = h->split_status.data(); *count = (int64_t)h->split_status.size();
     } else if (which == HELLO_SV_STATUS) {
         *data = h->status.data(); *count = (int64_t)h->status.size();
     } else {

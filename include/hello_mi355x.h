@@ -327,7 +327,11 @@ enum {
     HELLO_BAM_MOD_PROBS = 13,  /* uint8: its ML byte */
     HELLO_BAM_MOD_OFFSETS = 14, /* int64 [R + 1] into the two */
     HELLO_BAM_MOD_MODE = 15,   /* uint8: 0 implicit ('.' or absent), 1 unknown ('?') */
-    HELLO_BAM_MOD_STATE = 16   /* uint8: 0 no modifications, 1 usable, 2 bad */
+    HELLO_BAM_MOD_STATE = 16,  /* uint8: 0 no modifications, 1 usable, 2 bad */
+    /* after hello_bam_fetch_sa alone (after the other two fetches both selectors are refused, as every selector above 16 was
+       before them): the SA tags, DESIGN.md section 7q */
+    HELLO_BAM_SA_BYTES = 17,   /* uint8: the bytes of every record's SA:Z tag without the NUL, all records concatenated */
+    HELLO_BAM_SA_OFFSETS = 18  /* int64 [R + 1] into them; a record without SA, or with SA of another type than Z, has an empty range */
 };
 int hello_bam_open(const char* path, int32_t n_threads, hello_bam** out);
 int hello_bam_n_references(const hello_bam* bam);
@@ -337,6 +341,9 @@ int hello_bam_fetch(hello_bam* bam, const char* chromosome, int64_t start, int64
 /* hello_bam_fetch, and per record the C+m group of MM:Z with its bytes of ML:B:C (hello_amd/csrc/mods.h; never an error) */
 int hello_bam_fetch_mods(hello_bam* bam, const char* chromosome, int64_t start, int64_t stop, int32_t use_index,
                          hello_bam_reads** out);
+/* hello_bam_fetch, and per record the raw text of its SA:Z tag (never an error) */
+int hello_bam_fetch_sa(hello_bam* bam, const char* chromosome, int64_t start, int64_t stop, int32_t use_index,
+                       hello_bam_reads** out);
 int hello_bam_reads_info(const hello_bam_reads* reads, int64_t* n_reads, int32_t* used_index, int64_t* n_blocks);
 /* a pointer into `reads` (valid until hello_bam_reads_free) and its element count */
 int hello_bam_reads_array(const hello_bam_reads* reads, int32_t which, const void** data, int64_t* count);
@@ -1081,8 +1088,21 @@ int hello_contam_identity(const int64_t* r1, const int64_t* a1, const int64_t* o
  *   hello_sv_genotype: host only, no device.  `dv`, `dr`: per candidate the reads with the event and the spanning reads without;
  *          out int64 [n][HELLO_SV_GENOTYPE_COLUMNS]: GT (0, 1, 2 for 0/0, 0/1, 1/1), GQ, PL of the three.  Refused: NULL, a
  *          negative n or count.
- * Host memory in and out; sv.hip, sv.h. */
-#define HELLO_SV_STATS 10
+ * Split alignments (off unless hello_sv_add_split is called):
+ *   hello_sv_contigs: the names of the BAM header's sequences in its order and `own`, the index of the handle's chromosome among
+ *          them.  Called once, before the first hello_sv_add_split; host only.  Refused: NULL, n < 1, own outside [0, n), a name
+ *          twice, two names of one 64-bit FNV-1a hash, a second call.
+ *   hello_sv_add_split: hello_sv_add, and the junctions of the split alignments: `sa_bytes` / `sa_offsets` [n_reads + 1] are the
+ *          arrays HELLO_BAM_SA_BYTES / HELLO_BAM_SA_OFFSETS of hello_bam_fetch_sa.  Every counting, belonging read with a
+ *          non-empty tag is parsed by a wave (sv_split.h: parse_sa_entry); each pair of segments that follow each other on the
+ *          read becomes a row of the SIGNATURES columns -- DEL 0, INS 1, DUP 2, INV 3 (3' ends joined) and 4 (5' ends), BND 5
+ *          (LEN: the mate's contig index or -1, SHIFT: its breakpoint) -- with the operation index -(k + 1).  A handle may mix
+ *          the two adds, one call per span.  Refused: what hello_sv_add refuses, a handle without contigs, offsets that begin
+ *          below 0, decrease or run past n_sa_bytes.  The text itself is never a refusal: it sets the read's SPLIT_STATUS.
+ *          A refused call leaves the handle as it was.
+ *   hello_sv_cluster_split: hello_sv_cluster over the types 0 to 4, with SR (the distinct reads with a split row) as 14th column.
+ * Host memory in and out; sv.hip, sv.h, sv_split.h. */
+#define HELLO_SV_STATS 19
 #define HELLO_SV_GENOTYPE_COLUMNS 5
 enum {
     HELLO_SV_SIGNATURES_TYPE = 0,        /* 0 DEL, 1 INS */
@@ -1113,7 +1133,10 @@ enum {
     HELLO_SV_CANDIDATES_PL0 = 25,
     HELLO_SV_CANDIDATES_PL1 = 26,
     HELLO_SV_CANDIDATES_PL2 = 27,
-    HELLO_SV_STATUS = 28                 /* 0 not belonging or not counted, 1 counting, 2 walked, 3 walked with a signature */
+    HELLO_SV_STATUS = 28,                /* 0 not belonging or not counted, 1 counting, 2 walked, 3 walked with a signature */
+    HELLO_SV_CANDIDATES_SR = 29,         /* int64: the distinct supporting reads with a row of a split alignment */
+    HELLO_SV_SPLIT_STATUS = 30           /* uint8 per read of the last add: 0 no tag or not counting, 1 parsed without a row, 2 with a
+                                            row, 3 BAD_SA, 4 TOO_MANY (more than 7 entries) */
 };
 typedef struct hello_sv hello_sv;
 int hello_sv_create(const uint8_t* reference, int64_t reference_length, int32_t min_size, int32_t flank, int32_t mapq_threshold,
@@ -1124,8 +1147,9 @@ int hello_sv_add(hello_sv* sv, const uint8_t* bases, const uint8_t* quals, const
 int hello_sv_finish(hello_sv* sv, int64_t cluster_gap, int32_t len_ratio_percent, int32_t min_support);
 /* a pointer into `sv` (valid until the next hello_sv_* call on it) and its element count */
 int hello_sv_array(hello_sv* sv, int32_t which, const void** data, int64_t* count);
-/* stats[HELLO_SV_STATS]: reads given, belonging, counting, walked, walked reads with a signature, signatures, candidates, cover /
- * reads / finish kernel ms (HIP events) */
+/* stats[HELLO_SV_STATS]: reads given, belonging, counting, walked, walked reads with a signature, signatures of CIGAR operations,
+ * candidates, cover / reads / finish kernel ms (HIP events); then of hello_sv_add_split: reads with a tag, BAD_SA reads, TOO_MANY
+ * reads, junctions, junctions dropped / small / unplaced, rows of junctions, split kernel ms */
 int hello_sv_stats(const hello_sv* sv, double* stats);
 void hello_sv_free(hello_sv* sv);
 int hello_sv_genotype(const int64_t* dv, const int64_t* dr, int64_t n, int64_t* out);
@@ -1134,6 +1158,14 @@ int hello_sv_genotype(const int64_t* dv, const int64_t* dr, int64_t n, int64_t* 
 #define HELLO_SV_CLUSTER_COLUMNS 13
 int hello_sv_cluster(const int64_t* signatures, int64_t n, int64_t cluster_gap, int32_t len_ratio_percent, int32_t min_support,
                      int64_t* out, int64_t* n_out);
+#define HELLO_SV_CLUSTER_SPLIT_COLUMNS 14
+int hello_sv_cluster_split(const int64_t* signatures, int64_t n, int64_t cluster_gap, int32_t len_ratio_percent, int32_t min_support,
+                           int64_t* out, int64_t* n_out);
+int hello_sv_contigs(hello_sv* sv, const char* const* names, int64_t n, int64_t own);
+int hello_sv_add_split(hello_sv* sv, const uint8_t* bases, const uint8_t* quals, const int64_t* read_offsets, const uint32_t* cigars,
+                       const int64_t* cigar_offsets, const int64_t* ref_starts, const int64_t* ref_ends, const uint8_t* mapq,
+                       const uint16_t* flags, const uint64_t* name_hash, const uint8_t* hp, const uint8_t* sa_bytes,
+                       const int64_t* sa_offsets, int64_t n_sa_bytes, int64_t n_reads, int64_t lo, int64_t hi);
 
 #ifdef __cplusplus
 }

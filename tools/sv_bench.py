@@ -4,7 +4,12 @@ ms (HIP events, ``hello_sv_stats``), the wall ms of ``hello_sv_add`` and of ``he
 of the same reads -- the wall ms of a ``hello_sv_add`` on a handle made for a device that does not exist, which runs the span check,
 ``sv_walk`` and the kernels' lists and is refused where it opens the device.
 
-    python tools/sv_bench.py [--load short|long|both] [--warmup 2] [--repeats 7] [--profile FILE]
+    python tools/sv_bench.py [--load short|long|both|split] [--warmup 2] [--repeats 7] [--profile FILE]
+
+``--load split`` is the long load with the 300D of one read in four carried as a split alignment instead: the
+primary ends where the deletion begins and the SA tag names the rest of the read.  It reports the split kernel's ms and the wall ms
+of ``hello_sv_add_split`` beside the host's walk of the same reads, and, on the long load itself (no read has a tag), the wall ms of
+``hello_sv_add`` beside ``hello_sv_add_split`` with empty tags.
 
 --warmup untimed runs, then --repeats timed ones; prints one JSON line per load with the minimum, the median and the maximum of each
 time and, with --profile, appends it to FILE."""
@@ -20,7 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from hello_amd import sv  # noqa: E402
-from hello_amd.bam import Reads  # noqa: E402
+from hello_amd.bam import Reads, Splits  # noqa: E402
 
 M, I, D = 0, 1, 2
 
@@ -44,6 +49,8 @@ def synthesize(load: str, seed: int = 1):
         with_event = rng.random(n_reads) < 0.25
         unit = [(M, 29), (I, 1), (M, 29), (D, 1)]
         plain, event, before, grid = unit * 250 + [(M, 250)], unit * 125 + [(D, 300)] + unit * 125 + [(M, 250)], 125 * 59, 50_000
+        if load == "split":                              # the read leaves the reference where the deletion begins; the tag has the rest
+            event = unit * 125 + [(4, read_len - 125 * 59)]
     # the events lie on a grid, so that clusters form
     starts[with_event] = np.maximum((starts[with_event] + before) // grid * grid, grid) - before
     order = np.argsort(starts, kind="stable")
@@ -53,7 +60,7 @@ def synthesize(load: str, seed: int = 1):
     which = with_event.astype(np.int64)
     cigars = np.concatenate([packed[k] for k in which])
     cigar_offsets = np.concatenate([[0], np.cumsum(np.array([len(plain), len(event)])[which])]).astype(np.int64)
-    on_ref = np.array([sum(n for op, n in ops if op != I) for ops in (plain, event)], np.int64)[which]
+    on_ref = np.array([sum(n for op, n in ops if op in (M, D)) for ops in (plain, event)], np.int64)[which]
     on_read = np.array([sum(n for op, n in ops if op != D) for ops in (plain, event)], np.int64)[which]
     assert int(on_read.min()) == int(on_read.max()) == read_len
     n_bases = int(on_read.sum())
@@ -62,15 +69,22 @@ def synthesize(load: str, seed: int = 1):
                   ref_starts=starts.astype(np.int64), ref_ends=(starts + on_ref).astype(np.int64), mapq=np.full(n_reads, 60, np.uint8),
                   flags=(rng.integers(0, 2, size=n_reads) * 0x10).astype(np.uint16), name_hash=np.arange(n_reads, dtype=np.uint64),
                   strand=np.zeros(n_reads, np.uint8), hp=rng.integers(0, 3, size=n_reads).astype(np.uint8))
+    if load == "split":
+        tags = [b"chr1,%d,%s,%dS%dM,60,7;" % (s + 125 * 60 + 300 + 1, b"-" if f else b"+", 125 * 59, read_len - 125 * 59) if e else b""
+                for s, e, f in zip(starts, with_event, reads.flags)]                 # the other segment lies on the primary's strand
+        splits = Splits(np.frombuffer(b"".join(tags), np.uint8).copy(), np.concatenate([[0], np.cumsum([len(t) for t in tags])]).astype(np.int64))
+        return reference, reads, float(np.diff(cigar_offsets).mean()), splits
     return reference, reads, float(np.diff(cigar_offsets).mean())
 
 
-def host_walk_ms(reference, reads) -> float:
+def host_walk_ms(reference, reads, splits=None) -> float:
     """The wall ms of an add that is refused where it opens the device: the span check, sv_walk and the kernels' lists."""
     with sv.Caller(reference, device=1 << 20) as caller:
+        if splits is not None:
+            caller.set_contigs(["chr1", "chr2"], 0)
         t0 = time.perf_counter()
         try:
-            caller.add(reads, 0, reference.shape[0])
+            caller.add(reads, 0, reference.shape[0], splits=splits)
         except RuntimeError as refused:
             if "device" not in str(refused):
                 raise
@@ -79,7 +93,46 @@ def host_walk_ms(reference, reads) -> float:
         return (time.perf_counter() - t0) * 1e3
 
 
+def run_split(warmup: int, repeats: int) -> dict:
+    reference, reads, ops, splits = synthesize("split")
+    _, untagged, _ = synthesize("long")
+    empty = Splits(np.zeros(0, np.uint8), np.zeros(untagged.n_reads + 1, np.int64))
+    names = ("split_ms", "reads_ms", "cover_ms", "add_split_wall_ms", "host_walk_ms", "no_sa_add_wall_ms", "no_sa_add_split_wall_ms")
+    times = {k: [] for k in names}
+    counts = {}
+    for n in range(warmup + repeats):
+        with sv.Caller(reference) as caller:
+            caller.set_contigs(["chr1", "chr2"], 0)
+            t0 = time.perf_counter()
+            caller.add(reads, 0, reference.shape[0], splits=splits)
+            t1 = time.perf_counter()
+            caller.finish()
+            stats = caller.stats()
+        walk = host_walk_ms(reference, reads, splits)
+        with sv.Caller(reference) as caller:
+            t2 = time.perf_counter()
+            caller.add(untagged, 0, reference.shape[0])
+            t3 = time.perf_counter()
+        with sv.Caller(reference) as caller:
+            caller.set_contigs(["chr1", "chr2"], 0)
+            t4 = time.perf_counter()
+            caller.add(untagged, 0, reference.shape[0], splits=empty)
+            t5 = time.perf_counter()
+        if n < warmup:
+            continue
+        for k in names[:3]:
+            times[k].append(stats[k])
+        for k, v in zip(names[3:], ((t1 - t0) * 1e3, walk, (t3 - t2) * 1e3, (t5 - t4) * 1e3)):
+            times[k].append(v)
+        counts = {k: int(stats[k]) for k in sv.COUNT_NAMES + sv.SPLIT_COUNT_NAMES}
+    return dict(load="split", reads=reads.n_reads, bases=int(reads.bases.shape[0]), sa_bytes=int(splits.bytes.shape[0]),
+                operations_per_read=round(ops, 1), reference_bases=int(reference.shape[0]), warmup=warmup, repeats=repeats, **counts,
+                **{k: spread(v) for k, v in times.items()})
+
+
 def run(load: str, warmup: int, repeats: int) -> dict:
+    if load == "split":
+        return run_split(warmup, repeats)
     reference, reads, ops = synthesize(load)
     times = {k: [] for k in ("cover_ms", "reads_ms", "finish_ms", "add_wall_ms", "finish_wall_ms", "host_walk_ms")}
     counts = {}
@@ -106,7 +159,7 @@ def run(load: str, warmup: int, repeats: int) -> dict:
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
-    ap.add_argument("--load", choices=["short", "long", "both"], default="both")
+    ap.add_argument("--load", choices=["short", "long", "both", "split"], default="both")
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--profile", help="append every JSON line to this file")
