@@ -236,11 +236,14 @@ def _mapq(rng) -> int:
 
 
 @functools.lru_cache(maxsize=None)
-def corpus(seed: int, profile: str = "short", acgt_only: bool = False):
-    """-> (reference, rows sorted by position, records).  ``acgt_only``: the variant whose read bases are all upper-case ACGT."""
+def corpus(seed: int, profile: str = "short", acgt_only: bool = False, reference_of: str = None):
+    """-> (reference, rows sorted by position, records).  ``acgt_only``: the variant whose read bases are all upper-case ACGT.
+    ``reference_of``: the profile whose generator draws the reference and the records; the reads stay the profile's own, so the
+    long and the short reads of one seed can share a chromosome (tests/candidate_fuzz.py, the two-BAM route)."""
     rng = np.random.default_rng([seed, PROFILES.index(profile), 20261020])
-    reference = _reference(rng)
-    records, alleles = _records(rng, reference)
+    source = rng if reference_of is None else np.random.default_rng([seed, PROFILES.index(reference_of), 20261020])
+    reference = _reference(source)
+    records, alleles = _records(source, reference)
     planted = [{rec.start: (rec, al[h]) for rec, al in zip(records, alleles)} for h in range(2)]
     units: List[List[tuple]] = []
     name = [0]

@@ -2,6 +2,7 @@
 against the restatements of sections 7f - 7k on every seed, every rule of the oracle shown to be reached, the rows through a BAM
 file and back, and the host walks of cigar.h over every corpus as a stand-alone program under AddressSanitizer and UBSan."""
 import dataclasses
+import hashlib
 import os
 import shutil
 import subprocess
@@ -27,6 +28,21 @@ def test_census_every_situation_really_occurs():
     assert all(got[k] >= 10 for k in rf.CENSUS_CAUSES), {k: got[k] for k in rf.CENSUS_CAUSES}
     sizes = [len(rf.corpus(seed, "short")[1]) for seed in rf.SEEDS]
     assert 130 <= min(sizes) and max(sizes) <= 150 and all(10 <= len(rf.corpus(seed, "long")[1]) <= 16 for seed in rf.SEEDS)
+
+
+def test_every_corpus_is_the_pinned_one():
+    """The digest over (reference, rows, records) of all 64 corpora, computed before ``corpus`` gained ``reference_of``: with the
+    default every corpus stays byte for byte what sections 7l, 7n and 7p were tested on.  With ``reference_of="short"`` a long
+    corpus has the short one's chromosome and records and its own reads' CIGARs."""
+    h = hashlib.sha256()
+    for seed, profile in CORPORA:
+        reference, rows, records = rf.corpus(seed, profile)
+        h.update(repr((reference, rows, [(r.start, r.end, r.a, r.b, r.allele_a, r.allele_b) for r in records])).encode())
+    assert h.hexdigest() == "8bf628aa5311bb0ae2ea763db4cdaaa28fea93f13f9298a4cc796961ecd0dece"
+    for seed in (0, 7):
+        short, long_, shared = rf.corpus(seed, "short"), rf.corpus(seed, "long"), rf.corpus(seed, "long", reference_of="short")
+        assert shared[0] == short[0] and shared[2] == short[2] and shared[0] != long_[0]
+        assert all(not r[3] or len(r[4]) >= 512 for r in shared[1])         # the long profile's reads
 
 
 def test_alignment_table_is_the_plain_expansion():
