@@ -26,6 +26,8 @@ _MOD_ARRAYS = (  # after hello_bam_fetch_mods
 
 _SA_ARRAYS = (("bytes", 17, np.uint8), ("offsets", 18, np.int64))  # after hello_bam_fetch_sa
 
+_MATE_ARRAYS = (("tid", 19, np.int32), ("pos", 20, np.int64), ("tlen", 21, np.int32))  # after hello_bam_fetch_pairs, with the SA arrays
+
 _PROTOTYPES = (
     ("hello_bam_open", [C.c_char_p, i32, C.POINTER(vp)]),
     ("hello_bam_n_references", [vp]),
@@ -33,6 +35,7 @@ _PROTOTYPES = (
     ("hello_bam_fetch", [vp, C.c_char_p, i64, i64, i32, C.POINTER(vp)]),
     ("hello_bam_fetch_mods", [vp, C.c_char_p, i64, i64, i32, C.POINTER(vp)]),
     ("hello_bam_fetch_sa", [vp, C.c_char_p, i64, i64, i32, C.POINTER(vp)]),
+    ("hello_bam_fetch_pairs", [vp, C.c_char_p, i64, i64, i32, C.POINTER(vp)]),
     ("hello_bam_reads_info", [vp, C.POINTER(i64), C.POINTER(i32), C.POINTER(i64)]),
     ("hello_bam_reads_array", ARRAY_GETTER),
     ("hello_bam_reads_free", [vp], None),
@@ -113,6 +116,14 @@ class Splits:
     offsets: np.ndarray        # int64 [R + 1]; a record without SA, or with SA of another type, has an empty range
 
 
+@dataclass
+class Mates:
+    """The mate fields of one region's records, read for read beside a ``Reads``, as the records hold them."""
+    tid: np.ndarray            # int32: next_refID
+    pos: np.ndarray            # int64: next_pos, 0-based, -1 when absent
+    tlen: np.ndarray           # int32: carried, used by no rule
+
+
 class BamFile:
     """An open BAM: ``references`` from its header, ``fetch(chromosome, start, stop)`` -> ``Reads``.  Not thread-safe."""
 
@@ -142,6 +153,11 @@ class BamFile:
         """``fetch``, and the text of every record's SA tag (never an error: a record without one has an empty range)."""
         return self._fetch(self._lib.hello_bam_fetch_sa, chromosome, start, stop, use_index, _SA_ARRAYS)
 
+    def fetch_pairs(self, chromosome: str, start: int = 0, stop: Optional[int] = None,
+                    use_index: Optional[bool] = None) -> Tuple[Reads, Splits, "Mates"]:
+        """``fetch_with_sa``, and every record's mate fields (never an error: the values are what the record holds)."""
+        return self._fetch(self._lib.hello_bam_fetch_pairs, chromosome, start, stop, use_index, _MATE_ARRAYS)
+
     def _fetch(self, entry, chromosome, start, stop, use_index, with_mods=False):
         if stop is None:
             stop = dict(self.references).get(chromosome, 0)
@@ -158,6 +174,9 @@ class BamFile:
                     marks.apply(chromosome, reads)
             if not with_mods:
                 return reads, None
+            if with_mods is _MATE_ARRAYS:
+                get = lambda table: {f: handle_array(self._lib.hello_bam_reads_array, r, which, dtype) for f, which, dtype in table}  # noqa: E731
+                return reads, Splits(**get(_SA_ARRAYS)), Mates(**get(_MATE_ARRAYS))
             if with_mods is _SA_ARRAYS:
                 return reads, Splits(**{field: handle_array(self._lib.hello_bam_reads_array, r, which, dtype) for field, which, dtype in _SA_ARRAYS})
             return reads, Mods(**{field: handle_array(self._lib.hello_bam_reads_array, r, which, dtype) for field, which, dtype in _MOD_ARRAYS})

@@ -85,7 +85,10 @@ person, and writes ``<workdir>/contamination.illumina.*`` and / or ``contaminati
 ``--sv_split`` the SA tags of the reads are read too and the junctions of split alignments join the same clusters (``<DUP>`` and
 ``<INV>`` alleles, the ``SR`` field).  A read's haplotype
 comes from ``--haplotag_vcf``, else from the phased VCF of ``--phase``, else from its HP tag; under ``--mark_duplicates`` the marked
-reads leave the pass.  Split alignments, clipped ends and discordant pairs are not looked at.
+reads leave the pass.  With ``--sv_pairs`` the mate fields are read as well: discordant read pairs become rows (``<DEL>``, ``<DUP>``,
+``<INV>``; the ``PR`` field), imprecise events are called from pairs alone and the clipped ends near an event are counted (``CE``); the
+library's inner distances are sampled from the BAM or given with ``--sv_pairs_library`` (it reads the SA tags
+as ``--sv_split`` does).
 """
 from __future__ import annotations
 
@@ -364,6 +367,11 @@ def parser() -> argparse.ArgumentParser:
                          "/ sv.pacbio.* (vcf, npz); the haplotypes come from --haplotag_vcf, else --phase, else the HP tags (not in "
                          "the reference; one GPU; DESIGN.md 7p)")
     sv.add_options(ap, given_or_none=True)
+    ap.add_argument("--sv_pairs", action="store_true", default=False,
+                    help="with --sv: also read the mate fields (and the SA tags) of the reads and call deletions, duplications, inversions "
+                         "and translocation ends from discordant read pairs; sv.*.vcf gains the PR, CE, IMPRECISE and CIEND fields (not "
+                         "in the reference; DESIGN.md section 7s)")
+    sv.add_pairs_options(ap, "sv_", given_or_none=True)
     ap.add_argument("--sv_split", action="store_true", default=False,
                     help="with --sv: also read the SA tags of the reads and call deletions, insertions, duplications and inversions "
                          "from split alignments; sv.*.vcf gains <DUP> and <INV> alleles and the SR field (not in the reference; "
@@ -642,7 +650,8 @@ def haplotag_passes(args) -> str:
     logger = logging.getLogger("hello_amd.call")
     first = argparse.Namespace(**vars(args))
     first.haplotag = first.gvcf = first.annotate = first.annotate_evidence = first.qc = first.methylation = False
-    first.contamination = first.sv = first.sv_split = False
+    first.contamination = first.sv = first.sv_split = first.sv_pairs = False
+    first.sv_pairs_library = first.sv_pairs_k = first.sv_clip_min = None
     first.qc_regions = first.qc_window = first.contamination_sites = None
     for flag in SV_OPTIONS:
         setattr(first, flag, None)
@@ -851,17 +860,34 @@ def _sv_values(args) -> Tuple[int, int, int, int, float]:
     return tuple(d if getattr(args, flag, None) is None else getattr(args, flag) for flag, d in zip(SV_OPTIONS, defaults))
 
 
+SV_PAIRS_OPTIONS = ("sv_pairs_library", "sv_pairs_k", "sv_clip_min")
+
+
+def _sv_pairs_values(args) -> Tuple[int, int]:
+    """(k, clip_min): --sv_pairs_k and --sv_clip_min where given, else the defaults of ``hello_amd.sv``."""
+    from . import sv
+    k, clip_min = getattr(args, "sv_pairs_k", None), getattr(args, "sv_clip_min", None)
+    return (sv.PAIRS_K if k is None else k, sv.CLIP_MIN if clip_min is None else clip_min)
+
+
 def check_sv(args) -> None:
     """The refusals of --sv and the --sv_* options, each naming the fix."""
     if not getattr(args, "sv", False):
         if getattr(args, "sv_split", False):
             raise SystemExit("--sv_split adds the split alignments to the pass over large deletions and insertions and there is none in "
                              "this run: add --sv, or drop --sv_split")
-        for flag in SV_OPTIONS:
+        if getattr(args, "sv_pairs", False):
+            raise SystemExit("--sv_pairs adds the discordant read pairs to the pass over large deletions and insertions and there is none "
+                             "in this run: add --sv, or drop --sv_pairs")
+        for flag in SV_OPTIONS + SV_PAIRS_OPTIONS:
             if getattr(args, flag, None) is not None:
                 raise SystemExit(f"--{flag} is an option of the pass over large deletions and insertions and there is none in this "
                                  f"run: add --sv, or drop --{flag}")
         return
+    if not getattr(args, "sv_pairs", False):
+        for flag in SV_PAIRS_OPTIONS:
+            if getattr(args, flag, None) is not None:
+                raise SystemExit(f"--{flag} is an option of the read pairs and this run looks at none: add --sv_pairs, or drop --{flag}")
     if args.shards:
         raise SystemExit("--sv reads the CIGARs of the reads of the BAM(s), and shard files hold reads that were fetched and filtered "
                          "before: drop --shards and start from the BAM with --from_bam or --from_bams, or drop --sv")
@@ -873,6 +899,9 @@ def check_sv(args) -> None:
                          "drop --sv and run python -m hello_amd.sv on the BAM(s)")
     from . import sv
     sv.check_options(*_sv_values(args))
+    if getattr(args, "sv_pairs", False):
+        sv.library_option(args.sv_pairs_library, "sv_pairs_library")
+        sv.check_pairs_options(*_sv_pairs_values(args), "sv_")
 
 
 def sv_pass(args, genome: Dict[str, str], result_path: str) -> List[str]:
@@ -888,12 +917,19 @@ def sv_pass(args, genome: Dict[str, str], result_path: str) -> List[str]:
     phased = getattr(args, "haplotag_vcf", None) or (result_path[:-len(".vcf")] + ".phased.vcf" if getattr(args, "phase", False) else None)
     tagger = haplotag.Haplotagger(phased, route.chromosomes, route.q_threshold, route.mapq_threshold, route.device) if phased else None
     written: List[str] = []
+    pairs = bool(getattr(args, "sv_pairs", False))
+    pairs_k, clip_min = _sv_pairs_values(args)
     try:
         for bam, name in zip(route.bams, names):
             stats: dict = {}
-            found = sv.measure(bam, genome, route.chromosomes or list(genome), tagger, min_size, flank, route.mapq_threshold, cluster_gap,
-                               sv.percent_of(len_ratio), min_support, device=route.device, stats=stats,
-                               split=bool(getattr(args, "sv_split", False)))
+            try:
+                found = sv.measure(bam, genome, route.chromosomes or list(genome), tagger, min_size, flank, route.mapq_threshold, cluster_gap,
+                                   sv.percent_of(len_ratio), min_support, device=route.device, stats=stats,
+                                   split=bool(getattr(args, "sv_split", False)), pairs=pairs,
+                                   library=sv.library_option(getattr(args, "sv_pairs_library", None), "sv_pairs_library") if pairs else None,
+                                   k=pairs_k, clip_min=clip_min)
+            except sv.LibraryError as refused:
+                raise SystemExit("--sv_pairs %s: %s" % (name, refused)) from None
             written += found.write_all(os.path.join(args.workdir, "sv." + name))
             total = found.total()
             logging.getLogger("hello_amd.call").info(
@@ -905,6 +941,12 @@ def sv_pass(args, genome: Dict[str, str], result_path: str) -> List[str]:
                 logging.getLogger("hello_amd.call").info(
                     "--sv_split %s: %d reads with an SA tag (%d malformed, %d with more than 7 entries), %d junctions, %d rows", name,
                     total["split_reads"], total["bad_sa"], total["too_many"], total["junctions"], total["split_signatures"])
+            if found.pairs:
+                logging.getLogger("hello_amd.call").info(
+                    "--sv_pairs %s: library median %d, normal %d to %d (%s); %d pair-counted reads, %d rows (%d joined a cluster), %d "
+                    "events from pairs alone, %d reads with a clipped end, %d reads with unusable mate fields", name, *found.library,
+                    found.library_source, total["pair_reads"], total["pair_signatures"], total["pairs_assigned"],
+                    total["pair_candidates"], total["clipped_reads"], total["bad_mate"])
     finally:
         if tagger is not None:
             tagger.close()

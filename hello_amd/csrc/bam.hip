@@ -47,7 +47,10 @@ struct hello_bam_reads {
     std::vector<int64_t> mod_off{0};
     std::vector<uint8_t> sa_bytes;      // hello_bam_fetch_sa alone fills these two
     std::vector<int64_t> sa_off;
-    bool with_sa = false;               // made by hello_bam_fetch_sa: the two SA selectors exist for it alone
+    bool with_sa = false;               // made by hello_bam_fetch_sa or hello_bam_fetch_pairs: the two SA selectors exist for them alone
+    std::vector<int32_t> mate_tid, tlen;        // hello_bam_fetch_pairs alone fills these three
+    std::vector<int64_t> mate_pos;
+    bool with_pairs = false;
     int32_t used_index = 0;
     int64_t blocks = 0;
 };
@@ -369,7 +372,7 @@ size_t find_sa_tag(const uint8_t* aux, const uint8_t* end, const uint8_t** text)
     return 0;
 }
 
-enum FetchKind { kFetchPlain = 0, kFetchMods = 1, kFetchSa = 2 };
+enum FetchKind { kFetchPlain = 0, kFetchMods = 1, kFetchSa = 2, kFetchPairs = 3 };
 
 // append one record (the bytes after its block_size field) to the flat arrays
 void decode(hello_bam_reads* r, const uint8_t* b, int32_t block_size, const std::string& path, FetchKind kind = kFetchPlain) {
@@ -424,7 +427,12 @@ void decode(hello_bam_reads* r, const uint8_t* b, int32_t block_size, const std:
         r->mod_mode.push_back(m.mode);
         r->mod_state.push_back(m.state);
     }
-    if (kind == kFetchSa) {
+    if (kind == kFetchPairs) {                                       // next_refID, next_pos, tlen of the fixed core, as they stand
+        r->mate_tid.push_back((int32_t)rd32(b + 20));
+        r->mate_pos.push_back((int64_t)(int32_t)rd32(b + 24));
+        r->tlen.push_back((int32_t)rd32(b + 28));
+    }
+    if (kind == kFetchSa || kind == kFetchPairs) {
         const uint8_t* text = nullptr;
         const size_t n = find_sa_tag(b + need, b + block_size, &text);
         if (n) r->sa_bytes.insert(r->sa_bytes.end(), text, text + n);
@@ -510,10 +518,11 @@ static int fetch_records(hello_bam* bam, const char* chromosome, int64_t start, 
     if (tid < 0) return set_last_error(HELLO_ERR_ARG, "%s: no reference named '%s' in its header", bam->path.c_str(), chromosome);
     auto* r = new hello_bam_reads();
     std::unique_ptr<hello_bam_reads> own(r);
-    if (kind == kFetchSa) {
+    if (kind == kFetchSa || kind == kFetchPairs) {
         r->with_sa = true;
         r->sa_off.push_back(0);
     }
+    r->with_pairs = kind == kFetchPairs;
     Stream s(bam->fh, bam->threads, bam->path);
     bool empty = false;
     uint64_t voff = use_index == 0 ? UINT64_MAX : index_offset(bam->path, tid, start, &empty);
@@ -566,6 +575,10 @@ int hello_bam_fetch_sa(hello_bam* bam, const char* chromosome, int64_t start, in
     return fetch_records(bam, chromosome, start, stop, use_index, kFetchSa, out, "hello_bam_fetch_sa");
 }
 
+int hello_bam_fetch_pairs(hello_bam* bam, const char* chromosome, int64_t start, int64_t stop, int32_t use_index, hello_bam_reads** out) {
+    return fetch_records(bam, chromosome, start, stop, use_index, kFetchPairs, out, "hello_bam_fetch_pairs");
+}
+
 int hello_bam_reads_info(const hello_bam_reads* reads, int64_t* n_reads, int32_t* used_index, int64_t* n_blocks) {
     if (!reads) return set_last_error(HELLO_ERR_ARG, "NULL pointer");
     if (n_reads) *n_reads = (int64_t)reads->ref_start.size();
@@ -596,9 +609,17 @@ int hello_bam_reads_array(const hello_bam_reads* r, int32_t which, const void** 
         case HELLO_BAM_MOD_STATE: *data = r->mod_state.data(); *count = (int64_t)r->mod_state.size(); break;
         case HELLO_BAM_SA_BYTES:
         case HELLO_BAM_SA_OFFSETS:
-            if (!r->with_sa) return set_last_error(HELLO_ERR_ARG, "no read array %d: hello_bam_fetch_sa alone fills it", which);
+            if (!r->with_sa) return set_last_error(HELLO_ERR_ARG, "no read array %d: hello_bam_fetch_sa alone fills it (and hello_bam_fetch_pairs)", which);
             if (which == HELLO_BAM_SA_BYTES) { *data = r->sa_bytes.data(); *count = (int64_t)r->sa_bytes.size(); }
             else { *data = r->sa_off.data(); *count = (int64_t)r->sa_off.size(); }
+            break;
+        case HELLO_BAM_MATE_TID:
+        case HELLO_BAM_MATE_POS:
+        case HELLO_BAM_TLEN:
+            if (!r->with_pairs) return set_last_error(HELLO_ERR_ARG, "no read array %d: hello_bam_fetch_pairs alone fills it", which);
+            if (which == HELLO_BAM_MATE_TID) { *data = r->mate_tid.data(); *count = (int64_t)r->mate_tid.size(); }
+            else if (which == HELLO_BAM_MATE_POS) { *data = r->mate_pos.data(); *count = (int64_t)r->mate_pos.size(); }
+            else { *data = r->tlen.data(); *count = (int64_t)r->tlen.size(); }
             break;
         default: return set_last_error(HELLO_ERR_ARG, "no read array %d", which);
     }

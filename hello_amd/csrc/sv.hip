@@ -17,15 +17,21 @@
 //     segment; shuffles rank the segments along the read, a lane per pair of neighbours classifies the junction (sv_junction), and
 //     each DEL moves to the left with the loop the reads kernel uses (sv_wave_left_shift).  Lane 0 takes the rows' slots with one
 //     returning atomicAdd: the host counted at most 7 per read.  Status and junction counts go to per-read arrays.
+//   pairs (hello_sv_add_pairs alone): a lane per read.  The host has marked the pair-counted reads with valid
+//     mate fields and the reads whose clips count; sv_pair_classify (sv_pairs.h) turns own and mate fields into an outcome.  The
+//     workgroup counts the inner distances in 4 096 LDS counters and flushes the non-zero ones to the 64-bit histogram once; a
+//     ballot of "emits a row" and one returning atomicAdd per wave hand out the rows' slots; the clips add to two int32 arrays.
 // and at hello_sv_finish two more:
 //   tile: a workgroup per 1 024 positions sums the difference array into a 64-bit sum; the host scans the sums.
 //   span: a wave per candidate adds its tile's prefix to the lanes' sum of diff[tile start .. pos].
+//   clips (with pairs): a wave per candidate sums the two clip arrays over the windows around its two ends.
 // The cover is an integer sum and the signatures are sorted by the host before anyone sees them: two runs give the same bytes.
 #include <memory>
 
 #include "read_walk.h"
 #include "stage_host.h"
 #include "sv.h"
+#include "sv_pairs.h"
 #include "sv_split.h"
 
 namespace hello {
@@ -367,6 +373,76 @@ __global__ __launch_bounds__(kSvThreads) void sv_split_kernel(SvSplitArgs a) {
     }
 }
 
+struct SvPairsArgs {
+    const uint32_t* cigars;
+    const int64_t* cigar_off;
+    const int64_t* ref_start;
+    const int64_t* ref_end;
+    const uint16_t* flags;
+    const uint8_t* hp;
+    const int32_t* mate_tid;
+    const int64_t* mate_pos;
+    const uint8_t* todo;         // [n_reads]: kPairClassify | kPairClips, by the host's checks
+    int64_t n_reads, n_contigs;
+    int own, min_size, clip_min;
+    SvLibrary lib;
+    unsigned long long* inner;   // [kInnerBins]
+    int* clip_left;              // [length + 1]
+    int* clip_right;             // [length + 1]
+    uint8_t* status;             // [n_reads]: PAIR_STATUS | clips << 4
+    SvSig* out;                  // [capacity]
+    unsigned long long* cursor;  // zeroed: the slots taken
+    unsigned long long capacity;
+};
+
+// A lane per read.  Every lane reaches both barriers.  The indices: a bin is clamped by sv_pair_classify;
+// s and e of a kPairClips read lie inside [0, length] by the host's walk; a slot is below capacity by the guard.
+__global__ __launch_bounds__(kSvThreads) void sv_pairs_kernel(SvPairsArgs a) {
+    __shared__ int inner[kInnerBins];
+    const int lane = threadIdx.x & 63;
+    for (int b = threadIdx.x; b < kInnerBins; b += kSvThreads) inner[b] = 0;
+    __syncthreads();
+    const int64_t r = (int64_t)blockIdx.x * kSvThreads + threadIdx.x;
+    const uint8_t todo = r < a.n_reads ? a.todo[r] : 0;
+    SvPairOutcome o;
+    if (todo & kPairClassify) {
+        o = sv_pair_classify(a.flags[r], a.ref_start[r], a.ref_end[r], a.own, a.mate_tid[r], a.mate_pos[r], a.n_contigs, a.lib, a.min_size);
+        if (o.inner) atomicAdd(&inner[o.bin], 1);
+    }
+    int clips = 0;
+    if (todo & kPairClips) {
+        const int64_t c0 = a.cigar_off[r];
+        clips = sv_clips(a.cigars + c0, a.cigar_off[r + 1] - c0, a.clip_min);
+        if (clips & 1) atomicAdd(a.clip_right + a.ref_start[r], 1);
+        if (clips & 2) atomicAdd(a.clip_left + a.ref_end[r], 1);
+    }
+    const bool is_row = o.status == kPairRow || o.status == kPairBndRow;
+    const unsigned long long rows = __ballot(is_row);
+    unsigned long long base = 0;
+    if (lane == 0 && rows) base = atomicAdd(a.cursor, (unsigned long long)__popcll(rows));
+    base = __shfl(base, 0, 64);
+    const unsigned long long slot = base + (unsigned long long)__popcll(rows & ((1ull << lane) - 1ull));
+    if (is_row && slot < a.capacity) {                                    // always: a slot per kPairClassify read
+        SvSig g;
+        g.pos = o.pos;
+        g.ordinal = r;                                                    // the read: the host puts its pair ordinal here
+        g.op_index = kPairOp;
+        g.len = (int32_t)o.len;
+        g.shift = (int32_t)o.shift;
+        g.type = (uint8_t)o.type;
+        g.strand = (a.flags[r] & 0x10) ? 1 : 0;
+        g.hp = a.hp[r];
+        g.pad = 0;
+        a.out[slot] = g;
+    }
+    if (r < a.n_reads) a.status[r] = (uint8_t)(o.status | clips << 4);
+    __syncthreads();
+    for (int b = threadIdx.x; b < kInnerBins; b += kSvThreads) {
+        const int n = inner[b];
+        if (n) atomicAdd(a.inner + b, (unsigned long long)n);
+    }
+}
+
 struct SvSpanArgs {
     const int* diff;             // [length + 1]
     int64_t n_diff, n_tiles;
@@ -404,6 +480,28 @@ __global__ __launch_bounds__(kSvThreads) void sv_span_kernel(SvSpanArgs a) {
     if (lane == 0) a.depth[c] = a.tile_sum[tile] + sum;
 }
 
+struct SvClipArgs {
+    const int* clip_left;        // [length + 1]
+    const int* clip_right;
+    const int64_t* pos;          // [n_candidates]
+    const int64_t* end;
+    int64_t n_candidates, length;
+    int flank;
+    long long* ce;               // [n_candidates]
+};
+
+__global__ __launch_bounds__(kSvThreads) void sv_clips_kernel(SvClipArgs a) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t c = (int64_t)blockIdx.x * kSvWaves + wave;
+    if (c >= a.n_candidates) return;                                      // the whole wave
+    const SvClipWindows w = sv_clip_windows(a.pos[c], a.end[c], a.flank, a.length);     // inside [0, length]
+    long long sum = 0;
+    for (int64_t j = w.lo1 + lane; j <= w.hi1; j += 64) sum += (long long)a.clip_left[j] + a.clip_right[j];
+    for (int64_t j = w.lo2 + lane; j <= w.hi2; j += 64) sum += (long long)a.clip_left[j] + a.clip_right[j];
+    for (int d = 32; d > 0; d >>= 1) sum += __shfl_down(sum, d, 64);
+    if (lane == 0) a.ce[c] = sum;
+}
+
 constexpr int kSvSigColumns = 8, kSvCandColumns = 20;
 
 }  // namespace
@@ -421,6 +519,19 @@ struct hello_sv : hello::SpanHandle<HELLO_SV_STATS> {
     std::vector<uint64_t> contigs;               // hello_sv_contigs: FNV-1a of the names; empty until then
     int32_t own = -1;
     std::vector<uint8_t> split_status;           // of the last add, per read
+    // ---- discordant pairs and clipped ends
+    bool has_library = false, pairs_built = false;
+    hello::SvLibrary library;
+    int32_t clip_min = 20;
+    int64_t pairs_given = 0;                     // the belonging pair-counted reads so far: the ordinal of the next
+    int64_t pairs_given_adds = 0;                // the calls of hello_sv_add_pairs that passed
+    unsigned long long* inner = nullptr;         // [kInnerBins]
+    int* clip_left = nullptr;                    // [length + 1]
+    int* clip_right = nullptr;
+    std::vector<uint8_t> pair_status;            // of the last add, per read
+    std::vector<int64_t> inner_host, cand_pairs[5];      // PR, CE, END_MIN, END_MAX, IMPRECISE
+    std::vector<int32_t> clip_host[2];
+    double pair_stats[hello::kPairStats] = {0};
 };
 
 extern "C" {
@@ -439,6 +550,23 @@ static void sv_build(hello_sv* h) {
     h->diff = diff;
     std::vector<uint8_t>().swap(h->reference);
     h->built = true;
+}
+
+// The device side of the pairs, built when the first hello_sv_add_pairs has passed its checks.
+static void sv_build_pairs(hello_sv* h) {
+    using namespace hello;
+    if (h->pairs_built) return;
+    DevMem keep;
+    unsigned long long* inner = keep.zeros<unsigned long long>(kInnerBins);
+    int* left = keep.zeros<int>((size_t)h->length + 1);
+    int* right = keep.zeros<int>((size_t)h->length + 1);
+    // ---- nothing can fail from here on
+    h->mem.ptrs.insert(h->mem.ptrs.end(), keep.ptrs.begin(), keep.ptrs.end());
+    keep.ptrs.clear();
+    h->inner = inner;
+    h->clip_left = left;
+    h->clip_right = right;
+    h->pairs_built = true;
 }
 
 // The SIGNATURES columns of the handle, in sv_sort's order.
@@ -475,19 +603,20 @@ int hello_sv_create(const uint8_t* reference, int64_t reference_length, int32_t 
     return HELLO_OK;
 } HS_ENTRY_END("hello_sv_create")
 
-// hello_sv_add (sa_offsets == nullptr) and hello_sv_add_split: refusals are thrown.
+// hello_sv_add (sa_offsets == nullptr), hello_sv_add_split and hello_sv_add_pairs (mate_tid != nullptr): refusals are thrown.
 static void sv_add(hello_sv* h, const uint8_t* bases, const uint8_t* quals, const int64_t* read_offsets, const uint32_t* cigars,
                    const int64_t* cigar_offsets, const int64_t* ref_starts, const int64_t* ref_ends, const uint8_t* mapq,
                    const uint16_t* flags, const uint64_t* name_hash, const uint8_t* hp, const uint8_t* sa_bytes,
-                   const int64_t* sa_offsets, int64_t n_sa_bytes, int64_t n_reads, int64_t lo, int64_t hi) {
+                   const int64_t* sa_offsets, int64_t n_sa_bytes, int64_t n_reads, int64_t lo, int64_t hi,
+                   const int32_t* mate_tid = nullptr, const int64_t* mate_pos = nullptr) {
     using namespace hello;
-    const char* entry = sa_offsets ? "hello_sv_add_split" : "hello_sv_add";
+    const char* entry = mate_tid ? "hello_sv_add_pairs" : sa_offsets ? "hello_sv_add_split" : "hello_sv_add";
     if (!h || !read_offsets || !cigar_offsets || (n_reads > 0 && (!bases || !cigars || !ref_starts || !ref_ends || !mapq || !flags || !hp)))
         raise(HELLO_ERR_ARG, "NULL pointer");
     if (n_reads < 0) raise(HELLO_ERR_ARG, "negative count");
     if (h->finished) raise(HELLO_ERR_ARG, "%s after hello_sv_finish: the handle takes no more reads", entry);
     if (sa_offsets) {
-        if (h->contigs.empty()) raise(HELLO_ERR_ARG, "hello_sv_add_split before hello_sv_contigs: the handle knows no contig names");
+        if (h->contigs.empty()) raise(HELLO_ERR_ARG, "%s before hello_sv_contigs: the handle knows no contig names", entry);
         if (n_sa_bytes < 0 || (n_sa_bytes > 0 && !sa_bytes)) raise(HELLO_ERR_ARG, "%lld SA bytes", (long long)n_sa_bytes);
         if (sa_offsets[0] < 0) raise(HELLO_ERR_ARG, "SA offsets begin at %lld", (long long)sa_offsets[0]);
         for (int64_t r = 0; r < n_reads; ++r)
@@ -495,6 +624,8 @@ static void sv_add(hello_sv* h, const uint8_t* bases, const uint8_t* quals, cons
         if (sa_offsets[n_reads] > n_sa_bytes)
             raise(HELLO_ERR_ARG, "SA offsets end at %lld, %lld SA bytes", (long long)sa_offsets[n_reads], (long long)n_sa_bytes);
     }
+    if (mate_tid && !h->has_library)
+        raise(HELLO_ERR_ARG, "hello_sv_add_pairs before hello_sv_library: the handle knows no insert sizes");
     h->check_span(lo, hi);
 
     // ---- the reads: validated, then the kernels' lists
@@ -524,32 +655,53 @@ static void sv_add(hello_sv* h, const uint8_t* bases, const uint8_t* quals, cons
     }
     const int64_t n_list = (int64_t)list.size(), n_walk = (int64_t)walk.walk.size(), n_split = (int64_t)split_list.size();
     h->take_counting(n_list, kSvMaxReads, "cover sums");
+    // ---- the pairs: what the kernel may classify and whose clips count, by the host's checks alone (sv_pairs.h)
+    SvPairMarks marks;
+    if (mate_tid) marks = sv_pairs_mark(in, walk.kind, sa_offsets, mate_tid, mate_pos, h->own, h->length, h->mapq_threshold, h->pairs_given);
+    std::vector<uint8_t>&pair_todo = marks.todo, &pair_state = marks.state;
+    std::vector<int64_t>& pair_ordinal = marks.ordinal;
+    const int64_t n_pair_reads = marks.n_pair_reads, n_bad_mate = marks.n_bad_mate, n_classify = marks.n_classify, n_pair_work = marks.n_work;
+    // room for every row this add can give, so that no insert below the kernels can fail; grown by doubling
+    const size_t need = h->sigs.size() + (size_t)walk.n_ops + (size_t)split_capacity + (size_t)n_classify;
+    if (need > h->sigs.capacity()) h->sigs.reserve(std::max(need, 2 * h->sigs.capacity()));
     const int64_t share = std::min<int64_t>(kSvShare, std::max<int64_t>(kSvWaves, (n_walk + kSvGroups - 1) / kSvGroups));
     const int64_t n_blocks = (n_walk + share - 1) / share;
 
     sv_build(h);
     HS_HIP(hipSetDevice(h->device));
+    if (mate_tid) sv_build_pairs(h);
+    std::vector<SvSig> paired;
+    float pairs_ms = 0.0f;
     std::vector<uint8_t> seen((size_t)n_walk, 0);
     std::vector<SvSig> found, joined;
     std::vector<uint8_t> split_state((size_t)n_split, 0);
     std::vector<uint32_t> split_counts((size_t)n_split, 0);
     float cover_ms = 0.0f, reads_ms = 0.0f, split_ms = 0.0f;
+    // One copy of a per-read array on the device for all the kernels of this add: uploaded by the first that needs it.
+    DevMem m;
+    const int64_t *d_start = nullptr, *d_end = nullptr, *d_cigar_off = nullptr;
+    const uint32_t* d_cigars = nullptr;
+    const uint16_t* d_flags = nullptr;
+    const uint8_t* d_hp = nullptr;
+    auto shared = [&m](auto*& on_device, auto* host, size_t n) {
+        if (!on_device) on_device = m.put(host, n);
+        return on_device;
+    };
+    const size_t n_cigar_ops = (size_t)cigar_offsets[n_reads];
     if (n_list > 0) {
-        DevMem m;
-        const int64_t* d_start = m.put(ref_starts, (size_t)n_reads);
-        const int64_t* d_end = m.put(ref_ends, (size_t)n_reads);
+        shared(d_start, ref_starts, (size_t)n_reads);
+        shared(d_end, ref_ends, (size_t)n_reads);
         SvReadsArgs a{};
         SvSig* got = nullptr;
         if (n_walk > 0) {                            // every upload before the first kernel: a failure leaves the cover as it was
-            const size_t nb = (size_t)read_offsets[n_reads], nc = (size_t)cigar_offsets[n_reads];
-            a.bases = m.put(bases, nb);
+            a.bases = m.put(bases, (size_t)read_offsets[n_reads]);
             a.read_off = m.put(read_offsets, (size_t)n_reads + 1);
-            a.cigars = m.put(cigars, nc);
-            a.cigar_off = m.put(cigar_offsets, (size_t)n_reads + 1);
+            a.cigars = shared(d_cigars, cigars, n_cigar_ops);
+            a.cigar_off = shared(d_cigar_off, cigar_offsets, (size_t)n_reads + 1);
             a.ref_start = d_start;
             a.ref_end = d_end;
-            a.flags = m.put(flags, (size_t)n_reads);
-            a.hp = m.put(hp, (size_t)n_reads);
+            a.flags = shared(d_flags, flags, (size_t)n_reads);
+            a.hp = shared(d_hp, hp, (size_t)n_reads);
             a.list = m.put(walk.walk.data(), walk.walk.size());
             a.ordinal = m.put(ordinal.data(), ordinal.size());
             a.seen = m.zeros<uint8_t>((size_t)n_walk);
@@ -577,12 +729,12 @@ static void sv_add(hello_sv* h, const uint8_t* bases, const uint8_t* quals, cons
         }
         if (n_split > 0) {                           // the split alignments: nothing of the handle is touched either
             SvSplitArgs p{};
-            p.cigars = a.cigars ? a.cigars : m.put(cigars, (size_t)cigar_offsets[n_reads]);
-            p.cigar_off = a.cigar_off ? a.cigar_off : m.put(cigar_offsets, (size_t)n_reads + 1);
+            p.cigars = shared(d_cigars, cigars, n_cigar_ops);
+            p.cigar_off = shared(d_cigar_off, cigar_offsets, (size_t)n_reads + 1);
             p.ref_start = d_start;
             p.mapq = m.put(mapq, (size_t)n_reads);
-            p.flags = a.flags ? a.flags : m.put(flags, (size_t)n_reads);
-            p.hp = a.hp ? a.hp : m.put(hp, (size_t)n_reads);
+            p.flags = shared(d_flags, flags, (size_t)n_reads);
+            p.hp = shared(d_hp, hp, (size_t)n_reads);
             p.sa = m.put(sa_bytes, (size_t)sa_offsets[n_reads]);
             p.sa_off = m.put(sa_offsets, (size_t)n_reads + 1);
             p.list = m.put(split_list.data(), split_list.size());
@@ -615,11 +767,56 @@ static void sv_add(hello_sv* h, const uint8_t* bases, const uint8_t* quals, cons
             HS_HIP(hipMemcpy(split_state.data(), p.status, (size_t)n_split, hipMemcpyDeviceToHost));
             HS_HIP(hipMemcpy(split_counts.data(), p.counts, (size_t)n_split * sizeof(uint32_t), hipMemcpyDeviceToHost));
         }
-        h->sigs.reserve(h->sigs.size() + found.size() + joined.size());
         SvCoverArgs c{d_start, d_end, m.put(list.data(), list.size()), n_list, h->length, h->flank, h->diff};
         timer.start();
         hipLaunchKernelGGL(sv_cover_kernel, dim3((unsigned)((n_list + kSvThreads - 1) / kSvThreads)), dim3(kSvThreads), 0, 0, c);
         cover_ms = timer.stop();
+    }
+    // The pairs come last, like the cover: only a failing HIP call can stop them, and the handle is of no use after one.
+    if (n_pair_work > 0) {                           // a span without a paired or a clipped read launches nothing
+        SvPairsArgs p{};                             // the reads' arrays are those the kernels above uploaded, where they did
+        p.cigars = shared(d_cigars, cigars, n_cigar_ops);
+        p.cigar_off = shared(d_cigar_off, cigar_offsets, (size_t)n_reads + 1);
+        p.ref_start = shared(d_start, ref_starts, (size_t)n_reads);
+        p.ref_end = shared(d_end, ref_ends, (size_t)n_reads);
+        p.flags = shared(d_flags, flags, (size_t)n_reads);
+        p.hp = shared(d_hp, hp, (size_t)n_reads);
+        p.mate_tid = m.put(mate_tid, (size_t)n_reads);
+        p.mate_pos = m.put(mate_pos, (size_t)n_reads);
+        p.todo = m.put(pair_todo.data(), (size_t)n_reads);
+        p.n_reads = n_reads;
+        p.n_contigs = (int64_t)h->contigs.size();
+        p.own = h->own;
+        p.min_size = h->min_size;
+        p.clip_min = h->clip_min;
+        p.lib = h->library;
+        p.inner = h->inner;
+        p.clip_left = h->clip_left;
+        p.clip_right = h->clip_right;
+        p.status = m.zeros<uint8_t>((size_t)n_reads);
+        SvSig* rows = m.room<SvSig>((size_t)n_classify);
+        p.out = rows;
+        p.cursor = m.zeros<unsigned long long>(1);
+        p.capacity = (unsigned long long)n_classify;
+        std::vector<uint8_t> state((size_t)n_reads);
+        paired.reserve((size_t)n_classify);
+        KernelTimer timer;
+        timer.start();
+        hipLaunchKernelGGL(sv_pairs_kernel, dim3((unsigned)((n_reads + kSvThreads - 1) / kSvThreads)), dim3(kSvThreads), 0, 0, p);
+        pairs_ms = timer.stop();
+        unsigned long long taken = 0;
+        HS_HIP(hipMemcpy(&taken, p.cursor, sizeof(taken), hipMemcpyDeviceToHost));
+        if (taken > p.capacity) raise(HELLO_ERR_HIP, "%llu pair rows for %llu pair-counted reads", taken, p.capacity);
+        paired.resize((size_t)taken);
+        if (taken) HS_HIP(hipMemcpy(paired.data(), rows, (size_t)taken * sizeof(SvSig), hipMemcpyDeviceToHost));
+        for (SvSig& g : paired) {                    // the kernel names the read; its ordinal is the host's
+            if (g.ordinal < 0 || g.ordinal >= n_reads) raise(HELLO_ERR_HIP, "a pair row of read %lld of %lld", (long long)g.ordinal, (long long)n_reads);
+            g.ordinal = pair_ordinal[(size_t)g.ordinal];
+        }
+        HS_HIP(hipMemcpy(state.data(), p.status, (size_t)n_reads, hipMemcpyDeviceToHost));
+        for (int64_t r = 0; r < n_reads; ++r)
+            if (pair_todo[(size_t)r] & kPairClassify) pair_state[(size_t)r] = state[(size_t)r];
+            else if (pair_todo[(size_t)r]) pair_state[(size_t)r] |= state[(size_t)r] & 0xF0;        // a BAD_MATE read's clips still count
     }
 
     // ---- nothing can fail from here on
@@ -628,10 +825,35 @@ static void sv_add(hello_sv* h, const uint8_t* bases, const uint8_t* quals, cons
         status[(size_t)walk.walk[(size_t)k]] = seen[(size_t)k] ? 3 : 2;
         n_seen += seen[(size_t)k] ? 1 : 0;
     }
-    if (!found.empty() || !joined.empty()) {
+    if (!found.empty() || !joined.empty() || !paired.empty()) {
         h->sigs.insert(h->sigs.end(), found.begin(), found.end());
         h->sigs.insert(h->sigs.end(), joined.begin(), joined.end());
+        h->sigs.insert(h->sigs.end(), paired.begin(), paired.end());
         h->sorted = false;
+    }
+    if (mate_tid) {                                  // the statistics of the pairs: reduced here from the per-read outcomes
+        double* st = h->pair_stats;
+        for (int64_t r = 0; r < n_reads; ++r) {
+            const uint8_t state = pair_state[(size_t)r] & 15;
+            const bool same = state >= kPairNormal && state <= kPairRow && state != kPairUnplaced;
+            st[1] += same;                           // pairs_left
+            st[2] += state == kPairRight;
+            st[3] += state == kPairNormal;
+            st[4] += state == kPairShort;
+            st[5] += state == kPairSmall;
+            st[6] += state == kPairUnplaced;
+            st[9] += (pair_state[(size_t)r] >> 4) != 0;     // clipped_reads
+            pair_state[(size_t)r] = state;
+        }
+        st[0] += (double)n_pair_reads;
+        st[7] += (double)n_bad_mate;
+        st[8] += (double)paired.size();
+        st[12] += pairs_ms;
+        h->pairs_given += n_pair_reads;
+        ++h->pairs_given_adds;
+        h->pair_status = std::move(pair_state);
+    } else {
+        h->pair_status.assign((size_t)n_reads, kPairNone);
     }
     for (int64_t k = 0; k < n_split; ++k) {
         const uint32_t c = split_counts[(size_t)k];
@@ -677,6 +899,38 @@ int hello_sv_add_split(hello_sv* h, const uint8_t* bases, const uint8_t* quals, 
            n_sa_bytes, n_reads, lo, hi);
     return HELLO_OK;
 } HS_ENTRY_END("hello_sv_add_split")
+
+int hello_sv_add_pairs(hello_sv* h, const uint8_t* bases, const uint8_t* quals, const int64_t* read_offsets, const uint32_t* cigars,
+                       const int64_t* cigar_offsets, const int64_t* ref_starts, const int64_t* ref_ends, const uint8_t* mapq,
+                       const uint16_t* flags, const uint64_t* name_hash, const uint8_t* hp, const uint8_t* sa_bytes,
+                       const int64_t* sa_offsets, int64_t n_sa_bytes, const int32_t* mate_tid, const int64_t* mate_pos, int64_t n_reads,
+                       int64_t lo, int64_t hi) try {
+    if (!sa_offsets || !mate_tid || !mate_pos) return hello::set_last_error(HELLO_ERR_ARG, "NULL pointer");
+    sv_add(h, bases, quals, read_offsets, cigars, cigar_offsets, ref_starts, ref_ends, mapq, flags, name_hash, hp, sa_bytes, sa_offsets,
+           n_sa_bytes, n_reads, lo, hi, mate_tid, mate_pos);
+    return HELLO_OK;
+} HS_ENTRY_END("hello_sv_add_pairs")
+
+int hello_sv_library(hello_sv* h, int32_t median, int32_t lo, int32_t hi) try {
+    using namespace hello;
+    if (!h) return set_last_error(HELLO_ERR_ARG, "NULL pointer");
+    if (h->has_library) return set_last_error(HELLO_ERR_ARG, "hello_sv_library twice: the handle has its insert sizes");
+    if (lo > median || median > hi) return set_last_error(HELLO_ERR_ARG, "library (%d, %d, %d): lo <= median <= hi", median, lo, hi);
+    h->library.median = median;
+    h->library.lo = lo;
+    h->library.hi = hi;
+    h->has_library = true;
+    return HELLO_OK;
+} HS_ENTRY_END("hello_sv_library")
+
+int hello_sv_clip_min(hello_sv* h, int32_t clip_min) try {
+    using namespace hello;
+    if (!h) return set_last_error(HELLO_ERR_ARG, "NULL pointer");
+    if (clip_min < 1) return set_last_error(HELLO_ERR_ARG, "clip_min %d: at least 1", clip_min);
+    if (h->pairs_given_adds) return set_last_error(HELLO_ERR_ARG, "hello_sv_clip_min after hello_sv_add_pairs: clips were counted already");
+    h->clip_min = clip_min;
+    return HELLO_OK;
+} HS_ENTRY_END("hello_sv_clip_min")
 
 int hello_sv_contigs(hello_sv* h, const char* const* names, int64_t n, int64_t own) try {
     using namespace hello;
@@ -755,9 +1009,20 @@ int hello_sv_finish(hello_sv* h, int64_t cluster_gap, int32_t len_ratio_percent,
     if (h->finished) return set_last_error(HELLO_ERR_ARG, "hello_sv_finish twice: the handle is finished");
     if (int rc = sv_check_clustering(cluster_gap, len_ratio_percent, min_support)) return rc;
     sv_signature_columns(h);
-    const std::vector<SvCandidate> found = sv_cluster(h->sigs, cluster_gap, len_ratio_percent, min_support);
+    int64_t n_assigned = 0, n_pair_only = 0;
+    std::vector<SvPairCandidate> found;
+    if (h->has_library) {
+        found = sv_cluster_pairs(h->sigs, cluster_gap, len_ratio_percent, min_support, h->library, h->flank, &n_assigned);
+    } else {
+        for (const SvCandidate& c : sv_cluster(h->sigs, cluster_gap, len_ratio_percent, min_support)) {
+            SvPairCandidate p{};
+            static_cast<SvCandidate&>(p) = c;
+            p.end = p.end_min = p.end_max = sv_candidate_end(c);
+            found.push_back(p);
+        }
+    }
     const size_t n = found.size();
-    std::vector<long long> depth(n, 0);
+    std::vector<long long> depth(n, 0), ce(n, 0);
     float ms = 0.0f;
     if (n > 0) {                                     // a candidate has signatures, so an add has built the device side
         HS_HIP(hipSetDevice(h->device));
@@ -788,14 +1053,27 @@ int hello_sv_finish(hello_sv* h, int64_t cluster_gap, int32_t len_ratio_percent,
         hipLaunchKernelGGL(sv_span_kernel, dim3((unsigned)((n + kSvWaves - 1) / kSvWaves)), dim3(kSvThreads), 0, 0, a);
         ms += timer.stop();
         HS_HIP(hipMemcpy(depth.data(), a.depth, n * sizeof(long long), hipMemcpyDeviceToHost));
+        if (h->pairs_built) {                        // CE: the clipped ends around both ends of every candidate
+            std::vector<int64_t> end(n);
+            for (size_t i = 0; i < n; ++i) end[i] = found[i].end;
+            SvClipArgs k{h->clip_left, h->clip_right, a.pos, m.put(end.data(), n), (int64_t)n, h->length, h->flank, m.room<long long>(n)};
+            timer.start();
+            hipLaunchKernelGGL(sv_clips_kernel, dim3((unsigned)((n + kSvWaves - 1) / kSvWaves)), dim3(kSvThreads), 0, 0, k);
+            ms += timer.stop();
+            HS_HIP(hipMemcpy(ce.data(), k.ce, n * sizeof(long long), hipMemcpyDeviceToHost));
+        }
     }
-    std::vector<int64_t> cols[kSvCandColumns], sr(n);
+    std::vector<int64_t> cols[kSvCandColumns], sr(n), of_pairs[5];
     for (auto& c : cols) c.resize(n);
+    for (auto& c : of_pairs) c.resize(n);
     for (size_t i = 0; i < n; ++i) {
-        const SvCandidate& c = found[i];
+        const SvPairCandidate& c = found[i];
         int64_t g[kSvGenotypeColumns];
         const int64_t dp = (int64_t)depth[i], dr = sv_depth_ref(dp, c.dv, c.sr);
-        sv_genotype(c.dv, dr, g);
+        sv_genotype(c.dv + c.pr, dr, g);             // pair supporters end before the breakpoint: they are not in DP
+        const int64_t more[5] = {c.pr, (int64_t)ce[i], c.end_min, c.end_max, c.imprecise};
+        for (int k = 0; k < 5; ++k) of_pairs[k][i] = more[k];
+        n_pair_only += c.imprecise;
         const int64_t row[kSvCandColumns] = {c.type, c.pos, c.len, c.dv, c.dv_fwd, c.dv_rev, c.hp[0], c.hp[1], c.hp[2], c.pos_min,
                                              c.pos_max, c.len_min, c.len_max, dp, dr, g[0], g[1], g[2], g[3], g[4]};
         for (int k = 0; k < kSvCandColumns; ++k) cols[k][i] = row[k];
@@ -804,6 +1082,9 @@ int hello_sv_finish(hello_sv* h, int64_t cluster_gap, int32_t len_ratio_percent,
     // ---- nothing can fail from here on
     for (int k = 0; k < kSvCandColumns; ++k) h->cand_cols[k].swap(cols[k]);
     h->cand_sr.swap(sr);
+    for (int k = 0; k < 5; ++k) h->cand_pairs[k].swap(of_pairs[k]);
+    h->pair_stats[10] = (double)n_assigned;
+    h->pair_stats[11] = (double)n_pair_only;
     h->finished = true;
     h->stats[6] = (double)n;
     h->stats[9] += ms;
@@ -833,6 +1114,87 @@ int hello_sv_array(hello_sv* h, int32_t which, const void** data, int64_t* count
     }
     return HELLO_OK;
 } HS_ENTRY_END("hello_sv_array")
+
+int hello_sv_pairs_array(hello_sv* h, int32_t which, const void** data, int64_t* count) try {
+    using namespace hello;
+    if (!h || !data || !count) return set_last_error(HELLO_ERR_ARG, "NULL pointer");
+    if (which == HELLO_SV_PAIRS_INNER) {
+        h->inner_host.assign(kInnerBins, 0);
+        if (h->pairs_built) {
+            HS_HIP(hipSetDevice(h->device));
+            HS_HIP(hipMemcpy(h->inner_host.data(), h->inner, kInnerBins * sizeof(int64_t), hipMemcpyDeviceToHost));
+        }
+        *data = h->inner_host.data(); *count = kInnerBins;
+    } else if (which == HELLO_SV_PAIRS_CLIP_LEFT || which == HELLO_SV_PAIRS_CLIP_RIGHT) {
+        std::vector<int32_t>& c = h->clip_host[which - HELLO_SV_PAIRS_CLIP_LEFT];
+        c.assign((size_t)h->length + 1, 0);
+        if (h->pairs_built) {
+            HS_HIP(hipSetDevice(h->device));
+            HS_HIP(hipMemcpy(c.data(), which == HELLO_SV_PAIRS_CLIP_LEFT ? h->clip_left : h->clip_right, c.size() * sizeof(int32_t),
+                             hipMemcpyDeviceToHost));
+        }
+        *data = c.data(); *count = (int64_t)c.size();
+    } else if (which == HELLO_SV_PAIRS_STATUS) {
+        *data = h->pair_status.data(); *count = (int64_t)h->pair_status.size();
+    } else if (which >= HELLO_SV_PAIRS_CANDIDATES_PR && which <= HELLO_SV_PAIRS_CANDIDATES_IMPRECISE) {
+        if (!h->finished) return set_last_error(HELLO_ERR_ARG, "array selector %d before hello_sv_finish", which);
+        const std::vector<int64_t>& c = h->cand_pairs[which - HELLO_SV_PAIRS_CANDIDATES_PR];
+        *data = c.data(); *count = (int64_t)c.size();
+    } else {
+        return set_last_error(HELLO_ERR_ARG, "array selector %d", which);
+    }
+    return HELLO_OK;
+} HS_ENTRY_END("hello_sv_pairs_array")
+
+int hello_sv_pairs_stats(const hello_sv* h, double* stats) {
+    if (!h || !stats) return hello::set_last_error(HELLO_ERR_ARG, "NULL pointer");
+    std::copy(h->pair_stats, h->pair_stats + hello::kPairStats, stats);
+    return HELLO_OK;
+}
+
+int hello_sv_library_of(const int64_t* inner, int64_t k, int64_t* out) try {
+    using namespace hello;
+    if (!inner || !out) return set_last_error(HELLO_ERR_ARG, "NULL pointer");
+    if (k < 1) return set_last_error(HELLO_ERR_ARG, "k %lld: at least 1", (long long)k);
+    for (int b = 0; b < kInnerBins; ++b)
+        if (inner[b] < 0) return set_last_error(HELLO_ERR_ARG, "bin %d counts %lld", b, (long long)inner[b]);
+    if (!sv_library_of(inner, k, out)) return set_last_error(HELLO_ERR_ARG, "an empty histogram has no library");
+    return HELLO_OK;
+} HS_ENTRY_END("hello_sv_library_of")
+
+int hello_sv_cluster_pairs(const int64_t* signatures, int64_t n, int64_t cluster_gap, int32_t len_ratio_percent, int32_t min_support,
+                           int32_t median, int32_t lo, int32_t hi, int32_t flank, int64_t* out, int64_t* n_out) try {
+    using namespace hello;
+    if (!n_out || (n > 0 && (!signatures || !out))) return set_last_error(HELLO_ERR_ARG, "NULL pointer");
+    if (n < 0) return set_last_error(HELLO_ERR_ARG, "negative count");
+    if (int rc = sv_check_clustering(cluster_gap, len_ratio_percent, min_support)) return rc;
+    if (lo > median || median > hi) return set_last_error(HELLO_ERR_ARG, "library (%d, %d, %d): lo <= median <= hi", median, lo, hi);
+    if (flank < 1) return set_last_error(HELLO_ERR_ARG, "flank %d: at least 1", flank);
+    std::vector<SvSig> sigs((size_t)n);
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t* g = signatures + i * kSvSigColumns;
+        const bool pair = g[5] == kPairOp;
+        if (g[0] < 0 || g[0] > kSvBnd || g[2] < (g[0] == kSvBnd ? 0 : 1) || g[2] > INT32_MAX || g[3] < (pair ? 0 : INT32_MIN) || g[3] > INT32_MAX
+            || g[6] < 0 || g[6] > 1 || g[7] < 0 || g[7] > 255)
+            return set_last_error(HELLO_ERR_ARG, "signature %lld: type %lld, len %lld, shift %lld, strand %lld, hp %lld", (long long)i,
+                                  (long long)g[0], (long long)g[2], (long long)g[3], (long long)g[6], (long long)g[7]);
+        sigs[(size_t)i] = SvSig{g[1], g[4], g[5], (int32_t)g[2], (int32_t)g[3], (uint8_t)g[0], (uint8_t)g[6], (uint8_t)g[7], 0};
+    }
+    sv_sort(sigs);
+    int64_t n_assigned = 0;
+    SvLibrary lib;
+    lib.median = median; lib.lo = lo; lib.hi = hi;
+    const std::vector<SvPairCandidate> found = sv_cluster_pairs(sigs, cluster_gap, len_ratio_percent, min_support, lib, flank, &n_assigned);
+    for (size_t i = 0; i < found.size(); ++i) {
+        const SvPairCandidate& c = found[i];
+        const int64_t row[HELLO_SV_CLUSTER_PAIRS_COLUMNS] = {c.type, c.pos, c.len, c.dv, c.dv_fwd, c.dv_rev, c.hp[0], c.hp[1], c.hp[2],
+                                                             c.pos_min, c.pos_max, c.len_min, c.len_max, c.sr, c.pr, c.end_min, c.end_max,
+                                                             c.imprecise};
+        std::copy(row, row + HELLO_SV_CLUSTER_PAIRS_COLUMNS, out + i * HELLO_SV_CLUSTER_PAIRS_COLUMNS);
+    }
+    *n_out = (int64_t)found.size();
+    return HELLO_OK;
+} HS_ENTRY_END("hello_sv_cluster_pairs")
 
 int hello_sv_stats(const hello_sv* h, double* stats) {
     if (!h || !stats) return hello::set_last_error(HELLO_ERR_ARG, "NULL pointer");

@@ -74,7 +74,7 @@ class Handle:
 
 def measure_spans(bam: str, fasta, chromosomes: Optional[Sequence[str]], max_span: Optional[int], stats: Optional[dict],
                   restatement: bool, *, open_handle: Callable, restated: Callable, done: Callable, with_mods: bool = False,
-                  retag: Optional[Callable] = None, with_sa: bool = False) -> None:
+                  retag: Optional[Callable] = None, with_sa: bool = False, with_pairs: bool = False) -> None:
     """One BAM, chromosome after chromosome (default: every sequence of ``fasta``, a path or {chromosome: sequence}), each in spans
     of ``span_step(max_span)`` positions.  Per chromosome ``c`` with its text ``ref`` (uint8):
 
@@ -82,7 +82,7 @@ def measure_spans(bam: str, fasta, chromosomes: Optional[Sequence[str]], max_spa
     read after the last; it is closed on every path.  It is not called under ``restatement``, and where it returns None the
     chromosome is restated too: the spans are collected and ``restated(c, ref, [(reads[, mods], lo, hi)])`` -> (tables, counts).  Either pair
     goes to ``done(c, ref, tables, counts)``.  ``with_mods``: the reads come with their modifications (``fetch_with_mods``);
-    ``with_sa``: with their SA tags (``fetch_with_sa``);
+    ``with_sa``: with their SA tags (``fetch_with_sa``); ``with_pairs``: with their SA tags and mate fields (``fetch_pairs``);
     ``retag(c, reads)`` replaces the reads of a span.  Added to ``stats``: the handle's TIMES, the seconds of decoding
     (``decode_s``), of the library's calls (``device_s``) and of the whole pass (``total_s``)."""
     from .bam import BamFile
@@ -110,8 +110,8 @@ def measure_spans(bam: str, fasta, chromosomes: Optional[Sequence[str]], max_spa
                 for lo in range(0, ref.shape[0], step):
                     hi = min(lo + step, ref.shape[0])
                     t0 = time.perf_counter()
-                    batch = (tuple(source.fetch_with_mods(c, lo, hi)) if with_mods else tuple(source.fetch_with_sa(c, lo, hi)) if with_sa
-                             else (source.fetch(c, lo, hi),))
+                    batch = (tuple(source.fetch_with_mods(c, lo, hi)) if with_mods else tuple(source.fetch_pairs(c, lo, hi)) if with_pairs
+                             else tuple(source.fetch_with_sa(c, lo, hi)) if with_sa else (source.fetch(c, lo, hi),))
                     t1 = time.perf_counter()
                     if retag is not None:
                         batch = (retag(c, batch[0]),) + batch[1:]

@@ -2,14 +2,20 @@
 
     python -m hello_amd.call --from_bam | --from_bams [--resident] ... --sv [--sv_min_size 50] [--sv_min_support 3] [--sv_flank 20]
                              [--sv_cluster_gap 100] [--sv_len_ratio 0.7] [--sv_split]
+                             [--sv_pairs [--sv_pairs_library M,LO,HI] [--sv_pairs_k 8] [--sv_clip_min 20]]
     python -m hello_amd.sv --bam B[,P] --ref F --output_prefix P [--phased_vcf V] [--chromosomes a,b] [--mapq_threshold 10]
-                           [--sv_min_size 50] ... [--split] [--device N]
+                           [--sv_min_size 50] ... [--split] [--pairs [--pairs_library M,LO,HI] [--pairs_k 8] [--clip_min 20]]
+                           [--device N]
 
 Not in the reference; DESIGN.md section 7p defines the rules.  By default intra-alignment events only: an ``I`` or ``D`` operation of
 at least ``min_size`` bases inside one alignment record.  With ``--sv_split`` / ``--split`` (section 7q) the ``SA`` tags are read too and
 every junction between two segments of a split alignment is a row as well (DEL, INS, DUP, INV, BND): ``segments_of``, ``junctions_of``
-and ``split_rows_of`` restate those rules.  Clipped ends and discordant pairs are not looked at, so this is no complete
-structural-variant caller.  ``signatures_of``, ``restated``, ``clustered`` and ``genotyped`` restate the rules in plain
+and ``split_rows_of`` restate those rules.  With ``--sv_pairs`` / ``--pairs`` (section 7s) the mate fields are read as well: a pair
+whose mates lie too far apart, face the wrong way or sit on two chromosomes is a row (DEL, DUP, INV, BND), pair rows support the
+clusters of the other rows or form imprecise clusters of their own, and soft-clipped ends near a candidate are counted
+(``pair_counted``, ``pair_rows_of``, ``library_of``, ``assigned``, ``clustered_pairs``).  Still not looked at: the mate's mapping
+quality, pairs that support the reference, insertions from short inserts, pairing the two BNDs of a translocation, assembly and
+joint calls over two BAMs.  ``signatures_of``, ``restated``, ``clustered`` and ``genotyped`` restate the rules in plain
 Python / NumPy without a GPU; ``Caller`` binds ``hello_sv_*`` (hello_amd/csrc/sv.hip, sv.h), whose arrays equal the restatement
 integer for integer, and ``clustered_native`` / ``genotyped_native`` run the host rules of the library alone.  ``measure`` is the pass
 over one BAM (``spans.measure_spans``); its result, ``Events``, writes the VCF and the ``.npz``.
@@ -27,8 +33,8 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from ._abi import ARRAY_GETTER, READS, STATS_GETTER, bind, check, i32, i64, vp
-from .bam import Reads, Splits
+from ._abi import ARRAY_GETTER, READS, STATS_GETTER, bind, check, handle_array, handle_stats, i32, i64, vp
+from .bam import Mates, Reads, Splits
 from .gvcf import _bytes_of, counted
 from .spans import Handle, measure_spans, save_tables
 
@@ -57,6 +63,21 @@ MIN_SIZE, FLANK, CLUSTER_GAP, LEN_RATIO, MIN_SUPPORT = 50, 20, 100, 0.7, 3
 EPSILON = 0.05
 GT_TEXT = ("0/0", "0/1", "1/1")
 MAX_COUNTING_READS = (1 << 31) - 1
+
+# discordant pairs and clipped ends
+PAIR_OP = -16                                               # the OP column of a pair row
+INNER_BINS, INNER_ZERO = 4096, 1024
+MATE_MAX_POS = (1 << 31) - 1
+UNSET_LIBRARY = (0, -(1 << 31), (1 << 31) - 1)
+PAIRS_K, CLIP_MIN, LIBRARY_MIN_PAIRS, LIBRARY_SAMPLE = 8, 20, 100, 10000
+PAIR_STATUS_NAMES = ("not_pair_counted", "bad_mate", "right", "normal", "short", "small", "unplaced", "with_a_row", "with_a_bnd_row")
+NOT_PAIR, BAD_MATE, RIGHT, NORMAL, SHORT, SMALL, UNPLACED, PAIR_ROW, PAIR_BND_ROW = range(9)
+PAIR_COUNT_NAMES = ("pair_reads", "pairs_left", "pairs_right", "pairs_normal", "pairs_short", "pairs_small", "pairs_unplaced", "bad_mate",
+                    "pair_signatures", "clipped_reads", "pairs_assigned", "pair_candidates")
+PAIR_STAT_NAMES = PAIR_COUNT_NAMES + ("pairs_ms",)
+PAIR_METRIC_STATS = SPLIT_METRIC_STATS + PAIR_COUNT_NAMES
+PAIR_CANDIDATE_COLUMNS = ("PR", "CE", "END_MIN", "END_MAX", "IMPRECISE")
+CLUSTER_PAIRS_COLUMNS = CLUSTER_COLUMNS + ("SR",) + ("PR", "END_MIN", "END_MAX", "IMPRECISE")
 
 _log = logging.getLogger(__name__)
 
@@ -375,6 +396,238 @@ def restated(spans: Sequence[tuple], ref, min_size: int = MIN_SIZE, flank: int =
 
 
 # ------------------------------------------------------------------------------------------------
+# the rules of the read pairs and the clipped ends, restated
+# ------------------------------------------------------------------------------------------------
+def pair_counted(flag: int, mapq: int, mapq_threshold: int) -> bool:
+    """Paired, mapped with a mapped mate, primary, no duplicate, not QC-fail, at the threshold; flag 0x2 is not consulted."""
+    return bool(flag & 0x1) and not flag & (0x4 | 0x8 | 0x100 | 0x800 | 0x400 | 0x200) and mapq >= mapq_threshold
+
+
+def clips_of(ops: Sequence[Tuple[int, int]], clip_min: int) -> int:
+    """Bit 0: the leading soft clip (the first operation, or the second behind an H) has ``clip_min`` bases; bit 1: the trailing."""
+    if not ops:
+        return 0
+    i = 1 if ops[0][0] == 5 else 0
+    j = len(ops) - 2 if ops[-1][0] == 5 else len(ops) - 1
+    found = 1 if i < len(ops) and ops[i][0] == 4 and ops[i][1] >= clip_min else 0
+    return found | (2 if j > i and ops[j][0] == 4 and ops[j][1] >= clip_min else 0)
+
+
+def pair_outcome(flag: int, s: int, e: int, own: int, mt: int, ms: int, n_contigs: int, library: Tuple[int, int, int],
+                 min_size: int) -> Tuple[int, Optional[int], Optional[Tuple[int, int, int, int]]]:
+    """One belonging, pair-counted record with valid mate fields -> (PAIR_STATUS, its INNER bin or None, (type, pos, len, shift) of
+    its row or None)."""
+    median, lo, hi = library
+    rev, mrev = bool(flag & 0x10), bool(flag & 0x20)
+    if mt != own:
+        if not 0 <= mt < n_contigs:
+            return UNPLACED, None, None
+        return PAIR_BND_ROW, None, (BND, s if rev else e, mt, ms)
+    if not (s < ms or (s == ms and flag & 0x40)):
+        return RIGHT, None, None
+    at = None
+    if not rev and mrev:
+        g = ms - e
+        at = min(max(g + INNER_ZERO, 0), INNER_BINS - 1)
+        if g <= hi:
+            return (SHORT if g < lo else NORMAL), at, None
+        row = (DEL, e, g - median, ms)
+    elif rev and not mrev:
+        if ms < e:
+            return SMALL, None, None
+        row = (DUP, s, ms - s, ms)
+    else:
+        pos = s if rev else e
+        row = (INV5 if rev else INV3, pos, abs(ms - pos), ms)
+    return (PAIR_ROW, at, row) if min_size <= row[2] <= MATE_MAX_POS else (SMALL, at, None)
+
+
+def pair_rows_of(reads: Reads, splits: Splits, mates: "Mates", lo: int, own: int, n_contigs: int, length: int, min_size: int,
+                 mapq_threshold: int, library: Tuple[int, int, int], clip_min: int = CLIP_MIN, pairs_given: int = 0) -> Dict[str, object]:
+    """One span that begins at ``lo`` with the reads overlapping it -> ``rows`` (of SIGNATURE_COLUMNS, OP = PAIR_OP, in the reads'
+    order), ``inner`` ([bin] per left FR record), ``clip_left`` / ``clip_right`` ([position] per counting clip), ``status``
+    (PAIR_STATUS per read) and ``counts`` (PAIR_COUNT_NAMES but the two of finish)."""
+    rows: List[Tuple[int, ...]] = []
+    inner: List[int] = []
+    clip_left: List[int] = []
+    clip_right: List[int] = []
+    status = np.zeros(reads.n_reads, np.uint8)
+    counts = dict.fromkeys(PAIR_COUNT_NAMES, 0)
+    ordinal = pairs_given
+    for r in range(reads.n_reads):
+        s, e = int(reads.ref_starts[r]), int(reads.ref_ends[r])
+        if s < lo:
+            continue
+        flag, mapq = int(reads.flags[r]), int(reads.mapq[r])
+        if pair_counted(flag, mapq, mapq_threshold):
+            counts["pair_reads"] += 1
+            mt, ms = int(mates.tid[r]), int(mates.pos[r])
+            if not (0 <= ms <= MATE_MAX_POS and (mt != own or ms <= length) and e <= length):
+                status[r] = BAD_MATE
+                counts["bad_mate"] += 1
+            else:
+                status[r], at, row = pair_outcome(flag, s, e, own, mt, ms, n_contigs, library, min_size)
+                if at is not None:
+                    inner.append(at)
+                if row is not None:
+                    rows.append(row[:2] + (row[2], row[3], ordinal, PAIR_OP, int(bool(flag & 0x10)), int(reads.hp[r])))
+                key = {RIGHT: "pairs_right", NORMAL: "pairs_normal", SHORT: "pairs_short", SMALL: "pairs_small", UNPLACED: "pairs_unplaced"}
+                if int(status[r]) in key:
+                    counts[key[int(status[r])]] += 1
+                counts["pairs_left"] += int(status[r]) in (NORMAL, SHORT, SMALL, PAIR_ROW)
+            ordinal += 1
+        if counted(flag, mapq, mapq_threshold) and splits.offsets[r + 1] == splits.offsets[r] and e <= length:
+            ops = [(int(c) & 15, int(c) >> 4) for c in reads.cigars[int(reads.cigar_offsets[r]):int(reads.cigar_offsets[r + 1])]]
+            found = clips_of(ops, clip_min)
+            if found & 1:
+                clip_right.append(s)
+            if found & 2:
+                clip_left.append(e)
+            counts["clipped_reads"] += found != 0
+    counts["pair_signatures"] = len(rows)
+    return dict(rows=rows, inner=inner, clip_left=clip_left, clip_right=clip_right, status=status, counts=counts)
+
+
+def _histogram_median(h: np.ndarray) -> int:
+    """The lower median of the values a histogram counts."""
+    total = int(h.sum())
+    return int(np.searchsorted(np.cumsum(h), (total - 1) // 2 + 1))
+
+
+def library_of(histogram, k: int = PAIRS_K) -> Tuple[int, int, int]:
+    """INNER -> (median, lo, hi): the lower median, and k max(mad, 1) to either side, where mad is the lower median of the absolute
+    deviations over the histogram without its two clamped bins.  Integer arithmetic throughout."""
+    h = np.asarray(histogram, np.int64)
+    if h.shape != (INNER_BINS,) or h.sum() == 0:
+        raise ValueError("an empty histogram has no library")
+    at = _histogram_median(h)
+    dev = np.zeros(INNER_BINS, np.int64)
+    for v in range(1, INNER_BINS - 1):
+        dev[abs(v - at)] += h[v]
+    mad = max(_histogram_median(dev), 1) if dev.sum() else 1
+    return at - INNER_ZERO, at - INNER_ZERO - k * mad, at - INNER_ZERO + k * mad
+
+
+def _cluster_end(c: Sequence[int]) -> int:
+    return c[1] if c[0] == INS else c[1] + c[2]
+
+
+def assigned(clusters: Sequence[Sequence[int]], pair_rows: Sequence[Sequence[int]], library: Tuple[int, int, int],
+             flank: int) -> Tuple[List[int], List[Tuple[int, ...]]]:
+    """Clusters (rows that begin with TYPE, POS, LEN) in (pos, type, len) order and pair rows sorted by (type, pos, len, ordinal) ->
+    (PR per cluster, the pair rows no cluster took).  The first cluster that accepts a row takes it; a BND is never taken nor left."""
+    _, lo, hi = library
+    pr, left = [0] * len(clusters), []
+    for g in pair_rows:
+        kind, a, b = int(g[0]), int(g[1]), int(g[3])
+        if kind >= BND:
+            continue
+        for i, c in enumerate(clusters):
+            P, L = int(c[1]), int(c[2])
+            if int(c[0]) != kind:
+                continue
+            if (a - flank <= P and P + L <= b + flank and lo <= (b - a) - L <= hi) if kind == DEL else (abs(a - P) <= hi and abs(b - (P + L)) <= hi):
+                pr[i] += 1
+                break
+        else:
+            left.append(tuple(int(v) for v in g))
+    return pr, left
+
+
+def clustered_pairs(rows: Sequence[Sequence[int]], library: Tuple[int, int, int], min_support: int = MIN_SUPPORT) -> List[Tuple[int, ...]]:
+    """The pair rows no cluster took -> rows of CLUSTER_PAIRS_COLUMNS, in the order (type, first a) they are found."""
+    _, lo, hi = library
+    left = sorted((tuple(int(v) for v in g) for g in rows), key=lambda g: (g[0], g[1], g[3], g[4]))
+    out, group, top, bottom = [], [], 0, 0
+
+    def close():
+        if len(group) < min_support:
+            return
+        a, b, n = sorted(g[1] for g in group), sorted(g[3] for g in group), sorted(g[2] for g in group)
+        m = (len(group) - 1) // 2
+        kind = group[0][0]
+        out.append((kind, a[-1] if kind == DEL else a[m], n[m], 0, 0, 0, 0, 0, 0, a[0], a[-1], n[0], n[-1], 0, len(group), b[0], b[-1], 1))
+
+    for g in left:
+        x, y = min(g[1], g[3]), max(g[1], g[3])
+        if group and not (g[0] == group[-1][0] and g[1] - group[-1][1] <= hi - lo and x <= bottom and y >= top):
+            close()
+            group = []
+        top, bottom = (max(top, x), min(bottom, y)) if group else (x, y)
+        group.append(g)
+    close()
+    return out
+
+
+def clustered_with_pairs(signatures: Sequence[Sequence[int]], library: Tuple[int, int, int], flank: int, cluster_gap: int = CLUSTER_GAP,
+                         len_ratio_percent: int = percent_of(LEN_RATIO), min_support: int = MIN_SUPPORT) -> Tuple[List[Tuple[int, ...]], int]:
+    """Rows of SIGNATURE_COLUMNS of all kinds -> (rows of CLUSTER_PAIRS_COLUMNS sorted by (pos, type, len, imprecise), the pair rows a
+    cluster took): what ``hello_sv_cluster_pairs`` computes."""
+    rows = sorted((tuple(int(v) for v in g) for g in signatures), key=lambda g: (g[0], g[1], g[2], g[4], g[5]))
+    plain, pairs = [g for g in rows if g[5] != PAIR_OP], [g for g in rows if g[5] == PAIR_OP]
+    clusters = clustered(plain, cluster_gap, len_ratio_percent, min_support, with_sr=True)
+    pr, left = assigned(clusters, pairs, library, flank)
+    out = [c + (n, _cluster_end(c), _cluster_end(c), 0) for c, n in zip(clusters, pr)] + clustered_pairs(left, library, min_support)
+    return sorted(out, key=lambda c: (c[1], c[0], c[2], c[17])), sum(pr)
+
+
+def clip_sum(clip_left: np.ndarray, clip_right: np.ndarray, pos: int, end: int, flank: int) -> int:
+    """CE: CLIP_LEFT + CLIP_RIGHT over [pos - flank, pos + flank] and what [end - flank, end + flank] adds to it, inside the arrays."""
+    length = clip_left.shape[0] - 1
+    lo1, hi1 = max(pos - flank, 0), min(pos + flank, length)
+    lo2, hi2 = max(end - flank, 0, hi1 + 1), min(end + flank, length)
+    both = np.asarray(clip_left, np.int64) + np.asarray(clip_right, np.int64)
+    return int(both[lo1:hi1 + 1].sum()) + (int(both[lo2:hi2 + 1].sum()) if lo2 <= hi2 else 0)
+
+
+def restated_pairs(spans: Sequence[tuple], ref, library: Tuple[int, int, int], contigs: Sequence[str], own: int, min_size: int = MIN_SIZE,
+                   flank: int = FLANK, mapq_threshold: int = 10, cluster_gap: int = CLUSTER_GAP,
+                   len_ratio_percent: int = percent_of(LEN_RATIO), min_support: int = MIN_SUPPORT,
+                   clip_min: int = CLIP_MIN) -> Tuple[Dict[str, np.ndarray], Dict[str, int]]:
+    """``restated`` for spans (reads, splits, mates, lo, hi): the tables of a handle whose every add is ``hello_sv_add_pairs`` -- and
+    INNER, CLIP_LEFT, CLIP_RIGHT, PAIR_STATUS of the last span, CANDIDATES_PR .. CANDIDATES_IMPRECISE -- and the counts of both
+    getters."""
+    ref = _bytes_of(ref)
+    length = int(ref.shape[0])
+    diff = np.zeros(length + 1, np.int64)
+    counts = dict.fromkeys(COUNT_NAMES + SPLIT_COUNT_NAMES + PAIR_COUNT_NAMES, 0)
+    inner = np.zeros(INNER_BINS, np.int64)
+    clip_left, clip_right = np.zeros(length + 1, np.int32), np.zeros(length + 1, np.int32)
+    rows: List[Tuple[int, ...]] = []
+    status = split_status = pair_status = np.zeros(0, np.uint8)
+    for reads, splits, mates, lo, hi in spans:
+        part = signatures_of(reads, ref, lo, hi, min_size, flank, mapq_threshold, counts["counting"], splits, contigs, own)
+        more = pair_rows_of(reads, splits, mates, lo, own, len(contigs), length, min_size, mapq_threshold, library, clip_min,
+                            counts["pair_reads"])
+        rows += part["signatures"] + more["rows"]
+        for at, by in part["cover"]:
+            diff[at] += by
+        np.add.at(inner, np.array(more["inner"], np.int64), 1)
+        np.add.at(clip_left, np.array(more["clip_left"], np.int64), 1)
+        np.add.at(clip_right, np.array(more["clip_right"], np.int64), 1)
+        for k, v in list(part["counts"].items()) + list(more["counts"].items()):
+            counts[k] += v
+        status, split_status, pair_status = part["status"], part["split_status"], more["status"]
+    rows.sort(key=lambda g: (g[0], g[1], g[2], g[4], g[5]))
+    clusters, counts["pairs_assigned"] = clustered_with_pairs(rows, library, flank, cluster_gap, len_ratio_percent, min_support)
+    spanning = np.cumsum(diff)
+    found = []
+    for c in clusters:
+        dp = int(spanning[c[1]])
+        dr = max(0, dp - (c[3] - c[13]))
+        end = c[15] if c[17] and c[0] == DEL else _cluster_end(c)
+        found.append(c[:13] + (dp, dr) + genotype_of(c[3] + c[14], dr) + (c[13], c[14], clip_sum(clip_left, clip_right, c[1], end, flank))
+                     + c[15:])
+    counts["candidates"] = len(found)
+    counts["pair_candidates"] = sum(c[17] for c in clusters)
+    tables = dict(_columns(rows, SIGNATURE_COLUMNS, "SIGNATURES_"),
+                  **_columns(found, CANDIDATE_COLUMNS + ("SR",) + PAIR_CANDIDATE_COLUMNS, "CANDIDATES_"))
+    tables.update(STATUS=status, SPLIT_STATUS=split_status, PAIR_STATUS=pair_status, DIFF=diff, INNER=inner, CLIP_LEFT=clip_left,
+                  CLIP_RIGHT=clip_right)
+    return tables, counts
+
+
+# ------------------------------------------------------------------------------------------------
 # the library
 # ------------------------------------------------------------------------------------------------
 _PROTOTYPES = (
@@ -389,6 +642,13 @@ _PROTOTYPES = (
     ("hello_sv_cluster_split", [vp, i64, i64, i32, i32, vp, C.POINTER(i64)]),
     ("hello_sv_contigs", [vp, C.POINTER(C.c_char_p), i64, i64]),
     ("hello_sv_add_split", [vp] + READS + [vp, vp, i64, i64, i64, i64]),
+    ("hello_sv_library", [vp, i32, i32, i32]),
+    ("hello_sv_clip_min", [vp, i32]),
+    ("hello_sv_add_pairs", [vp] + READS + [vp, vp, i64, vp, vp, i64, i64, i64]),
+    ("hello_sv_pairs_array", ARRAY_GETTER),
+    ("hello_sv_pairs_stats", STATS_GETTER),
+    ("hello_sv_cluster_pairs", [vp, i64, i64, i32, i32, i32, i32, i32, i32, vp, C.POINTER(i64)]),
+    ("hello_sv_library_of", [vp, i64, vp]),
 )
 
 
@@ -412,12 +672,14 @@ class Caller(Handle):
     ARRAYS = (tuple(("SIGNATURES_" + name, i, np.int64, None) for i, name in enumerate(SIGNATURE_COLUMNS))
               + tuple(("CANDIDATES_" + name, 8 + i, np.int64, None) for i, name in enumerate(CANDIDATE_COLUMNS))
               + (("STATUS", 28, np.uint8, None), ("CANDIDATES_SR", 29, np.int64, None), ("SPLIT_STATUS", 30, np.uint8, None)))
+    PAIR_ARRAYS = ((("INNER", 0, np.int64), ("CLIP_LEFT", 1, np.int32), ("CLIP_RIGHT", 2, np.int32), ("PAIR_STATUS", 3, np.uint8))
+                   + tuple(("CANDIDATES_" + name, 4 + i, np.int64) for i, name in enumerate(PAIR_CANDIDATE_COLUMNS)))
 
     def __init__(self, ref, min_size: int = MIN_SIZE, flank: int = FLANK, mapq_threshold: int = 10, device: int = 0,
                  cluster_gap: int = CLUSTER_GAP, len_ratio_percent: int = percent_of(LEN_RATIO), min_support: int = MIN_SUPPORT):
         ref = np.ascontiguousarray(_bytes_of(ref))
         super().__init__(_lib())
-        self.finished = self.split = False
+        self.finished = self.split = self.pairs = False
         self.clustering = (int(cluster_gap), int(len_ratio_percent), int(min_support))
         check(self._lib.hello_sv_create(ref.ctypes.data, int(ref.shape[0]), int(min_size), int(flank), int(mapq_threshold), int(device),
                                         C.byref(self._h)))
@@ -429,11 +691,29 @@ class Caller(Handle):
         check(self._lib.hello_sv_contigs(self._h, table, len(names), int(own)))
         self.split = True
 
-    def add(self, reads: Reads, *span, splits: Optional[Splits] = None) -> None:
-        """``add(reads, lo, hi)``, ``add(reads, lo, hi, splits=...)`` or, as ``measure_spans`` calls it, ``add(reads, splits, lo, hi)``."""
-        if len(span) == 3:
+    def set_library(self, median: int, lo: int, hi: int, clip_min: Optional[int] = None) -> None:
+        """The library's inner distances, or ``UNSET_LIBRARY``: once, before the first add with ``mates``."""
+        check(self._lib.hello_sv_library(self._h, int(median), int(lo), int(hi)))
+        if clip_min is not None:
+            check(self._lib.hello_sv_clip_min(self._h, int(clip_min)))
+        self.pairs = True
+
+    def add(self, reads: Reads, *span, splits: Optional[Splits] = None, mates: Optional[Mates] = None) -> None:
+        """``add(reads, lo, hi)``, ``add(reads, lo, hi, splits=...[, mates=...])`` or, as ``measure_spans`` calls it,
+        ``add(reads, splits, lo, hi)`` and ``add(reads, splits, mates, lo, hi)``."""
+        if len(span) == 4:
+            splits, mates, span = span[0], span[1], span[2:]
+        elif len(span) == 3:
             splits, span = span[0], span[1:]
         lo, hi = span
+        if mates is not None:
+            text, offsets = np.ascontiguousarray(splits.bytes, np.uint8), np.ascontiguousarray(splits.offsets, np.int64)
+            tid, pos = np.ascontiguousarray(mates.tid, np.int32), np.ascontiguousarray(mates.pos, np.int64)
+            if offsets.shape[0] != reads.n_reads + 1 or tid.shape[0] != reads.n_reads or pos.shape[0] != reads.n_reads:
+                raise ValueError(f"{offsets.shape[0]} SA offsets, {tid.shape[0]} and {pos.shape[0]} mate fields for {reads.n_reads} reads")
+            check(self._lib.hello_sv_add_pairs(self._h, *reads.pointers(reads.hp), text.ctypes.data, offsets.ctypes.data, int(text.shape[0]),
+                                               tid.ctypes.data, pos.ctypes.data, int(reads.n_reads), int(lo), int(hi)))
+            return
         if splits is None:
             check(self._lib.hello_sv_add(self._h, *reads.pointers(reads.hp), int(reads.n_reads), int(lo), int(hi)))
             return
@@ -454,6 +734,19 @@ class Caller(Handle):
             return False
         return self.finished or not name.startswith("CANDIDATES_")
 
+    def arrays(self) -> Dict[str, np.ndarray]:
+        out = super().arrays()
+        if self.pairs:
+            out.update({name: handle_array(self._lib.hello_sv_pairs_array, self._h, which, dtype)
+                        for name, which, dtype in self.PAIR_ARRAYS if self._has(name)})
+        return out
+
+    def stats(self) -> Dict[str, float]:
+        out = super().stats()
+        if self.pairs:
+            out.update(handle_stats(self._lib.hello_sv_pairs_stats, self._h, PAIR_STAT_NAMES))
+        return out
+
     def results(self):
         """After the last add: finishes with the handle's own clustering values where nobody has yet."""
         if not self.finished:
@@ -463,12 +756,15 @@ class Caller(Handle):
 
 def found_on_gpu(spans: Sequence[tuple], ref, min_size: int = MIN_SIZE, flank: int = FLANK, mapq_threshold: int = 10,
                  cluster_gap: int = CLUSTER_GAP, len_ratio_percent: int = percent_of(LEN_RATIO), min_support: int = MIN_SUPPORT,
-                 device: int = 0, contigs: Optional[Sequence[str]] = None, own: Optional[int] = None) -> Tuple[Dict[str, np.ndarray], Dict[str, float]]:
+                 device: int = 0, contigs: Optional[Sequence[str]] = None, own: Optional[int] = None,
+                 library: Optional[Tuple[int, int, int]] = None, clip_min: Optional[int] = None) -> Tuple[Dict[str, np.ndarray], Dict[str, float]]:
     """``restated`` on the GPU: ({SIGNATURES_*, CANDIDATES_*, STATUS and SPLIT_STATUS of the last span}, the statistics of
     ``hello_sv_stats``)."""
     with Caller(ref, min_size, flank, mapq_threshold, device, cluster_gap, len_ratio_percent, min_support) as caller:
         if contigs is not None:
             caller.set_contigs(contigs, own)
+        if library is not None:
+            caller.set_library(*library, clip_min=clip_min)
         for span in spans:
             caller.add(*span)
         return caller.results()
@@ -492,6 +788,25 @@ def clustered_split_native(signatures: Sequence[Sequence[int]], cluster_gap: int
     check(_lib().hello_sv_cluster_split(rows.ctypes.data, int(rows.shape[0]), int(cluster_gap), int(len_ratio_percent), int(min_support),
                                         out.ctypes.data, C.byref(n)))
     return [tuple(int(v) for v in row) for row in out[:n.value]]
+
+
+def clustered_pairs_native(signatures: Sequence[Sequence[int]], library: Tuple[int, int, int], flank: int, cluster_gap: int = CLUSTER_GAP,
+                           len_ratio_percent: int = percent_of(LEN_RATIO), min_support: int = MIN_SUPPORT) -> List[Tuple[int, ...]]:
+    """``clustered_with_pairs(...)[0]`` from ``hello_sv_cluster_pairs`` (host only)."""
+    rows = np.ascontiguousarray(np.array(signatures, np.int64).reshape(-1, len(SIGNATURE_COLUMNS)))
+    out, n = np.zeros((rows.shape[0], len(CLUSTER_PAIRS_COLUMNS)), np.int64), C.c_int64()
+    check(_lib().hello_sv_cluster_pairs(rows.ctypes.data, int(rows.shape[0]), int(cluster_gap), int(len_ratio_percent), int(min_support),
+                                        int(library[0]), int(library[1]), int(library[2]), int(flank), out.ctypes.data, C.byref(n)))
+    return [tuple(int(v) for v in row) for row in out[:n.value]]
+
+
+def library_of_native(histogram, k: int = PAIRS_K) -> Tuple[int, int, int]:
+    """``library_of`` from ``hello_sv_library_of`` (host only)."""
+    h, out = np.ascontiguousarray(histogram, np.int64), np.zeros(3, np.int64)
+    if h.shape != (INNER_BINS,):
+        raise ValueError(f"a histogram of {INNER_BINS} bins")
+    check(_lib().hello_sv_library_of(h.ctypes.data, int(k), out.ctypes.data))
+    return tuple(int(v) for v in out)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -525,16 +840,30 @@ SPLIT_VCF_HEADER = VCF_HEADER.replace(
     "inside one alignment record", "inside one alignment record or between the segments of a split alignment")
 
 
-def vcf_line(chromosome: str, ref: np.ndarray, c: Dict[str, int], split: bool = False) -> str:
-    """One candidate (a dict over CANDIDATE_COLUMNS; ``split``: and SR).  POS is ``pos``, the 1-based base before the event; an
-    event at position 0 has none and is written at POS 0 with REF N."""
+PAIRS_VCF_HEADER = SPLIT_VCF_HEADER.replace(
+    '##FORMAT=<ID=GT', '##INFO=<ID=PR,Number=1,Type=Integer,Description="Supporting read pairs whose mates lie too far apart or face the wrong way">\n'
+                       '##INFO=<ID=CE,Number=1,Type=Integer,Description="Soft-clipped read ends within the flank of the two ends of the event">\n'
+                       '##INFO=<ID=IMPRECISE,Number=0,Type=Flag,Description="Called from read pairs alone: POS and END bound the breakpoints">\n'
+                       '##INFO=<ID=CIEND,Number=2,Type=Integer,Description="Least and greatest mate position of the supporting pairs, relative to END">\n'
+                       '##FORMAT=<ID=GT').replace(
+    "Distinct reads that show the event", "Distinct reads (DV) and read pairs (PR) that show the event").replace(
+    "from split alignments", "from split alignments or read pairs")
+
+
+def vcf_line(chromosome: str, ref: np.ndarray, c: Dict[str, int], split: bool = False, pairs: bool = False) -> str:
+    """One candidate (a dict over CANDIDATE_COLUMNS; ``split``: and SR; ``pairs``: and PAIR_CANDIDATE_COLUMNS).  POS is ``pos``, the
+    1-based base before the event; an event at position 0 has none and is written at POS 0 with REF N."""
     pos, n, kind = c["POS"], c["LEN"], c["TYPE"]
     base = chr(int(ref[pos - 1])) if pos >= 1 else "N"
+    only = pairs and c["IMPRECISE"]
+    end = c["END_MIN"] if only and kind == DEL else pos if kind == INS else pos + n
     info = "SVTYPE=%s;SVLEN=%d;END=%d;SUPPORT=%d;CIPOS=%d,%d;CILEN=%d,%d;STRANDS=%d,%d" % (
-        SPLIT_TYPE_NAMES[kind], -n if kind == DEL else n, pos if kind == INS else pos + n, c["DV"], c["POS_MIN"] - pos, c["POS_MAX"] - pos,
+        SPLIT_TYPE_NAMES[kind], -n if kind == DEL else n, end, c["DV"] + (c["PR"] if pairs else 0), c["POS_MIN"] - pos, c["POS_MAX"] - pos,
         c["LEN_MIN"] - n, c["LEN_MAX"] - n, c["DV_FWD"], c["DV_REV"])
     if split:
         info += ";SR=%d" % c["SR"] + (";JUNCTION=%s" % ("3to3" if kind == INV3 else "5to5") if kind in (INV3, INV5) else "")
+    if pairs:
+        info += ";PR=%d;CE=%d" % (c["PR"], c["CE"]) + (";IMPRECISE;CIEND=%d,%d" % (c["END_MIN"] - end, c["END_MAX"] - end) if only else "")
     sample = "%s:%d:%d:%d:%d,%d,%d:%d,%d,%d" % (GT_TEXT[c["GT"]], c["GQ"], c["DR"], c["DV"], c["PL0"], c["PL1"], c["PL2"], c["HP0"],
                                                  c["HP1"], c["HP2"])
     return "%s\t%d\t.\t%s\t<%s>\t.\tPASS\t%s\tGT:GQ:DR:DV:PL:HPS\t%s\n" % (chromosome, pos, base, SPLIT_TYPE_NAMES[kind], info, sample)
@@ -545,10 +874,13 @@ class Events:
     chromosomes' texts, ``lengths`` their lengths.  ``split``: of a run with split alignments -- CANDIDATES_SR is kept, STATS is
     SPLIT_METRIC_STATS and the VCF has the lines of section 7q."""
 
-    def __init__(self, split: bool = False):
-        self.split = bool(split)
-        self.stat_names = SPLIT_METRIC_STATS if split else METRIC_STATS
-        self.candidate_columns = CANDIDATE_COLUMNS + (("SR",) if split else ())
+    def __init__(self, split: bool = False, pairs: bool = False):
+        self.pairs = bool(pairs)                     # a run with read pairs (section 7s) is one with split alignments too
+        self.split = bool(split) or self.pairs
+        self.library: Optional[Tuple[int, int, int]] = None      # of a pairs run, and how it was obtained
+        self.library_source = ""
+        self.stat_names = PAIR_METRIC_STATS if pairs else SPLIT_METRIC_STATS if split else METRIC_STATS
+        self.candidate_columns = CANDIDATE_COLUMNS + (("SR",) if self.split else ()) + (PAIR_CANDIDATE_COLUMNS if pairs else ())
         self.tables: Dict[str, Dict[str, np.ndarray]] = {}
         self.refs: Dict[str, np.ndarray] = {}
 
@@ -567,14 +899,16 @@ class Events:
 
     def vcf_text(self) -> str:
         out = ["##fileformat=VCFv4.2\n"] + ["##contig=<ID=%s,length=%d>\n" % (c, self.refs[c].shape[0]) for c in self.tables]
-        out.append(SPLIT_VCF_HEADER if self.split else VCF_HEADER)
+        out.append(PAIRS_VCF_HEADER if self.pairs else SPLIT_VCF_HEADER if self.split else VCF_HEADER)
         for c in self.tables:
-            out += [vcf_line(c, self.refs[c], row, self.split) for row in self.candidates(c)]
+            out += [vcf_line(c, self.refs[c], row, self.split, self.pairs) for row in self.candidates(c)]
         return "".join(out)
 
     def save(self, path: str) -> str:
         names = list(self.tables)
         out = dict(chromosomes=np.array(names, dtype=np.str_))
+        if self.pairs:
+            out.update(library=np.array(self.library, np.int64), library_source=np.array(self.library_source, dtype=np.str_))
         for i, c in enumerate(names):
             for name, a in self.tables[c].items():
                 out["%s_%d" % (name, i)] = a
@@ -590,35 +924,156 @@ class Events:
 def measure(bam: str, fasta, chromosomes: Optional[Sequence[str]] = None, haplotagger=None, min_size: int = MIN_SIZE, flank: int = FLANK,
             mapq_threshold: int = 10, cluster_gap: int = CLUSTER_GAP, len_ratio_percent: int = percent_of(LEN_RATIO),
             min_support: int = MIN_SUPPORT, max_span: Optional[int] = None, device: int = 0, restatement: bool = False,
-            stats: Optional[dict] = None, split: bool = False) -> Events:
+            stats: Optional[dict] = None, split: bool = False, pairs: bool = False, library: Optional[Tuple[int, int, int]] = None,
+            k: int = PAIRS_K, clip_min: int = CLIP_MIN) -> Events:
     """The events of one BAM, chromosome after chromosome (default: every sequence of the FASTA).  ``fasta``: a path, or
     {chromosome: sequence}; ``haplotagger``: its ``retag(chromosome, reads)`` replaces the BAM's own HP; ``restatement``: from the
     plain-Python rules instead of the GPU.  ``stats``: the library's kernel times and the seconds of decoding (``decode_s``), of
     the library's calls (``device_s``) and of the whole pass (``total_s``) are added.  ``split``: the reads come with their SA tags
-    (``fetch_with_sa``) and the junctions of the split alignments are rows too; the contigs are the BAM header's sequences."""
-    out = Events(split)
+    (``fetch_with_sa``) and the junctions of the split alignments are rows too; the contigs are the BAM header's sequences.
+    ``pairs``: the reads come with their mate fields as well (``fetch_pairs``) and the rules of section 7s apply; ``library``:
+    (median, lo, hi) of the inner distances, or None to sample it (``sampled_library``) with ``k``."""
+    out = Events(split, pairs)
     contigs: Optional[List[str]] = None
-    if split:
+    if pairs:
+        if library is None:
+            out.library = sampled_library(bam, fasta, chromosomes, min_size, flank, mapq_threshold, max_span, device, restatement, k)
+            out.library_source = "sampled with k = %d" % k if out.library != UNSET_LIBRARY else "unset: the BAM has no paired reads"
+        else:
+            out.library, out.library_source = tuple(int(v) for v in library), "given"
+        _log.info("%s: inner distances of the library: median %d, normal from %d to %d (%s)", os.path.basename(bam), *out.library,
+                  out.library_source)
+    if split or pairs:
         from .bam import BamFile
         with BamFile(bam) as source:
             contigs = [name for name, _ in source.references]
 
     def open_handle(c, ref):
         caller = Caller(ref, min_size, flank, mapq_threshold, device, cluster_gap, len_ratio_percent, min_support)
-        if split:
+        if split or pairs:
             try:
                 caller.set_contigs(contigs, contigs.index(c))
+                if pairs:
+                    caller.set_library(*out.library, clip_min=clip_min)
             except Exception:
                 caller.close()
                 raise
         return caller
 
-    measure_spans(bam, fasta, chromosomes, max_span, stats, restatement, open_handle=open_handle,
-                  restated=lambda c, ref, spans: restated(spans, ref, min_size, flank, mapq_threshold, cluster_gap, len_ratio_percent,
-                                                          min_support, contigs, contigs.index(c) if split else None),
+    def restate(c, ref, spans):
+        if pairs:
+            return restated_pairs(spans, ref, out.library, contigs, contigs.index(c), min_size, flank, mapq_threshold, cluster_gap,
+                                  len_ratio_percent, min_support, clip_min)
+        return restated(spans, ref, min_size, flank, mapq_threshold, cluster_gap, len_ratio_percent, min_support, contigs,
+                        contigs.index(c) if split else None)
+
+    measure_spans(bam, fasta, chromosomes, max_span, stats, restatement, open_handle=open_handle, restated=restate,
                   done=lambda c, ref, tables, counts: out.set(c, ref, tables, counts),
-                  retag=haplotagger.retag if haplotagger is not None else None, with_sa=split)
+                  retag=haplotagger.retag if haplotagger is not None else None, with_sa=split, with_pairs=pairs)
     return out
+
+
+class LibraryError(ValueError):
+    """A BAM with paired reads but too few forward-reverse pairs to sample a library from; the message names the fix."""
+
+
+class _Sampled(Exception):
+    """Ends the sampling pass once INNER holds enough pairs."""
+
+
+def sampled_library(bam: str, fasta, chromosomes: Optional[Sequence[str]] = None, min_size: int = MIN_SIZE, flank: int = FLANK,
+                    mapq_threshold: int = 10, max_span: Optional[int] = None, device: int = 0, restatement: bool = False,
+                    k: int = PAIRS_K) -> Tuple[int, int, int]:
+    """(median, lo, hi) of the BAM's own inner distances: the leading spans of the chromosomes in order go through a throw-away handle
+    with the unset triple (under ``restatement`` through ``pair_rows_of``) until INNER holds LIBRARY_SAMPLE pairs or the BAM ends.
+    A BAM without a single pair-counted read (PacBio) has no library and needs none: ``UNSET_LIBRARY``, under which it yields no
+    pair row.  Paired reads but fewer than LIBRARY_MIN_PAIRS forward-reverse pairs: ``LibraryError``."""
+    from .bam import BamFile
+    with BamFile(bam) as source:
+        contigs = [name for name, _ in source.references]
+    inner = np.zeros(INNER_BINS, np.int64)
+    pair_reads = [0]
+
+    class Sampler:
+        """What ``measure_spans`` takes for a handle; ``caller`` is the library's, or None under ``restatement``."""
+        TIMES = ()
+
+        def __init__(self, c, ref):
+            self.own, self.length, self.given, self.base, self.seen = contigs.index(c), int(ref.shape[0]), 0, inner.copy(), pair_reads[0]
+            self.caller = None
+            if not restatement:
+                self.caller = Caller(ref, min_size, flank, mapq_threshold, device)
+                try:
+                    self.caller.set_contigs(contigs, self.own)
+                    self.caller.set_library(*UNSET_LIBRARY)
+                except Exception:
+                    self.caller.close()
+                    raise
+
+        def add(self, reads, splits, mates, lo, hi):
+            if self.caller is not None:
+                self.caller.add(reads, splits, mates, lo, hi)
+                inner[:] = self.base + handle_array(self.caller._lib.hello_sv_pairs_array, self.caller._h, 0, np.int64)
+                pair_reads[0] = self.seen + int(self.caller.stats()["pair_reads"])
+            else:
+                part = pair_rows_of(reads, splits, mates, lo, self.own, len(contigs), self.length, min_size, mapq_threshold, UNSET_LIBRARY,
+                                    CLIP_MIN, self.given)
+                self.given += part["counts"]["pair_reads"]
+                pair_reads[0] = self.seen + self.given
+                np.add.at(inner, np.array(part["inner"], np.int64), 1)
+            if inner.sum() >= LIBRARY_SAMPLE:
+                raise _Sampled()
+
+        def results(self):
+            return {}, {}
+
+        def close(self):
+            if self.caller is not None:
+                self.caller.close()
+
+    try:
+        measure_spans(bam, fasta, chromosomes, max_span, None, False, open_handle=Sampler, restated=None, done=lambda *a: None,
+                      with_pairs=True)
+    except _Sampled:
+        pass
+    if pair_reads[0] == 0:
+        return UNSET_LIBRARY
+    if inner.sum() < LIBRARY_MIN_PAIRS:
+        raise LibraryError("%s: %d forward-reverse pairs on one chromosome, too few for a library (at least %d): give the inner distances "
+                         "with --sv_pairs_library MEDIAN,LO,HI (--pairs_library of hello_amd.sv)" % (bam, int(inner.sum()), LIBRARY_MIN_PAIRS))
+    return library_of(inner, k)
+
+
+def add_pairs_options(p: argparse.ArgumentParser, prefix: str, given_or_none: bool = False) -> None:
+    """``--<prefix>pairs_library``, ``--<prefix>pairs_k`` and ``--[sv_]clip_min`` (prefix: "sv_" for hello_amd.call, "" here)."""
+    pick = lambda v: None if given_or_none else v                   # noqa: E731
+    p.add_argument("--%spairs_library" % prefix, default=None, metavar="M,LO,HI",
+                   help="with pairs: the library's inner distance (mate start minus read end) as median and the least and greatest "
+                        "normal value, instead of sampling them from the BAM")
+    p.add_argument("--%spairs_k" % prefix, type=int, default=pick(PAIRS_K),
+                   help="with pairs: a sampled library calls normal what lies within k median absolute deviations (default %d)" % PAIRS_K)
+    p.add_argument("--%sclip_min" % prefix, type=int, default=pick(CLIP_MIN),
+                   help="with pairs: the fewest bases of a soft clip that counts as a clipped end (default %d)" % CLIP_MIN)
+
+
+def library_option(text: Optional[str], name: str) -> Optional[Tuple[int, int, int]]:
+    """``M,LO,HI`` -> the triple, refused with the fix where it is none."""
+    if text is None:
+        return None
+    try:
+        median, lo, hi = (int(v) for v in text.split(","))
+    except ValueError:
+        raise SystemExit(f"--{name} takes three integers MEDIAN,LO,HI: give for instance --{name} 200,40,360") from None
+    if not -(1 << 31) <= lo <= median <= hi < (1 << 31):
+        raise SystemExit(f"--{name} is MEDIAN,LO,HI with LO <= MEDIAN <= HI: give for instance --{name} 200,40,360")
+    return median, lo, hi
+
+
+def check_pairs_options(k: int, clip_min: int, prefix: str) -> None:
+    if k < 1:
+        raise SystemExit(f"--{prefix}pairs_k is a number of median absolute deviations: give 1 or more")
+    if clip_min < 1:
+        raise SystemExit(f"--{prefix}clip_min is the fewest bases of a soft clip that counts: give 1 or more")
 
 
 def add_options(p: argparse.ArgumentParser, given_or_none: bool = False) -> None:
@@ -659,6 +1114,10 @@ def parser() -> argparse.ArgumentParser:
     add_options(p)
     p.add_argument("--split", action="store_true", default=False,
                    help="Also call deletions, insertions, duplications and inversions from split alignments (the SA tags; DESIGN.md 7q)")
+    p.add_argument("--pairs", action="store_true", default=False,
+                   help="Also call deletions, duplications, inversions and translocation ends from discordant read pairs, and count "
+                        "the clipped ends near every event (DESIGN.md 7s)")
+    add_pairs_options(p, "", given_or_none=True)
     p.add_argument("--device", type=int, default=0, help="GPU index")
     return p
 
@@ -668,6 +1127,13 @@ def main(argv=None) -> List[str]:
     args = parser().parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="%(asctime)-15s %(message)s")
     check_options(args.sv_min_size, args.sv_min_support, args.sv_flank, args.sv_cluster_gap, args.sv_len_ratio)
+    if not args.pairs:
+        for flag in ("pairs_library", "pairs_k", "clip_min"):
+            if getattr(args, flag) is not None:
+                raise SystemExit(f"--{flag} is an option of the read pairs and this run looks at none: add --pairs, or drop --{flag}")
+    library = library_option(args.pairs_library, "pairs_library")
+    pairs_k, clip_min = PAIRS_K if args.pairs_k is None else args.pairs_k, CLIP_MIN if args.clip_min is None else args.clip_min
+    check_pairs_options(pairs_k, clip_min, "")
     chromosomes = args.chromosomes.split(",") if args.chromosomes else None
     genome = read_fasta(args.ref, chromosomes)
     bams = args.bam.split(",")
@@ -681,8 +1147,12 @@ def main(argv=None) -> List[str]:
     try:
         for n, bam in enumerate(bams):
             stats: dict = {}
-            found = measure(bam, genome, chromosomes, tagger, args.sv_min_size, args.sv_flank, args.mapq_threshold, args.sv_cluster_gap,
-                            percent_of(args.sv_len_ratio), args.sv_min_support, device=args.device, stats=stats, split=args.split)
+            try:
+                found = measure(bam, genome, chromosomes, tagger, args.sv_min_size, args.sv_flank, args.mapq_threshold, args.sv_cluster_gap,
+                                percent_of(args.sv_len_ratio), args.sv_min_support, device=args.device, stats=stats, split=args.split,
+                                pairs=args.pairs, library=library, k=pairs_k, clip_min=clip_min)
+            except LibraryError as refused:
+                raise SystemExit(str(refused)) from None
             written += found.write_all(args.output_prefix + (".%d" % (n + 1) if len(bams) > 1 else ""))
             total = found.total()
             _log.info("%s: %d reads counting, %d walked, %d signatures, %d events (kernels %.1f ms)", os.path.basename(bam),

@@ -331,7 +331,12 @@ enum {
     /* after hello_bam_fetch_sa alone (after the other two fetches both selectors are refused, as every selector above 16 was
        before them): the SA tags, DESIGN.md section 7q */
     HELLO_BAM_SA_BYTES = 17,   /* uint8: the bytes of every record's SA:Z tag without the NUL, all records concatenated */
-    HELLO_BAM_SA_OFFSETS = 18  /* int64 [R + 1] into them; a record without SA, or with SA of another type than Z, has an empty range */
+    HELLO_BAM_SA_OFFSETS = 18, /* int64 [R + 1] into them; a record without SA, or with SA of another type than Z, has an empty range */
+    /* after hello_bam_fetch_pairs alone, which fills 17 and 18 too (refused after the other fetches): the mate fields of the record's
+       fixed core, DESIGN.md section 7s */
+    HELLO_BAM_MATE_TID = 19,   /* int32: next_refID */
+    HELLO_BAM_MATE_POS = 20,   /* int64: next_pos, 0-based, -1 when absent */
+    HELLO_BAM_TLEN = 21        /* int32: tlen, carried; no rule uses it */
 };
 int hello_bam_open(const char* path, int32_t n_threads, hello_bam** out);
 int hello_bam_n_references(const hello_bam* bam);
@@ -344,6 +349,9 @@ int hello_bam_fetch_mods(hello_bam* bam, const char* chromosome, int64_t start, 
 /* hello_bam_fetch, and per record the raw text of its SA:Z tag (never an error) */
 int hello_bam_fetch_sa(hello_bam* bam, const char* chromosome, int64_t start, int64_t stop, int32_t use_index,
                        hello_bam_reads** out);
+/* hello_bam_fetch_sa, and per record the mate fields of its fixed core as they stand (never an error) */
+int hello_bam_fetch_pairs(hello_bam* bam, const char* chromosome, int64_t start, int64_t stop, int32_t use_index,
+                          hello_bam_reads** out);
 int hello_bam_reads_info(const hello_bam_reads* reads, int64_t* n_reads, int32_t* used_index, int64_t* n_blocks);
 /* a pointer into `reads` (valid until hello_bam_reads_free) and its element count */
 int hello_bam_reads_array(const hello_bam_reads* reads, int32_t which, const void** data, int64_t* count);
@@ -1166,6 +1174,54 @@ int hello_sv_add_split(hello_sv* sv, const uint8_t* bases, const uint8_t* quals,
                        const int64_t* cigar_offsets, const int64_t* ref_starts, const int64_t* ref_ends, const uint8_t* mapq,
                        const uint16_t* flags, const uint64_t* name_hash, const uint8_t* hp, const uint8_t* sa_bytes,
                        const int64_t* sa_offsets, int64_t n_sa_bytes, int64_t n_reads, int64_t lo, int64_t hi);
+
+/* Discordant read pairs and clipped ends (off unless hello_sv_add_pairs is called):
+ *   hello_sv_library: the library's inner distances (median, lo, hi), once, before the first hello_sv_add_pairs; host only.  The
+ *          unset triple (0, INT32_MIN, INT32_MAX) is valid too: then only orientation and BND rows arise, which is how a library is
+ *          sampled.  Refused: NULL, lo > median, median > hi, a second call.
+ *   hello_sv_clip_min: the fewest bases of a soft clip that counts (default 20), before the first hello_sv_add_pairs; host only.
+ *   hello_sv_add_pairs: hello_sv_add_split, and per belonging read the pair rules: `mate_tid` / `mate_pos` are the arrays
+ *          HELLO_BAM_MATE_TID / HELLO_BAM_MATE_POS of hello_bam_fetch_pairs.  A pair-counted read (flag 0x1, none of 0x4 0x8 0x100
+ *          0x800 0x400 0x200, mapq at the threshold; 0x2 is not consulted) needs mate_pos in [0, 2^31 - 1], mate_pos <= length
+ *          when mate_tid is the handle's chromosome, and its own end inside the chromosome: else its PAIR_STATUS is BAD_MATE, it
+ *          emits nothing and is counted.  The host checks this before any launch; no kernel indexes with an unchecked value.
+ *          Refused: what hello_sv_add_split refuses, a handle without a library.  A refused call leaves the handle as it was.  A
+ *          handle may mix the three adds.
+ *   hello_sv_pairs_array / hello_sv_pairs_stats: new getters; hello_sv_array and hello_sv_stats keep their selectors and meanings,
+ *          and with pairs on SIGNATURES_* and CANDIDATES_* of hello_sv_array also hold the pair rows (OP = -16) and the pair-only
+ *          candidates.
+ *   hello_sv_cluster_pairs: host only.  signatures int64 [n][8] of all kinds -> out int64 [*n_out][HELLO_SV_CLUSTER_PAIRS_COLUMNS]:
+ *          the 14 columns of hello_sv_cluster_split, then PR, END_MIN, END_MAX, IMPRECISE; `out` has room for n rows.
+ *   hello_sv_library_of: host only.  inner int64 [4096] -> out[3] = (median, lo, hi) with hi - median = median - lo = k max(mad, 1). */
+#define HELLO_SV_PAIRS_STATS 13
+#define HELLO_SV_CLUSTER_PAIRS_COLUMNS 18
+enum {
+    HELLO_SV_PAIRS_INNER = 0,            /* int64 [4096]: bin clamp(mate_pos - ref_end + 1024, 0, 4095) of the left FR records */
+    HELLO_SV_PAIRS_CLIP_LEFT = 1,        /* int32 [length + 1]: reads whose aligned part ends here before a counting soft clip */
+    HELLO_SV_PAIRS_CLIP_RIGHT = 2,       /* int32 [length + 1]: reads whose aligned part starts here behind a counting soft clip */
+    HELLO_SV_PAIRS_STATUS = 3,           /* uint8 per read of the last add: 0 not pair-counted, 1 BAD_MATE, 2 right record, 3 normal,
+                                            4 short, 5 small, 6 unplaced, 7 with a row, 8 with a BND row */
+    HELLO_SV_PAIRS_CANDIDATES_PR = 4,    /* int64, after hello_sv_finish: the supporting pairs */
+    HELLO_SV_PAIRS_CANDIDATES_CE = 5,    /* the clipped ends within flank of the candidate's two ends */
+    HELLO_SV_PAIRS_CANDIDATES_END_MIN = 6,
+    HELLO_SV_PAIRS_CANDIDATES_END_MAX = 7,
+    HELLO_SV_PAIRS_CANDIDATES_IMPRECISE = 8      /* 1: from pair rows alone */
+};
+int hello_sv_library(hello_sv* sv, int32_t median, int32_t lo, int32_t hi);
+int hello_sv_clip_min(hello_sv* sv, int32_t clip_min);
+int hello_sv_add_pairs(hello_sv* sv, const uint8_t* bases, const uint8_t* quals, const int64_t* read_offsets, const uint32_t* cigars,
+                       const int64_t* cigar_offsets, const int64_t* ref_starts, const int64_t* ref_ends, const uint8_t* mapq,
+                       const uint16_t* flags, const uint64_t* name_hash, const uint8_t* hp, const uint8_t* sa_bytes,
+                       const int64_t* sa_offsets, int64_t n_sa_bytes, const int32_t* mate_tid, const int64_t* mate_pos, int64_t n_reads,
+                       int64_t lo, int64_t hi);
+int hello_sv_pairs_array(hello_sv* sv, int32_t which, const void** data, int64_t* count);
+/* stats[HELLO_SV_PAIRS_STATS]: pair-counted belonging reads, left records, right records, normal, short, small, unplaced, BAD_MATE,
+ * pair rows, reads with a counting clip, pair rows a cluster took, pair-only candidates (the last two after hello_sv_finish), the
+ * pairs kernel's ms */
+int hello_sv_pairs_stats(const hello_sv* sv, double* stats);
+int hello_sv_cluster_pairs(const int64_t* signatures, int64_t n, int64_t cluster_gap, int32_t len_ratio_percent, int32_t min_support,
+                           int32_t median, int32_t lo, int32_t hi, int32_t flank, int64_t* out, int64_t* n_out);
+int hello_sv_library_of(const int64_t* inner, int64_t k, int64_t* out);
 
 #ifdef __cplusplus
 }
